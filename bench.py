@@ -22,6 +22,11 @@ Further entries of the same JSON line (the other BASELINE configs):
   c4        panda_spheres GPMP2 B=2048, H=128, D=7 (N = 1 only; structured-FLOP roofline against the fp64 matrix peak,
             CPU baseline on a small batch and extrapolated, as SURVEY 8d prescribes).
 One JSON line is printed by rank 0.
+
+--dump-outputs DIR: after the timed blocks, rank 0 writes what the main line's LAST timed block computed -- the (P,H,d)
+trajectory optimize() returned, the samples / costs / weights of its last step and, with N > 1, the gathered means -- as
+DIR/<name>.npy (float32).  Inputs, noise seed and step counts are fixed by the arguments, so two builds run with the same
+arguments can be compared output for output.
 """
 import argparse
 import glob
@@ -370,6 +375,31 @@ def spread(blocks, steps):
                  'ms_per_step_max': 1e3 * b[-1] / steps}
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: every array as out_dir/<name>.npy in float32, smallest first.  The C3 outputs come to ~15 MB; an array
+    that would take the total past 64 MB is cut to a fixed, seeded sample of its leading-axis rows, whose indices are written
+    next to it as <name>_rows.npy (float64)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    total = 0
+    for name, t in sorted(arrays.items(), key=lambda kv: (kv[1].numel(), kv[0])):
+        a = t.detach().cpu().to(torch.float32).contiguous().numpy()
+        if total + a.nbytes > DUMP_LIMIT_BYTES:
+            row = a.nbytes // max(a.shape[0], 1) + 8
+            n = min(a.shape[0], (DUMP_LIMIT_BYTES - total) // row) if a.ndim > 0 else 0
+            if n < 1:
+                raise RuntimeError('--dump-outputs: %s does not fit in the %d MB budget' % (name, DUMP_LIMIT_BYTES >> 20))
+            rows = np.sort(np.random.RandomState(0).choice(a.shape[0], size=n, replace=False))
+            a = np.ascontiguousarray(a[rows])
+            np.save(os.path.join(out_dir, name + '_rows.npy'), rows.astype(np.float64))
+            total += 8 * n
+        np.save(os.path.join(out_dir, name + '.npy'), a)
+        total += a.nbytes
+
+
 def make_stomp(P, S, dev, rank, pos_only=False, H=64):
     from motion_planning_baselines_amd import workloads
     from motion_planning_baselines_amd.planners.stomp import STOMP
@@ -527,8 +557,10 @@ def bench_crowded(dev, rank, P, S, steps):
     return out
 
 
-def run_stomp(planner, clock, dist, world, steps, warmup, repeats, preheat, cold=False):
-    """W untimed steps, then R blocks of EXACTLY `steps` steps (one C-ABI call = 2K launches) + the final gather."""
+def run_stomp(planner, clock, dist, world, steps, warmup, repeats, preheat, cold=False, keep=None):
+    """W untimed steps, then R blocks of EXACTLY `steps` steps (one C-ABI call = 2K launches) + the final gather.
+    `keep` (a dict, or None): receives what the LAST timed block computed -- the trajectory optimize() returned, the samples,
+    costs and weights of its last step and, with N > 1, the gathered means -- as host copies taken after the timed region."""
     # the final gather's destination: one flat (world * P, H, d) tensor (all_gather_into_tensor: one RCCL kernel, no
     # per-rank copy-out kernels)
     gathered = (torch.empty((world * planner._particle_means.shape[0],) + tuple(planner._particle_means.shape[1:]),
@@ -568,8 +600,10 @@ def run_stomp(planner, clock, dist, world, steps, warmup, repeats, preheat, cold
     if dist is not None:                             # RCCL communicator / xGMI set-up is part of the warm-up
         gather()
 
+    last = [None]
+
     def block():
-        planner.optimize(opt_iters=steps)
+        last[0] = planner.optimize(opt_iters=steps)
         if dist is not None:
             gather()                                 # final gather of the (P,H,d) means over xGMI
         return dist is not None                      # (the all-gather closes the block: Clock.blocks)
@@ -580,6 +614,12 @@ def run_stomp(planner, clock, dist, world, steps, warmup, repeats, preheat, cold
             spans.append(planner._status.device_span_ms())
         planner._particle_means.copy_(means_init)
     blocks = clock.blocks(block, repeats, before=reset)
+    if keep is not None:                             # (the blocks have synchronised: these are the last block's results)
+        keep.update(trajectory=last[0].cpu(), samples=planner.state_particles.cpu(), costs=planner.costs.cpu(),
+                    weights=planner._weights_buf.cpu())
+        if gathered is not None:
+            keep['means_gathered'] = gathered.cpu()
+    last[0] = None
     reset()
     run_stomp.device_span_ms = sorted(spans[-repeats:]) if len(spans) >= repeats else None
     assert torch.isfinite(planner._particle_means).all()
@@ -990,6 +1030,8 @@ def main():
     ap.add_argument('--no-other-configs', action='store_true', help='main line only (profiling runs)')
     ap.add_argument('--main-only', action='store_true', help='(rocprofv3 stats pass) no side measurements either: the only launches of the '
                     'persistent kernel are the pre-heat, warm-up and timed K-step launches, so the trace\'s average is the timed launch')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the main line\'s last timed step computed as DIR/<name>.npy (float32; rank 0)')
     args = ap.parse_args()
 
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
@@ -1024,7 +1066,11 @@ def main():
     prm = wl['params']
     H, d, D = prm['n_support_points'], wl['means0'].shape[-1], 7
     preheat = args.preheat if args.preheat >= 0 else max(8, min(60, 1200 // max(args.steps, 1)))
-    blocks = run_stomp(planner, clock, dist, world, args.steps, args.warmup, args.repeats, preheat=preheat, cold=not args.main_only)
+    kept = {} if args.dump_outputs else None
+    blocks = run_stomp(planner, clock, dist, world, args.steps, args.warmup, args.repeats, preheat=preheat, cold=not args.main_only,
+                       keep=kept)
+    if kept is not None and rank == 0:
+        dump_outputs(args.dump_outputs, kept)
     cold_block_s = run_stomp.cold_block_s
     elapsed, sp = spread(blocks, args.steps)
     timed_launch_ms = run_stomp.launch_ms[len(run_stomp.launch_ms) // 2]    # median over the R event-timed launches

@@ -16,8 +16,8 @@ import numpy as np
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-# output directory: next to this script, or MPB_GOLDEN_OUT (tests/test_goldens_regenerate.py writes to a temp dir and
-# compares with the committed fixtures bit for bit)
+# output directory: next to this script, or MPB_GOLDEN_OUT (a temp dir, to compare a regeneration with the committed
+# fixtures bit for bit)
 HERE = os.environ.get('MPB_GOLDEN_OUT') or os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 sys.dont_write_bytecode = True
