@@ -308,10 +308,13 @@ __global__ __launch_bounds__(256) void gpmp2_lr_gradient(const float* __restrict
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, b = blockIdx.x;
     // The capacitance kernel lasts as long as its largest system (one particle with 116 active rows: 87 us; the median particle has
     // none), and two workgroups fit a CU: in batch order the largest system of C4 started in the third of four rounds.  So every
-    // particle gets a size class here -- rows with a non-zero hinge value, LR_ORD classes of 16 --, one extra workgroup of the
-    // solve that follows sorts the particles by class, largest first (a counting sort in LDS; one atomic per particle on a
+    // particle gets a size class here -- rows with a non-zero hinge value OR Jacobian, LR_ORD classes of 16 --, one extra workgroup
+    // of the solve that follows sorts the particles by class, largest first (a counting sort in LDS; one atomic per particle on a
     // counter per class in global memory cost this kernel 19 us: 2 048 returning atomics on nine addresses), and gpmp2_lr_cap
-    // takes them in that order.  (Scheduling only: the class is an estimate, nothing else reads it.)
+    // takes them in that order.  The class is an estimate of the system's size, but its last class is exact and read: gpmp2_lr_cap
+    // steps such a particle by u0 alone, so it must have no row with h_t != 0 (the compaction's predicate).  The hinge alone does
+    // not tell: with n_interp > 0 the row of a support point clear of the margin carries the gradients of the interpolated points
+    // of its two segments (gpmp2_linearize_kernel), c_t = 0 with h_t != 0.
     int n_est = 0;
     const int dim = 2 * D;
     const LrCoef C = lr_coef(K);
@@ -330,10 +333,34 @@ __global__ __launch_bounds__(256) void gpmp2_lr_gradient(const float* __restrict
             tmp[u] = (e < nx) ? xg[e] : 0.f;
         }
         // (the size estimate's loads behind the trajectory's, ahead of the first wait)
-        for (int r0 = 0; r0 < F * H; r0 += 256) {
-            const int r = r0 + tid, f = r / H, t = r - f * H;
-            const bool a = r < F * H && t > 0 && jac[(((size_t)f * B + b) * H + t) * (D + 1) + D] != 0.f;
-            n_est += __popcll(__ballot(a));
+        if (D == 7) {
+            // rows of 8 floats, 32-byte aligned: a lane per half row (one 16-byte load, the field's rows of the particle in whole
+            // lines), the partner lane holds the other half.  (A lane per row walking its 8 floats: C4 +5 us per iteration)
+            for (int f = 0; f < F; ++f) {
+                const float4* jf = reinterpret_cast<const float4*>(jac + ((size_t)f * B + b) * H * 8);
+                for (int e0 = 0; e0 < 2 * H; e0 += 256) {
+                    const int e = e0 + tid;
+                    int nz = 0;
+                    if (e < 2 * H) {
+                        const float4 v = jf[e];
+                        nz = (v.x != 0.f) | (v.y != 0.f) | (v.z != 0.f) | (v.w != 0.f);
+                    }
+                    nz |= __shfl_xor(nz, 1);
+                    n_est += __popcll(__ballot(nz && (e & 1) == 0 && e < 2 * H && e >= 2));       // (row 0 takes no collision factor)
+                }
+            }
+        } else {
+            for (int r0 = 0; r0 < F * H; r0 += 256) {
+                const int r = r0 + tid, f = r / H, t = r - f * H;
+                bool a = false;
+                if (r < F * H && t > 0) {
+                    const float* jr = jac + (((size_t)f * B + b) * H + t) * (D + 1);
+#pragma unroll
+                    for (int i = 0; i <= MPB_MAX_DOF; ++i)
+                        if (i <= D) a |= jr[i] != 0.f;           // h_t (D floats) and c_t
+                }
+                n_est += __popcll(__ballot(a));
+            }
         }
 #pragma unroll
         for (int u = 0; u < (LR_HMAX * 2 * MPB_MAX_DOF + 255) / 256; ++u) {
@@ -603,9 +630,10 @@ __global__ __launch_bounds__(CAP_THREADS, CAP_WPE) void gpmp2_lr_cap(const float
 #else
 #define CAP_CLK(k)
 #endif
-    // a particle of the last size class has no hinge anywhere (every c_t is zero, so every h_t is): its collision cost is zero, w = 0,
-    // and its step is u0's.  This workgroup takes that step, x += step u0, and is done -- no compaction (its jac rows are not even
-    // read), and gpmp2_lr_apply is left with the particles that have rows.  (More than half of C4's particles: with the compaction
+    // a particle of the last size class has no row with c_t or h_t non-zero (gpmp2_lr_gradient looks at both: with n_interp > 0 a
+    // zero c_t does not make h_t zero): its collision cost is zero, it has no collision factor, w = 0, and its step is u0's.  This
+    // workgroup takes that step, x += step u0, and is done -- no compaction (its jac rows are not even read again), and
+    // gpmp2_lr_apply is left with the particles that have rows.  (More than half of C4's particles: with the compaction
     // in front of the test the kernel did not get below 41 us however small the systems had become.)
     if (ord[b] == LR_ORD - 1) {                                  // (block-uniform)
         if (costs_out != nullptr && tid == 0) costs_out[b] = (float)gpcost[b];

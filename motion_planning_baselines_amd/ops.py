@@ -670,8 +670,8 @@ def gpmp2_linearize(x, geom, workspace, n_interp=0):
 def gpmp2_collision_rows(x, geom, n_interp=0):
     """The collision factor's rows as the GPMP2 solve consumes them: (F, B, H, D+1) fp32 with [..., :D] = h_t =
     -d c_t / d q_t (with n_interp > 0: of the INTERPOLATED trajectory's summed cost, cost_functions.py:115-119,
-    field_factor.py:42-54) and [..., D] = c_t, one set per chained field, each scaled by sqrt(s_f); row 0 is zero
-    (traj_range [1, None]).  Runs mpb_gpmp2_linearize into a scratch buffer that holds only the Jacobian section of
+    field_factor.py:42-54) and [..., D] = c_t, one set per chained field, each scaled by sqrt(s_f); row 0 takes no
+    collision factor (traj_range [1, None]): its c is zero, and so is its h unless n_interp > 0.  Runs mpb_gpmp2_linearize into a scratch buffer that holds only the Jacobian section of
     the GPMP2 workspace (the kernel writes nothing else)."""
     B, H, dim = x.shape
     D = dim // 2

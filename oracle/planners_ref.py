@@ -242,14 +242,10 @@ def interpolate_trajs(x, n):
     return torch.cat((seg.flatten(1, 2), x[:, -1:]), dim=1)
 
 
-def gpmp2_linear_system(x, robot, field, start_state, goal_state, D, dt,
-                        sigma_start, sigma_gp, sigma_goal, sigma_coll, tensor_args, n_interp=None):
-    """Dense (A, b, K) exactly as CostComposite.get_linear_system stacks it (cost_functions.py:107-144)
-    for the cost list of build_gpmp2_cost_composite (gpmp2.py:23-91): CostGP (:291-314), CostGoalPrior
-    (:538-554), CostCollision (:191-231; Jacobian = -d err/d q by autograd, field_factor.py:41-57).
-    x (B,H,2D).  Returns A (B,M,N), b (B,M,1), K (B,M,M) with N = 2D*H, M = N + 2D + (H-1).
-    goal_state None: the composite has no CostGoalPrior (gpmp2.py:63-73, goal_directed False :135-137).
-    """
+def gpmp2_prior_system(x, start_state, goal_state, D, dt, sigma_start, sigma_gp, sigma_goal, tensor_args):
+    """The start prior + GP rows (cost_functions.py:291-314) and the goal prior rows (:538-554) of the stack that
+    CostComposite.get_linear_system builds (:107-144): (A1, b1, K1), (A2, b2, K2).  Their A does not depend on x: the
+    same for every particle.  goal_state None: no goal prior rows (gpmp2.py:63-73, goal_directed False :135-137)."""
     B, H, dim = x.shape
     N = dim * H
     Phi = gp_phi(D, dt, tensor_args)
@@ -278,9 +274,17 @@ def gpmp2_linear_system(x, robot, field, start_state, goal_state, D, dt,
     else:
         A2, b2, K2 = (torch.zeros(B, 0, N, **tensor_args), torch.zeros(B, 0, 1, **tensor_args),
                       torch.zeros(B, 0, 0, **tensor_args))
-    # ---- collision (cost_functions.py:191-231): one block of H-1 rows per collision field (gpmp2.py:70-78)
+    return (A1, b1, K1), (A2, b2, K2)
+
+
+def gpmp2_collision_rows(x, robot, field, D, n_interp=None):
+    """The collision factors' rows alone (cost_functions.py:191-231, one block of H-1 rows per collision field,
+    gpmp2.py:70-78): h (F, B, H-1, D) = -d err / d q_t of support points t = 1..H-1 by autograd (field_factor.py:54;
+    with n_interp: of the INTERPOLATED trajectory's summed error, field_factor.py:42-54, cost_functions.py:115-119) and
+    the support-point error c (F, B, H-1).  Row i of field f sits at column block i+1 of A, positions only."""
+    B, H, dim = x.shape
     fields = list(field) if isinstance(field, (list, tuple)) else [field]
-    A3s, b3s, K3s = [], [], []
+    hs, cs = [], []
     for fld in fields:
         xg = x.detach().clone().requires_grad_(True)
         q_pos = robot.get_position(xg)
@@ -291,17 +295,32 @@ def gpmp2_linear_system(x, robot, field, start_state, goal_state, D, dt,
             xi = interpolate_trajs(xg, n_interp)                                      # the support-point error
             qi = robot.get_position(xi)                                               # (field_factor.py:42-54,
             err_j = fld.compute_cost(qi[:, 1:], robot.fk_map_collision(qi)[:, 1:])    #  cost_functions.py:115-119)
-        Hobst = -torch.autograd.grad(err_j.sum(), xg)[0][:, 1:, :D]                   # field_factor.py:54
-        A3f = torch.zeros(B, H - 1, N, **tensor_args)
+        hs.append(-torch.autograd.grad(err_j.sum(), xg)[0][:, 1:, :D])                # field_factor.py:54
+        cs.append(err.detach())
+    return torch.stack(hs), torch.stack(cs)
+
+
+def gpmp2_linear_system(x, robot, field, start_state, goal_state, D, dt,
+                        sigma_start, sigma_gp, sigma_goal, sigma_coll, tensor_args, n_interp=None):
+    """Dense (A, b, K) exactly as CostComposite.get_linear_system stacks it (cost_functions.py:107-144)
+    for the cost list of build_gpmp2_cost_composite (gpmp2.py:23-91): CostGP (:291-314), CostGoalPrior
+    (:538-554), CostCollision (:191-231; Jacobian = -d err/d q by autograd, field_factor.py:41-57).
+    x (B,H,2D).  Returns A (B,M,N), b (B,M,1), K (B,M,M) with N = 2D*H, M = N + 2D + (H-1).
+    goal_state None: the composite has no CostGoalPrior (gpmp2.py:63-73, goal_directed False :135-137).
+    """
+    B, H, dim = x.shape
+    N = dim * H
+    (A1, b1, K1), (A2, b2, K2) = gpmp2_prior_system(x, start_state, goal_state, D, dt, sigma_start, sigma_gp, sigma_goal,
+                                                    tensor_args)
+    # ---- collision (cost_functions.py:191-231): one block of H-1 rows per collision field (gpmp2.py:70-78)
+    h, c = gpmp2_collision_rows(x, robot, field, D, n_interp)
+    F = h.shape[0]
+    A3 = torch.zeros(B, F * (H - 1), N, **tensor_args)
+    for f in range(F):
         for i in range(H - 1):
-            A3f[:, i, (i + 1) * dim:(i + 1) * dim + D] = Hobst[:, i]
-        A3s.append(A3f)
-        b3s.append(err.detach().unsqueeze(-1))
-        K3s.append((torch.eye(H - 1, **tensor_args) / sigma_coll ** 2).expand(B, H - 1, H - 1))
-    A3, b3 = torch.cat(A3s, 1), torch.cat(b3s, 1)
-    K3 = torch.zeros(B, A3.shape[1], A3.shape[1], **tensor_args)
-    for i, Kf in enumerate(K3s):
-        K3[:, i * (H - 1):(i + 1) * (H - 1), i * (H - 1):(i + 1) * (H - 1)] = Kf
+            A3[:, f * (H - 1) + i, (i + 1) * dim:(i + 1) * dim + D] = h[f, :, i]
+    b3 = c.permute(1, 0, 2).reshape(B, F * (H - 1), 1)
+    K3 = (torch.eye(F * (H - 1), **tensor_args) / sigma_coll ** 2).expand(B, F * (H - 1), F * (H - 1))
     A = torch.cat([A1, A2, A3], 1)
     b = torch.cat([b1, b2, b3], 1)
     M = A.shape[1]
@@ -314,17 +333,36 @@ def gpmp2_linear_system(x, robot, field, start_state, goal_state, D, dt,
     return A, b, K
 
 
-def gpmp2_normal_equations(A, b, K, delta, trust_region):
-    """A^T K A (+ damping), A^T K b  (gpmp2.py:355-368, incl. Q9: batch-mean diagonal damping)."""
+def gpmp2_normal_equations(A, b, K, delta, trust_region, damping=None):
+    """A^T K A (+ damping), A^T K b  (gpmp2.py:355-368, incl. Q9: batch-mean diagonal damping).
+    damping: (N,) the batch mean of diag(A^T K A) taken over a batch of which A holds only some particles
+    (gpmp2_batch_damping); None: the mean over A's own batch, as gpmp2.py:361-367 does."""
     N = A.shape[-1]
     I = torch.eye(N, dtype=A.dtype)
     AtK = A.transpose(-2, -1) @ K
     AtA = AtK @ A
     if trust_region:
-        JtJ = AtA + delta * (AtA.mean(0) * I)
+        JtJ = AtA + delta * ((AtA.mean(0) if damping is None else torch.diag(damping)) * I)
     else:
         JtJ = AtA + delta * I
     return JtJ, AtK @ b
+
+
+def gpmp2_batch_damping(h, H, D, dt, sigma_start, sigma_gp, sigma_goal, sigma_coll, goal_directed=True):
+    """Q9's diagonal, the batch mean of diag(A^T K A) (gpmp2.py:361-367), without the dense A of every particle: K is
+    block diagonal, so the diagonal is the prior / GP rows' part (gpmp2_prior_system: the same for every particle) plus
+    the collision rows' kc sum_f h^2 on the position columns of waypoints 1..H-1 (gpmp2_collision_rows; each collision
+    row has one non-zero block, K3 = I / sigma_coll^2).  h: (F, B, H-1, D) of the WHOLE batch.  Returns (2D H,)."""
+    dim = 2 * D
+    ta = dict(device='cpu', dtype=torch.float64)
+    x = torch.zeros(1, H, dim, **ta)
+    z = torch.zeros(dim, **ta)
+    (A1, _, K1), (A2, _, K2) = gpmp2_prior_system(x, z, z if goal_directed else None, D, dt, sigma_start, sigma_gp,
+                                                  sigma_goal, ta)
+    d = torch.diagonal(A1[0].t() @ K1[0] @ A1[0]) + torch.diagonal(A2[0].t() @ K2[0] @ A2[0])
+    d = d.clone().view(H, dim)
+    d[1:, :D] += (h.double() ** 2).sum(0).mean(0) / sigma_coll ** 2
+    return d.reshape(-1)
 
 
 def gpmp2_iteration(x, robot, field, start_state, goal_state, D, dt, sigma_start, sigma_gp, sigma_goal,
