@@ -493,6 +493,25 @@ int mpb_gp_prior_sample_dense(float *out, const double *means, const double *eps
 int mpb_mvn_sample_dense(float *out, const double *means, const double *eps, const double *tril_t,
                          int G, int n, int M, uint64_t seed, void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * torch's CPU generator on the device (noise = 'mt19937'): n_calls successive `torch.empty(n).normal_()` draws of a
+ * contiguous fp32 block of n >= 16 elements from torch's mt19937 state, written to out (n_calls, n) -- the uniforms and the
+ * state bit for bit, the normals within a few ULP (torch's vectorised log / sincos are not restated).  Host side and tables:
+ * motion_planning_baselines_amd/mt19937.py; kernels: csrc/mpb_mt19937.h.  Three launches: a prefix of 20 560 raw words from
+ * state_in (one workgroup), the first 624 words of every segment by jump ahead (one workgroup per segment, the prefix in 83 KB
+ * of LDS), and the segments' words, tempered and Box-Muller'd (one workgroup per segment).
+ * state_in: torch's 624-word array (device, uint32); pos: the index of the next word drawn, 624 when `left` == 1, else `next`;
+ * state_out (may alias state_in): torch's array after the draw, the 624 words at final_idx of the final window (-1: the draw
+ * does not reach the end of the array, which is copied); segs (n_segs, 4) int: call, first 16-chunk, 16-chunks, last segment
+ * of its call; jump_idx (n_segs + 1, jump_stride) uint16, jump_cnt (n_segs + 1): the set coefficients of t^offset mod phi
+ * per segment and for the final window, padded to a multiple of 8 with 20 560; work: 20 608 + 624 (n_segs + 1) words of
+ * scratch that every call writes (one per stream).  The same draw with events around its launches: mpb_debug.h.
+ * Measured at C3 (16 calls of 3 670 016, 256 segments): prefix 0.026 ms, jump 0.21 ms, generation 0.31 ms a draw.
+ * ------------------------------------------------------------------------------------------- */
+int mpb_mt19937_normals(float *out, int n, int n_calls, const uint32_t *state_in, int pos, int final_idx, uint32_t *state_out,
+                        const uint16_t *jump_idx, const int *jump_cnt, int jump_stride, const int *segs, int n_segs,
+                        uint32_t *work, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -36,6 +36,18 @@ int mpb_debug_stomp_normals_h(float *out, int P, int S, int d, int H, int n_iter
  * iter0 + it), Box-Muller on 23-bit uniforms (csrc/mpb_common.h box_muller_m23). */
 int mpb_debug_mppi_normals(float *out, int NP, int S, int T, int c, int n_iters, uint64_t seed, uint32_t iter0, void *stream);
 
+/* mpb_debug_mt19937_uniforms: mpb_mt19937_normals's generator with `torch.empty(n).uniform_()` calls instead (n words a call,
+ * no tail rule): the device words against the CPU generator's, bit for bit.  Same arguments; segs / tables laid out for n words
+ * a call (motion_planning_baselines_amd/mt19937.py, uniform=True). */
+int mpb_debug_mt19937_uniforms(float *out, int n, int n_calls, const uint32_t *state_in, int pos, int final_idx,
+                               uint32_t *state_out, const uint16_t *jump_idx, const int *jump_cnt, int jump_stride,
+                               const int *segs, int n_segs, uint32_t *work, void *stream);
+/* mpb_debug_mt19937_normals_timed: mpb_mt19937_normals with four hipEvent_t (events: an array of four handles) recorded before
+ * the prefix, the jump, the generation and after it -- the split of a draw's device time (scripts/bench_seeded_mt.py). */
+int mpb_debug_mt19937_normals_timed(float *out, int n, int n_calls, const uint32_t *state_in, int pos, int final_idx,
+                                    uint32_t *state_out, const uint16_t *jump_idx, const int *jump_cnt, int jump_stride,
+                                    const int *segs, int n_segs, uint32_t *work, void *events, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -63,6 +63,7 @@ SIGNATURES = {
     'mpb_point_dynamics': [_p, _p, _p, _p, _p, _p, _p, ctypes.c_size_t, _i, _f, _p],
     'mpb_point_traj_cost': [_p, _p, _p, _p, _f, _f, _f, _f, _f, _p, _i, _i, _i, _i, _p],
     'mpb_mppi_step': [_p] * 11 + [_i] + [_p] * 6 + [_i, _i, _i, _i, _i, _f, _f, _f, _f, _f, _i, _u64, _u32, _p],
+    'mpb_mt19937_normals': [_p, _i, _i, _p, _i, _i, _p, _p, _p, _i, _p, _i, _p, _p],
 }
 
 # test aids (include/mpb_debug.h): a separate library, csrc/libmpb_hip_debug.so
@@ -73,6 +74,8 @@ DEBUG_SIGNATURES = {
     'mpb_debug_stomp_normals': [_p, _i, _i, _i, _i, _u64, _u32, _u32, _p],
     'mpb_debug_stomp_normals_h': [_p, _i, _i, _i, _i, _i, _u64, _u32, _u32, _p],
     'mpb_debug_mppi_normals': [_p, _i, _i, _i, _i, _i, _u64, _u32, _p],
+    'mpb_debug_mt19937_uniforms': [_p, _i, _i, _p, _i, _i, _p, _p, _p, _i, _p, _i, _p, _p],
+    'mpb_debug_mt19937_normals_timed': [_p, _i, _i, _p, _i, _i, _p, _p, _p, _i, _p, _i, _p, _p, _p],
 }
 ABI_VERSION = 6          # include/mpb.h MPB_ABI_VERSION
 

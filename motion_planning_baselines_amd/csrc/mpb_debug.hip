@@ -5,6 +5,9 @@
 //                             Box-Muller on the hardware log2 / sqrt / sin / cos units), laid out (iters, P, S, d, 64 ceil(H / 64))
 //                             -- for the statistical tests of the throughput-mode noise (tests/test_gpu_rng.py).
 //   mpb_debug_mppi_normals    the standard normals of the MPPI kernel's device draw, in the layout of its injected eps;
+//   mpb_debug_mt19937_uniforms  the device mt19937 generator (mpb_mt19937.h) drawing uniform_() blocks: its words against torch's CPU
+//                             generator bit for bit;
+//   mpb_debug_mt19937_normals_timed  mpb_mt19937_normals with events around its three launches (the split of its device time);
 //   mpb_debug_occupy          workgroups that each hold a CU's LDS for a given time (the lost-launch tests).
 // None is on a product path: this file is the ONLY source of libmpb_hip_debug.so (include/mpb_debug.h), a library of its
 // own that the tests load next to the product library; it shares device code with the product through the headers only.
@@ -12,6 +15,7 @@
 
 #include "mpb_common.h"
 #include "mpb_stomp_noise.h"
+#include "mpb_mt19937.h"
 #include "../../include/mpb_debug.h"
 
 // (this library's own last-error buffer: mpb_common.h's helpers write through mpb_err_buf())
@@ -132,4 +136,30 @@ extern "C" int mpb_debug_occupy(int n_blocks, uint64_t usec, uint32_t* sink, voi
     if (n_blocks < 1 || !sink) return mpb_fail(MPB_E_INVALID, "mpb_debug_occupy: bad argument");
     hipLaunchKernelGGL(occupy_kernel, dim3(n_blocks), dim3(64), 0, (hipStream_t)stream, usec * 100ull, sink);
     return mpb_check_launch("mpb_debug_occupy");
+}
+
+extern "C" int mpb_debug_mt19937_uniforms(float* out, int n, int n_calls, const uint32_t* state_in, int pos, int final_idx,
+                                          uint32_t* state_out, const uint16_t* jump_idx, const int* jump_cnt, int jump_stride,
+                                          const int* segs, int n_segs, uint32_t* work, void* stream) {
+    if (!out || !state_in || !state_out || !jump_idx || !jump_cnt || !segs || !work)
+        return mpb_fail(MPB_E_INVALID, "mpb_debug_mt19937_uniforms: null pointer");
+    if (const char* why = mt19937_bad_args(n, n_calls, pos, final_idx, jump_stride, n_segs)) return mpb_fail(MPB_E_INVALID, why);
+    if (((uintptr_t)jump_idx & 15u) || ((uintptr_t)work & 15u)) return mpb_fail(MPB_E_INVALID, "mpb_debug_mt19937_uniforms: misaligned");
+    if (mt19937_launch<true>(out, n, state_in, pos, final_idx, state_out, jump_idx, jump_cnt, jump_stride, segs, n_segs, work, nullptr,
+                             (hipStream_t)stream) != hipSuccess)
+        return mpb_fail(MPB_E_HIP, "mpb_debug_mt19937_uniforms: HIP launch failed");
+    return MPB_OK;
+}
+
+extern "C" int mpb_debug_mt19937_normals_timed(float* out, int n, int n_calls, const uint32_t* state_in, int pos, int final_idx,
+                                               uint32_t* state_out, const uint16_t* jump_idx, const int* jump_cnt, int jump_stride,
+                                               const int* segs, int n_segs, uint32_t* work, void* events, void* stream) {
+    if (!out || !state_in || !state_out || !jump_idx || !jump_cnt || !segs || !work || !events)
+        return mpb_fail(MPB_E_INVALID, "mpb_debug_mt19937_normals_timed: null pointer");
+    if (const char* why = mt19937_bad_args(n, n_calls, pos, final_idx, jump_stride, n_segs)) return mpb_fail(MPB_E_INVALID, why);
+    if (((uintptr_t)jump_idx & 15u) || ((uintptr_t)work & 15u)) return mpb_fail(MPB_E_INVALID, "mpb_debug_mt19937_normals_timed: misaligned");
+    if (mt19937_launch<false>(out, n, state_in, pos, final_idx, state_out, jump_idx, jump_cnt, jump_stride, segs, n_segs, work,
+                              (hipEvent_t*)events, (hipStream_t)stream) != hipSuccess)
+        return mpb_fail(MPB_E_HIP, "mpb_debug_mt19937_normals_timed: HIP launch failed");
+    return MPB_OK;
 }

@@ -861,3 +861,171 @@ def stoch_gpmp_costs(samples, means, start, goal, geom, costs, S, sig_cost, sig_
         _ptr(samples), _ptr(means), _ptr(start), _ptr(goal), _ptr(geom.buf), _ptr(costs), P, S, H, dim // 2, float(dt),
         float(sig_cost[0]), float(sig_cost[1]), float(sig_cost[2]), float(sig_cost[3]), float(sig_sample[0]),
         float(sig_sample[1]), float(sig_sample[2]), float(temperature), _stream()), 'mpb_stoch_gpmp_costs')
+
+
+# ---- torch's CPU generator on the device (noise = 'mt19937') ---------------------------------------------------------------------
+class _MTTables:
+    """The device copy of a draw shape's jump tables (mt19937.jump_tables); read-only, shared by every stream."""
+
+    def __init__(self, n, n_calls, device, uniform):
+        from . import mt19937 as MT
+        spc = MT.segments_per_call(n, n_calls)
+        polys, rows, self.total, self.host_s = MT.jump_tables(n, n_calls, spc, uniform)
+        idx, cnt = MT.jump_lists(polys)
+        self.n_segs = len(rows)
+        self.stride = idx.shape[1]
+        self.idx = torch.from_numpy(idx.view(np.int16)).to(device)
+        self.cnt = torch.from_numpy(cnt).to(device)
+        self.segs = torch.from_numpy(rows[:, 1:].astype(np.int32)).contiguous().to(device)
+        self.work_words = 20608 + MT.N * (self.n_segs + 1)
+
+
+_MT_TABLES = {}
+_MT_WORK = {}
+
+
+def _mt_device(device):
+    """A device with its index: torch.device('cuda') is the current device (planners accept that spelling)."""
+    device = torch.device(device)
+    if device.type != 'cuda':
+        raise _lib.MPBError(f'torch_cpu_normal_: the draw runs on a GPU, not on {device}')
+    return device if device.index is not None else torch.device('cuda', torch.cuda.current_device())
+
+
+def _mt_tables(n, n_calls, device, uniform=False):
+    key = (int(n), int(n_calls), _mt_device(device), bool(uniform))
+    t = _MT_TABLES.get(key)
+    if t is None:
+        if len(_MT_TABLES) >= 16:
+            _MT_TABLES.pop(next(iter(_MT_TABLES)))
+        t = _MT_TABLES[key] = _MTTables(n, n_calls, key[2], uniform)
+    return t
+
+
+def _mt_work(tb, device):
+    """The prefix + windows scratch of a draw: written by every draw, so one buffer per (device, current stream) -- two
+    generators drawing on different streams never share one.  Grown to the largest draw seen."""
+    device = _mt_device(device)
+    key = (device, raw_stream(device.index))
+    w = _MT_WORK.get(key)
+    if w is None or w.numel() < tb.work_words:
+        w = _MT_WORK[key] = torch.empty(tb.work_words, dtype=torch.int32, device=device)
+    return w
+
+
+def _mt_check_out(out, n_calls):
+    if not isinstance(out, torch.Tensor) or not out.is_cuda:
+        raise _lib.MPBError('torch_cpu_normal_: out must be a GPU tensor (the CPU generator draws CPU tensors itself)')
+    if out.dtype != torch.float32:
+        raise _lib.MPBError(f'torch_cpu_normal_: only float32 draws are served (got {out.dtype}; fp64 takes 53-bit uniforms '
+                            f'from two words)')
+    if not out.is_contiguous():
+        raise _lib.MPBError('torch_cpu_normal_: out must be contiguous (torch draws a non-contiguous tensor another way)')
+    n_calls = int(n_calls)
+    if n_calls < 1 or out.dim() < 1 or out.shape[0] != n_calls:
+        raise _lib.MPBError(f'torch_cpu_normal_: out must have shape (n_calls = {n_calls}, *block), got {tuple(out.shape)}')
+    n = out.numel() // n_calls
+    if n < 16:
+        raise _lib.MPBError(f'torch_cpu_normal_: a block of {n} < 16 elements takes torch\'s scalar normal_ path, not served')
+    if n >= 2 ** 31 - 16:
+        raise _lib.MPBError('torch_cpu_normal_: block too large')
+    return n
+
+
+class TorchCpuGeneratorOnDevice:
+    """A torch CPU generator's mt19937 state held on a device across several draws: the constructor copies it in (2.5 KB),
+    every `normal_` draws on the device and keeps the state there, `store` writes it back to the generator.  `stage` queues
+    the copy back behind the draws made so far, so that `store` waits for them only, not for work queued after `stage`.
+    Between the constructor and `store` the generator must not be used by anything else."""
+
+    def __init__(self, device, generator=None):
+        from . import mt19937 as MT
+        self.gen = generator if generator is not None else torch.default_generator
+        if self.gen.device.type != 'cpu':
+            raise _lib.MPBError('TorchCpuGeneratorOnDevice: the generator must be a CPU generator')
+        self.device = _mt_device(device)
+        self.host = MT.MTState.from_bytes(self.gen.get_state())
+        self.pos = self.host.pos
+        self.words = 0
+        self.state = torch.from_numpy(self.host.arr.view(np.int32).copy()).to(self.device)
+        self._staged = None              # (pinned host copy of the state, its event, pos, words) queued by stage()
+
+    def normal_(self, out, n_calls, events=None):
+        """out (n_calls, *block) on this object's device: n_calls successive normal_() draws of the block.
+        events: four torch.cuda.Event(enable_timing=True) recorded around the three launches (a measurement aid: the draw is
+        then made through the test-aid library's timed entry)."""
+        from . import mt19937 as MT
+        n = _mt_check_out(out, n_calls)
+        if out.device != self.device:
+            raise _lib.MPBError(f'torch_cpu_normal_: out lives on {out.device}, the state on {self.device}')
+        tb = _mt_tables(n, n_calls, self.device)
+        with torch.cuda.device(self.device):
+            work = _mt_work(tb, self.device)
+            args = (_ptr(out), n, int(n_calls), _ptr(self.state), self.pos, MT.final_index(self.pos, tb.total), _ptr(self.state),
+                    _ptr(tb.idx), _ptr(tb.cnt), tb.stride, _ptr(tb.segs), tb.n_segs, _ptr(work))
+            if events is None:
+                _lib.check(_lib.lib().mpb_mt19937_normals(*args, _stream()), 'mpb_mt19937_normals')
+            else:
+                for e in events:
+                    e.record()                   # (torch creates an event's handle at its first record)
+                ev = (ctypes.c_void_p * 4)(*[e.cuda_event for e in events])
+                _lib.debug_check(_lib.debug_lib().mpb_debug_mt19937_normals_timed(*args, ctypes.cast(ev, ctypes.c_void_p), _stream()),
+                                 'mpb_debug_mt19937_normals_timed')
+        self.pos = MT.pos_after(self.pos, tb.total)
+        self.words += tb.total
+        self._staged = None
+        return out
+
+    def stage(self):
+        """Queue the copy of the state after the draws so far to pinned host memory (no wait)."""
+        if self.words:
+            host = torch.empty(self.state.shape, dtype=self.state.dtype).pin_memory()
+            with torch.cuda.device(self.device):
+                host.copy_(self.state, non_blocking=True)
+                ev = torch.cuda.Event()
+                ev.record()
+            self._staged = (host, ev, self.pos, self.words)
+
+    def store(self):
+        """Write the state after every draw so far back to the generator (waits for the draws, or for the staged copy)."""
+        from . import mt19937 as MT
+        if not self.words:
+            return
+        if self._staged is None:
+            self.stage()
+        host, ev, pos, words = self._staged
+        ev.synchronize()
+        st = self.host.copy()
+        st.arr, st.next, st.left = host.numpy().view(np.uint32).copy(), pos, MT.N + 1 - pos
+        self.gen.set_state(st.to_tensor())
+        self.host, self.words, self._staged = st, 0, None
+
+
+def torch_cpu_normal_(out, n_calls, generator=None):
+    """Fill the GPU tensor out (n_calls, *block) with what n_calls successive `torch.empty(block).normal_(generator=g)` on the
+    CPU produce, and advance g (default: the global CPU generator) as those draws do.  The uniforms and the generator state
+    are torch's bit for bit; the normals agree within a few ULP (torch's vectorised log / sincos are not restated).
+    fp32, contiguous, blocks of >= 16 elements only (torch takes other paths for the rest): anything else raises MPBError."""
+    _mt_check_out(out, n_calls)
+    g = TorchCpuGeneratorOnDevice(out.device, generator)
+    g.normal_(out, n_calls)
+    g.store()
+    return out
+
+
+def debug_mt19937_uniforms(n, n_calls, device, generator=None):
+    """Test aid: n_calls successive `torch.empty(n).uniform_()` draws on the device (the generator of torch_cpu_normal_ with
+    uniform_()'s n words a call); returns (out (n_calls, n), the state after them as MTState).  The generator is not advanced."""
+    from . import mt19937 as MT
+    gen = generator if generator is not None else torch.default_generator
+    host = MT.MTState.from_bytes(gen.get_state())
+    out = torch.empty(n_calls, n, device=device, dtype=torch.float32)
+    tb = _mt_tables(n, n_calls, device, uniform=True)
+    st_in = torch.from_numpy(host.arr.view(np.int32).copy()).to(device)
+    st_out = torch.empty_like(st_in)
+    with torch.cuda.device(out.device):
+        _lib.debug_check(_lib.debug_lib().mpb_debug_mt19937_uniforms(
+            _ptr(out), int(n), int(n_calls), _ptr(st_in), host.pos, MT.final_index(host.pos, tb.total), _ptr(st_out),
+            _ptr(tb.idx), _ptr(tb.cnt), tb.stride, _ptr(tb.segs), tb.n_segs, _ptr(_mt_work(tb, out.device)), _stream()),
+            'mpb_debug_mt19937_uniforms')
+    return out, MT.state_after(host, tb.total, st_out.cpu().numpy().view(np.uint32))

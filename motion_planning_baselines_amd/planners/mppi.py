@@ -24,7 +24,8 @@ class MPPI(MPPlanner):
     """Drop-in for mp_baselines.planners.mppi.MPPI (ctor kwargs mppi.py:8-21).
 
     ``optimize(state=..., goal_state=..., cost=...)`` as in the reference (mppi.py:136-162).  Extra kwargs:
-    noise 'philox' | 'torch_cpu' | 'torch' and seed, as for STOMP.
+    noise 'philox' | 'torch_cpu' | 'torch' | 'mt19937' and seed, as for STOMP ('mt19937': the 'torch_cpu' draws, c blocks of
+    (S, T) per iteration, made on the device by ops.torch_cpu_normal_; the CPU generator is advanced as by those draws).
     """
 
     def __init__(self, system, num_ctrl_samples, rollout_steps, opt_iters, control_std=None, initial_mean=None,
@@ -80,6 +81,9 @@ class MPPI(MPPlanner):
         if self.noise == 'philox':
             return None
         S, T, c = self.num_ctrl_samples, self.rollout_steps, self.control_dim
+        if self.noise == 'mt19937':
+            out = torch.empty(n_iters * c, S, T, device=self.device, dtype=torch.float32)
+            return ops.torch_cpu_normal_(out, n_iters * c).reshape(n_iters, 1, c, S, T)
         dev = 'cpu' if self.noise == 'torch_cpu' else self.device
         # the reference draws one (S,T) block per control dimension per iteration (gaussian.py:291-297)
         blocks = [torch.stack([torch.empty(S, T, device=dev).normal_() for _ in range(c)]) for _ in range(n_iters)]

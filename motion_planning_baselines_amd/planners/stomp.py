@@ -53,7 +53,12 @@ class STOMP(OptimizationPlanner):
       noise: 'philox' (default) -- standard normals generated inside the kernel (counter-based, result
              independent of sharding); 'torch_cpu' -- drawn per iteration with the CPU generator in the
              reference's (S,d,P,H) order, so that `torch.manual_seed(s)` reproduces a CPU reference run
-             bit for bit in the noise; 'torch' -- same draw on the planner's device.
+             bit for bit in the noise; 'torch' -- same draw on the planner's device; 'mt19937' -- the 'torch_cpu' draws (same
+             order, same generator, same sharding: a rank draws from its own global CPU generator) made ON THE DEVICE by
+             ops.torch_cpu_normal_ (torch's Mersenne Twister by jump ahead, csrc/mpb_mt19937.hip): the uniforms and the
+             generator state are the CPU's bit for bit, the normals agree within a few ULP.  The generator's state is copied to
+             the device once per optimize() and written back before it returns, so later host draws continue as after the CPU
+             draws.
       seed / particle_offset: Philox key and global index of this shard's first particle.
       persistent: run a collision-only cost's loop as ONE persistent launch (mpb_stomp_run) where the shape allows it
              (default); False keeps the two-kernels-per-iteration path (mpb_stomp_step).
@@ -85,7 +90,7 @@ class STOMP(OptimizationPlanner):
                          multi_goal_states=multi_goal_states, sigma_start_init=sigma_start_init,
                          sigma_goal_init=sigma_goal_init, sigma_gp_init=sigma_gp_init, pos_only=pos_only,
                          tensor_args=tensor_args)
-        assert noise in ('philox', 'torch', 'torch_cpu')
+        assert noise in ('philox', 'torch', 'torch_cpu', 'mt19937')
         assert check in ('deferred', 'sync')
         self.check = check
         self._status = None              # host-visible status block of the persistent launches (allocated on first use)
@@ -93,7 +98,7 @@ class STOMP(OptimizationPlanner):
         self._last_tag = 0               # tag of the persistent launch the current optimize() call has made (0: none)
         self._spare_copy = None          # the next call's return buffer (allocated while the previous launch runs)
         self._eps_ring = None            # noise='torch_cpu': pinned host / device double buffer of one iteration's normals
-        self._eps_dev = None             # noise='torch': device chunk buffer of normals
+        self._eps_dev = None             # noise='torch' / 'mt19937': device chunk buffer of normals
         self._traj_out = None
         self.lr = step_size
         self.sigma_spectral = sigma_spectral
@@ -158,6 +163,8 @@ class STOMP(OptimizationPlanner):
         if self.noise == 'philox':
             return None
         S, d, P, H = self.num_samples, self.d_state_opt, self.num_particles, self.n_support_points
+        if self.noise == 'mt19937':
+            return ops.torch_cpu_normal_(torch.empty(n_iters, S, d, P, H, device=self.device, dtype=torch.float32), n_iters)
         dev = 'cpu' if self.noise == 'torch_cpu' else self.device
         blocks = [torch.empty(S, d, P, H, device=dev, dtype=torch.float32).normal_() for _ in range(n_iters)]
         return torch.stack(blocks).to(self.device).contiguous()
@@ -320,7 +327,9 @@ class STOMP(OptimizationPlanner):
         drawn while the GPU copies and consumes block k - 1 (async H2D on the launch stream, one n_iters = 1 launch per
         iteration); an iteration costs max(host draw, H2D + kernel) = the host draw.  (Until round 5: all K blocks drawn,
         stacked, copied from pageable memory, then one launch -- draw + stack + copy + kernel in series.)
-        torch: the draw is a device kernel per iteration into a chunk buffer, one launch per chunk of up to 16 iterations."""
+        torch: the draw is a device kernel per iteration into a chunk buffer, one launch per chunk of up to 16 iterations.
+        mt19937: the torch_cpu draws made on the device, a chunk of up to 16 iterations per draw (ops.TorchCpuGeneratorOnDevice:
+        the generator's state stays on the device between chunks and is written back at the end), one launch per chunk."""
         run = lambda eps, n, it0, cp: ops.stomp_run(
             self._particle_means, eps, self.state_particles, self.costs, self._weights_buf, self.scale_tril, self.Sigma, geom,
             self.num_samples, self.n_dof, cc.k_sigma, weight, self.lr, self.temperature, self._run_ws if self.persistent else None,
@@ -330,18 +339,28 @@ class STOMP(OptimizationPlanner):
             return run(None, opt_iters, self._iter, copy)
         S, d, P, H = self.num_samples, self.d_state_opt, self.num_particles, self.n_support_points
         tag = 0
-        if self.noise == 'torch':
+        if self.noise in ('torch', 'mt19937'):
             chunk = min(opt_iters, 16)
             buf = self._eps_dev
             if buf is None or buf.shape != (chunk, S, d, P, H) or buf.device != self.device:
                 buf = self._eps_dev = torch.empty(chunk, S, d, P, H, device=self.device, dtype=torch.float32)
+            gen = ops.TorchCpuGeneratorOnDevice(self.device) if self.noise == 'mt19937' else None
             done = 0
-            while done < opt_iters:
-                n = min(chunk, opt_iters - done)
-                for i in range(n):
-                    buf[i].normal_()                    # one generator call per iteration, like the reference
-                tag = run(buf[:n], n, self._iter + done, copy if done + n == opt_iters else None)
-                done += n
+            try:
+                while done < opt_iters:
+                    n = min(chunk, opt_iters - done)
+                    if gen is not None:
+                        gen.normal_(buf[:n], n)         # the CPU generator's n calls, on the device
+                        if done + n == opt_iters:
+                            gen.stage()                 # the final state's copy back is queued before the last launch
+                    else:
+                        for i in range(n):
+                            buf[i].normal_()            # one generator call per iteration, like the reference
+                    tag = run(buf[:n], n, self._iter + done, copy if done + n == opt_iters else None)
+                    done += n
+            finally:
+                if gen is not None:
+                    gen.store()                         # (waits for the draws, not for the last launch; also when a launch raised)
             return tag
         ring = self._eps_ring
         if ring is None or ring['host'][0].shape != (1, S, d, P, H) or ring['dev'][0].device != self.device:
