@@ -15,13 +15,20 @@ ranks; `ms_per_step` / `value` are the MEDIAN block, min / max are reported next
 128 start/goal problems (weak scaling, no data-path collective), the final means are all-gathered over RCCL inside
 the timed region.
 
-Further entries of the same JSON line (the other BASELINE configs):
+A plain run does only what that figure needs: set-up, pre-heat, the W warm-up steps, the R timed blocks, --dump-outputs if
+given, and the line -- `metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step`, the blocks' spread, the
+configuration and the roofline priced from the timed launches' own device-clock span and the committed counter summaries.
+
+--full adds everything that takes runs of its own: the `cold` first block, the kernel timed with HIP events, its fixed part
+and later iterations, the two-kernel path, `k1`, `seeded`, `generic_model`, `crowded`, the CPU baselines and `parity`
+against the oracle (--no-cpu-baseline drops those two), and the further entries below (--no-other-configs drops them;
+--main-only: no side measurement at all, for profiling passes):
   c5        BASELINE configs[4]'s per-GPU load: 4096 particles (131072 rollouts) per rank, same protocol, at every N
             -- at N = 8 that is the 32768-problem job; compare c5.value across N for its weak scaling;
   c2        pointmass_dense_2d CHOMP B=1024 (N = 1 only);
   c4        panda_spheres GPMP2 B=2048, H=128, D=7 (N = 1 only; structured-FLOP roofline against the fp64 matrix peak,
             CPU baseline on a small batch and extrapolated, as SURVEY 8d prescribes).
-One JSON line is printed by rank 0.
+One JSON line is printed by rank 0; the noise of the timed blocks is the same with or without --full.
 
 --dump-outputs DIR: after the timed blocks, rank 0 writes what the main line's LAST timed block computed -- the (P,H,d)
 trajectory optimize() returned, the samples / costs / weights of its last step and, with N > 1, the gathered means -- as
@@ -557,10 +564,12 @@ def bench_crowded(dev, rank, P, S, steps):
     return out
 
 
-def run_stomp(planner, clock, dist, world, steps, warmup, repeats, preheat, cold=False, keep=None):
+def run_stomp(planner, clock, dist, world, steps, warmup, repeats, preheat, cold=False, keep=None, events=True):
     """W untimed steps, then R blocks of EXACTLY `steps` steps (one C-ABI call = 2K launches) + the final gather.
     `keep` (a dict, or None): receives what the LAST timed block computed -- the trajectory optimize() returned, the samples,
-    costs and weights of its last step and, with N > 1, the gathered means -- as host copies taken after the timed region."""
+    costs and weights of its last step and, with N > 1, the gathered means -- as host copies taken after the timed region.
+    `cold` = None: the cold block is not run, but the noise counter advances past it as if it had been (single process), so
+    that the timed blocks draw the same normals either way.  `events`: R more launches timed with HIP events after the blocks."""
     # the final gather's destination: one flat (world * P, H, d) tensor (all_gather_into_tensor: one RCCL kernel, no
     # per-rank copy-out kernels)
     gathered = (torch.empty((world * planner._particle_means.shape[0],) + tuple(planner._particle_means.shape[1:]),
@@ -579,6 +588,8 @@ def run_stomp(planner, clock, dist, world, steps, warmup, repeats, preheat, cold
         clock.barrier(spin=True)
         run_stomp.cold_block_s = time.perf_counter() - t0
         planner._particle_means.copy_(means_init)
+    elif cold is None and dist is None:
+        planner._iter += warmup + steps
     if preheat:
         # device pre-heat (untimed set-up, not part of W or K): `preheat` untimed blocks of the very shape that is timed below
         # (K steps from the initial means, synchronize).  The chip is power-managed: right after ONE long launch (round 2's
@@ -629,7 +640,7 @@ def run_stomp(planner, clock, dist, world, steps, warmup, repeats, preheat, cold
     # reports; events recorded around the launch on the stream add the marker packets' own ~20 us).  Kept out of the timed
     # blocks above.
     ev_ms = []
-    for _ in range(repeats):
+    for _ in range(repeats if events else 0):
         reset()
         clock.barrier()
         ms = planner.optimize_timed(steps)
@@ -641,7 +652,7 @@ def run_stomp(planner, clock, dist, world, steps, warmup, repeats, preheat, cold
             clock.barrier(spin=True)
             ms = e0.elapsed_time(e1)
         ev_ms.append(ms)
-    run_stomp.launch_ms = sorted(ev_ms)
+    run_stomp.launch_ms = sorted(ev_ms) or None
     return blocks
 
 
@@ -1026,10 +1037,13 @@ def main():
     ap.add_argument('--particles', type=int, default=128)
     ap.add_argument('--samples', type=int, default=32)
     ap.add_argument('--pos-only', action='store_true')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-other-configs', action='store_true', help='main line only (profiling runs)')
-    ap.add_argument('--main-only', action='store_true', help='(rocprofv3 stats pass) no side measurements either: the only launches of the '
-                    'persistent kernel are the pre-heat, warm-up and timed K-step launches, so the trace\'s average is the timed launch')
+    ap.add_argument('--full', action='store_true', help='also every side measurement, check, CPU baseline and further configuration '
+                    '(the plain run: the headline line alone)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='(with --full) no CPU baselines, no parity')
+    ap.add_argument('--no-other-configs', action='store_true', help='(with --full) main line only (profiling runs)')
+    ap.add_argument('--main-only', action='store_true', help='(with --full; rocprofv3 stats pass) no side measurements either: the only '
+                    'launches of the persistent kernel are the pre-heat, warm-up, timed and event-timed K-step launches, so the '
+                    'trace\'s average is the timed launch')
     ap.add_argument('--dump-outputs', metavar='DIR', default=None,
                     help='write what the main line\'s last timed step computed as DIR/<name>.npy (float32; rank 0)')
     args = ap.parse_args()
@@ -1067,13 +1081,15 @@ def main():
     H, d, D = prm['n_support_points'], wl['means0'].shape[-1], 7
     preheat = args.preheat if args.preheat >= 0 else max(8, min(60, 1200 // max(args.steps, 1)))
     kept = {} if args.dump_outputs else None
-    blocks = run_stomp(planner, clock, dist, world, args.steps, args.warmup, args.repeats, preheat=preheat, cold=not args.main_only,
-                       keep=kept)
+    side = args.full and not args.main_only          # the side measurements of --full
+    blocks = run_stomp(planner, clock, dist, world, args.steps, args.warmup, args.repeats, preheat=preheat,
+                       cold=side if args.full else None, keep=kept, events=args.full)
     if kept is not None and rank == 0:
         dump_outputs(args.dump_outputs, kept)
     cold_block_s = run_stomp.cold_block_s
     elapsed, sp = spread(blocks, args.steps)
-    timed_launch_ms = run_stomp.launch_ms[len(run_stomp.launch_ms) // 2]    # median over the R event-timed launches
+    ev = run_stomp.launch_ms
+    timed_launch_ms = ev[len(ev) // 2] if ev else None                      # median over the R event-timed launches (--full)
     span = run_stomp.device_span_ms
     span_ms = span[len(span) // 2] if span else None                        # median over the R TIMED launches themselves
 
@@ -1101,10 +1117,10 @@ def main():
     # the launch of the timed region: K iterations from the initial means.  (Iterations get cheaper as the trajectories
     # leave the obstacles -- fewer broad-phase candidates: the K iterations after these run ~10 % faster; `later_ms`.)
     # one iteration of the timed launch, its fixed part included: the device-clock span of the timed launches themselves
-    # where the kernel reports it (persistent path), else the event figure
-    k_ms = (span_ms if span_ms else timed_launch_ms) / args.steps
+    # where the kernel reports it (persistent path), else the event figure (--full), else the timed blocks' own wall time
+    k_ms = (span_ms or timed_launch_ms or 1e3 * elapsed) / args.steps
     later_ms = launch_fixed_ms = two_ms = None
-    if not args.main_only:
+    if side:
         t2a, t2b = launch_ms(n_prof), launch_ms(2 * n_prof)
         later_ms = (t2b - t2a) / n_prof                        # one of iterations n_prof .. 2 n_prof
         l1, l2 = launch_ms(1), launch_ms(2)
@@ -1196,19 +1212,22 @@ def main():
                  'kernel_ms': k_ms, 'kernel_ms_note': 'duration of the K-iteration persistent launches OF THE TIMED BLOCKS on the device\'s '
                  'real-time counter (first unit started -> last workgroup left; the kernel stamps its pinned status block, no cost), '
                  'median over the R blocks, divided by K; agrees with rocprofv3 --kernel-trace (profiles/)',
-                 'kernel_ms_hip_events': timed_launch_ms / args.steps,
+                 'kernel_ms_hip_events': timed_launch_ms / args.steps if timed_launch_ms else None,
                  'kernel_ms_hip_events_note': 'HIP event pair recorded on the dispatch (hipExtLaunchKernelGGL, launch stream) of the same '
                  'launch repeated R times right after the timed blocks; those launches run ~10 % slower than the timed ones (rocprofv3 '
                  'shows the kernels themselves longer: the profiled dispatch and the blocking wait behind it change the clock state)',
                  'launch_fixed_ms': launch_fixed_ms,
                  'kernel_ms_iterations_%d_to_%d' % (n_prof, 2 * n_prof): later_ms,
                  'two_kernel_path_ms_per_step': two_ms, 'two_kernel_path_iters_per_sec': (1e3 / two_ms) if two_ms else None})
+    if not span_ms and not timed_launch_ms:
+        roof['kernel_ms_note'] = ('the timed blocks\' wall time per step: this path reports no device-clock span (--full adds launches '
+                                  'timed with HIP events)')
 
     # ---- `k1`: the reference examples' calling pattern -- ONE iteration per optimize() call, each call waited for
     # (check='sync', the planner's default; examples/pointmass_grid_circles_2d_STOMP.py:104-106: `for i in range(opt_iters):
     # trajs = planner.optimize(opt_iters=1)`): every iteration pays the launch, the constants into LDS and the host side of a call
     k1 = None
-    if not args.main_only and world == 1:
+    if side and world == 1:
         n_k1 = 150
         planner.check = 'sync'
         for _ in range(20):
@@ -1235,19 +1254,19 @@ def main():
     # ---- parity of the headline workload against the oracle (GPU side here, untimed; the oracle side rides on the CPU baseline)
     par_gpu = eps_parity = par_philox_gpu = None
     consts = (planner.scale_tril.cpu(), planner.Sigma.cpu())
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not args.main_only:
+    if rank == 0 and world == 1 and not args.no_cpu_baseline and side:
         eps_parity = torch.randn(2, S, d, P, H, generator=torch.Generator().manual_seed(1234))
         par_gpu = stomp_parity_gpu(wl, planner, cost, geom, eps_parity)
         par_philox_gpu = stomp_parity_philox_gpu(wl, planner, cost, geom, n_it=max(2, min(args.steps, 20)))
     seeded = generic = crowded = None
-    if rank == 0 and world == 1 and not args.main_only and not args.no_other_configs:
+    if rank == 0 and world == 1 and side and not args.no_other_configs:
         seeded = bench_seeded(wl, cost, dev, rank, P, args.steps)
         generic = bench_generic_model(wl, dev, rank, P, S, args.steps)
         crowded = bench_crowded(dev, rank, P, S, args.steps)
 
     # ---- BASELINE configs[4]'s per-GPU load with the same protocol (every N)
     c5 = None
-    if not args.no_other_configs and not args.main_only:
+    if side and not args.no_other_configs:
         del planner
         torch.cuda.empty_cache()
         P5 = 4096
@@ -1303,7 +1322,8 @@ def main():
                                 'chip is power-managed, the timed blocks measure the steady state of the protocol itself (DESIGN 6.2)'},
             'scaling_note': 'weak scaling, 128 particles per GPU on this line at every N; its N-GPU ratio is capped at ~0.92 by the one '
                             'fixed-cost collective (the final all-gather, ~26 us) inside a ~0.36 ms block at --steps 20.  The entry that '
-                            'answers ">= 6x at 8 GPUs" is `c5` (BASELINE configs[4]: 4096 particles per GPU, 25 ms blocks): compare c5.value across N',
+                            'answers ">= 6x at 8 GPUs" is `c5` (--full; BASELINE configs[4]: 4096 particles per GPU, 25 ms blocks): compare '
+                            'c5.value across N',
         }
         if dist is not None:
             line['dist'] = {'backend': dist.get_backend(), 'world': world, 'rccl_ranks_seen': dist.get_world_size(), 'forced_at_world_1': bool(forced and world == 1),
@@ -1325,7 +1345,7 @@ def main():
             line['crowded'] = crowded
         if c5 is not None:
             line['c5'] = c5
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             med, cores, n_it, kept = cpu_baseline_stomp(wl, consts[0], consts[1], eps_parity if eps_parity is not None else [])
             if par_gpu is not None:
                 line['parity'] = stomp_parity(wl, consts[0], consts[1], eps_parity, par_gpu, kept)
@@ -1336,7 +1356,7 @@ def main():
                 'sample': 'oracle/planners_ref.py stomp_iteration (PyTorch-CPU restatement of stomp.py:157-160 + build-defined '
                           'FK/SDF) on the full workload (P=%d x S=%d), median of %d iterations = %.3f s, %d intra-op threads'
                           % (P, S, n_it, med, cores)}
-        if world == 1 and not args.no_other_configs and not args.main_only:
+        if world == 1 and side and not args.no_other_configs:
             line['c2'] = bench_c2(dev, 500, with_cpu=not args.no_cpu_baseline)
             line['c4'] = bench_c4(dev, 10, with_cpu=not args.no_cpu_baseline)
             line['h128'] = bench_h128(dev, 50, with_cpu=not args.no_cpu_baseline)

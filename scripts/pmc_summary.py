@@ -35,7 +35,7 @@ for f in glob.glob(os.path.join(src, 'stats', '**', '*_results.db'), recursive=T
     for name, dur in db.execute('select name, duration from kernels'):
         per[name].append(dur)
     # every dispatch of the persistent STOMP kernel in launch order: the stats pass of profile_round.sh runs
-    # `bench.py --steps K --warmup 5 --main-only`, i.e. pre-heat blocks (untimed), ONE warm-up launch of 5 steps, the R timed
+    # `bench.py --steps K --warmup 5 --full --main-only`, i.e. pre-heat blocks (untimed), ONE warm-up launch of 5 steps, the R timed
     # K-step launches and the R launches with a HIP event pair on the dispatch
     try:
         seq = [(n, d) for n, d in db.execute('select name, duration from kernels order by start')]
@@ -45,7 +45,7 @@ for f in glob.glob(os.path.join(src, 'stats', '**', '*_results.db'), recursive=T
     if fused:
         with open(os.path.join(prof, f'{tag}_fused_dispatches.txt'), 'w') as fh:
             fh.write('# rocprofv3 --kernel-trace: duration (us) of every dispatch of the persistent STOMP kernel, in launch order, of\n'
-                     '# `bench.py --steps K --warmup 5 --main-only` (scripts/profile_round.sh): pre-heat blocks, one 5-step warm-up launch\n'
+                     '# `bench.py --steps K --warmup 5 --full --main-only` (scripts/profile_round.sh): pre-heat blocks, one 5-step warm-up launch\n'
                      '# (the short one), the R = 9 TIMED K-step launches, then the R = 9 launches with an event pair on the dispatch.\n')
             fh.write(' '.join('%.1f' % (d / 1e3) for d in fused) + '\n')
             short = [i for i, d in enumerate(fused) if d < 0.5 * sorted(fused)[len(fused) // 2]]

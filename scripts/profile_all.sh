@@ -1,7 +1,7 @@
 #!/bin/bash
 # Everything kept under profiles/ for one round, in one go (run on the GPU box from the repo root; ~6 minutes):
 #     bash scripts/profile_all.sh r03
-#   * bench.py (the driver's command)                         -> profiles/<tag>_bench.json
+#   * bench.py --full (every entry of the line)               -> profiles/<tag>_bench.json
 #   * rocprofv3 stats + PMC of the headline (profile_round.sh) -> <tag>_kernel_stats_bench.csv, <tag>_pmc_per_wave.md, <tag>_pmc_stomp.json
 #   * GPMP2 C4 (profile_gpmp2.sh), CHOMP C2, MPPI NP=1024      -> <tag>_gpmp2_*, <tag>_chomp_*, <tag>_mppi_*
 #   * c5 (<14,1,2> at P = 4096) and H = 128 PMC passes        -> <tag>_pmc_stomp_c5.json, <tag>_pmc_stomp_h128.json
@@ -34,11 +34,11 @@ python3 scripts/bench_large_b.py > profiles/${TAG}_large_b_sweep.txt 2> gpurun_o
 echo "large-B sweep done"
 ( python3 scripts/bench_hx.py; python3 scripts/bench_grad.py ) > profiles/${TAG}_other_shapes.txt 2> gpurun_out/${TAG}_other.err
 # the bench line LAST: it reads the instruction counts of the PMC summaries written above (profiles/<tag>_pmc_*.json)
-python3 bench.py --steps 20 --warmup 5 > gpurun_out/${TAG}_bench.json 2> gpurun_out/${TAG}_bench.err
-cp gpurun_out/${TAG}_bench.json profiles/${TAG}_bench.json
+python3 bench.py --full --steps 20 --warmup 5 > $TMPDIR/${TAG}_bench.json
+cp $TMPDIR/${TAG}_bench.json profiles/${TAG}_bench.json
 echo "bench done"
 # the two-rank rehearsal on this box's one GPU (gloo: ranks share the device; the 8-GPU node runs the same command on RCCL)
-MPB_DIST_BACKEND=gloo python3 bench.py --gpus 2 --steps 20 --warmup 5 > profiles/${TAG}_bench_2ranks_one_gpu_gloo.json 2> gpurun_out/${TAG}_bench2.err || true
+MPB_DIST_BACKEND=gloo python3 bench.py --full --gpus 2 --steps 20 --warmup 5 > profiles/${TAG}_bench_2ranks_one_gpu_gloo.json || true
 echo "two-rank rehearsal done"
 # round 6: refuse to finish on stale counters -- every profiles/*_pmc_*.json that bench.py would read (the newest per kind) must carry the
 # fingerprint of the kernel sources of THIS tree (scripts/pmc_summary.py stamps it; a file this run did not re-take, or one taken

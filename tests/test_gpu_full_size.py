@@ -345,7 +345,7 @@ def test_bench_line_contract(gpu_device):
     import json, os, subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     out = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '1', '--steps', '20', '--warmup', '3',
-                          '--no-cpu-baseline'], check=True, capture_output=True, text=True, timeout=600, cwd=root).stdout
+                          '--full', '--no-cpu-baseline'], check=True, capture_output=True, text=True, timeout=600, cwd=root).stdout
     lines = [l for l in out.splitlines() if l.strip().startswith('{')]
     assert len(lines) == 1
     j = json.loads(lines[0])
@@ -383,6 +383,39 @@ def test_bench_line_contract(gpu_device):
     # timings are reported, not asserted against a bar: a rare ~70 ms device stall on this pool would fail it
     assert r['kernel_ms'] > 0 and r['two_kernel_path_iters_per_sec'] > 0 and j['value'] > 0
     assert r['kernel_ms'] <= 1.25 * j['ms_per_step']        # the kernel's iteration cannot be slower than the step it is most of
+
+
+def test_bench_plain_line_is_the_headline_alone(gpu_device, tmp_path):
+    """bench.py without --full prints the headline line alone -- no cold block, event-timed launches, k1, parity, CPU baseline
+    or further configuration -- and its timed blocks draw the same noise as those of a --full run: the outputs of the last
+    timed block dumped by both runs are the same bits."""
+    import json, os, subprocess, sys
+    import numpy as np
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+    def run(name, *extra):
+        out_dir = str(tmp_path / name)
+        out = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '1', '--steps', '20', '--warmup', '3',
+                              '--dump-outputs', out_dir] + list(extra), check=True, capture_output=True, text=True, timeout=600,
+                             cwd=root).stdout
+        lines = [l for l in out.splitlines() if l.strip().startswith('{')]
+        assert len(lines) == 1
+        return json.loads(lines[0]), out_dir
+    j, plain = run('plain')
+    assert j['metric'] == 'stomp_trajectory_update_iters_per_sec' and j['unit'] == 'iters/s' and j['dtype'] == 'f32'
+    assert j['higher_is_better'] is True and j['steps'] == 20 and j['warmup'] == 3 and j['repeats']['n'] == 9
+    assert abs(j['value'] * j['ms_per_step'] * 1e-3 - 1.0) < 1e-6
+    for k in ('cold', 'k1', 'parity', 'cpu_baseline', 'seeded', 'generic_model', 'crowded', 'c5', 'c2', 'c4', 'h128', 'mppi'):
+        assert k not in j, k
+    r = j['roofline']
+    assert 0 < r['kernel_ms'] <= 1.25 * j['ms_per_step'] and abs(r['frac'] - r['achieved'] / r['peak']) < 1e-9
+    assert r['kernel_ms_hip_events'] is None and r['launch_fixed_ms'] is None and r['two_kernel_path_ms_per_step'] is None
+    jf, full = run('full', '--full', '--no-cpu-baseline', '--no-other-configs')
+    assert 'cold' in jf and 'k1' in jf and jf['roofline']['kernel_ms_hip_events'] > 0
+    names = sorted(os.listdir(plain))
+    assert 'samples.npy' in names and 'trajectory.npy' in names and names == sorted(os.listdir(full))
+    for n in names:
+        assert np.array_equal(np.load(os.path.join(plain, n)), np.load(os.path.join(full, n))), n
 
 
 def test_gpmp2_low_rank_form_equals_block_elimination_at_c4(gpu_device, monkeypatch):

@@ -65,7 +65,7 @@ def test_bench_bare_command_launches_its_own_ranks(gpu_device):
     env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE', 'MASTER_ADDR', 'MASTER_PORT',
                                                              'MPB_FORCE_DIST')}
     env.update(MPB_DIST_BACKEND='gloo', HSA_ENABLE_IPC_MODE_LEGACY='0')
-    p = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '20', '--warmup', '5'],
+    p = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '20', '--warmup', '5', '--full'],
                        env=env, capture_output=True, text=True, timeout=1100)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [ln for ln in p.stdout.strip().splitlines() if ln.startswith('{')]
