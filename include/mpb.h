@@ -197,7 +197,10 @@ int mpb_field_cost_points_vjp(const float *pts, const float *geom, const float *
  * mpb_stomp_step runs the fused path (sample+cost kernel, update kernel per iteration).  Everything is
  * enqueued asynchronously; only for n_iters > 256 (and never under stream capture) the call blocks on its
  * own events so that at most 256 iterations are queued ahead of the GPU.
- * mpb_stomp_update accepts Sigma == NULL (update without the covariance product, used by StochGPMP).
+ * mpb_stomp_update accepts Sigma == NULL (update without the covariance product, used by StochGPMP).  Its envelope:
+ *      S >= 1, 3 <= H <= MPB_MAX_H, 1 <= d <= 2 * MPB_MAX_DOF (the update kernels have no channel tile: StochGPMP's positions
+ *      + velocities of up to 12 joints; the sampling kernels keep d <= 16, one matrix-core tile), and its LDS within
+ *      150 KB: S + 5 H d floats (plus H*H for lr*Sigma while that fits 64 KB) -- MPB_E_UNSUPPORTED beyond it.
  * mpb_stomp_sample / mpb_stomp_update expose the two halves (the two kernels of one iteration) so that
  * a caller-supplied cost callable (any Python cost on device tensors) can sit between them; with
  * geom + costs given, mpb_stomp_sample is exactly the first kernel of mpb_stomp_step.
@@ -462,7 +465,9 @@ int mpb_stoch_gpmp_costs(const float *samples, const float *means, const float *
 /* The whole loop, n_iters iterations enqueued by one call (device Philox noise, iteration i draws with seed + i exactly
  * like n_iters single-iteration rounds of the three calls above): means (P,H,2D) in/out; means64 (P,H,2D) fp64 scratch;
  * samples (P*S,H,2D), costs (P,S), weights (P,S): outputs of the last iteration; Udiag / Uoff / scale_tril: the sampling
- * prior as for mpb_gp_prior_sample(_dense) (scale_tril NULL or H > 128: chain form). */
+ * prior as for mpb_gp_prior_sample(_dense) (scale_tril NULL or H > 128: chain form).  The whole envelope of the three stages
+ * (3 <= H <= MPB_MAX_H, 1 <= D <= MPB_MAX_DOF, mpb_stomp_update's LDS budget) is checked before anything is enqueued;
+ * mpb_stoch_gpmp_costs alone also takes H = 2. */
 int mpb_stoch_gpmp_step(float *means, double *means64, float *samples, float *costs, float *weights,
                         const double *Udiag, const double *Uoff, const double *scale_tril,
                         const float *start, const float *goal, const float *geom,

@@ -27,6 +27,9 @@ static inline bool mpb_misaligned16(const void* a, const void* b = nullptr, cons
                                     const void* e = nullptr, const void* f = nullptr) {
     return ((((uintptr_t)a) | ((uintptr_t)b) | ((uintptr_t)c) | ((uintptr_t)d) | ((uintptr_t)e) | ((uintptr_t)f)) & 15u) != 0;
 }
+// the shapes and LDS budget mpb_stomp_update takes (defined in mpb_kernels.hip): MPB_OK, or the code and message (under the name
+// `who`) of the refusal -- for callers that enqueue the update behind other stages and must refuse before the first launch
+int mpb_update_envelope(int S, int H, int d, const char* who);
 static inline int mpb_check_launch(const char* what) {
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) {

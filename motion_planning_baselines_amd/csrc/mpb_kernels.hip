@@ -964,6 +964,18 @@ static bool update_lds(int S, int H, int d, size_t& bytes, int& sigma_in_lds) {
     return bytes <= 150 * 1024;
 }
 
+// What mpb_stomp_update takes (declared in mpb_common.h: mpb_stoch_gpmp_step checks it before its first stage launches).
+// Neither update kernel tiles the channels -- the v4 kernel keeps delta as d padded LDS rows, the generic one walks the
+// H*d row -- so d goes up to the positions + velocities of MPB_MAX_DOF joints; MPB_MAX_D (16) is the sampling kernels'
+// matrix-core tile and does not apply here.  Shapes the v4 kernel serves always pass update_lds.
+int mpb_update_envelope(int S, int H, int d, const char* who) {
+    if (S < 1 || H < 3 || H > MPB_MAX_H || d < 1 || d > 2 * MPB_MAX_DOF) return fail(MPB_E_INVALID, "%s: bad shape", who);
+    size_t lds;
+    int sig_lds;
+    if (!update_lds(S, H, d, lds, sig_lds)) return fail(MPB_E_UNSUPPORTED, "%s: S + H*d too large for LDS", who);
+    return MPB_OK;
+}
+
 // kernel B launcher: vectorised path when the (H,d) tile is float4-divisible and fits 1024 threads
 static bool launch_update(float* means, const float* samples, const float* costs, float* weights, const float* Sigma,
                           int P, int S, int H, int d, float lr, float temperature, hipStream_t st) {
@@ -1078,12 +1090,12 @@ extern "C" int mpb_stomp_update(float* means, const float* samples, const float*
                                 void* stream) {
     if (P == 0) return MPB_OK;
     if (!means || !samples || !costs || !weights) return fail(MPB_E_INVALID, "%s: null pointer", __func__);
-    if (P < 0 || S < 1 || H < 3 || H > MPB_MAX_H || d < 1 || d > MPB_MAX_D) return fail(MPB_E_INVALID, "%s: bad shape", __func__);
+    if (P < 0) return fail(MPB_E_INVALID, "%s: bad shape", __func__);
+    if (const int rc = mpb_update_envelope(S, H, d, __func__)) return rc;
     if (!(temperature > 0.f)) return fail(MPB_E_INVALID, "%s: temperature must be > 0", __func__);
     if (mpb_misaligned16(means, samples, Sigma)) return fail(MPB_E_INVALID, "%s: means / samples / Sigma must be 16-byte aligned", __func__);
     if (P == 0) return MPB_OK;
-    if (!launch_update(means, samples, costs, weights, Sigma, P, S, H, d, lr, temperature, (hipStream_t)stream))
-        return fail(MPB_E_UNSUPPORTED, "%s: S + H*d too large for LDS", __func__);
+    launch_update(means, samples, costs, weights, Sigma, P, S, H, d, lr, temperature, (hipStream_t)stream);   // (within the envelope)
     return check_launch(__func__);
 }
 

@@ -160,6 +160,9 @@ extern "C" int mpb_stoch_gpmp_step(float* means, double* means64, float* samples
         return mpb_fail(MPB_E_INVALID, "mpb_stoch_gpmp_step: null pointer");
     if (P < 0 || S < 1 || H < 2 || H > MPB_MAX_H || D < 1 || D > MPB_MAX_DOF || n_iters < 0)
         return mpb_fail(MPB_E_INVALID, "mpb_stoch_gpmp_step: bad shape");
+    // the update, the last stage, takes H >= 3 and its own LDS budget: refused here, before the sampler and the cost kernel of
+    // the first iteration are enqueued (they take every other shape this call accepts)
+    if (const int rc = mpb_update_envelope(S, H, 2 * D, "mpb_stoch_gpmp_step")) return rc;
     if (P == 0) return MPB_OK;
     const size_t n = (size_t)P * H * 2 * D;
     for (int it = 0; it < n_iters; ++it) {

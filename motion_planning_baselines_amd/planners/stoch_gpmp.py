@@ -9,6 +9,7 @@ evaluated factor-wise (csrc/mpb_stoch_gpmp.hip).
 import torch
 
 from .. import ops
+from ..geometry import MAX_DOF
 from .base import OptimizationPlanner, gp_prior_factor, gp_prior_scale_tril
 
 
@@ -23,6 +24,11 @@ class StochGPMP(OptimizationPlanner):
                  sigma_gp_init=None, sigma_gp_sample=None, num_samples=2, temperature=1., collision_fields=None,
                  sigma_start=1e-5, sigma_gp=1e-2, sigma_coll=1e-5, sigma_goal_prior=1e-5, tensor_args=None,
                  noise='torch_cpu', seed=0, **kwargs):
+        # the envelope of mpb_stoch_gpmp_step / mpb_stomp_update, refused before any device state is built
+        if n_support_points is None or not 3 <= n_support_points <= 256:
+            raise ValueError(f'StochGPMP needs 3 <= n_support_points <= 256 (MPB_MAX_H), got {n_support_points}')
+        if n_dof is None or not 1 <= n_dof <= MAX_DOF:
+            raise ValueError(f'StochGPMP needs 1 <= n_dof <= {MAX_DOF} (MPB_MAX_DOF), got {n_dof}')
         super().__init__(name='StochGPMP', n_dof=n_dof, n_support_points=n_support_points,
                          num_particles_per_goal=num_particles_per_goal, opt_iters=opt_iters, dt=dt,
                          start_state=start_state, initial_particle_means=initial_particle_means,

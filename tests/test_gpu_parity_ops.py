@@ -187,7 +187,9 @@ def test_stomp_free_running_vs_golden(gpu_device, name):
     (5, 24, 8, 2),      # H*d = 16: a quarter wave of workers
     (2, 64, 64, 14),    # full waves, S = 64 (tail loop), C3's tile
     (4, 32, 64, 14),    # C3's shape
-    (3, 33, 64, 7), (2, 9, 20, 3), (2, 70, 64, 4), (2, 5, 100, 4)])   # generic kernel: odd sizes / S > 64 / H > 64
+    (3, 33, 64, 7), (2, 9, 20, 3), (2, 70, 64, 4), (2, 5, 100, 4),    # generic kernel: odd sizes / S > 64 / H > 64
+    # StochGPMP chains of 9-12 joints (d = 2D > 16): the v4 kernel at H*d = 768, the generic kernel beyond 1024
+    (2, 16, 32, 24), (2, 9, 64, 18), (3, 20, 100, 24)])
 @pytest.mark.parametrize('with_sigma', [True, False])
 def test_stomp_update_vs_oracle_shapes(gpu_device, P, S, H, d, with_sigma):
     """Kernel B alone (softmax weights + covariance-weighted update, stomp.py:199-220) against the oracle on random
