@@ -6,6 +6,7 @@
 #include <type_traits>
 
 #include "mpb_common.h"
+#include "mpb_host.h"
 #include "mpb_geom.h"
 
 #define MPB_MAX_D (2 * MPB_MAX_DOF)

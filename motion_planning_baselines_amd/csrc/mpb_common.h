@@ -1,8 +1,8 @@
-// mpb_common.h -- error plumbing and small device helpers shared by the translation units.
+// mpb_common.h -- the tuning-switch guard and the small device helpers shared by the translation units (the host side
+// of the C-ABI -- error returns, argument checks -- is mpb_host.h).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <stdio.h>
 
 #include "../../include/mpb.h"
 
@@ -14,30 +14,6 @@
                                    defined(FUSED_T_SKIP_NOISE) || defined(FUSED_T_SKIP_COST) || defined(FUSED_T_A_NOMEAN) || defined(FUSED_T_A_NOSTORE) || defined(LR_T_NOLOAD) || defined(LR_T_NOSTORE) || defined(LR_T_CAP_NOASM) || defined(LR_T_CAP_NOCHOL) || defined(LR_T_CAP_NOBACK) || defined(LR_T_CLK) || defined(FUSED_T_PRE_STATS) || defined(LR_T_GRAD_NOSTORE))
 #error "a wrong-result tuning switch (GP_T_*) was defined without -DMPB_TUNING_BUILD"
 #endif
-
-// thread-local last-error string (defined in mpb_kernels.hip)
-char* mpb_err_buf();
-static inline int mpb_fail(int code, const char* msg) {
-    snprintf(mpb_err_buf(), 512, "%s", msg);
-    return code;
-}
-// the STOMP kernels read eps / L / Sigma / the means and write the samples as 16-byte vectors: a pointer the C-ABI is handed must
-// be 16-byte aligned (a view at a 4-byte offset into an allocation would be misaligned dwordx4 accesses)
-static inline bool mpb_misaligned16(const void* a, const void* b = nullptr, const void* c = nullptr, const void* d = nullptr,
-                                    const void* e = nullptr, const void* f = nullptr) {
-    return ((((uintptr_t)a) | ((uintptr_t)b) | ((uintptr_t)c) | ((uintptr_t)d) | ((uintptr_t)e) | ((uintptr_t)f)) & 15u) != 0;
-}
-// the shapes and LDS budget mpb_stomp_update takes (defined in mpb_kernels.hip): MPB_OK, or the code and message (under the name
-// `who`) of the refusal -- for callers that enqueue the update behind other stages and must refuse before the first launch
-int mpb_update_envelope(int S, int H, int d, const char* who);
-static inline int mpb_check_launch(const char* what) {
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        snprintf(mpb_err_buf(), 512, "%s: HIP launch failed: %s", what, hipGetErrorString(e));
-        return MPB_E_HIP;
-    }
-    return MPB_OK;
-}
 
 // Wave reductions on the DPP path (data-parallel primitives: the VALU reads a neighbouring lane directly) instead of
 // ds_bpermute shuffles through the LDS crossbar: four dependent full-rate instructions bring every 16-lane row to its

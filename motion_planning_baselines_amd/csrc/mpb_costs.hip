@@ -8,6 +8,7 @@
 // so a CostComposite of several such terms costs one read of the batch.  HBM-bound: algorithmic bytes
 // 4*B*H*d read + 4*B written.  Sums are carried in fp64 (free: the kernel waits on memory).
 #include "mpb_common.h"
+#include "mpb_host.h"
 
 #define COSTS_WAVES 4
 

@@ -14,11 +14,12 @@
 #include <hip/hip_runtime.h>
 
 #include "mpb_common.h"
+#include "mpb_host.h"
 #include "mpb_stomp_noise.h"
 #include "mpb_mt19937.h"
 #include "../../include/mpb_debug.h"
 
-// (this library's own last-error buffer: mpb_common.h's helpers write through mpb_err_buf())
+// (this library's own last-error buffer: mpb_host.h's helpers write through mpb_err_buf())
 static thread_local char g_debug_err[512] = "";
 char* mpb_err_buf() { return g_debug_err; }
 extern "C" const char* mpb_debug_last_error(void) { return g_debug_err; }

@@ -25,6 +25,7 @@
 #include <string.h>
 
 #include "mpb_common.h"
+#include "mpb_host.h"
 #include "mpb_geom.h"
 #include "mpb_gpmp2.h"
 static_assert(MPB_GP_MAX_FIELDS == MPB_MAX_FIELDS, "mpb_gpmp2.h mirrors mpb_geom.h");

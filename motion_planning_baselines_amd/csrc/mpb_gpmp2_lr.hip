@@ -41,6 +41,7 @@
 #include <type_traits>
 
 #include "mpb_common.h"
+#include "mpb_host.h"
 #include "mpb_gpmp2.h"
 
 #define LR_NMAX 127                    // active rows a particle may have (with the right-hand side 128 rows: 36 tiles of 16 x 16 doubles, 72 KB of LDS)

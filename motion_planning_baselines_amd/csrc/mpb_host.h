@@ -1,0 +1,40 @@
+// mpb_host.h -- host-only helpers shared by the translation units: the last-error buffer, the error returns and the
+// argument checks of the C-ABI.  No device code, and no kernel's counters depend on it (build.PMC_SOURCES does not list it).
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdarg.h>
+#include <stdint.h>
+#include <stdio.h>
+
+#include "../../include/mpb.h"
+
+// thread-local last-error string (512 bytes) of the library the file is linked into: the product library's is defined in
+// mpb_lib.hip, the test-aid library's in mpb_debug.hip
+char* mpb_err_buf();
+// `msg` as it stands (it may come from anywhere: never read as a format)
+static inline int mpb_fail(int code, const char* msg) {
+    snprintf(mpb_err_buf(), 512, "%s", msg);
+    return code;
+}
+__attribute__((format(printf, 2, 3))) static inline int mpb_failf(int code, const char* fmt, ...) {
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(mpb_err_buf(), 512, fmt, ap);
+    va_end(ap);
+    return code;
+}
+static inline int mpb_check_launch(const char* what) {
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return mpb_failf(MPB_E_HIP, "%s: HIP launch failed: %s", what, hipGetErrorString(e));
+    return MPB_OK;
+}
+// the STOMP kernels read eps / L / Sigma / the means and write the samples as 16-byte vectors: a pointer the C-ABI is handed must
+// be 16-byte aligned (a view at a 4-byte offset into an allocation would be misaligned dwordx4 accesses)
+static inline bool mpb_misaligned16(const void* a, const void* b = nullptr, const void* c = nullptr, const void* d = nullptr,
+                                    const void* e = nullptr, const void* f = nullptr) {
+    return ((((uintptr_t)a) | ((uintptr_t)b) | ((uintptr_t)c) | ((uintptr_t)d) | ((uintptr_t)e) | ((uintptr_t)f)) & 15u) != 0;
+}
+// the shapes and LDS budget mpb_stomp_update takes (defined beside the update kernels in mpb_kernels.hip): MPB_OK, or the code and
+// message (under the name `who`) of the refusal -- for callers that enqueue the update behind other stages and must refuse before
+// the first launch
+int mpb_update_envelope(int S, int H, int d, const char* who);

@@ -1,4 +1,6 @@
-// mpb_kernels.hip -- gfx950 kernels + C-ABI (include/mpb.h) for the STOMP / CHOMP / collision-cost paths.
+// mpb_kernels.hip -- the two kernels of a STOMP iteration (sample + cost, update) with the launchers that choose their
+// instantiation (the STOMP C-ABI that calls them is mpb_stomp_api.hip), and the stand-alone collision cost / gradient
+// with its two entry points.
 //
 // Work mapping (CDNA4: 64-lane waves, 4 SIMDs per CU, 256 CUs):
 //   * one WAVE per rollout (trajectory), one LANE per waypoint -- H = 64 fills a wave exactly; longer
@@ -8,228 +10,11 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
-#include <stdio.h>
-#include <string.h>
 
 #include "mpb_common.h"
-#include <hip/hip_ext.h>
+#include "mpb_stomp_host.h"
 #include "mpb_geom.h"
 #include "mpb_stomp_noise.h"
-
-// ------------------------------------------------------------------------------------------------
-// error plumbing
-// ------------------------------------------------------------------------------------------------
-static thread_local char g_err[512] = "";
-char* mpb_err_buf() { return g_err; }
-
-static int fail(int code, const char* fmt, const char* a = "", long b = 0, long c = 0) {
-    snprintf(g_err, sizeof(g_err), fmt, a, b, c);
-    return code;
-}
-
-#define MPB_REQUIRE(cond, msg)                                                     \
-    do {                                                                           \
-        if (!(cond)) return fail(MPB_E_INVALID, "%s: requirement failed: " msg " [%ld,%ld]", __func__, 0, 0); \
-    } while (0)
-
-static int check_launch(const char* what) {
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        snprintf(g_err, sizeof(g_err), "%s: HIP launch failed: %s", what, hipGetErrorString(e));
-        return MPB_E_HIP;
-    }
-    return MPB_OK;
-}
-
-#ifdef MPB_TUNING_BUILD
-extern "C" int mpb_version(void) { return MPB_ABI_VERSION | MPB_VERSION_TUNING_BUILD; }
-#else
-extern "C" int mpb_version(void) { return MPB_ABI_VERSION; }
-#endif
-extern "C" const char* mpb_last_error(void) { return g_err; }
-
-// A buffer tagged with a compile-time robot model (header word 29) must carry exactly that model's tables: the joint
-// transforms bit for bit, and as link table the model's collision spheres selected by the keep mask (word 30), of
-// which only spheres on frame 1 may be missing.  The model kernels never read these tables -- they trust the tag.
-template <class M>
-static int model_check_as(const float* g, const char* who) {
-    const int32_t* gi = reinterpret_cast<const int32_t*>(g);
-    const uint32_t keep = (uint32_t)gi[30];
-    if (gi[2] != MPB_KIND_CHAIN || gi[3] != M::N_DOF || gi[4] != M::N_TF) return fail(MPB_E_INVALID, "%s: model tag does not match the robot", who);
-    if (memcmp(g + gi[9], M::TF, sizeof(float) * 12 * M::N_TF) != 0) return fail(MPB_E_INVALID, "%s: joint transforms differ from the tagged model", who);
-    int n = 0;
-    for (int l = 0; l < M::N_LINKS; ++l) {
-        if (!((keep >> l) & 1u)) {
-            if (M::LINK_FRAME[l] != 1) return fail(MPB_E_INVALID, "%s: only frame-1 spheres of a model may be pruned", who);
-            continue;
-        }
-        if (n >= gi[5]) return fail(MPB_E_INVALID, "%s: keep mask and link table disagree", who);
-        const float* lk = g + gi[10] + 8 * n;
-        if (reinterpret_cast<const int32_t*>(lk)[0] != M::LINK_FRAME[l] || memcmp(lk + 1, M::LINK[l], 4 * sizeof(float)) != 0)
-            return fail(MPB_E_INVALID, "%s: link table differs from the tagged model", who);
-        ++n;
-    }
-    if (n != gi[5] || (M::N_LINKS < 32 && (keep >> M::N_LINKS) != 0u)) return fail(MPB_E_INVALID, "%s: keep mask and link table disagree", who);
-    // the model kernels clamp a hinge to [0, 1] (mpb_geom.h, UNIT): margin + largest collision sphere + deepest possible
-    // penetration (sphere radius / smallest half extent of a box) must stay below 1
-    float rl_max = 0.f, deepest = 0.f;
-    for (int l = 0; l < M::N_LINKS; ++l) rl_max = M::LINK[l][3] > rl_max ? M::LINK[l][3] : rl_max;
-    for (int o = 0; o < gi[6]; ++o) deepest = g[gi[11] + 4 * o + 3] > deepest ? g[gi[11] + 4 * o + 3] : deepest;
-    for (int o = 0; o < gi[7]; ++o) {
-        const float* h = g + gi[12] + 8 * o + 4;
-        const float m = h[0] < h[1] ? (h[0] < h[2] ? h[0] : h[2]) : (h[1] < h[2] ? h[1] : h[2]);
-        deepest = m > deepest ? m : deepest;
-    }
-    if (!(g[8] + rl_max + deepest < 1.0f)) return fail(MPB_E_INVALID, "%s: a model-tagged scene must keep every hinge below 1 (margin + radii)", who);
-    return MPB_OK;
-}
-
-static int model_check(const float* g, const char* who) {
-    const int model = reinterpret_cast<const int32_t*>(g)[29];
-    if (model == 0) return MPB_OK;
-    if (model == PandaModel::ID) return model_check_as<PandaModel>(g, who);
-    return fail(MPB_E_INVALID, "%s: unknown robot model id", who);
-}
-
-static int geom_check_one(const float* g, int n_words, const char* who) {
-    if (!g || n_words < MPB_GEOM_HEADER_WORDS) return fail(MPB_E_INVALID, "%s: geometry buffer too small", who);
-    const int32_t* gi = reinterpret_cast<const int32_t*>(g);
-    if (gi[0] != MPB_GEOM_MAGIC || (gi[1] != MPB_GEOM_VERSION && gi[1] != MPB_GEOM_VERSION_LIST)) return fail(MPB_E_INVALID, "%s: bad magic/version", who);
-    const bool list = gi[1] == MPB_GEOM_VERSION_LIST;       // version 7: the grid section is a list grid (mpb_geom.h, spheres_hinge_list)
-    const int kind = gi[2], n_dof = gi[3], n_tf = gi[4], n_links = gi[5], n_sph = gi[6], n_box = gi[7];
-    if (kind != MPB_KIND_POINT && kind != MPB_KIND_CHAIN) return fail(MPB_E_INVALID, "%s: unknown robot kind", who);
-    if (n_dof < 1 || n_dof > MPB_MAX_DOF) return fail(MPB_E_INVALID, "%s: n_dof out of range", who);
-    if (kind == MPB_KIND_POINT && (n_dof < 2 || n_dof > 3 || n_links != 1)) return fail(MPB_E_INVALID, "%s: point robot must be 2-D/3-D with one sphere", who);
-    if (kind == MPB_KIND_CHAIN && n_tf != n_dof + 1) return fail(MPB_E_INVALID, "%s: chain needs n_dof+1 transforms", who);
-    if (n_links < 1 || n_sph < 0 || n_box < 0 || n_sph + n_box < 1) return fail(MPB_E_INVALID, "%s: empty link/obstacle set", who);
-    const int off_tf = gi[9], off_links = gi[10], off_sph = gi[11], off_box = gi[12], total = gi[13];
-    const int off_cull = gi[14], off_fs = gi[15], off_grid = gi[16];
-    const int gnx = gi[17], gny = gi[18], gnz = gi[19], n_cells = gi[26];
-    const int n_sph_pad = (n_sph + 3) / 4 * 4;
-    const int n_frames = n_tf > 1 ? n_tf : 1;
-    const int n_fs = (n_frames + 1 + 3) / 4 * 4;
-    if (off_tf != MPB_GEOM_HEADER_WORDS || off_links != off_tf + 12 * n_tf || off_sph != off_links + 8 * n_links ||
-        off_box != off_sph + 4 * n_sph || off_cull != off_box + 8 * n_box || off_fs != off_cull + 8 * n_sph_pad ||
-        off_grid != off_fs + n_fs || total > n_words)
-        return fail(MPB_E_INVALID, "%s: inconsistent section offsets", who);
-    const int off_cand = off_grid + (n_cells + MPB_GRID_PAD - 1) / MPB_GRID_PAD * MPB_GRID_PAD;
-    if (list ? (total < off_cand + 4 || ((total - off_cand) & 3)) : total != off_cand) return fail(MPB_E_INVALID, "%s: inconsistent section offsets", who);
-    if (list && (n_cells < 1 || n_cells > MPB_GRID_MAX_CELLS || n_sph > MPB_LIST_MAX_SPH || n_box > MPB_LIST_MAX_BOX ||
-                 4 * (total - off_cand) > MPB_LIST_MAX_CAND + 16))
-        return fail(MPB_E_INVALID, "%s: a list grid needs 1..4096 cells, <= 255 spheres, <= 127 boxes, <= 16 KB of candidates", who);
-    if ((off_links | off_sph | off_box | off_cull | off_fs | off_grid) & 3) return fail(MPB_E_INVALID, "%s: sections must be 16-byte aligned", who);
-    if (n_cells < 0 || (n_cells > 0 && (gnx < 1 || gny < 1 || gnz < 1 || gnx * gny * gnz != n_cells)))
-        return fail(MPB_E_INVALID, "%s: bad broad-phase grid dims", who);
-    if (n_cells > 0) {
-        // version 6: cells on a lattice through the origin -- lo = (K - 1/2) h per axis with integer K, and header word 31 =
-        // Kx + gnx (Ky + gny Kz): what grid_cell_rel (mpb_geom.h) turns round(x / h) into a cell with
-        long K[3];
-        for (int a = 0; a < 3; ++a) {
-            if (!(g[23 + a] > 0.f)) return fail(MPB_E_INVALID, "%s: bad grid cell size", who);
-            const double k = (double)g[20 + a] * (double)g[23 + a] + 0.5;
-            K[a] = lrint(k);
-            // (lo and 1/h are fp32: their product carries ~|K| 1.2e-7 of rounding, so the tolerance scales with |K| -- an absolute
-            // 1e-3 refused the grids build_grid makes beyond |K| ~ 16 700)
-            if (fabs(k - (double)K[a]) > 1e-3 + 4e-7 * fabs((double)K[a]) || labs(K[a]) > 100000) return fail(MPB_E_INVALID, "%s: grid origin is not on the cell lattice", who);
-        }
-        if ((long)gi[31] != K[0] + (long)gnx * (K[1] + (long)gny * K[2])) return fail(MPB_E_INVALID, "%s: grid lattice index (word 31) does not match the origin", who);
-        if (labs((long)gi[31]) + (long)n_cells >= (1L << 21)) return fail(MPB_E_INVALID, "%s: grid too far from the origin for the fp32 cell index", who);
-    }
-    if (list) {   // every cell's candidate range must lie inside the candidate bytes and name existing obstacles
-        const unsigned char* cand = reinterpret_cast<const unsigned char*>(g + off_cand);
-        const int n_cand = 4 * (total - off_cand);
-        for (int i = 0; i < n_cells; ++i) {
-            const uint32_t w = (uint32_t)gi[off_grid + i];
-            if (w & 0x80000000u) continue;                    // overflowing cell: the kernels test every obstacle
-            const int start = (int)(w & 0x7FFFu), ns = (int)((w >> 15) & 0x7Fu), nb = (int)((w >> 22) & 0x3Fu);
-            if ((w & 0x70000000u) || ns > MPB_LIST_CELL_MAX_SPH || nb > MPB_LIST_CELL_MAX_BOX || start + ns + nb > n_cand)
-                return fail(MPB_E_INVALID, "%s: list-grid cell out of range", who);
-            for (int k = 0; k < ns; ++k)
-                if ((int)cand[start + k] >= n_sph) return fail(MPB_E_INVALID, "%s: grid cell references a missing obstacle", who);
-            for (int k = 0; k < nb; ++k)
-                if ((int)cand[start + ns + k] >= n_box) return fail(MPB_E_INVALID, "%s: grid cell references a missing obstacle", who);
-        }
-    } else
-    for (int i = 0; i < n_cells; ++i) {   // every packed obstacle index must exist
-        const uint32_t w = (uint32_t)gi[off_grid + i];
-        if (w == 0xFFFFFFFEu) continue;
-        for (int k = 0; k < 4; ++k) {
-            const uint32_t idx = (w >> (8 * k)) & 0xFFu;      // n_sph = unused slot (the far dummy the kernels append)
-            if ((int)idx > n_sph) return fail(MPB_E_INVALID, "%s: grid cell references a missing obstacle", who);
-        }
-    }
-    // frame -> link ranges must be monotone and end at n_links
-    for (int j = 0; j < n_frames; ++j)
-        if (gi[off_fs + j] < 0 || gi[off_fs + j] > gi[off_fs + j + 1] || gi[off_fs + j + 1] > n_links)
-            return fail(MPB_E_INVALID, "%s: bad frame_start table", who);
-    if (gi[off_fs] != 0 || gi[off_fs + n_frames] != n_links) return fail(MPB_E_INVALID, "%s: frame_start must cover all links", who);
-    int prev = 1;
-    for (int l = 0; l < n_links; ++l) {
-        const int f = gi[off_links + 8 * l];
-        if (kind == MPB_KIND_CHAIN && (f < prev || f > n_dof + 1)) return fail(MPB_E_INVALID, "%s: link frames must be sorted in [1, n_dof+1]", who);
-        prev = f > prev ? f : prev;
-    }
-    if (!(g[28] >= 0.f)) return fail(MPB_E_INVALID, "%s: field scale must be >= 0", who);
-    return model_check(g, who);
-}
-
-
-extern "C" int mpb_geom_check(const float* g, int n_words) {
-    // a buffer may chain up to MPB_MAX_FIELDS fields: header word 27 = words from this header to the next one
-    int off = 0;
-    for (int f = 0; f < MPB_MAX_FIELDS; ++f) {
-        if (!g || n_words - off < MPB_GEOM_HEADER_WORDS) return fail(MPB_E_INVALID, "%s: geometry buffer too small", __func__);
-        const int rc = geom_check_one(g + off, n_words - off, "mpb_geom_check");
-        if (rc) return rc;
-        const int32_t* gi = reinterpret_cast<const int32_t*>(g + off);
-        if (f > 0 && (gi[2] != reinterpret_cast<const int32_t*>(g)[2] || gi[3] != reinterpret_cast<const int32_t*>(g)[3]))
-            return fail(MPB_E_INVALID, "%s: chained fields must share the robot", __func__);
-        const int next = gi[27];
-        if (next == 0) return MPB_OK;
-        if (next < gi[13] || (next & 3)) return fail(MPB_E_INVALID, "%s: bad offset to the next field", __func__);
-        off += next;
-    }
-    return fail(MPB_E_INVALID, "%s: more than MPB_MAX_FIELDS chained fields", __func__);
-}
-
-extern "C" int mpb_geom_flags(const float* g, int n_words, int* flags) {
-    if (!flags) return fail(MPB_E_INVALID, "%s: null pointer", __func__);
-    *flags = 0;
-    const int rc = mpb_geom_check(g, n_words);
-    if (rc) return rc;
-    int model = -1, max_cells = 0, n_fields = 0;
-    bool all_grids = true, all_lists = true;
-    for (int off = 0;;) {
-        const int32_t* gi = reinterpret_cast<const int32_t*>(g + off);
-        const bool is_list = gi[1] == MPB_GEOM_VERSION_LIST;                                                // (checked above: usable as it stands)
-        const bool grid_ok = !is_list && gi[26] > 0 && gi[26] <= MPB_GRID_MAX_CELLS && gi[6] <= MPB_GRID_MAX_SPH;   // grid_usable()
-        all_grids = all_grids && grid_ok;
-        all_lists = all_lists && is_list;
-        if (gi[26] > max_cells) max_cells = gi[26];
-        ++n_fields;
-        const int m = (grid_ok || is_list) ? gi[29] : 0;
-        model = (model < 0 || model == m) ? m : 0;
-        if (gi[27] == 0) break;
-        off += gi[27];
-    }
-    const int32_t* g0 = reinterpret_cast<const int32_t*>(g);
-    const bool point_small = g0[2] == MPB_KIND_POINT && g0[27] == 0 && g0[6] <= 32 && g0[7] <= 8;
-    *flags = (model > 0 ? (model & 0xFF) : 0) | (all_grids ? 0x100 : 0) | (point_small ? 0x200 : 0) |
-             (g0[2] == MPB_KIND_POINT ? 0x400 : 0) | (n_fields == 1 ? 0x1000 : 0) | (all_lists ? 0x2000 : 0) |
-             ((all_grids || all_lists) ? (max_cells & 0x1FFF) << 16 : 0);
-    return MPB_OK;
-}
-
-#define MPB_MAX_D 16       // channels of a STOMP rollout (one matrix-core tile of channels): D <= 8 with velocities, D <= 12 position only
-
-// Measurement aid (mpb_stomp_step_profile): while these are set, the STOMP kernel launches record the pair on the
-// dispatch itself (hipExtLaunchKernelGGL: kernel begin / end timestamps, the quantity rocprofv3 --kernel-trace reports).
-static thread_local hipEvent_t t_ev0 = nullptr, t_ev1 = nullptr;
-#define MPB_LAUNCH(kernel, grid, block, lds, st, ...)                                                   \
-    do {                                                                                                \
-        if (t_ev0) hipExtLaunchKernelGGL(kernel, grid, block, lds, st, t_ev0, t_ev1, 0, __VA_ARGS__);   \
-        else hipLaunchKernelGGL(kernel, grid, block, lds, st, __VA_ARGS__);                             \
-    } while (0)
 
 // ------------------------------------------------------------------------------------------------
 // STOMP kernel A, H = 64 fast path: the time-correlated noise  N = L * eps  (64x64 lower-triangular L,
@@ -953,7 +738,34 @@ __global__ __launch_bounds__(256) void collision_cost_kernel(
 }
 
 // ------------------------------------------------------------------------------------------------
-// C-ABI
+// C-ABI of the stand-alone collision cost
+// ------------------------------------------------------------------------------------------------
+extern "C" int mpb_cost_collision_eval(const float* trajs, const float* geom, float* out, float* per_waypoint,
+                                       int B, int H, int d, int h_begin, float k_sigma, float weight, void* stream) {
+    if (B == 0) return MPB_OK;   // empty batch: nothing to do (and torch hands out null pointers for it)
+    if (!trajs || !geom || !out) return mpb_failf(MPB_E_INVALID, "%s: null pointer", __func__);
+    if (B < 0 || H < 1 || d < 1 || d > 2 * MPB_MAX_DOF || h_begin < 0) return mpb_failf(MPB_E_INVALID, "%s: bad shape", __func__);   // (rows of any width up to positions + velocities of 12 joints; the first n_dof channels are read)
+    hipLaunchKernelGGL((collision_cost_kernel<false, 0>), dim3((B + 3) / 4), dim3(256), 0, (hipStream_t)stream, trajs, geom,
+                       out, per_waypoint, (float*)nullptr, B, H, d, h_begin, k_sigma, weight);
+    return mpb_check_launch(__func__);
+}
+
+extern "C" int mpb_cost_collision_grad(const float* trajs, const float* geom, int geom_flags, float* out, float* grad, int B,
+                                       int H, int d, int h_begin, float k_sigma, float weight, void* stream) {
+    if (B == 0) return MPB_OK;
+    if (!trajs || !geom || !out || !grad) return mpb_failf(MPB_E_INVALID, "%s: null pointer", __func__);
+    if (B < 0 || H < 1 || d < 1 || d > 2 * MPB_MAX_DOF || h_begin < 0) return mpb_failf(MPB_E_INVALID, "%s: bad shape", __func__);   // (rows of any width up to positions + velocities of 12 joints; the first n_dof channels are read)
+    if ((geom_flags & 0xFF) == PandaModel::ID && (geom_flags & 0x100))
+        hipLaunchKernelGGL((collision_cost_kernel<true, PandaModel::ID>), dim3((B + 3) / 4), dim3(256), 0, (hipStream_t)stream, trajs,
+                           geom, out, (float*)nullptr, grad, B, H, d, h_begin, k_sigma, weight);
+    else
+        hipLaunchKernelGGL((collision_cost_kernel<true, 0>), dim3((B + 3) / 4), dim3(256), 0, (hipStream_t)stream, trajs, geom,
+                           out, (float*)nullptr, grad, B, H, d, h_begin, k_sigma, weight);
+    return mpb_check_launch(__func__);
+}
+
+// ------------------------------------------------------------------------------------------------
+// launchers of the STOMP kernels (mpb_stomp_host.h)
 // ------------------------------------------------------------------------------------------------
 // LDS budget of the update kernel: weights + delta + 4 partial tiles (+ lr*Sigma when it fits)
 static bool update_lds(int S, int H, int d, size_t& bytes, int& sigma_in_lds) {
@@ -964,55 +776,52 @@ static bool update_lds(int S, int H, int d, size_t& bytes, int& sigma_in_lds) {
     return bytes <= 150 * 1024;
 }
 
-// What mpb_stomp_update takes (declared in mpb_common.h: mpb_stoch_gpmp_step checks it before its first stage launches).
+// What mpb_stomp_update takes (declared in mpb_host.h: mpb_stoch_gpmp_step checks it before its first stage launches).
 // Neither update kernel tiles the channels -- the v4 kernel keeps delta as d padded LDS rows, the generic one walks the
 // H*d row -- so d goes up to the positions + velocities of MPB_MAX_DOF joints; MPB_MAX_D (16) is the sampling kernels'
 // matrix-core tile and does not apply here.  Shapes the v4 kernel serves always pass update_lds.
 int mpb_update_envelope(int S, int H, int d, const char* who) {
-    if (S < 1 || H < 3 || H > MPB_MAX_H || d < 1 || d > 2 * MPB_MAX_DOF) return fail(MPB_E_INVALID, "%s: bad shape", who);
+    if (S < 1 || H < 3 || H > MPB_MAX_H || d < 1 || d > 2 * MPB_MAX_DOF) return mpb_failf(MPB_E_INVALID, "%s: bad shape", who);
     size_t lds;
     int sig_lds;
-    if (!update_lds(S, H, d, lds, sig_lds)) return fail(MPB_E_UNSUPPORTED, "%s: S + H*d too large for LDS", who);
+    if (!update_lds(S, H, d, lds, sig_lds)) return mpb_failf(MPB_E_UNSUPPORTED, "%s: S + H*d too large for LDS", who);
     return MPB_OK;
 }
 
 // kernel B launcher: vectorised path when the (H,d) tile is float4-divisible and fits 1024 threads
-static bool launch_update(float* means, const float* samples, const float* costs, float* weights, const float* Sigma,
-                          int P, int S, int H, int d, float lr, float temperature, hipStream_t st) {
-    const int n = H * d;
+bool mpb_stomp_launch_update(const StompCall& c, hipStream_t st, const StompEvents* ev) {
+    const int P = c.P, S = c.S, H = c.H, d = c.d, n = H * d;
     if ((n & 3) == 0 && n <= 1024 && H <= 64 && (H & 3) == 0 && S <= 64) {   // Sigma may be NULL (no covariance product)
         const int n4 = n >> 2;
         const int SG = (1024 / n4) < 4 ? (1024 / n4) : 4;
         const size_t lds = (size_t)d * UPD_LD * 4 + (size_t)SG * n4 * 16 + (size_t)H * UPD_LD * 4;
-        MPB_LAUNCH(stomp_update_v4_kernel, dim3(P), dim3(1024), lds, st, means, samples, costs, weights, Sigma, P,
-                           S, H, d, lr, temperature);
+        MPB_LAUNCH(ev, stomp_update_v4_kernel, dim3(P), dim3(1024), lds, st, c.means, (const float*)c.samples, (const float*)c.costs,
+                   c.weights, c.Sigma, P, S, H, d, c.lr, c.temperature);
         return true;
     }
     size_t lds;
     int sig_lds;
     if (!update_lds(S, H, d, lds, sig_lds)) return false;
-    MPB_LAUNCH(stomp_update_kernel, dim3(P), dim3(1024), lds, st, means, samples, costs, weights, Sigma, P, S, H,
-                       d, lr, temperature, sig_lds);
+    MPB_LAUNCH(ev, stomp_update_kernel, dim3(P), dim3(1024), lds, st, c.means, (const float*)c.samples, (const float*)c.costs,
+               c.weights, c.Sigma, P, S, H, d, c.lr, c.temperature, sig_lds);
     return true;
 }
 
 // kernel A launcher: H = 64 takes the MFMA fast path for the channel counts of the reference's robots
 template <bool WITH_COST>
-static void launch_sample(const float* means, const float* eps, float* samples, float* costs, const float* L,
-                          const float* geom, int geom_flags, int P, int S, int H, int d, float k_sigma, float weight,
-                          uint64_t seed, uint32_t iter, uint32_t particle_offset, hipStream_t st) {
-    const int B = P * S;
+static void launch_sample(const StompCall& c, const float* eps, uint32_t iter, hipStream_t st, const StompEvents* ev) {
+    const int P = c.P, S = c.S, H = c.H, d = c.d, B = P * S;
     const dim3 grid((B + 3) / 4), block(256);
-    const uint32_t lo = (uint32_t)seed, hi = (uint32_t)(seed >> 32);
-#define MPB_A_CASE(DCH, MODEL)                                                                                   \
-    case DCH:                                                                                                    \
-        MPB_LAUNCH((stomp_sample_cost_h64_kernel<DCH, WITH_COST, MODEL>), dim3((B + MPB_A_WPB - 1) / MPB_A_WPB),  \
-                           dim3(64 * MPB_A_WPB), 0, st, means, eps, samples, costs, L, geom, P, S, k_sigma, weight, \
-                           lo, hi, iter, particle_offset);                                                       \
+    const uint32_t lo = (uint32_t)c.seed, hi = (uint32_t)(c.seed >> 32);
+#define MPB_A_CASE(DCH, MODEL)                                                                                        \
+    case DCH:                                                                                                         \
+        MPB_LAUNCH(ev, (stomp_sample_cost_h64_kernel<DCH, WITH_COST, MODEL>), dim3((B + MPB_A_WPB - 1) / MPB_A_WPB),   \
+                   dim3(64 * MPB_A_WPB), 0, st, (const float*)c.means, eps, c.samples, c.costs, c.L, c.geom, P, S,     \
+                   c.k_sigma, c.weight, lo, hi, iter, c.particle_offset);                                              \
         return;
     // (bit 8: every field COMPACT-grid-backed -- since round 6 the model byte is also set for list-grid scenes, which this kernel
     // serves through the exhaustive walk)
-    if (H == 64 && WITH_COST && (geom_flags & 0xFF) == PandaModel::ID && (geom_flags & 0x100)) {   // the Panda's channel counts (pos_only / not)
+    if (H == 64 && WITH_COST && (c.geom_flags & 0xFF) == PandaModel::ID && (c.geom_flags & 0x100)) {   // the Panda's channel counts (pos_only / not)
         switch (d) {
             MPB_A_CASE(7, (WITH_COST ? PandaModel::ID : 0)) MPB_A_CASE(14, (WITH_COST ? PandaModel::ID : 0))
             default: break;
@@ -1027,9 +836,9 @@ static void launch_sample(const float* means, const float* eps, float* samples, 
 #undef MPB_A_CASE
     // any other horizon / channel count (H <= MPB_MAX_H = 256, d <= MPB_MAX_D = 16): chunked MFMA kernel
     {
-#define MPB_HX(M)                                                                                                   \
-    MPB_LAUNCH((stomp_sample_cost_hx_kernel<WITH_COST, M>), grid, block, 0, st, means, eps, samples, costs, L, \
-                       geom, P, S, H, d, k_sigma, weight, lo, hi, iter, particle_offset)
+#define MPB_HX(M)                                                                                                      \
+    MPB_LAUNCH(ev, (stomp_sample_cost_hx_kernel<WITH_COST, M>), grid, block, 0, st, (const float*)c.means, eps, c.samples, \
+               c.costs, c.L, c.geom, P, S, H, d, c.k_sigma, c.weight, lo, hi, iter, c.particle_offset)
         if (H <= 64) MPB_HX(1);
         else if (H <= 128) MPB_HX(2);
         else MPB_HX(4);
@@ -1037,151 +846,7 @@ static void launch_sample(const float* means, const float* eps, float* samples, 
     }
 }
 
-static bool shape_ok(int H, int d, int D) {
-    return H >= 3 && H <= MPB_MAX_H && D >= 1 && D <= MPB_MAX_DOF && (d == D || d == 2 * D);
+void mpb_stomp_launch_sample(const StompCall& c, const float* eps_it, uint32_t iter, hipStream_t st, const StompEvents* ev) {
+    if (c.geom) launch_sample<true>(c, eps_it, iter, st, ev);
+    else launch_sample<false>(c, eps_it, iter, st, ev);
 }
-
-extern "C" int mpb_cost_collision_eval(const float* trajs, const float* geom, float* out, float* per_waypoint,
-                                       int B, int H, int d, int h_begin, float k_sigma, float weight, void* stream) {
-    if (B == 0) return MPB_OK;   // empty batch: nothing to do (and torch hands out null pointers for it)
-    if (!trajs || !geom || !out) return fail(MPB_E_INVALID, "%s: null pointer", __func__);
-    if (B < 0 || H < 1 || d < 1 || d > 2 * MPB_MAX_DOF || h_begin < 0) return fail(MPB_E_INVALID, "%s: bad shape", __func__);   // (rows of any width up to positions + velocities of 12 joints; the first n_dof channels are read)
-    if (B == 0) return MPB_OK;
-    hipLaunchKernelGGL((collision_cost_kernel<false, 0>), dim3((B + 3) / 4), dim3(256), 0, (hipStream_t)stream, trajs, geom,
-                       out, per_waypoint, (float*)nullptr, B, H, d, h_begin, k_sigma, weight);
-    return check_launch(__func__);
-}
-
-extern "C" int mpb_cost_collision_grad(const float* trajs, const float* geom, int geom_flags, float* out, float* grad, int B,
-                                       int H, int d, int h_begin, float k_sigma, float weight, void* stream) {
-    if (B == 0) return MPB_OK;
-    if (!trajs || !geom || !out || !grad) return fail(MPB_E_INVALID, "%s: null pointer", __func__);
-    if (B < 0 || H < 1 || d < 1 || d > 2 * MPB_MAX_DOF || h_begin < 0) return fail(MPB_E_INVALID, "%s: bad shape", __func__);   // (rows of any width up to positions + velocities of 12 joints; the first n_dof channels are read)
-    if (B == 0) return MPB_OK;
-    if ((geom_flags & 0xFF) == PandaModel::ID && (geom_flags & 0x100))
-        hipLaunchKernelGGL((collision_cost_kernel<true, PandaModel::ID>), dim3((B + 3) / 4), dim3(256), 0, (hipStream_t)stream, trajs,
-                           geom, out, (float*)nullptr, grad, B, H, d, h_begin, k_sigma, weight);
-    else
-        hipLaunchKernelGGL((collision_cost_kernel<true, 0>), dim3((B + 3) / 4), dim3(256), 0, (hipStream_t)stream, trajs, geom,
-                           out, (float*)nullptr, grad, B, H, d, h_begin, k_sigma, weight);
-    return check_launch(__func__);
-}
-
-extern "C" int mpb_stomp_sample(const float* means, const float* eps, float* samples, const float* L,
-                                const float* geom, int geom_flags, float* costs, int P, int S, int H, int d, float k_sigma,
-                                float weight, uint64_t seed, uint32_t iter, uint32_t particle_offset, void* stream) {
-    if (P == 0) return MPB_OK;
-    if (!means || !samples || !L) return fail(MPB_E_INVALID, "%s: null pointer", __func__);
-    if ((geom == nullptr) != (costs == nullptr)) return fail(MPB_E_INVALID, "%s: geom and costs must be given together", __func__);
-    if (P < 0 || S < 1 || H < 3 || H > MPB_MAX_H || d < 1 || d > MPB_MAX_D) return fail(MPB_E_INVALID, "%s: bad shape", __func__);
-    if (mpb_misaligned16(means, eps, samples, L, geom)) return fail(MPB_E_INVALID, "%s: means / eps / samples / L / geom must be 16-byte aligned", __func__);
-    if (P == 0) return MPB_OK;
-    if (geom)
-        launch_sample<true>(means, eps, samples, costs, L, geom, geom_flags, P, S, H, d, k_sigma, weight, seed, iter,
-                            particle_offset, (hipStream_t)stream);
-    else
-        launch_sample<false>(means, eps, samples, nullptr, L, nullptr, 0, P, S, H, d, 0.f, 0.f, seed, iter,
-                             particle_offset, (hipStream_t)stream);
-    return check_launch(__func__);
-}
-
-extern "C" int mpb_stomp_update(float* means, const float* samples, const float* costs, float* weights,
-                                const float* Sigma, int P, int S, int H, int d, float lr, float temperature,
-                                void* stream) {
-    if (P == 0) return MPB_OK;
-    if (!means || !samples || !costs || !weights) return fail(MPB_E_INVALID, "%s: null pointer", __func__);
-    if (P < 0) return fail(MPB_E_INVALID, "%s: bad shape", __func__);
-    if (const int rc = mpb_update_envelope(S, H, d, __func__)) return rc;
-    if (!(temperature > 0.f)) return fail(MPB_E_INVALID, "%s: temperature must be > 0", __func__);
-    if (mpb_misaligned16(means, samples, Sigma)) return fail(MPB_E_INVALID, "%s: means / samples / Sigma must be 16-byte aligned", __func__);
-    if (P == 0) return MPB_OK;
-    launch_update(means, samples, costs, weights, Sigma, P, S, H, d, lr, temperature, (hipStream_t)stream);   // (within the envelope)
-    return check_launch(__func__);
-}
-
-extern "C" int mpb_stomp_step(float* means, const float* eps, float* samples, float* costs, float* weights,
-                              const float* L, const float* Sigma, const float* geom, int geom_flags, int P, int S, int H, int d, int D,
-                              float k_sigma, float weight, float lr, float temperature, int n_iters, uint64_t seed,
-                              uint32_t iter0, uint32_t particle_offset, void* stream) {
-    if (P == 0) return MPB_OK;
-    if (!means || !samples || !costs || !weights || !L || !Sigma || !geom) return fail(MPB_E_INVALID, "%s: null pointer", __func__);
-    if (P < 0 || S < 1 || !shape_ok(H, d, D) || n_iters < 0) return fail(MPB_E_INVALID, "%s: bad shape", __func__);
-    if (!(temperature > 0.f)) return fail(MPB_E_INVALID, "%s: temperature must be > 0", __func__);
-    if (mpb_misaligned16(means, eps, samples, L, Sigma, geom))
-        return fail(MPB_E_INVALID, "%s: means / eps / samples / L / Sigma / geom must be 16-byte aligned", __func__);
-    size_t lds_b;
-    int sig_lds;
-    if (!update_lds(S, H, d, lds_b, sig_lds)) return fail(MPB_E_UNSUPPORTED, "%s: S + H*d too large for LDS", __func__);
-    if (P == 0) return MPB_OK;
-    const size_t eps_stride = (size_t)S * d * P * H;
-    // Launch-queue throttle: long runs keep at most two chunks of MPB_CHUNK iterations queued ahead of the
-    // GPU (before queueing chunk k+2 the host waits on an event recorded after chunk k), so the host never
-    // sits on thousands of pending launches.  Short calls (<= 2 chunks) and calls made while the stream is
-    // being captured into a graph never wait.
-    constexpr int MPB_CHUNK = 128;
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    const bool throttle = n_iters > 2 * MPB_CHUNK &&
-                          hipStreamIsCapturing((hipStream_t)stream, &cap) == hipSuccess && cap == hipStreamCaptureStatusNone;
-    for (int it = 0; it < n_iters; ++it) {
-        if (throttle && it % MPB_CHUNK == 0) {
-            const int k = (it / MPB_CHUNK) & 1;
-            if (ev[k]) (void)hipEventSynchronize(ev[k]);                 // chunk it/MPB_CHUNK - 2 has finished
-            else (void)hipEventCreateWithFlags(&ev[k], hipEventDisableTiming);
-        }
-        launch_sample<true>(means, eps ? eps + (size_t)it * eps_stride : nullptr, samples, costs, L, geom, geom_flags, P, S, H, d,
-                            k_sigma, weight, seed, iter0 + (uint32_t)it, particle_offset, (hipStream_t)stream);
-        launch_update(means, samples, costs, weights, Sigma, P, S, H, d, lr, temperature, (hipStream_t)stream);
-        if (throttle && it % MPB_CHUNK == MPB_CHUNK - 1) (void)hipEventRecord(ev[(it / MPB_CHUNK) & 1], (hipStream_t)stream);
-    }
-    for (int k = 0; k < 2; ++k)
-        if (ev[k]) (void)hipEventDestroy(ev[k]);
-    return check_launch(__func__);
-}
-
-extern "C" int mpb_stomp_step_profile(float* means, float* samples, float* costs, float* weights, const float* L,
-                                      const float* Sigma, const float* geom, int geom_flags, int P, int S, int H, int d, int D,
-                                      float k_sigma, float weight, float lr, float temperature, int n_iters, uint64_t seed,
-                                      uint32_t iter0, uint32_t particle_offset, void* stream, float* sample_kernel_ms,
-                                      float* update_kernel_ms) {
-    if (!means || !samples || !costs || !weights || !L || !Sigma || !geom || !sample_kernel_ms || !update_kernel_ms)
-        return fail(MPB_E_INVALID, "%s: null pointer", __func__);
-    if (P < 1 || S < 1 || !shape_ok(H, d, D) || n_iters < 1 || n_iters > 1024) return fail(MPB_E_INVALID, "%s: bad shape", __func__);
-    if (!(temperature > 0.f)) return fail(MPB_E_INVALID, "%s: temperature must be > 0", __func__);
-    size_t lds_b;
-    int sig_lds;
-    if (!update_lds(S, H, d, lds_b, sig_lds)) return fail(MPB_E_UNSUPPORTED, "%s: S + H*d too large for LDS", __func__);
-    hipEvent_t* ev = new hipEvent_t[4 * (size_t)n_iters];
-    for (int i = 0; i < 4 * n_iters; ++i)
-        if (hipEventCreate(&ev[i]) != hipSuccess) {
-            for (int k = 0; k < i; ++k) (void)hipEventDestroy(ev[k]);
-            delete[] ev;
-            return fail(MPB_E_HIP, "%s: hipEventCreate failed", __func__);
-        }
-    for (int it = 0; it < n_iters; ++it) {
-        t_ev0 = ev[4 * it + 0]; t_ev1 = ev[4 * it + 1];
-        launch_sample<true>(means, nullptr, samples, costs, L, geom, geom_flags, P, S, H, d, k_sigma, weight, seed, iter0 + (uint32_t)it,
-                            particle_offset, (hipStream_t)stream);
-        t_ev0 = ev[4 * it + 2]; t_ev1 = ev[4 * it + 3];
-        launch_update(means, samples, costs, weights, Sigma, P, S, H, d, lr, temperature, (hipStream_t)stream);
-    }
-    t_ev0 = t_ev1 = nullptr;
-    int rc = check_launch(__func__);
-    if (rc == MPB_OK && hipStreamSynchronize((hipStream_t)stream) != hipSuccess) rc = fail(MPB_E_HIP, "%s: synchronize failed", __func__);
-    double sa = 0.0, sb = 0.0;
-    for (int it = 0; it < n_iters && rc == MPB_OK; ++it) {
-        float ma = 0.f, mb = 0.f;
-        if (hipEventElapsedTime(&ma, ev[4 * it + 0], ev[4 * it + 1]) != hipSuccess ||
-            hipEventElapsedTime(&mb, ev[4 * it + 2], ev[4 * it + 3]) != hipSuccess)
-            rc = fail(MPB_E_HIP, "%s: hipEventElapsedTime failed", __func__);
-        sa += ma;
-        sb += mb;
-    }
-    for (int i = 0; i < 4 * n_iters; ++i) (void)hipEventDestroy(ev[i]);
-    delete[] ev;
-    if (rc != MPB_OK) return rc;
-    *sample_kernel_ms = (float)(sa / n_iters);
-    *update_kernel_ms = (float)(sb / n_iters);
-    return MPB_OK;
-}
-

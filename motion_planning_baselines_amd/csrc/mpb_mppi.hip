@@ -17,6 +17,7 @@
 // reference's dynamics slices an empty tensor (point.py:114-118 uses the doubled self.state_dim) and
 // cannot run, so there is nothing to match.
 #include "mpb_common.h"
+#include "mpb_host.h"
 #include "mpb_geom.h"
 #include "mpb_stomp_noise.h"   // the permuted MFMA image of a 64 x 64 lower-triangular factor (stomp_l_image_index)
 

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 
 #include "mpb_common.h"
+#include "mpb_host.h"
 #include "mpb_mt19937.h"
 #include "../../include/mpb.h"
 
@@ -11,18 +12,10 @@ extern "C" int mpb_mt19937_normals(float* out, int n, int n_calls, const uint32_
                                    uint32_t* work, void* stream) {
     if (!out || !state_in || !state_out || !jump_idx || !jump_cnt || !segs || !work)
         return mpb_fail(MPB_E_INVALID, "mpb_mt19937_normals: null pointer");
-    if (const char* why = mt19937_bad_args(n, n_calls, pos, final_idx, jump_stride, n_segs)) {
-        char msg[256];
-        snprintf(msg, sizeof msg, "mpb_mt19937_normals: %s", why);
-        return mpb_fail(MPB_E_INVALID, msg);
-    }
+    if (const char* why = mt19937_bad_args(n, n_calls, pos, final_idx, jump_stride, n_segs)) return mpb_failf(MPB_E_INVALID, "mpb_mt19937_normals: %s", why);
     if (((uintptr_t)jump_idx & 15u) || ((uintptr_t)work & 15u)) return mpb_fail(MPB_E_INVALID, "mpb_mt19937_normals: jump_idx / work must be 16-byte aligned");
     hipError_t e = mt19937_launch<false>(out, n, state_in, pos, final_idx, state_out, jump_idx, jump_cnt, jump_stride, segs, n_segs, work,
                                          nullptr, (hipStream_t)stream);
-    if (e != hipSuccess) {
-        char msg[256];
-        snprintf(msg, sizeof msg, "mpb_mt19937_normals: HIP launch failed: %s", hipGetErrorString(e));
-        return mpb_fail(MPB_E_HIP, msg);
-    }
+    if (e != hipSuccess) return mpb_failf(MPB_E_HIP, "mpb_mt19937_normals: HIP launch failed: %s", hipGetErrorString(e));
     return MPB_OK;
 }

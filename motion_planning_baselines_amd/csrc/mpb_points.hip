@@ -7,6 +7,7 @@
 // (CostCollision / FieldFactor) run against this package's robot and field objects on GPU tensors.
 // Mapping: one wave per trajectory, one lane per waypoint, like every cost kernel here.
 #include "mpb_common.h"
+#include "mpb_host.h"
 #include "mpb_geom.h"
 
 // ---- forward kinematics of the collision spheres: q (B,H,d) -> pts (B,H,L,3) ----------------------------

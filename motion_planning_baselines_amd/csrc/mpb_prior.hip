@@ -10,6 +10,7 @@
 // substitution along the horizon.  The host computes the H small 2x2 factors in fp64
 // (planners/base.py: gp_prior_factor); this kernel does the substitution, one thread per chain, in fp64.
 #include "mpb_common.h"
+#include "mpb_host.h"
 
 // 1/x in fp64: v_rcp_f64 + two Newton steps (the IEEE division hipcc emits is ~40 instructions, twice per step)
 __device__ __forceinline__ double prior_rcp(double x) {

@@ -8,6 +8,7 @@
 // dense N x N matrix of the reference (N = 2D*H) is never formed.
 // One wave per sample trajectory, lane = waypoint; every term is local to (row t, row t+1).
 #include "mpb_common.h"
+#include "mpb_host.h"
 #include "mpb_geom.h"
 
 struct SgConst {

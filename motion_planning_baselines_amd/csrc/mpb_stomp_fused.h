@@ -3,7 +3,6 @@
 // the agent-scope accessors and the tagged granules of the exchange between the workgroups of a particle.
 #pragma once
 #include <hip/hip_runtime.h>
-#include <hip/hip_ext.h>
 #include <stdint.h>
 
 #define FUSED_WAVES 16
@@ -44,16 +43,6 @@ __device__ __forceinline__ void st_granule(granule_t* p, float v, unsigned tag) 
     __hip_atomic_store(p, ((granule_t)tag << 32) | (granule_t)__float_as_uint(v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 __device__ __forceinline__ granule_t ld_granule(const granule_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-
-// Measurement aid (mpb_stomp_run_timed): while these are set, the persistent launch records the pair on the dispatch
-// itself (hipExtLaunchKernelGGL: kernel begin / end timestamps, the quantity rocprofv3 --kernel-trace reports).
-struct FusedProfile { hipEvent_t start, stop; };
-#define MPB_FUSED_LAUNCH(prof, kernel, grid, block, st, ...)                                                        \
-    do {                                                                                                            \
-        if ((prof) != nullptr) hipExtLaunchKernelGGL(kernel, grid, block, 0, st, (prof)->start, (prof)->stop, 0, __VA_ARGS__); \
-        else hipLaunchKernelGGL(kernel, grid, block, 0, st, __VA_ARGS__);                                           \
-    } while (0)
 
 // unit of a workgroup of the exchange layout, by ticket (see the header comment of mpb_stomp_fused.hip): returns the unit
 // index u = particle * nc + chunk, or sets `why` (1: an earlier workgroup of this call gave up; 2: header not zeroed)

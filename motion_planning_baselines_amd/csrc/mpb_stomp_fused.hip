@@ -32,13 +32,10 @@
 // path, so both layouts produce the same bits (tests/test_gpu_stomp_fused.py).
 #include <hip/hip_runtime.h>
 
-#include <stdlib.h>
-
-#include <atomic>
 #include <type_traits>
-#include <chrono>
 
 #include "mpb_common.h"
+#include "mpb_stomp_host.h"
 #include "mpb_geom.h"
 #include "mpb_stomp_noise.h"
 #include "mpb_stomp_fused.h"
@@ -677,156 +674,21 @@ __global__ __launch_bounds__(FUSED_THREADS, 4) void stomp_fused_kernel(
 }
 
 // ------------------------------------------------------------------------------------------------
-// C-ABI
+// launcher (called by mpb_stomp_run_checked, mpb_stomp_api.hip, which has checked the arguments and picked the layout)
 // ------------------------------------------------------------------------------------------------
-static int device_cu_count() {       // (every GPU of a node is the same part: asked once)
-    static const int n_cu = [] {
-        int dev = 0, n = 256;
-        if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
-        return n > 0 ? n : 256;
-    }();
-    return n_cu;
-}
+size_t mpb_fused_ws_floats(int P, int nc) { return fused_ws_floats(P, nc); }
 
-// the generalised kernel (mpb_stomp_fused_hx.hip): any H <= 128, d <= 16, S <= 128
-bool mpb_fused_hx_plan(int geom_flags, int n_cu, int P, int S, int H, int d, int* nc_out, int* nb_out, size_t* ws_bytes);
-int mpb_fused_hx_launch(float* means, const float* eps, float* samples, float* costs, float* weights, const float* L,
-                        const float* Sigma, const float* geom, int geom_flags, float* workspace, int P, int S, int H, int d, int nc,
-                        int nb, float k_sigma, float weight, float lr, float temperature, int n_iters, uint32_t lo, uint32_t hi,
-                        uint32_t iter0, uint32_t particle_offset, uint32_t tag0, unsigned long long timeout, unsigned* status_dev,
-                        float* means_copy, hipStream_t st, const FusedProfile* prof);
-
-// which form of the loop serves a call, and the workspace it needs
-struct FusedPlan {
-    int path;            // MPB_STOMP_PATH_*: 0 two-kernel loop, 1 persistent with exchange, 2 persistent one workgroup per particle
-    int nc;              // workgroups per particle (exchange layout)
-    bool two_batches;    // (H = 64 kernel) one workgroup per particle runs two batches of 16 samples
-    bool hx;             // served by the generalised kernel (any H <= 128, d <= 16, S <= 128)
-    int nb;              // (generalised kernel) passes per workgroup and iteration
-    size_t ws_bytes;     // workspace the persistent kernel needs (header only when nothing is exchanged)
-};
-static FusedPlan fused_plan(int geom_flags, int P, int S, int H, int d) {
-    FusedPlan f = {MPB_STOMP_PATH_TWO_KERNEL, 1, false, false, 1, 0};
-    if (P < 1 || S < 1) return f;
-    const int n_cu = device_cu_count();
-    // MPB_STOMP_HX = 1 sends every shape to the generalised kernel (a test aid: it is compared with the H = 64 kernel)
-    const char* hx_env = getenv("MPB_STOMP_HX");
-    const int force_hx = hx_env ? atoi(hx_env) : 0;
-    const bool v1 = !force_hx && H == 64 && S <= FUSED_WAVES * FUSED_MAX_CHUNKS && (geom_flags & 0x100) &&
-                    (d == 2 || d == 3 || d == 4 || d == 6 || d == 7 || d == 14);
-    if (!v1) {
-        if (!mpb_fused_hx_plan(geom_flags, n_cu, P, S, H, d, &f.nc, &f.nb, &f.ws_bytes)) return f;
-        f.hx = true;
-        f.path = f.nc > 1 ? MPB_STOMP_PATH_PERSISTENT_EXCHANGE : MPB_STOMP_PATH_PERSISTENT;
-        return f;
-    }
-    f.nc = (S + FUSED_WAVES - 1) / FUSED_WAVES;
-    // layout: one workgroup per (particle, chunk of 16 samples) with the exchange -- or, when there are at least as many
-    // particles as CUs and S <= 32, one workgroup per particle running two batches of 16 (no exchange; same bits).
-    // MPB_STOMP_BATCHES = 1 / 2 forces one or the other (2 only where it applies).
-    static const int force_nb = [] { const char* e = getenv("MPB_STOMP_BATCHES"); return e ? atoi(e) : 0; }();
-    // rounds of workgroups either layout needs on this chip: the two-batch workgroup takes ~1.88 x as long per iteration
-    const long r1 = (2L * P + n_cu - 1) / n_cu, r2 = ((long)P + n_cu - 1) / n_cu;
-    f.two_batches = f.nc == 2 && force_nb != 1 && (force_nb == 2 || 188 * r2 < 100 * r1);
-    const bool exchange = f.nc > 1 && !f.two_batches;
-    f.path = exchange ? MPB_STOMP_PATH_PERSISTENT_EXCHANGE : MPB_STOMP_PATH_PERSISTENT;
-    f.ws_bytes = (exchange ? fused_ws_floats(P, f.nc) : FUSED_HDR_WORDS) * sizeof(float);
-    return f;
-}
-
-extern "C" size_t mpb_stomp_workspace_bytes(int P, int S, int H, int d) {
-    if (P < 1 || S < 1) return 0;
-    // what the layout the launcher will pick needs (grid-backed fields assumed; a call the persistent kernel cannot
-    // serve needs none): the exchange area only when partner workgroups exchange partials, else just the header
-    const FusedPlan f = fused_plan(0x100, P, S, H, d);
-    // (a scene packed with LIST grids -- geometry version 7, flag bit 13 -- goes to the generalised kernel even at H = 64, whose
-    // exchange slots are larger: the workspace serves whichever of the two the geometry will select)
-    const FusedPlan fl = fused_plan(0x2000, P, S, H, d);
-    size_t b = f.path == MPB_STOMP_PATH_TWO_KERNEL ? FUSED_HDR_WORDS * sizeof(float) : f.ws_bytes;
-    if (fl.path != MPB_STOMP_PATH_TWO_KERNEL && fl.ws_bytes > b) b = fl.ws_bytes;
-    return b;
-}
-
-extern "C" int mpb_stomp_workspace_init(float* workspace, size_t workspace_bytes, void* stream) {
-    if (!workspace || workspace_bytes < FUSED_HDR_WORDS * sizeof(float)) return mpb_fail(MPB_E_INVALID, "mpb_stomp_workspace_init: workspace too small");
-    if (hipMemsetAsync(workspace, 0, FUSED_HDR_WORDS * sizeof(float), (hipStream_t)stream) != hipSuccess) return mpb_fail(MPB_E_HIP, "mpb_stomp_workspace_init: memset failed");
-    return MPB_OK;
-}
-
-extern "C" int mpb_stomp_run_path(int geom_flags, size_t workspace_bytes, int P, int S, int H, int d) {
-    const FusedPlan f = fused_plan(geom_flags, P, S, H, d);
-    return (f.path != MPB_STOMP_PATH_TWO_KERNEL && workspace_bytes >= f.ws_bytes) ? f.path : MPB_STOMP_PATH_TWO_KERNEL;
-}
-
-extern "C" int mpb_stomp_step(float* means, const float* eps, float* samples, float* costs, float* weights,
-                              const float* L, const float* Sigma, const float* geom, int geom_flags, int P, int S, int H, int d, int D,
-                              float k_sigma, float weight, float lr, float temperature, int n_iters, uint64_t seed,
-                              uint32_t iter0, uint32_t particle_offset, void* stream);
-
-static thread_local const FusedProfile* t_prof = nullptr;      // set by mpb_stomp_run_timed around its launch
-
-extern "C" int mpb_stomp_run_checked(float* means, const float* eps, float* samples, float* costs, float* weights,
-                                     const float* L, const float* Sigma, const float* geom, int geom_flags, float* workspace,
-                                     size_t workspace_bytes, int P, int S, int H, int d, int D, float k_sigma, float weight, float lr,
-                                     float temperature, int n_iters, uint64_t seed, uint32_t iter0, uint32_t particle_offset,
-                                     uint32_t* status, uint32_t* tag_out, float* means_copy, void* stream) {
-    if (tag_out) *tag_out = 0u;
-    if (P == 0) return MPB_OK;
-    const FusedPlan f = fused_plan(geom_flags, P, S, H, d);
-    if (n_iters == 0 || !workspace || f.path == MPB_STOMP_PATH_TWO_KERNEL || workspace_bytes < f.ws_bytes) {
-        const int rc = n_iters == 0 ? MPB_OK : mpb_stomp_step(means, eps, samples, costs, weights, L, Sigma, geom, geom_flags, P, S, H, d, D,
-                                                             k_sigma, weight, lr, temperature, n_iters, seed, iter0, particle_offset, stream);
-        if (rc == MPB_OK && means_copy && means &&
-            hipMemcpyAsync(means_copy, means, sizeof(float) * (size_t)P * H * d, hipMemcpyDeviceToDevice, (hipStream_t)stream) != hipSuccess)
-            return mpb_fail(MPB_E_HIP, "mpb_stomp_run: copy of the means failed");
-        return rc;
-    }
-    if (!means || !samples || !costs || !weights || !L || !Sigma || !geom) return mpb_fail(MPB_E_INVALID, "mpb_stomp_run: null pointer");
-    if (P < 0 || S < 1 || n_iters < 0 || !(d == D || d == 2 * D)) return mpb_fail(MPB_E_INVALID, "mpb_stomp_run: bad shape");
-    if (!(temperature > 0.f)) return mpb_fail(MPB_E_INVALID, "mpb_stomp_run: temperature must be > 0");
-    if (mpb_misaligned16(means, eps, samples, L, Sigma, geom) || mpb_misaligned16(workspace, means_copy))
-        return mpb_fail(MPB_E_INVALID, "mpb_stomp_run: means / eps / samples / L / Sigma / geom / workspace / means_copy must be 16-byte aligned");
-    hipStream_t st = (hipStream_t)stream;
-    // the status block is host memory the device can write (pinned + mapped): its device address
-    unsigned* status_dev = nullptr;
-    if (status) {
-        static thread_local uint32_t* seen_host = nullptr;      // (a planner passes the same block every call: asked once)
-        static thread_local unsigned* seen_dev = nullptr;
-        if (status != seen_host) {
-            unsigned* dp = nullptr;
-            if (hipHostGetDevicePointer(reinterpret_cast<void**>(&dp), status, 0) != hipSuccess) {
-                (void)hipGetLastError();
-                return mpb_fail(MPB_E_INVALID, "mpb_stomp_run: status is not pinned, device-mapped host memory");
-            }
-            seen_host = status;
-            seen_dev = dp;
-        }
-        status_dev = seen_dev;
-    }
-    // the granules' tags and the error word carry a per-call epoch (process-wide counter scrambled over 32 bits), so
-    // whatever an earlier call left in the exchange area does not match.  Header: word 0 = tag of the call in which a
-    // workgroup gave up, word 1 = tag of the last call; "lost" <=> word 0 == word 1 != 0.  Not capturable in a HIP
-    // graph: a replay would reuse the tag.
-    static std::atomic<uint32_t> epoch{(uint32_t)std::chrono::steady_clock::now().time_since_epoch().count()};
-    uint32_t tag0 = (epoch.fetch_add(1u) + 1u) * 0x9E3779B9u;
-    if (tag0 == 0u) tag0 = 0x9E3779B9u;      // 0 means "none" in the header and the status block
-    if (tag_out) *tag_out = tag0;
-    const uint32_t lo = (uint32_t)seed, hi = (uint32_t)(seed >> 32);
-    // bound of every wait for a partner; MPB_STOMP_TIMEOUT_US overrides it (a test aid)
-    unsigned long long timeout = FUSED_TIMEOUT_TICKS + FUSED_TIMEOUT_PER_ITER * (unsigned long long)n_iters;
-    if (const char* e = getenv("MPB_STOMP_TIMEOUT_US")) { const long long us = atoll(e); if (us > 0) timeout = 100ull * (unsigned long long)us; }
-    if (f.hx)
-        return mpb_fused_hx_launch(means, eps, samples, costs, weights, L, Sigma, geom, geom_flags, workspace, P, S, H, d, f.nc, f.nb,
-                                   k_sigma, weight, lr, temperature, n_iters, lo, hi, iter0, particle_offset, tag0, timeout, status_dev,
-                                   means_copy, st, t_prof);
-    const dim3 grid(f.two_batches ? P : P * f.nc), block(FUSED_THREADS);
-    const int nc_k = f.two_batches ? 1 : f.nc;
-    const int model = geom_flags & 0xFF;
-#define MPB_F_LAUNCH_(DCH, MODEL, NB, INJ, CHAIN)                                                                                      \
-    MPB_FUSED_LAUNCH(t_prof, (stomp_fused_kernel<DCH, MODEL, NB, INJ, CHAIN>), grid, block, st, means, eps, samples, costs, weights, L, \
-                     Sigma, geom, workspace, P, S, nc_k, k_sigma, weight, lr, temperature, n_iters, lo, hi, iter0,                      \
-                     particle_offset, tag0, timeout, status_dev, means_copy)
-    const bool one_field = (geom_flags & 0x1000) != 0;
+int mpb_fused_launch(const StompCall& c, const StompLaunch& l, const StompFusedGrid& g) {
+    const bool two_batches = g.nb == 2;
+    const dim3 grid(two_batches ? c.P : c.P * g.nc), block(FUSED_THREADS);
+    const int nc_k = two_batches ? 1 : g.nc;
+    const int model = c.geom_flags & 0xFF, d = c.d;
+    const uint32_t lo = (uint32_t)c.seed, hi = (uint32_t)(c.seed >> 32);
+#define MPB_F_LAUNCH_(DCH, MODEL, NB, INJ, CHAIN)                                                                                       \
+    MPB_LAUNCH(l.events, (stomp_fused_kernel<DCH, MODEL, NB, INJ, CHAIN>), grid, block, 0, l.stream, c.means, c.eps, c.samples, c.costs, \
+               c.weights, c.L, c.Sigma, c.geom, g.workspace, c.P, c.S, nc_k, c.k_sigma, c.weight, c.lr, c.temperature, l.n_iters, lo,   \
+               hi, l.iter0, c.particle_offset, g.tag0, g.timeout, g.status_dev, l.means_copy)
+    const bool one_field = (c.geom_flags & 0x1000) != 0;
 #define MPB_F_LAUNCH(DCH, MODEL, NB, INJ)                                              \
     do {                                                                               \
         if ((MODEL) != 0 && one_field) MPB_F_LAUNCH_(DCH, MODEL, NB, INJ, (MODEL) == 0); \
@@ -834,9 +696,9 @@ extern "C" int mpb_stomp_run_checked(float* means, const float* eps, float* samp
     } while (0)
 #define MPB_F_CASE(DCH, MODEL)                                             \
     do {                                                                   \
-        if (f.two_batches && eps) MPB_F_LAUNCH(DCH, MODEL, 2, true);       \
-        else if (f.two_batches) MPB_F_LAUNCH(DCH, MODEL, 2, false);        \
-        else if (eps) MPB_F_LAUNCH(DCH, MODEL, 1, true);                   \
+        if (two_batches && c.eps) MPB_F_LAUNCH(DCH, MODEL, 2, true);       \
+        else if (two_batches) MPB_F_LAUNCH(DCH, MODEL, 2, false);          \
+        else if (c.eps) MPB_F_LAUNCH(DCH, MODEL, 1, true);                 \
         else MPB_F_LAUNCH(DCH, MODEL, 1, false);                           \
     } while (0)
     if (model == PandaModel::ID && d == 7) MPB_F_CASE(7, PandaModel::ID);
@@ -851,105 +713,4 @@ extern "C" int mpb_stomp_run_checked(float* means, const float* eps, float* samp
 #undef MPB_F_LAUNCH
 #undef MPB_F_LAUNCH_
     return mpb_check_launch("mpb_stomp_run");
-}
-
-extern "C" int mpb_stomp_run(float* means, const float* eps, float* samples, float* costs, float* weights,
-                             const float* L, const float* Sigma, const float* geom, int geom_flags, float* workspace,
-                             size_t workspace_bytes, int P, int S, int H, int d, int D, float k_sigma, float weight, float lr,
-                             float temperature, int n_iters, uint64_t seed, uint32_t iter0, uint32_t particle_offset,
-                             void* stream) {
-    return mpb_stomp_run_checked(means, eps, samples, costs, weights, L, Sigma, geom, geom_flags, workspace, workspace_bytes, P, S,
-                                 H, d, D, k_sigma, weight, lr, temperature, n_iters, seed, iter0, particle_offset, nullptr,
-                                 nullptr, nullptr, stream);
-}
-
-/* A call of mpb_stomp_run_checked with everything but (n_iters, iter0, means_copy, stream) fixed, kept on the library's side:
-   a planner whose buffers do not change between optimize() calls hands over four values per call instead of twenty-eight
-   (the foreign-function marshalling of the long form is ~3 us of the ~11 us host side of a call).  Device noise only (eps = NULL). */
-struct mpb_stomp_plan_s {
-    float *means, *samples, *costs, *weights;
-    const float *L, *Sigma, *geom;
-    int geom_flags;
-    float* workspace;
-    size_t workspace_bytes;
-    int P, S, H, d, D;
-    float k_sigma, weight, lr, temperature;
-    uint64_t seed;
-    uint32_t particle_offset;
-    uint32_t* status;
-};
-
-extern "C" int mpb_stomp_plan_create(mpb_stomp_plan** plan, float* means, float* samples, float* costs, float* weights, const float* L,
-                                     const float* Sigma, const float* geom, int geom_flags, float* workspace, size_t workspace_bytes,
-                                     int P, int S, int H, int d, int D, float k_sigma, float weight, float lr, float temperature,
-                                     uint64_t seed, uint32_t particle_offset, uint32_t* status) {
-    if (!plan) return mpb_fail(MPB_E_INVALID, "mpb_stomp_plan_create: null pointer");
-    *plan = nullptr;
-    if (!means || !samples || !costs || !weights || !L || !Sigma || !geom) return mpb_fail(MPB_E_INVALID, "mpb_stomp_plan_create: null pointer");
-    if (P < 0 || S < 1 || !(d == D || d == 2 * D)) return mpb_fail(MPB_E_INVALID, "mpb_stomp_plan_create: bad shape");
-    if (!(temperature > 0.f)) return mpb_fail(MPB_E_INVALID, "mpb_stomp_plan_create: temperature must be > 0");
-    if (mpb_misaligned16(means, samples, L, Sigma, geom, workspace))
-        return mpb_fail(MPB_E_INVALID, "mpb_stomp_plan_create: means / samples / L / Sigma / geom / workspace must be 16-byte aligned");
-    mpb_stomp_plan_s* q = static_cast<mpb_stomp_plan_s*>(malloc(sizeof(mpb_stomp_plan_s)));
-    if (!q) return mpb_fail(MPB_E_HIP, "mpb_stomp_plan_create: out of host memory");
-    *q = mpb_stomp_plan_s{means, samples, costs, weights, L, Sigma, geom, geom_flags, workspace, workspace_bytes, P, S, H, d, D,
-                          k_sigma, weight, lr, temperature, seed, particle_offset, status};
-    *plan = q;
-    return MPB_OK;
-}
-
-extern "C" int mpb_stomp_plan_launch(mpb_stomp_plan* plan, int n_iters, uint32_t iter0, float* means_copy, void* stream, uint32_t* tag_out) {
-    if (!plan) return mpb_fail(MPB_E_INVALID, "mpb_stomp_plan_launch: null plan");
-    const mpb_stomp_plan_s& q = *plan;
-    return mpb_stomp_run_checked(q.means, nullptr, q.samples, q.costs, q.weights, q.L, q.Sigma, q.geom, q.geom_flags, q.workspace,
-                                 q.workspace_bytes, q.P, q.S, q.H, q.d, q.D, q.k_sigma, q.weight, q.lr, q.temperature, n_iters, q.seed,
-                                 iter0, q.particle_offset, q.status, tag_out, means_copy, stream);
-}
-
-extern "C" int mpb_stomp_plan_destroy(mpb_stomp_plan* plan) {
-    free(plan);
-    return MPB_OK;
-}
-
-/* measurement aid for bench.py: mpb_stomp_run_checked with the kernel's begin / end timestamps recorded on the dispatch
-   itself; synchronises the stream and returns the kernel's duration (0 when the call ran the two-kernel loop) */
-extern "C" int mpb_stomp_run_timed(float* means, const float* eps, float* samples, float* costs, float* weights,
-                                   const float* L, const float* Sigma, const float* geom, int geom_flags, float* workspace,
-                                   size_t workspace_bytes, int P, int S, int H, int d, int D, float k_sigma, float weight, float lr,
-                                   float temperature, int n_iters, uint64_t seed, uint32_t iter0, uint32_t particle_offset,
-                                   uint32_t* status, uint32_t* tag_out, float* means_copy, void* stream, float* kernel_ms) {
-    if (!kernel_ms) return mpb_fail(MPB_E_INVALID, "mpb_stomp_run_timed: null pointer");
-    *kernel_ms = 0.f;
-    FusedProfile pr = {nullptr, nullptr};
-    if (hipEventCreate(&pr.start) != hipSuccess || hipEventCreate(&pr.stop) != hipSuccess) {
-        if (pr.start) (void)hipEventDestroy(pr.start);
-        return mpb_fail(MPB_E_HIP, "mpb_stomp_run_timed: hipEventCreate failed");
-    }
-    uint32_t tag = 0;
-    t_prof = &pr;
-    int rc = mpb_stomp_run_checked(means, eps, samples, costs, weights, L, Sigma, geom, geom_flags, workspace, workspace_bytes, P, S, H,
-                                   d, D, k_sigma, weight, lr, temperature, n_iters, seed, iter0, particle_offset, status, &tag,
-                                   means_copy, stream);
-    t_prof = nullptr;
-    if (tag_out) *tag_out = tag;
-    if (rc == MPB_OK && hipStreamSynchronize((hipStream_t)stream) != hipSuccess) rc = mpb_fail(MPB_E_HIP, "mpb_stomp_run_timed: synchronize failed");
-    if (rc == MPB_OK && tag != 0u && hipEventElapsedTime(kernel_ms, pr.start, pr.stop) != hipSuccess) {
-        (void)hipGetLastError();
-        rc = mpb_fail(MPB_E_HIP, "mpb_stomp_run_timed: hipEventElapsedTime failed");
-    }
-    (void)hipEventDestroy(pr.start);
-    (void)hipEventDestroy(pr.stop);
-    return rc;
-}
-
-/* state of the last persistent launch on this workspace (host-side read of the header: synchronises the stream):
-   0 = fine (or no persistent launch yet), 1 = a workgroup gave up waiting for its partner, 2 = header not initialised */
-extern "C" int mpb_stomp_run_status(const float* workspace, void* stream, int* timed_out) {
-    if (!workspace || !timed_out) return mpb_fail(MPB_E_INVALID, "mpb_stomp_run_status: null pointer");
-    uint32_t w[4] = {0u};
-    if (hipMemcpyAsync(w, workspace, sizeof(w), hipMemcpyDeviceToHost, (hipStream_t)stream) != hipSuccess ||
-        hipStreamSynchronize((hipStream_t)stream) != hipSuccess)
-        return mpb_fail(MPB_E_HIP, "mpb_stomp_run_status: copy failed");
-    *timed_out = (w[FUSED_HDR_ERR] == w[FUSED_HDR_TAG] && w[FUSED_HDR_TAG] != 0u) ? (w[FUSED_HDR_WHY] == 2u ? 2 : 1) : 0;
-    return MPB_OK;
 }

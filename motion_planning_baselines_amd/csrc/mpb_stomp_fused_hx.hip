@@ -18,11 +18,10 @@
 // of a 64-waypoint horizon bit for bit, weights / means within 1e-6 (tests/test_gpu_stomp_fused_hx.py).
 #include <hip/hip_runtime.h>
 
-#include <stdlib.h>
-
 #include <type_traits>
 
 #include "mpb_common.h"
+#include "mpb_stomp_host.h"
 #include "mpb_geom.h"
 #include "mpb_stomp_noise.h"
 #include "mpb_stomp_fused.h"
@@ -571,7 +570,7 @@ __global__ __launch_bounds__(FUSED_THREADS, 4) void stomp_fused_hx_kernel(
 }
 
 // ------------------------------------------------------------------------------------------------
-// launcher (called by mpb_stomp_run_checked, mpb_stomp_fused.hip)
+// launcher (called by mpb_stomp_run_checked, mpb_stomp_api.hip)
 // ------------------------------------------------------------------------------------------------
 // can this kernel serve the shape, and with which split of the S samples over workgroups (nc) and passes (nb)?
 bool mpb_fused_hx_plan(int geom_flags, int n_cu, int P, int S, int H, int d, int* nc_out, int* nb_out, size_t* ws_bytes) {
@@ -598,28 +597,25 @@ bool mpb_fused_hx_plan(int geom_flags, int n_cu, int P, int S, int H, int d, int
     return true;
 }
 
-int mpb_fused_hx_launch(float* means, const float* eps, float* samples, float* costs, float* weights, const float* L,
-                        const float* Sigma, const float* geom, int geom_flags, float* workspace, int P, int S, int H, int d, int nc,
-                        int nb, float k_sigma, float weight, float lr, float temperature, int n_iters, uint32_t lo, uint32_t hi,
-                        uint32_t iter0, uint32_t particle_offset, uint32_t tag0, unsigned long long timeout, unsigned* status_dev,
-                        float* means_copy, hipStream_t st, const FusedProfile* prof) {
-    const dim3 grid(P * nc), block(FUSED_THREADS);
-    const int model = geom_flags & 0xFF;
+int mpb_fused_hx_launch(const StompCall& c, const StompLaunch& l, const StompFusedGrid& g) {
+    const dim3 grid(c.P * g.nc), block(FUSED_THREADS);
+    const int model = c.geom_flags & 0xFF, H = c.H, d = c.d;
+    const uint32_t lo = (uint32_t)c.seed, hi = (uint32_t)(c.seed >> 32);
 #define MPB_HX_LAUNCH_(DCH, MODEL, HC, INJ, LIST)                                                                                        \
-    MPB_FUSED_LAUNCH(prof, (stomp_fused_hx_kernel<DCH, MODEL, HC, INJ, LIST>), grid, block, st, means, eps, samples, costs, weights, L,  \
-                     Sigma, geom, workspace, P, S, H, d, nc, nb, k_sigma, weight, lr, temperature, n_iters, lo, hi, iter0,         \
-                     particle_offset, tag0, timeout, status_dev, means_copy)
+    MPB_LAUNCH(l.events, (stomp_fused_hx_kernel<DCH, MODEL, HC, INJ, LIST>), grid, block, 0, l.stream, c.means, c.eps, c.samples, c.costs, \
+               c.weights, c.L, c.Sigma, c.geom, g.workspace, c.P, c.S, H, d, g.nc, g.nb, c.k_sigma, c.weight, c.lr, c.temperature,        \
+               l.n_iters, lo, hi, l.iter0, c.particle_offset, g.tag0, g.timeout, g.status_dev, l.means_copy)
 #define MPB_HX_LAUNCH(DCH, MODEL, HC)                              \
     do {                                                           \
-        if (eps) MPB_HX_LAUNCH_(DCH, MODEL, HC, true, false);      \
+        if (c.eps) MPB_HX_LAUNCH_(DCH, MODEL, HC, true, false);    \
         else MPB_HX_LAUNCH_(DCH, MODEL, HC, false, false);         \
     } while (0)
 #define MPB_HX_LAUNCH_LIST(DCH, MODEL)                             \
     do {                                                           \
-        if (eps) MPB_HX_LAUNCH_(DCH, MODEL, 1, true, true);        \
+        if (c.eps) MPB_HX_LAUNCH_(DCH, MODEL, 1, true, true);      \
         else MPB_HX_LAUNCH_(DCH, MODEL, 1, false, true);           \
     } while (0)
-    if (!(geom_flags & 0x100)) {              // list grids (mpb_fused_hx_plan admitted them: H <= 64)
+    if (!(c.geom_flags & 0x100)) {            // list grids (mpb_fused_hx_plan admitted them: H <= 64)
         if (model == PandaModel::ID && d == 7) MPB_HX_LAUNCH_LIST(7, PandaModel::ID);
         else if (model == PandaModel::ID && d == 14) MPB_HX_LAUNCH_LIST(14, PandaModel::ID);
         else MPB_HX_LAUNCH_LIST(0, 0);

@@ -55,15 +55,19 @@ def _ptr(t):
     return ctypes.c_void_p(0 if t is None else t.data_ptr())
 
 
-def _chk(t, shape, name, allow_none=False):
+def _seed64(seed):
+    return int(seed) & (2 ** 64 - 1)
+
+
+def _chk(t, shape, name, allow_none=False, dtype=torch.float32):
     if t is None:
         if allow_none:
             return
         raise ValueError(f'{name} is required')
     if not t.is_cuda:
         raise ValueError(f'{name} must live on the GPU (got {t.device}); there is no CPU path')
-    if t.dtype != torch.float32:
-        raise ValueError(f'{name} must be float32 (got {t.dtype})')
+    if t.dtype != dtype:
+        raise ValueError(f'{name} must be {str(dtype).split(".")[-1]} (got {t.dtype})')
     if not t.is_contiguous():
         raise ValueError(f'{name} must be contiguous')
     if tuple(t.shape) != tuple(shape):
@@ -132,15 +136,8 @@ def cost_collision_grad(trajs, geom, k_sigma, weight=1.0, h_begin=1, grad=None):
 TERM_GP, TERM_START, TERM_GOAL, TERM_SMOOTH, TERM_JLIM, TERM_VEL_FD = 1, 2, 4, 8, 16, 32   # include/mpb.h MPB_TERM_*
 
 
-@_on_tensor_device
-def cost_terms_eval(trajs, n_dof, dt=0.0, k_gp=0.0, vel_fd=False, k_start=0.0, start_state=None, k_goal=0.0,
-                    goal_states=None, trajs_per_goal=1, k_smooth=0.0, k_jlim=0.0, q_min=None, q_max=None, jl_eps=0.0,
-                    out=None, accumulate=False, broadcast_jlim=True, terms=None):
-    """One pass over trajs (B,H,d) evaluating the enabled trajectory-only cost terms (mpb_cost_terms_eval).
-    A term is enabled by naming it in `terms` (iterable of 'gp','start','goal','smooth','jlim').
-    Returns (out (B,), jl_total 0-dim fp64 tensor or None)."""
-    B, H, d = trajs.shape
-    _chk(trajs, (B, H, d), 'trajs')
+def _term_flags(terms, B, n_dof, vel_fd, start_state, goal_states, trajs_per_goal, q_min, q_max):
+    """MPB_TERM_* flags of the named cost terms, with the tensors each enabled term reads checked (cost_terms_eval / _grad)."""
     terms = set(terms or ())
     unknown = terms - {'gp', 'start', 'goal', 'smooth', 'jlim'}
     if unknown:
@@ -160,12 +157,24 @@ def cost_terms_eval(trajs, n_dof, dt=0.0, k_gp=0.0, vel_fd=False, k_start=0.0, s
             raise ValueError(f'{goal_states.shape[0]} goals x {trajs_per_goal} trajectories do not cover B={B}')
     if 'smooth' in terms:
         flags |= TERM_SMOOTH
-    jl_total = None
     if 'jlim' in terms:
         flags |= TERM_JLIM
         _chk(q_min, (n_dof,), 'q_min')
         _chk(q_max, (n_dof,), 'q_max')
-        jl_total = torch.zeros((), device=trajs.device, dtype=torch.float64)
+    return flags
+
+
+@_on_tensor_device
+def cost_terms_eval(trajs, n_dof, dt=0.0, k_gp=0.0, vel_fd=False, k_start=0.0, start_state=None, k_goal=0.0,
+                    goal_states=None, trajs_per_goal=1, k_smooth=0.0, k_jlim=0.0, q_min=None, q_max=None, jl_eps=0.0,
+                    out=None, accumulate=False, broadcast_jlim=True, terms=None):
+    """One pass over trajs (B,H,d) evaluating the enabled trajectory-only cost terms (mpb_cost_terms_eval).
+    A term is enabled by naming it in `terms` (iterable of 'gp','start','goal','smooth','jlim').
+    Returns (out (B,), jl_total 0-dim fp64 tensor or None)."""
+    B, H, d = trajs.shape
+    _chk(trajs, (B, H, d), 'trajs')
+    flags = _term_flags(terms, B, n_dof, vel_fd, start_state, goal_states, trajs_per_goal, q_min, q_max)
+    jl_total = torch.zeros((), device=trajs.device, dtype=torch.float64) if flags & TERM_JLIM else None
     if out is None:
         if accumulate:
             raise ValueError('accumulate needs an existing out buffer')
@@ -256,25 +265,7 @@ def cost_terms_grad(trajs, n_dof, grad_in=None, grad_out=None, apply=False, R=No
     `trajs` in place (mpb_cost_terms_grad).  Term arguments as cost_terms_eval."""
     B, H, d = trajs.shape
     _chk(trajs, (B, H, d), 'trajs')
-    terms = set(terms or ())
-    unknown = terms - {'gp', 'start', 'goal', 'smooth', 'jlim'}
-    if unknown:
-        raise ValueError(f'unknown cost terms {sorted(unknown)}')
-    flags = 0
-    if 'gp' in terms:
-        flags |= TERM_GP | (TERM_VEL_FD if vel_fd else 0)
-    if 'start' in terms:
-        flags |= TERM_START
-        _chk(start_state, (2 * n_dof,), 'start_state')
-    if 'goal' in terms:
-        flags |= TERM_GOAL
-        _chk(goal_states, (goal_states.shape[0], 2 * n_dof), 'goal_states')
-    if 'smooth' in terms:
-        flags |= TERM_SMOOTH
-    if 'jlim' in terms:
-        flags |= TERM_JLIM
-        _chk(q_min, (n_dof,), 'q_min')
-        _chk(q_max, (n_dof,), 'q_max')
+    flags = _term_flags(terms, B, n_dof, vel_fd, start_state, goal_states, trajs_per_goal, q_min, q_max)
     if grad_in is not None:
         _chk(grad_in, (B, H, d), 'grad_in')
     if not apply:
@@ -327,9 +318,8 @@ def traj_finite_difference(pos, dt):
     return out
 
 
-@_on_tensor_device
-def stomp_step(means, eps, samples, costs, weights, L, Sigma, geom, S, D, k_sigma, weight, lr, temperature,
-               n_iters=1, seed=0, iter0=0, particle_offset=0):
+def _stomp_shapes(means, samples, costs, weights, L, Sigma, S):
+    """The buffers every whole-call STOMP entry point takes, checked against the means' (P, H, d); returns it."""
     P, H, d = means.shape
     _chk(means, (P, H, d), 'means')
     _chk(samples, (P, S, H, d), 'samples')
@@ -337,12 +327,28 @@ def stomp_step(means, eps, samples, costs, weights, L, Sigma, geom, S, D, k_sigm
     _chk(weights, (P, S), 'weights')
     _chk(L, (H, H), 'L')
     _chk(Sigma, (H, H), 'Sigma')
+    return P, H, d
+
+
+def _stomp_head(eps, means, samples, costs, weights, L, Sigma, geom, S, D, k_sigma, weight, lr, temperature, workspace=False):
+    """The leading C arguments of a whole-call STOMP entry point, in the order of include/mpb.h: the buffers, geom_flags,
+    [workspace, its bytes,] P S H d D and the four floats.  eps / workspace = False: the entry point has no such parameter
+    (None: it has, and gets NULL)."""
+    P, H, d = means.shape
+    bufs = (means,) + (() if eps is False else (eps,)) + (samples, costs, weights, L, Sigma, geom.buf)
+    ws = () if workspace is False else (_ptr(workspace), 0 if workspace is None else workspace.numel() * 4)
+    return (*map(_ptr, bufs), int(geom.flags), *ws, P, S, H, d, D, float(k_sigma), float(weight), float(lr), float(temperature))
+
+
+@_on_tensor_device
+def stomp_step(means, eps, samples, costs, weights, L, Sigma, geom, S, D, k_sigma, weight, lr, temperature,
+               n_iters=1, seed=0, iter0=0, particle_offset=0):
+    P, H, d = _stomp_shapes(means, samples, costs, weights, L, Sigma, S)
     if eps is not None:
         _chk(eps, (n_iters, S, d, P, H), 'eps')
     _lib.check(_lib.lib().mpb_stomp_step(
-        _ptr(means), _ptr(eps), _ptr(samples), _ptr(costs), _ptr(weights), _ptr(L), _ptr(Sigma), _ptr(geom.buf),
-        int(geom.flags), P, S, H, d, D, float(k_sigma), float(weight), float(lr), float(temperature), int(n_iters),
-        int(seed) & (2 ** 64 - 1), int(iter0), int(particle_offset), _stream()), 'mpb_stomp_step')
+        *_stomp_head(eps, means, samples, costs, weights, L, Sigma, geom, S, D, k_sigma, weight, lr, temperature),
+        int(n_iters), _seed64(seed), int(iter0), int(particle_offset), _stream()), 'mpb_stomp_step')
 
 
 def stomp_workspace(P, S, H, d, device):
@@ -416,13 +422,7 @@ def stomp_run(means, eps, samples, costs, weights, L, Sigma, geom, S, D, k_sigma
     two-kernel loop otherwise (the C side decides).  status: a StompRunStatus the kernel reports a lost call to
     (include/mpb.h, "Failure contract"); means_copy: a second (P,H,d) destination of the final means, written by the same
     launch.  Returns the call's tag (0: two-kernel loop)."""
-    P, H, d = means.shape
-    _chk(means, (P, H, d), 'means')
-    _chk(samples, (P, S, H, d), 'samples')
-    _chk(costs, (P, S), 'costs')
-    _chk(weights, (P, S), 'weights')
-    _chk(L, (H, H), 'L')
-    _chk(Sigma, (H, H), 'Sigma')
+    P, H, d = _stomp_shapes(means, samples, costs, weights, L, Sigma, S)
     if eps is not None:
         _chk(eps, (n_iters, S, d, P, H), 'eps')
     if workspace is not None:
@@ -430,10 +430,8 @@ def stomp_run(means, eps, samples, costs, weights, L, Sigma, geom, S, D, k_sigma
     if means_copy is not None:
         _chk(means_copy, (P, H, d), 'means_copy')
     _lib.check(_lib.lib().mpb_stomp_run_checked(
-        _ptr(means), _ptr(eps), _ptr(samples), _ptr(costs), _ptr(weights), _ptr(L), _ptr(Sigma), _ptr(geom.buf),
-        int(geom.flags), _ptr(workspace), 0 if workspace is None else workspace.numel() * 4,
-        P, S, H, d, D, float(k_sigma), float(weight), float(lr), float(temperature), int(n_iters),
-        int(seed) & (2 ** 64 - 1), int(iter0), int(particle_offset),
+        *_stomp_head(eps, means, samples, costs, weights, L, Sigma, geom, S, D, k_sigma, weight, lr, temperature, workspace),
+        int(n_iters), _seed64(seed), int(iter0), int(particle_offset),
         None if status is None else status.ptr(), None if status is None else ctypes.byref(status.tag_c), _ptr(means_copy),
         _stream()), 'mpb_stomp_run')
     return 0 if status is None else status.note_launch()
@@ -441,18 +439,12 @@ def stomp_run(means, eps, samples, costs, weights, L, Sigma, geom, S, D, k_sigma
 
 class StompRunPlan:
     """The arguments of stomp_run for a planner whose buffers do not change between optimize() calls, validated ONCE and
-    kept as ctypes values: launch() converts nothing but the iteration count and the stream.  (stomp_run's per-call
+    kept on the library's side (mpb_stomp_plan_*): launch() hands over four values per call.  (stomp_run's per-call
     checks and conversions are ~15 us of host time -- 4 % of a 20-iteration call at C3.)  Device-noise calls only."""
 
     def __init__(self, means, samples, costs, weights, L, Sigma, geom, S, D, k_sigma, weight, lr, temperature, workspace,
                  seed, particle_offset, status):
-        P, H, d = means.shape
-        _chk(means, (P, H, d), 'means')
-        _chk(samples, (P, S, H, d), 'samples')
-        _chk(costs, (P, S), 'costs')
-        _chk(weights, (P, S), 'weights')
-        _chk(L, (H, H), 'L')
-        _chk(Sigma, (H, H), 'Sigma')
+        P, H, d = _stomp_shapes(means, samples, costs, weights, L, Sigma, S)
         _chk(workspace, tuple(workspace.shape), 'workspace')
         devs = {t.device for t in (means, samples, costs, weights, L, Sigma, geom.buf, workspace)}
         if len(devs) != 1:
@@ -462,23 +454,16 @@ class StompRunPlan:
         self.key = (means.data_ptr(), samples.data_ptr(), costs.data_ptr(), weights.data_ptr(), L.data_ptr(),
                     Sigma.data_ptr(), geom.buf.data_ptr(), workspace.data_ptr(), S, D, float(k_sigma), float(weight),
                     float(lr), float(temperature), int(seed), int(particle_offset))
-        self._keep = (means, samples, costs, weights, L, Sigma, geom, workspace, status)     # the pointers below stay valid
-        c = ctypes
-        self._head = (_ptr(means), c.c_void_p(0), _ptr(samples), _ptr(costs), _ptr(weights), _ptr(L), _ptr(Sigma),
-                      _ptr(geom.buf), c.c_int(int(geom.flags)), _ptr(workspace), c.c_size_t(workspace.numel() * 4),
-                      c.c_int(P), c.c_int(S), c.c_int(H), c.c_int(d), c.c_int(D), c.c_float(k_sigma), c.c_float(weight),
-                      c.c_float(lr), c.c_float(temperature))
-        self._seed = c.c_uint64(int(seed) & (2 ** 64 - 1))
-        self._poff = c.c_uint32(int(particle_offset))
+        # launch_timed's arguments (it builds the long form when called); they also keep the plan's pointers valid
+        self._call = (means, samples, costs, weights, L, Sigma, geom, S, D, k_sigma, weight, lr, temperature, workspace)
+        self._seed, self._poff = _seed64(seed), int(particle_offset)
         self._status = status
         self._status_ptr = status.ptr()
-        self._tag_ref = c.byref(status.tag_c)
-        # the same arguments kept on the library's side (mpb_stomp_plan_*): launch() hands over four values per call
-        h = c.c_void_p(0)
+        self._tag_ref = ctypes.byref(status.tag_c)
+        h = ctypes.c_void_p(0)
         _lib.check(_lib.lib().mpb_stomp_plan_create(
-            c.byref(h), _ptr(means), _ptr(samples), _ptr(costs), _ptr(weights), _ptr(L), _ptr(Sigma), _ptr(geom.buf), int(geom.flags),
-            _ptr(workspace), workspace.numel() * 4, P, S, H, d, D, float(k_sigma), float(weight), float(lr), float(temperature),
-            int(seed) & (2 ** 64 - 1), int(particle_offset), self._status_ptr), 'mpb_stomp_plan_create')
+            ctypes.byref(h), *_stomp_head(False, *self._call), self._seed, self._poff, self._status_ptr),
+            'mpb_stomp_plan_create')
         self._handle = h
         self._launch = _lib.lib().mpb_stomp_plan_launch
         self._destroy = _lib.lib().mpb_stomp_plan_destroy
@@ -492,7 +477,8 @@ class StompRunPlan:
     def launch_timed(self, n_iters, iter0, means_copy=None):
         """launch() with the kernel's own duration measured on the dispatch (mpb_stomp_run_timed): synchronises; returns ms."""
         ms = ctypes.c_float(0.0)
-        rc = _lib.lib().mpb_stomp_run_timed(*self._head, int(n_iters), self._seed, int(iter0), self._poff, self._status_ptr,
+        rc = _lib.lib().mpb_stomp_run_timed(*_stomp_head(None, *self._call), int(n_iters), self._seed,
+                                            int(iter0), self._poff, self._status_ptr,
                                             self._tag_ref, None if means_copy is None else means_copy.data_ptr(),
                                             torch.cuda.current_stream(self.device).cuda_stream, ctypes.byref(ms))
         if rc != 0:
@@ -544,7 +530,7 @@ def debug_stomp_normals(P, S, d, n_iters, device, seed=0, iter0=0, particle_offs
     out = torch.empty(n_iters, P, S, d, Hp, device=device, dtype=torch.float32)
     with torch.cuda.device(out.device):
         _lib.debug_check(_lib.debug_lib().mpb_debug_stomp_normals_h(_ptr(out), int(P), int(S), int(d), int(H), int(n_iters),
-                                                                    int(seed) & (2 ** 64 - 1), int(iter0), int(particle_offset), _stream()),
+                                                                    _seed64(seed), int(iter0), int(particle_offset), _stream()),
                          'mpb_debug_stomp_normals_h')
     return out
 
@@ -554,7 +540,7 @@ def debug_mppi_normals(NP, S, T, c, n_iters, device, seed=0, iter0=0):
     out = torch.empty(n_iters, NP, c, S, T, device=device, dtype=torch.float32)
     with torch.cuda.device(out.device):
         _lib.debug_check(_lib.debug_lib().mpb_debug_mppi_normals(_ptr(out), int(NP), int(S), int(T), int(c), int(n_iters),
-                                                                 int(seed) & (2 ** 64 - 1), int(iter0), _stream()), 'mpb_debug_mppi_normals')
+                                                                 _seed64(seed), int(iter0), _stream()), 'mpb_debug_mppi_normals')
     return out
 
 
@@ -571,18 +557,11 @@ def stomp_step_profile(means, samples, costs, weights, L, Sigma, geom, S, D, k_s
                        n_iters=50, seed=0, iter0=0, particle_offset=0):
     """Measurement aid: n_iters iterations of stomp_step (device noise) with per-dispatch HIP events; returns the average
     duration in ms of (sample+cost kernel, update kernel) inside that loop.  Synchronises the stream."""
-    P, H, d = means.shape
-    _chk(means, (P, H, d), 'means')
-    _chk(samples, (P, S, H, d), 'samples')
-    _chk(costs, (P, S), 'costs')
-    _chk(weights, (P, S), 'weights')
-    _chk(L, (H, H), 'L')
-    _chk(Sigma, (H, H), 'Sigma')
+    _stomp_shapes(means, samples, costs, weights, L, Sigma, S)
     ka, kb = ctypes.c_float(0.0), ctypes.c_float(0.0)
     _lib.check(_lib.lib().mpb_stomp_step_profile(
-        _ptr(means), _ptr(samples), _ptr(costs), _ptr(weights), _ptr(L), _ptr(Sigma), _ptr(geom.buf), int(geom.flags),
-        P, S, H, d, D, float(k_sigma), float(weight), float(lr), float(temperature), int(n_iters),
-        int(seed) & (2 ** 64 - 1), int(iter0), int(particle_offset), _stream(),
+        *_stomp_head(False, means, samples, costs, weights, L, Sigma, geom, S, D, k_sigma, weight, lr, temperature),
+        int(n_iters), _seed64(seed), int(iter0), int(particle_offset), _stream(),
         ctypes.cast(ctypes.pointer(ka), ctypes.c_void_p), ctypes.cast(ctypes.pointer(kb), ctypes.c_void_p)),
         'mpb_stomp_step_profile')
     return float(ka.value), float(kb.value)
@@ -605,7 +584,7 @@ def stomp_sample(means, eps, samples, L, S, seed=0, it=0, particle_offset=0, geo
     _lib.check(_lib.lib().mpb_stomp_sample(_ptr(means), _ptr(eps), _ptr(samples), _ptr(L),
                                           _ptr(None if geom is None else geom.buf),
                                           0 if geom is None else int(geom.flags), _ptr(costs), P, S, H, d,
-                                          float(k_sigma), float(weight), int(seed) & (2 ** 64 - 1), int(it),
+                                          float(k_sigma), float(weight), _seed64(seed), int(it),
                                           int(particle_offset), _stream()), 'mpb_stomp_sample')
 
 
@@ -701,8 +680,7 @@ def gpmp2_solve(x, start, goal, diag_mean, workspace, sigmas, dt, delta, trust_r
     _chk(x, (B, H, dim), 'x')
     _chk(start, (B, dim), 'start')
     _chk(goal, (B, dim), 'goal')
-    if diag_mean is not None:
-        assert diag_mean.dtype == torch.float64 and diag_mean.is_cuda and diag_mean.numel() == H * dim
+    _chk(diag_mean, (H * dim,), 'diag_mean', allow_none=True, dtype=torch.float64)
     _lib.check(_lib.lib().mpb_gpmp2_solve(
         _ptr(x), _ptr(start), _ptr(goal), _ptr(diag_mean), _ptr(workspace), _ptr(costs_out), B, H, dim // 2, int(n_fields),
         float(dt), float(sigmas[0]), float(sigmas[1]), float(sigmas[2]), float(sigmas[3]), float(delta), int(bool(trust_region)),
@@ -740,7 +718,7 @@ def mppi_step(mean, eps, scale_tril, cov_inv, state0, goal, ctrl_min, ctrl_max, 
         _ptr(controls), _ptr(states),
         _ptr(costs), _ptr(weights), _ptr(best_cost), _ptr(best_states), NP, S, T, c, 0, float(dt), float(k_sigma),
         float(weight), float(temp),
-        float(step_size), int(n_iters), int(seed) & (2 ** 64 - 1), int(iter0), _stream()), 'mpb_mppi_step')
+        float(step_size), int(n_iters), _seed64(seed), int(iter0), _stream()), 'mpb_mppi_step')
 
 
 @_on_tensor_device
@@ -780,16 +758,12 @@ def mvn_sample_dense(means, eps, tril_t, n, seed=0):
     """x = mean + L eps from a dense scale_tril handed over transposed (mpb_mvn_sample_dense): means (G,M) fp64, eps None or
     (n,G,M) fp64, tril_t (M,M) fp64 with tril_t[k,m] = L[m,k] -> (G*n, M) fp32, row mode * n + sample."""
     G, M = means.shape
-    for t, nm in ((means, 'means'), (tril_t, 'tril_t')):
-        if not (t.is_cuda and t.dtype == torch.float64 and t.is_contiguous()):
-            raise ValueError(f'{nm} must be a contiguous CUDA float64 tensor')
-    if tuple(tril_t.shape) != (M, M):
-        raise ValueError('tril_t must be (M, M)')
-    if eps is not None and not (eps.is_cuda and eps.dtype == torch.float64 and eps.is_contiguous() and tuple(eps.shape) == (n, G, M)):
-        raise ValueError('eps must be a contiguous CUDA float64 tensor of shape (n, G, M)')
+    _chk(means, (G, M), 'means', dtype=torch.float64)
+    _chk(tril_t, (M, M), 'tril_t', dtype=torch.float64)
+    _chk(eps, (n, G, M), 'eps', allow_none=True, dtype=torch.float64)
     out = torch.empty(G * n, M, device=means.device, dtype=torch.float32)
     _lib.check(_lib.lib().mpb_mvn_sample_dense(_ptr(out), _ptr(means), _ptr(eps), _ptr(tril_t), G, n, M,
-                                              int(seed) & (2 ** 64 - 1), _stream()), 'mpb_mvn_sample_dense')
+                                              _seed64(seed), _stream()), 'mpb_mvn_sample_dense')
     return out
 
 
@@ -799,26 +773,21 @@ def gp_prior_sample(means, eps, Udiag, Uoff, n, D, seed=0, scale_tril=None, out=
     With `scale_tril` (2H,2H fp64, planners.base.gp_prior_scale_tril) and H <= 128 the product runs as a GEMM on
     the matrix cores; otherwise as the per-chain forward substitution."""
     G, H, dim = means.shape
-    for t, nm in ((means, 'means'), (Udiag, 'Udiag'), (Uoff, 'Uoff')):
-        if not (t.is_cuda and t.dtype == torch.float64 and t.is_contiguous()):
-            raise ValueError(f'{nm} must be a contiguous CUDA float64 tensor')
-    assert tuple(Udiag.shape) == (H, 3) and tuple(Uoff.shape) == (H - 1, 4) and dim == 2 * D
-    if eps is not None:
-        if not (eps.is_cuda and eps.dtype == torch.float64 and eps.is_contiguous() and tuple(eps.shape) == (n, G, H * dim)):
-            raise ValueError('eps must be a contiguous CUDA float64 tensor of shape (n, G, H*2D)')
+    _chk(means, (G, H, 2 * D), 'means', dtype=torch.float64)
+    _chk(Udiag, (H, 3), 'Udiag', dtype=torch.float64)
+    _chk(Uoff, (H - 1, 4), 'Uoff', dtype=torch.float64)
+    _chk(eps, (n, G, H * dim), 'eps', allow_none=True, dtype=torch.float64)
     if out is None:
         out = torch.empty(G * n, H, dim, device=means.device, dtype=torch.float32)
     else:
         _chk(out, (G * n, H, dim), 'out')
     if scale_tril is not None and H <= 128:
-        if not (scale_tril.is_cuda and scale_tril.dtype == torch.float64 and scale_tril.is_contiguous()
-                and tuple(scale_tril.shape) == (2 * H, 2 * H)):
-            raise ValueError('scale_tril must be a contiguous CUDA float64 tensor of shape (2H, 2H)')
+        _chk(scale_tril, (2 * H, 2 * H), 'scale_tril', dtype=torch.float64)
         _lib.check(_lib.lib().mpb_gp_prior_sample_dense(_ptr(out), _ptr(means), _ptr(eps), _ptr(scale_tril), G, n, H, D,
-                                                       int(seed) & (2 ** 64 - 1), _stream()), 'mpb_gp_prior_sample_dense')
+                                                       _seed64(seed), _stream()), 'mpb_gp_prior_sample_dense')
         return out
     _lib.check(_lib.lib().mpb_gp_prior_sample(_ptr(out), _ptr(means), _ptr(eps), _ptr(Udiag), _ptr(Uoff), G, n, H, D,
-                                             int(seed) & (2 ** 64 - 1), _stream()), 'mpb_gp_prior_sample')
+                                             _seed64(seed), _stream()), 'mpb_gp_prior_sample')
     return out
 
 
@@ -833,17 +802,15 @@ def stoch_gpmp_step(means, means64, samples, costs, weights, Udiag, Uoff, scale_
     _chk(weights, (P, S), 'weights')
     _chk(start, (P, dim), 'start')
     _chk(goal, (P, dim), 'goal')
-    for t, nm, shp in ((means64, 'means64', (P, H, dim)), (Udiag, 'Udiag', (H, 3)), (Uoff, 'Uoff', (H - 1, 4))):
-        if not (t.is_cuda and t.dtype == torch.float64 and t.is_contiguous() and tuple(t.shape) == shp):
-            raise ValueError(f'{nm} must be a contiguous CUDA float64 tensor of shape {shp}')
-    if scale_tril is not None and not (scale_tril.is_cuda and scale_tril.dtype == torch.float64 and scale_tril.is_contiguous()
-                                       and tuple(scale_tril.shape) == (2 * H, 2 * H)):
-        raise ValueError('scale_tril must be a contiguous CUDA float64 tensor of shape (2H, 2H)')
+    _chk(means64, (P, H, dim), 'means64', dtype=torch.float64)
+    _chk(Udiag, (H, 3), 'Udiag', dtype=torch.float64)
+    _chk(Uoff, (H - 1, 4), 'Uoff', dtype=torch.float64)
+    _chk(scale_tril, (2 * H, 2 * H), 'scale_tril', allow_none=True, dtype=torch.float64)
     _lib.check(_lib.lib().mpb_stoch_gpmp_step(
         _ptr(means), _ptr(means64), _ptr(samples), _ptr(costs), _ptr(weights), _ptr(Udiag), _ptr(Uoff), _ptr(scale_tril),
         _ptr(start), _ptr(goal), _ptr(geom.buf), P, S, H, dim // 2, float(dt), float(sig_cost[0]), float(sig_cost[1]),
         float(sig_cost[2]), float(sig_cost[3]), float(sig_sample[0]), float(sig_sample[1]), float(sig_sample[2]),
-        float(temperature), float(step_size), int(n_iters), int(seed) & (2 ** 64 - 1), _stream()), 'mpb_stoch_gpmp_step')
+        float(temperature), float(step_size), int(n_iters), _seed64(seed), _stream()), 'mpb_stoch_gpmp_step')
 
 
 @_on_tensor_device

@@ -3,8 +3,8 @@
 Host side (this file): constants R / Sigma / scale_tril computed with the same torch calls as the
 reference (stomp.py:63-64, :68-95 -- SURVEY.md H2: they are ill-conditioned in fp32 and must be
 bit-identical), buffer ownership, noise-source selection.  Device side: mpb_stomp_step
-(csrc/mpb_kernels.hip) runs sample -> cost -> softmax -> covariance-weighted update for all
-``opt_iters`` iterations without returning to Python.
+(entry point in csrc/mpb_stomp_api.hip, kernels in csrc/mpb_kernels.hip) runs sample -> cost ->
+softmax -> covariance-weighted update for all ``opt_iters`` iterations without returning to Python.
 """
 import time
 
