@@ -189,6 +189,8 @@ int mpb_field_cost_points_vjp(const float *pts, const float *geom, const float *
  *      else (n_iters, S, d, P, H): pre-drawn standard normals in the reference's draw order
  *      (one MultivariateNormal.sample((S,d)) of batch shape (P,) and event shape (H,) per iteration).
  * samples (P,S,H,d), costs (P,S), weights (P,S): outputs of the LAST iteration (all required).
+ *      A persistent launch (mpb_stomp_run*) writes them for its last iteration ONLY -- once per launch, never per iteration;
+ *      with n_iters = 0 they are not written at all.
  * Alignment: means, eps, samples, L, Sigma, geom (and the workspace / means_copy of mpb_stomp_run*) must be 16-byte aligned --
  *      the kernels move them as 16-byte vectors; a pointer that is not is refused with MPB_E_INVALID (allocations of hipMalloc /
  *      PyTorch-ROCm are 256-byte aligned; a VIEW at an odd element offset is what trips this).

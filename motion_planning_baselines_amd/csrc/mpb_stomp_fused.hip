@@ -9,6 +9,11 @@
 //   * L (permuted MFMA image), Sigma, the broad-phase grid + obstacle table and the particle mean live in LDS for the
 //     whole launch; the samples of an iteration stay in the waves' LDS tiles for the weighted-noise reduction
 //     (stomp.py:199-211), which therefore reads LDS instead of re-reading the 14.7 MB of samples from L2;
+//   * samples, costs and weights are OUTPUTS of the launch's last iteration (include/mpb.h) and leave the chip once per launch:
+//     in the exchange / single-chunk layouts an epilogue behind the iteration loop stores them from what the last iteration left
+//     in the tiles, in cst[] and in registers (the loop body does not touch the three pointers); the two-batch layout, whose
+//     tiles are reused inside an iteration, stores in place under a wave-uniform test on the last iteration.  Until round 7 every
+//     iteration wrote them: 14.7 MB of samples per iteration at C3 that the next iteration overwrote, half of it reaching HBM;
 //   * a particle with S > 16 is shared by nc = ceil(S / 16) workgroups: each reduces its own 16 samples to
 //     (m_k = max logit, z_k = sum exp(logit - m_k), D_k = sum exp(logit - m_k) (sample - mean)), publishes that (3.6 KB)
 //     and combines the nc partials IN CHUNK ORDER -- every partner computes bit-identical new means, so the copies
@@ -257,7 +262,12 @@ __global__ __launch_bounds__(FUSED_THREADS, 4) void stomp_fused_kernel(
 #ifdef FUSED_T_PRE_STATS
     int pre_miss_ = 0;
 #endif
+    float w_out = 0.f;                                // (NB = 1) this thread's weight of the last iteration that ran
     for (int it = 0; it < n_run; ++it) {
+        // samples, costs and weights are the launch's OUTPUTS, and only the last iteration's can be observed: the next
+        // iteration overwrites them inside the same launch.  NB = 1 stores nothing in the loop (epilogue below); two
+        // batches store under this wave-uniform test
+        const bool last_it = it + 1 == n_run;
         // (NB > 1) partials of the batches, as the exchange path would publish them
         float pm0 = -3.0e38f, pz0 = 0.f, pe0 = 0.f, pm1 = -3.0e38f, pz1 = 0.f, pe1 = 0.f;
         f32x4 sd0 = {0.f, 0.f, 0.f, 0.f}, sd1 = {0.f, 0.f, 0.f, 0.f};      // Sigma times the partial of batch 0 / 1 (or of the only chunk), waves 0-3
@@ -285,7 +295,7 @@ __global__ __launch_bounds__(FUSED_THREADS, 4) void stomp_fused_kernel(
 #pragma nounroll
         for (int bt = 0; bt < NB; ++bt) {
         if (NB > 1) { s = bt * FUSED_WAVES + wave; live = s < S; }
-        // ============ A. samples of this iteration: x = mean + noise, stored, kept packed in the wave's tile
+        // ============ A. samples of this iteration: x = mean + noise, kept packed in the wave's tile
         FSTAMP(0);
         float nz[16];
         stomp_noise_row<DCH>(nt, lane, nz);
@@ -313,11 +323,9 @@ __global__ __launch_bounds__(FUSED_THREADS, 4) void stomp_fused_kernel(
             for (int c = 0; c < DCH; ++c) nt[h * DCH + c] = x[c];
         }
         __builtin_amdgcn_wave_barrier();
-#ifdef FUSED_T_A_NOSTORE   // (wrong-result timing switch, tuning builds only)
-        if (false) {
-#else
-        if (live) {
-#endif
+        // (two batches: the tile is reused by the next batch, so the samples leave here -- in the launch's LAST iteration only;
+        // NB = 1: behind the loop, see "outputs" there)
+        if (NB > 1 && last_it && live) {
             const f32x4* pk4 = reinterpret_cast<const f32x4*>(nt);
             f32x4* out4 = reinterpret_cast<f32x4*>(samples + ((size_t)p * S + s) * N);     // uniform
 #pragma unroll
@@ -373,7 +381,7 @@ __global__ __launch_bounds__(FUSED_THREADS, 4) void stomp_fused_kernel(
             const float cw = weight * (k_sigma * (float)csum);
             if (lane == 0) {
                 cst[wave] = cw;
-                if (live) {
+                if (NB > 1 && last_it && live) {
                     if (bad) reinterpret_cast<unsigned*>(costs)[(size_t)p * S + s] = 0x7FC00000u;
                     else costs[(size_t)p * S + s] = cw;
                 }
@@ -471,6 +479,10 @@ __global__ __launch_bounds__(FUSED_THREADS, 4) void stomp_fused_kernel(
             // kernel, where recomputing them is twelve s_add on the scalar unit)
             uint32_t slo = seed_lo, shi = seed_hi;
             asm volatile("" : "+s"(slo), "+s"(shi));
+            // (and, two batches, the particle's counter word: the table-driven walk's kernel kept a vector copy of it across the
+            // cost phase -- 8 B of scratch)
+            uint32_t pg = particle_offset + (uint32_t)p;
+            if (NB > 1) asm volatile("" : "+s"(pg));
             // (a k-block pipelined form -- Philox of block q+1 issued between the MFMAs of block q, straight-line code -- was
             // measured 3 % slower: the waves of a SIMD already overlap one wave's matrix work with another's Philox)
             // issue priority by progress through the draws (mpb_stomp_noise.h).  Measured against it on the same box
@@ -486,7 +498,7 @@ __global__ __launch_bounds__(FUSED_THREADS, 4) void stomp_fused_kernel(
             if constexpr (PAIRED) {
                 if (wave < PAIR_STRIDE) {
                     stomp_noise_bf16_pair<DCH, FUSED_NOISE_PRIO>(Limg, acc, eps ? eps + (size_t)it_n * eps_stride : nullptr, P, S, p, jv, gv,
-                                                                 particle_offset + (uint32_t)p, (uint32_t)s_n, (uint32_t)(s_n + PAIR_STRIDE),
+                                                                 pg, (uint32_t)s_n, (uint32_t)(s_n + PAIR_STRIDE),
                                                                  iter0 + (uint32_t)it_n, slo, shi, 3 - (wave >> 1));
                     // (the partner's tile: its samples were consumed before barrier 2 like this wave's own)
                     stomp_noise_to_tile_pair<DCH>(nt, nt + PAIR_STRIDE * (H * NT_STRIDE), acc, lane_w);
@@ -515,11 +527,11 @@ __global__ __launch_bounds__(FUSED_THREADS, 4) void stomp_fused_kernel(
                 };
                 if constexpr (PRE)
                     stomp_noise_bf16<DCH, FUSED_NOISE_PRIO>(Limg, acc, eps ? eps + (size_t)it_n * eps_stride + (size_t)(s_n < S ? s_n : 0) * DCH * P * H : nullptr,
-                                                            P, p, jv, gv, particle_offset + (uint32_t)p, (uint32_t)s_n, iter0 + (uint32_t)it_n,
+                                                            P, p, jv, gv, pg, (uint32_t)s_n, iter0 + (uint32_t)it_n,
                                                             slo, shi, 3 - (wave >> 2), prefetch);
                 else
                     stomp_noise_bf16<DCH, FUSED_NOISE_PRIO>(Limg, acc, eps ? eps + (size_t)it_n * eps_stride + (size_t)(s_n < S ? s_n : 0) * DCH * P * H : nullptr,
-                                                            P, p, jv, gv, particle_offset + (uint32_t)p, (uint32_t)s_n, iter0 + (uint32_t)it_n,
+                                                            P, p, jv, gv, pg, (uint32_t)s_n, iter0 + (uint32_t)it_n,
                                                             slo, shi, 3 - (wave >> 2));
                 stomp_noise_to_tile(nt, acc, lane_w);         // (the samples packed in the tile were consumed before barrier 2)
             }
@@ -616,14 +628,16 @@ __global__ __launch_bounds__(FUSED_THREADS, 4) void stomp_fused_kernel(
             f_own = fast_expf(mb - m_all);
         }
         FSTAMP(8);
-        // ============ E. weights out; mean += lr * (sum_k f_k Sigma D_k) / z   (z >= 1: it holds the term exp(0) of the maximum;
+        // ============ E. weights; mean += lr * (sum_k f_k Sigma D_k) / z   (z >= 1: it holds the term exp(0) of the maximum;
         //              one v_rcp_f32 instead of an IEEE division per use, round 5)
         const float rz = fast_rcpf(z_all);
         if (NB > 1) {
             const int sl0 = tq & 15;
-            if (tq < FUSED_WAVES && sl0 < S) weights[(size_t)p * S + sl0] = pe0 * f_own0 * rz;
-            if (tq < FUSED_WAVES && sl < S) weights[(size_t)p * S + sl] = pe1 * f_own * rz;
-        } else if (tq < FUSED_WAVES && sl < S) weights[(size_t)p * S + sl] = ex * f_own * rz;
+            if (last_it && tq < FUSED_WAVES && sl0 < S) weights[(size_t)p * S + sl0] = pe0 * f_own0 * rz;
+            if (last_it && tq < FUSED_WAVES && sl < S) weights[(size_t)p * S + sl] = pe1 * f_own * rz;
+        } else {
+            w_out = ex * f_own * rz;           // (of sample chunk * 16 + (lane & 15): stored behind the loop)
+        }
         if (NB == 1 && nc > 1) {
             if (tq < N) mean_l[tq] += lr * (dsum * rz);
         } else if (wave < 4) {
@@ -649,6 +663,37 @@ __global__ __launch_bounds__(FUSED_THREADS, 4) void stomp_fused_kernel(
     if (pre_miss_ > 1) atomicAdd(&g_pre_miss[wave], (unsigned)(pre_miss_ - 1));     // (the last iteration has no prefetch)
 #endif
     const int aborted = s_abort;                        // (block-uniform: last written before a barrier every thread passed)
+    // ---- outputs (NB = 1): samples, costs and weights of the LAST iteration, written once per launch.  No noise was drawn
+    //      in that iteration (it_n < n_run failed), so every wave's tile still holds its packed samples, cst[wave] its cost,
+    //      and w_out the weight.  A lost call (or n_iters = 0) writes nothing: include/mpb.h leaves the outputs undefined there.
+    if (NB == 1 && !aborted && n_run > 0) {
+        if (live) {
+            const f32x4* pk4 = reinterpret_cast<const f32x4*>(nt);
+            f32x4* out4 = reinterpret_cast<f32x4*>(samples + ((size_t)p * S + s) * N);     // uniform
+#pragma unroll
+            for (int k = 0; k < (16 * DCH + 63) / 64; ++k) {
+                const unsigned idx = (unsigned)lane + 64u * k;
+                if (idx < 16u * DCH) out4[idx] = pk4[idx];
+            }
+            if (lane == 0) {
+                // the model tag check of phase B (a forged model tag, or a chained field under the one-field flag), redone from
+                // the headers: the NaN poison reaches the costs as it did from inside the loop
+                bool bad = false;
+                if (MODEL != 0) {
+                    for (const float* gp = geom;;) {
+                        const GeomView G = geom_view(gp);
+                        if (G.model != MODEL || (!CHAIN && G.next != 0)) bad = true;
+                        if (!CHAIN || G.next == 0) break;
+                        gp += G.next;
+                    }
+                }
+                if (bad) reinterpret_cast<unsigned*>(costs)[(size_t)p * S + s] = 0x7FC00000u;
+                else costs[(size_t)p * S + s] = cst[wave];
+            }
+        }
+        const int sl = chunk * FUSED_WAVES + (tid & 15);
+        if (tid < FUSED_WAVES && sl < S) weights[(size_t)p * S + sl] = w_out;
+    }
     if (!aborted && chunk == 0 && tid < N) {
         const float m = mean_l[tid];
         means[(size_t)p * N + tid] = m;

@@ -242,7 +242,10 @@ __global__ __launch_bounds__(FUSED_THREADS, 4) void stomp_fused_hx_kernel(
         using B1 = std::integral_constant<int, 1>;
         using B2 = std::integral_constant<int, 2>;
         float e[16];
-        operand(hcw, e);                                   // every wave draws the columns of ITS chunk
+        // every wave draws the columns of ITS chunk -- up front, except the second-chunk wave of an injected-noise call: it
+        // loads them behind the first chunk's product (below), sixteen registers less where the phase holds the most
+        const bool own_late = HC == 2 && eps != nullptr && hcw != 0;
+        if (!own_late) operand(hcw, e);
         if (HC == 1) {
             product(B0{}, e);
         } else {
@@ -271,6 +274,7 @@ __global__ __launch_bounds__(FUSED_THREADS, 4) void stomp_fused_hx_kernel(
                     operand(0, e0);
                 }
                 product(B1{}, e0);                         // same accumulation order as the two-kernel path: kc = 0, then 1
+                if (own_late) operand(hcw, e);
                 product(B2{}, e);
             }
         }
@@ -290,6 +294,10 @@ __global__ __launch_bounds__(FUSED_THREADS, 4) void stomp_fused_hx_kernel(
     if (n_run > 0) draw_noise(0, (chunk * nb) * RB + rw);
 
     for (int it = 0; it < n_run; ++it) {
+        // samples, costs and weights are the launch's OUTPUTS and only the last iteration's can be observed (the next one
+        // overwrites them inside the same launch): a wave's tile is reused within an iteration here, so the stores stay in
+        // their phases and run under this wave-uniform test (mpb_stomp_fused.hip: NB = 1 stores behind the loop)
+        const bool last_it = it + 1 == n_run;
         float m_run = -3.0e38f, z_run = 0.f, d_run[EPT];
 #pragma unroll
         for (int u = 0; u < EPT; ++u) d_run[u] = 0.f;
@@ -298,7 +306,7 @@ __global__ __launch_bounds__(FUSED_THREADS, 4) void stomp_fused_hx_kernel(
             HX_FRESH_LANE();
             const int s = (chunk * nb + bt) * RB + rw;                       // this wave's sample in this batch
             const bool live = s < S;
-            // ============ A. samples: x = mean + noise (zero at both ends, stomp.py:105-106), stored, kept packed in the tile
+            // ============ A. samples: x = mean + noise (zero at both ends, stomp.py:105-106), kept packed in the tile (last iteration: stored)
             const int h = 64 * hcw + lane;
             const bool on = h < H;
             float x[DX];
@@ -322,7 +330,9 @@ __global__ __launch_bounds__(FUSED_THREADS, 4) void stomp_fused_hx_kernel(
             __builtin_amdgcn_wave_barrier();
             if (live) {
                 float* sbase = samples + (((size_t)p * S + s) * H + 64 * hcw) * d;       // uniform
-                const int nfl = min(H - 64 * hcw, 64) * d;                              // floats of this chunk (<= 0: none)
+                // (the last-iteration test masks the stores through the float count instead of joining `live`: as a branch of its
+                // own it is invariant in the pass loop, the compiler clones the loop on it, and the run-time-d kernels pay in scratch)
+                const int nfl = last_it ? min(H - 64 * hcw, 64) * d : 0;                 // floats of this chunk to store (<= 0: none)
                 if (((H * d) & 3) == 0 && ((64 * d) & 3) == 0) {
                     const f32x4* pk4 = reinterpret_cast<const f32x4*>(nt);
                     f32x4* out4 = reinterpret_cast<f32x4*>(sbase);
@@ -388,7 +398,7 @@ __global__ __launch_bounds__(FUSED_THREADS, 4) void stomp_fused_hx_kernel(
             const float cw = weight * (k_sigma * (poisoned ? 0.f : c0 + c1));
             const int sl = (chunk * nb + bt) * RB + rq;
             const bool carries = (lq & 15) < RB && sl < S;                 // (all FOUR rows of a wave carry the pass's costs: below)
-            if (tq < RB && sl < S) reinterpret_cast<unsigned*>(costs)[(size_t)p * S + sl] = poisoned ? 0x7FC00000u : __float_as_uint(cw);
+            if (last_it && tq < RB && sl < S) reinterpret_cast<unsigned*>(costs)[(size_t)p * S + sl] = poisoned ? 0x7FC00000u : __float_as_uint(cw);
             const float xs = carries ? -cw * inv_temperature : -3.0e38f;
             // (row reductions over replicated rows and DPP row_newbcast in the weighted sum: csrc/mpb_stomp_fused.hip, phase C -- same bits
             // as the full-wave reductions over one carrying row, no v_readlane)
@@ -490,9 +500,9 @@ __global__ __launch_bounds__(FUSED_THREADS, 4) void stomp_fused_hx_kernel(
                 }
             }
         }
-        // ============ E. weights out, delta (transposed) -> mean += lr * Sigma @ delta on the matrix cores
+        // ============ E. weights out (last iteration), delta (transposed) -> mean += lr * Sigma @ delta on the matrix cores
         const float rz = fast_rcpf(z_all);          // (z >= 1; mpb_stomp_fused.hip, phase E)
-        for (int i = tq; i < nb * RB; i += FUSED_THREADS) {
+        for (int i = tq; last_it && i < nb * RB; i += FUSED_THREADS) {
             const int sl = chunk * nb * RB + i;
             if (sl < S) weights[(size_t)p * S + sl] = ewl[i] * fast_expf(mbl[i / RB] - m_all) * rz;
         }

@@ -7,7 +7,8 @@
 #   * c5 (<14,1,2> at P = 4096) and H = 128 PMC passes        -> <tag>_pmc_stomp_c5.json, <tag>_pmc_stomp_h128.json
 #   * large-B sweep                                             -> <tag>_large_b_sweep.txt
 #   * shapes beyond H = 64 / gradient evaluators                -> <tag>_other_shapes.txt
-# rocprofv3 counter passes run with --kernel-trace only (never with a sys / hip / hsa trace).
+# rocprofv3 counter passes run with --kernel-trace only (never with a sys / hip / hsa trace); every rocprofv3 pass and every bench.py
+# run has a time limit of its own, and the run stops at the first step that fails (set -e).
 set -e
 TAG=${1:-rXX}
 export TMPDIR=/tmp
@@ -21,9 +22,9 @@ echo "gpmp2 passes done"
 for drv in chomp mppi; do
   OUT=gpurun_out/prof_${TAG}_$drv
   mkdir -p $OUT
-  rocprofv3 --kernel-trace --stats -d $OUT/stats -o s -- python3 scripts/prof_$drv.py > $OUT/stats.log 2>&1
-  rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_SMEM SQ_INSTS_LDS SQ_WAVES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY -d $OUT/pmc1 -o p -- python3 scripts/prof_$drv.py > $OUT/pmc1.log 2>&1
-  rocprofv3 --kernel-trace --pmc SQ_ACTIVE_INST_VALU SQ_INSTS_MFMA SQ_INSTS_VMEM SQ_INSTS_BRANCH SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_WAIT_INST_LDS SQ_ACTIVE_INST_SCA -d $OUT/pmc2 -o p -- python3 scripts/prof_$drv.py > $OUT/pmc2.log 2>&1
+  timeout -k 10 600 rocprofv3 --kernel-trace --stats -d $OUT/stats -o s -- python3 scripts/prof_$drv.py > $OUT/stats.log 2>&1
+  timeout -k 10 600 rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_SMEM SQ_INSTS_LDS SQ_WAVES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY -d $OUT/pmc1 -o p -- python3 scripts/prof_$drv.py > $OUT/pmc1.log 2>&1
+  timeout -k 10 600 rocprofv3 --kernel-trace --pmc SQ_ACTIVE_INST_VALU SQ_INSTS_MFMA SQ_INSTS_VMEM SQ_INSTS_BRANCH SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_WAIT_INST_LDS SQ_ACTIVE_INST_SCA -d $OUT/pmc2 -o p -- python3 scripts/prof_$drv.py > $OUT/pmc2.log 2>&1
   python3 scripts/pmc_summary.py $OUT ${TAG}_$drv > /dev/null
   echo "$drv passes done"
 done
@@ -34,11 +35,11 @@ python3 scripts/bench_large_b.py > profiles/${TAG}_large_b_sweep.txt 2> gpurun_o
 echo "large-B sweep done"
 ( python3 scripts/bench_hx.py; python3 scripts/bench_grad.py ) > profiles/${TAG}_other_shapes.txt 2> gpurun_out/${TAG}_other.err
 # the bench line LAST: it reads the instruction counts of the PMC summaries written above (profiles/<tag>_pmc_*.json)
-python3 bench.py --full --steps 20 --warmup 5 > $TMPDIR/${TAG}_bench.json
+timeout -k 10 900 python3 bench.py --full --steps 20 --warmup 5 > $TMPDIR/${TAG}_bench.json
 cp $TMPDIR/${TAG}_bench.json profiles/${TAG}_bench.json
 echo "bench done"
 # the two-rank rehearsal on this box's one GPU (gloo: ranks share the device; the 8-GPU node runs the same command on RCCL)
-MPB_DIST_BACKEND=gloo python3 bench.py --full --gpus 2 --steps 20 --warmup 5 > profiles/${TAG}_bench_2ranks_one_gpu_gloo.json || true
+MPB_DIST_BACKEND=gloo timeout -k 10 900 python3 bench.py --full --gpus 2 --steps 20 --warmup 5 > profiles/${TAG}_bench_2ranks_one_gpu_gloo.json || true
 echo "two-rank rehearsal done"
 # round 6: refuse to finish on stale counters -- every profiles/*_pmc_*.json that bench.py would read (the newest per kind) must carry the
 # fingerprint of the kernel sources of THIS tree (scripts/pmc_summary.py stamps it; a file this run did not re-take, or one taken
