@@ -54,8 +54,9 @@ extern "C" {
  *                        kernel at H = 64, which serves list-grid scenes): a workspace sized by an older library is too small;
  *                        geometry buffers of version 7 (LIST broad-phase grid, per field) are accepted next to version 6;
  *                        MPB_MAX_DOF 8 -> 12; mpb_gpmp2_solve takes the low-rank form wherever n_fields (H - 1) <= 127 (same
- *                        results to the solver's fp64 rounding). */
-#define MPB_ABI_VERSION 6
+ *                        results to the solver's fp64 rounding);
+ *           7            batched RRT-Connect (mpb_rrt_connect_*) and mpb_collision_check added; nothing else changed. */
+#define MPB_ABI_VERSION 7
 #define MPB_VERSION_TUNING_BUILD 0x40000000
 int mpb_version(void);
 const char *mpb_last_error(void);
@@ -518,6 +519,59 @@ int mpb_mvn_sample_dense(float *out, const double *means, const double *eps, con
 int mpb_mt19937_normals(float *out, int n, int n_calls, const uint32_t *state_in, int pos, int final_idx, uint32_t *state_out,
                         const uint16_t *jump_idx, const int *jump_cnt, int jump_stride, const int *segs, int n_segs,
                         uint32_t *work, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Collision predicate (build-defined; the reference asks torch_robotics' task.compute_collision, rrt_base.py:100-101):
+ * a configuration is in collision iff the per-waypoint collision cost above is positive,
+ *   gap = sum_f s_f sum_l relu(margin + r_l - min_o sdf_o(x_l(q))) > 0.
+ * q (N,D); in_collision (N) bytes, 0 / 1; gap (N) optional (may be NULL): the hinge sum.  geom_flags as above.
+ * ------------------------------------------------------------------------------------------- */
+int mpb_collision_check(const float *q, const float *geom, int geom_flags, unsigned char *in_collision, float *gap,
+                        int N, int D, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Batched RRT-Connect -- replaces RRTConnect._run_optimization (rrt_connect.py:93-192) with RRTBase.get_pre_sample /
+ * remove_last_pre_sample / get_nearest_node (rrt_base.py:59-63, :94-98, :115-119), extend_path, safe_path and
+ * purge_duplicates_from_traj (utils.py:4-50), for B independent problems at once (what MultiSampleBasedPlanner fans out
+ * over a process pool).  One persistent launch, one workgroup per problem; workgroups never wait on each other.
+ *
+ * workspace: mpb_rrt_connect_workspace_bytes(B, max_nodes, n_pre, D) bytes, 16-byte aligned (0 = shape refused, see
+ *   mpb_last_error).  Layout in 32-bit words: 16 words (magic, B, max_nodes, n_pre, D, Dp = D rounded up to 4);
+ *   B x 16 words per problem (status, iterations used, nodes of tree 0, nodes of tree 1, swap bit, pool length);
+ *   node configurations (B, 2, max_nodes, Dp) fp32, zero padded; parents (B, 2, max_nodes) int32 (-1: root);
+ *   pool lists (B, (n_pre + 1) / 2) words of two uint16 indices into pre_samples.  Tree 0 is rooted at the start, tree 1
+ *   at the goal; the reference's name swap is the swap bit (`continue` leaves an iteration before the swap-back, so a
+ *   returned path may run goal -> start).
+ * mpb_rrt_connect_init: roots, counts, the full pool list 0 .. n_pre - 1, and the start / goal collision check
+ *   (rrt_connect.py:100-101: status START_OR_GOAL_IN_COLLISION, no path).  start, goal (B,D).
+ * mpb_rrt_connect_run: iterations iter0 .. min(iter0 + n_iters, total_iters) - 1 of every problem still RUNNING, resumed
+ *   from the workspace (call in chunks with iter0 advancing; a problem that reaches total_iters becomes EXHAUSTED_ITERS).
+ *   pre_samples: the pool, (n_pre, D) shared by all problems (pre_stride = 0) or one per problem (pre_stride = floats
+ *   between two problems' pools).  sample_idx: NULL -> the index of the iteration's target in the CURRENT pool list is
+ *   mulhi(Philox4x32-10(counter = (problem_offset + b, iteration, tag, 0), key = seed).x, pool length); else
+ *   (B, total_iters) int32 recorded indices (the reference's torch.randperm(len(pool))[0]), clamped to the list.
+ *   One index per iteration, also in iterations that `continue`.  A reached target (allclose) is deleted from the list,
+ *   order kept; an empty list ends the problem with POOL_EMPTY (refilling is not served on the device).
+ *   paths (B,Lmax,D), lengths (B): the purged path and its node count for FOUND problems (the layout mpb_traj_resample
+ *   takes); PATH_TOO_LONG when the un-purged path has more than Lmax nodes.  status (B): copy of the status words.
+ *   A tree that would exceed max_nodes ends with TREE_FULL (max_nodes >= total_iters + 1 cannot).
+ * ------------------------------------------------------------------------------------------- */
+#define MPB_RRT_RUNNING 0
+#define MPB_RRT_FOUND 1
+#define MPB_RRT_EXHAUSTED_ITERS 2
+#define MPB_RRT_START_OR_GOAL_IN_COLLISION 3
+#define MPB_RRT_POOL_EMPTY 4
+#define MPB_RRT_TREE_FULL 5
+#define MPB_RRT_PATH_TOO_LONG 6
+#define MPB_RRT_MAX_PRE_SAMPLES 16384
+size_t mpb_rrt_connect_workspace_bytes(int B, int max_nodes, int n_pre, int D);
+int mpb_rrt_connect_init(void *workspace, size_t workspace_bytes, const float *start, const float *goal,
+                         const float *geom, int geom_flags, int B, int max_nodes, int n_pre, int D, void *stream);
+int mpb_rrt_connect_run(void *workspace, size_t workspace_bytes, const float *geom, int geom_flags,
+                        const float *pre_samples, size_t pre_stride, const int *sample_idx, float *paths,
+                        int *lengths, int *status, int B, int max_nodes, int n_pre, int D, int Lmax, int iter0,
+                        int n_iters, int total_iters, float step_size, float n_radius, uint64_t seed,
+                        uint32_t problem_offset, void *stream);
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,453 @@
+// mpb_rrt_connect.hip -- batched RRT-Connect (rrt_connect.py:93-192 over rrt_base.py:94-119 and utils.py:4-50) and the
+// stand-alone collision predicate it rests on.
+//
+// The reference fans n_trajectories independent RRT-Connect planners out over a process pool
+// (multi_sample_based_planner.py); independent tree pairs are batch-parallel.  Here ONE persistent launch runs up to
+// n_iters iterations for B problems, one single-wave workgroup per problem:
+//   - workgroups never wait on each other, there is no spin wait, and every loop is bounded by n_iters, max_nodes, the
+//     pool length or the point count of one extension;
+//   - nearest node: the lanes stride over the tree's nodes, (distance, index) is reduced lexicographically (the lowest
+//     index wins a tie, as torch.argmin does);
+//   - extension (utils.py:4-14): one lane per point of the linspace, 64 points per trip, the first point in collision is
+//     the count of trailing zeros of a ballot -- and the trips after it are never evaluated (safe_path only needs the
+//     first one, utils.py:25-30);
+//   - the trees (configurations padded to float4s, int32 parents) live in a caller-allocated global workspace; tree 0 is
+//     rooted at the start, tree 1 at the goal, and the reference's name swap is one bit per problem (Q15: `continue`
+//     leaves an iteration BEFORE the swap-back, so the roles do not simply alternate and a path can run goal -> start);
+//   - the sample pool is a uint16 indirection list in LDS over the read-only pre_samples array; a reached target is
+//     deleted order-preserving (rrt_base.py:59-63) by a parallel shift.
+// Collision predicate (build-defined, torch_robotics being absent): a configuration is in collision iff the package's
+// per-waypoint collision cost  sum_f s_f sum_l relu(margin + r_l - min_o sdf_o(x_l))  is positive; evaluated with the
+// evaluators of mpb_geom.h (broad-phase grid where the field has one, the compile-time Panda model where geom_flags
+// allows, the exhaustive walk otherwise; chained fields in turn).
+#include "mpb_common.h"
+#include "mpb_host.h"
+#include "mpb_geom.h"
+#include "mpb_model_panda.h"
+
+#define RRT_MAGIC 0x52525443
+#define RRT_GLOBAL_WORDS 16      // workspace header: magic, B, max_nodes, n_pre, D, Dp
+#define RRT_HDR_WORDS 16         // per problem: status, iterations used, count 0, count 1, swap bit, pool length
+#define RRT_MAX_PRE 16384
+#define RRT_MAX_PTS (1 << 20)    // points of one extension (dist / step_size + 2): far beyond any sane step size
+
+struct RrtLayout {
+    size_t hdr, nodes, parents, pool, total;   // offsets in 32-bit words
+    int Dp, pool_words;
+};
+
+__host__ __device__ static inline RrtLayout rrt_layout(int B, int max_nodes, int n_pre, int D) {
+    RrtLayout L;
+    L.Dp = (D + 3) & ~3;
+    L.pool_words = (n_pre + 1) / 2;
+    L.hdr = RRT_GLOBAL_WORDS;
+    L.nodes = L.hdr + (size_t)B * RRT_HDR_WORDS;
+    L.parents = L.nodes + (size_t)B * 2 * max_nodes * L.Dp;
+    L.pool = L.parents + (size_t)B * 2 * max_nodes;
+    L.total = L.pool + (size_t)B * L.pool_words;
+    return L;
+}
+
+// Collision cost of one configuration per lane, chained fields in turn.  Block-uniform control flow: every thread of the
+// block calls it (a lane without work passes any valid configuration).  `staged` is the field whose grid sits in LDS.
+template <int MODEL>
+__device__ __forceinline__ float rrt_config_cost(const float* __restrict__ geom, unsigned* gridw, float4* otab,
+                                                 const float*& staged, const float (&q)[MPB_MAX_DOF]) {
+    float c = 0.f;
+    for (const float* gp = geom; gp != nullptr; gp = geom_next(gp)) {
+        const GeomView G = geom_view(gp);
+        if (grid_usable(G)) {
+            if (staged != gp) {
+                __syncthreads();
+                grid_stage(G, gridw, otab, threadIdx.x, blockDim.x);
+                __syncthreads();
+                staged = gp;
+            }
+            if (MODEL == PandaModel::ID && G.model == PandaModel::ID)
+                c = fmaf(G.fscale, waypoint_cost_grid_model<PandaModel>(G, gridw, otab, q), c);
+            else
+                c = fmaf(G.fscale, waypoint_cost_grid(G, gridw, otab, q), c);
+        } else {
+            float dq[MPB_MAX_DOF];
+            c = fmaf(G.fscale, waypoint_cost<false>(G, q, dq), c);
+        }
+    }
+    return c;
+}
+
+// torch.allclose(a, b) element: |a - b| <= atol + rtol |b| with the defaults rtol 1e-5, atol 1e-8
+__device__ __forceinline__ bool rrt_close(float a, float b) { return fabsf(a - b) <= 1e-8f + 1e-5f * fabsf(b); }
+
+// ---- stand-alone predicate: N configurations (N, D) -> flag (N) [and the hinge sum] --------------------------------
+template <int MODEL>
+__global__ __launch_bounds__(256) void collision_check_kernel(const float* __restrict__ q_in, const float* __restrict__ geom,
+                                                              unsigned char* __restrict__ flag, float* __restrict__ gap, int N,
+                                                              int D) {
+    __shared__ unsigned gridw[MPB_GRID_MAX_CELLS];
+    __shared__ float4 otab[MPB_GRID_MAX_SPH + 1];
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    const float* row = q_in + (size_t)min(i, N - 1) * D;
+    float q[MPB_MAX_DOF];
+#pragma unroll
+    for (int k = 0; k < MPB_MAX_DOF; ++k) q[k] = (k < D) ? row[k] : 0.f;
+    const float* staged = nullptr;
+    const float c = rrt_config_cost<MODEL>(geom, gridw, otab, staged, q);
+    if (i < N) {
+        flag[i] = (c > 0.f) ? 1 : 0;
+        if (gap != nullptr) gap[i] = c;
+    }
+}
+
+// ---- workspace initialisation: roots, counts, pool lists, status, start / goal collision check ---------------------
+template <int MODEL>
+__global__ __launch_bounds__(64) void rrt_init_kernel(int* __restrict__ ws, const float* __restrict__ start,
+                                                      const float* __restrict__ goal, const float* __restrict__ geom, int B,
+                                                      int max_nodes, int n_pre, int D) {
+    __shared__ unsigned gridw[MPB_GRID_MAX_CELLS];
+    __shared__ float4 otab[MPB_GRID_MAX_SPH + 1];
+    const int b = blockIdx.x, lane = threadIdx.x;
+    const RrtLayout L = rrt_layout(B, max_nodes, n_pre, D);
+    if (b == 0 && lane < RRT_GLOBAL_WORDS) {
+        const int g[6] = {RRT_MAGIC, B, max_nodes, n_pre, D, L.Dp};
+        int v = 0;
+#pragma unroll
+        for (int k = 0; k < 6; ++k) v = (lane == k) ? g[k] : v;
+        ws[lane] = v;
+    }
+    // lane 0 checks the start, every other lane the goal
+    const float* row = (lane == 0 ? start : goal) + (size_t)b * D;
+    float q[MPB_MAX_DOF];
+#pragma unroll
+    for (int k = 0; k < MPB_MAX_DOF; ++k) q[k] = (k < D) ? row[k] : 0.f;
+    const float* staged = nullptr;
+    const float c = rrt_config_cost<MODEL>(geom, gridw, otab, staged, q);
+    const bool hit = __ballot(c > 0.f) != 0ull;
+    float* nodes = reinterpret_cast<float*>(ws) + L.nodes + (size_t)b * 2 * max_nodes * L.Dp;
+    int* parents = ws + L.parents + (size_t)b * 2 * max_nodes;
+    if (lane < L.Dp) {
+        nodes[lane] = (lane < D) ? start[(size_t)b * D + lane] : 0.f;
+        nodes[(size_t)max_nodes * L.Dp + lane] = (lane < D) ? goal[(size_t)b * D + lane] : 0.f;
+    }
+    if (lane < 2) parents[(size_t)lane * max_nodes] = -1;
+    unsigned* pool = reinterpret_cast<unsigned*>(ws) + L.pool + (size_t)b * L.pool_words;
+    for (int w = lane; w < L.pool_words; w += 64) pool[w] = (unsigned)(2 * w) | ((unsigned)(2 * w + 1) << 16);
+    if (lane < RRT_HDR_WORDS) {
+        int* H = ws + L.hdr + (size_t)b * RRT_HDR_WORDS;
+        int v = 0;
+        if (lane == 0) v = hit ? MPB_RRT_START_OR_GOAL_IN_COLLISION : MPB_RRT_RUNNING;
+        if (lane == 2 || lane == 3) v = 1;
+        if (lane == 5) v = n_pre;
+        H[lane] = v;
+    }
+}
+
+struct RrtArgs {
+    int* ws;
+    const float* geom;
+    const float* pre;
+    size_t pre_stride;
+    const int* sample_idx;
+    float* paths;
+    int* lengths;
+    int* status;
+    int B, D, max_nodes, n_pre, Lmax, iter0, n_iters, total_iters;
+    float step, radius;
+    uint32_t seed_lo, seed_hi, problem_offset;
+};
+
+// ---- the persistent kernel ------------------------------------------------------------------------------------------
+template <int DT, int MODEL>
+__global__ __launch_bounds__(64) void rrt_connect_kernel(const RrtArgs a) {
+    __shared__ unsigned gridw[MPB_GRID_MAX_CELLS];
+    __shared__ float4 otab[MPB_GRID_MAX_SPH + 1];
+    __shared__ unsigned short pool[RRT_MAX_PRE];
+    constexpr int DM = DT ? DT : MPB_MAX_DOF;
+    constexpr int DM4 = (DM + 3) / 4;
+    const int D = DT ? DT : a.D;
+    const int b = blockIdx.x, lane = threadIdx.x;
+    const RrtLayout L = rrt_layout(a.B, a.max_nodes, a.n_pre, D);
+    int* H = a.ws + L.hdr + (size_t)b * RRT_HDR_WORDS;
+    int status = H[0];
+    if (status != MPB_RRT_RUNNING) {                       // block-uniform: a finished problem costs nothing
+        if (lane == 0) a.status[b] = status;
+        return;
+    }
+    int cnt[2] = {H[2], H[3]};
+    int bit = H[4], plen = H[5];
+    float* nodes_b = reinterpret_cast<float*>(a.ws) + L.nodes + (size_t)b * 2 * a.max_nodes * L.Dp;
+    int* parents_b = a.ws + L.parents + (size_t)b * 2 * a.max_nodes;
+    unsigned short* pool_g = reinterpret_cast<unsigned short*>(a.ws + L.pool + (size_t)b * L.pool_words);
+    for (int i = lane; i < plen; i += 64) pool[i] = pool_g[i];
+    const float* pre_b = a.pre + (size_t)b * a.pre_stride;
+    float* path_b = a.paths + (size_t)b * a.Lmax * D;
+    const float* staged = nullptr;
+    __syncthreads();
+
+    // one extension (extend_path + safe_path + the append): grows tree t from its node nearest to `tq` towards `tq`;
+    // returns false when the extension's first point is in collision (safe_path's []) or the tree is full
+    float nq[MPB_MAX_DOF];
+    auto extend = [&](int t, const float (&tq)[MPB_MAX_DOF]) -> bool {
+        const float* nd = nodes_b + (size_t)t * a.max_nodes * L.Dp;
+        const int n = cnt[t];
+        float best = 3.0e38f;
+        int bi = 0x7FFFFFFF;
+        for (int i = lane; i < n; i += 64) {
+            const float4* r = reinterpret_cast<const float4*>(nd + (size_t)i * L.Dp);
+            float d2 = 0.f;
+#pragma unroll
+            for (int kk = 0; kk < DM4; ++kk) {
+                if (4 * kk < L.Dp) {
+                    const float4 v = r[kk];
+                    const float e[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+                    for (int c = 0; c < 4; ++c) {
+                        if (4 * kk + c < DM) {
+                            const float df = __fsub_rn(e[c], tq[4 * kk + c]);
+                            d2 = __fadd_rn(d2, __fmul_rn(df, df));
+                        }
+                    }
+                }
+            }
+            const float ds = sqrtf(d2);
+            if (ds < best) { best = ds; bi = i; }
+        }
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {
+            const float od = __shfl_xor(best, off, 64);
+            const int oi = __shfl_xor(bi, off, 64);
+            if (od < best || (od == best && oi < bi)) { best = od; bi = oi; }
+        }
+        const float dist = best;
+        float q1[MPB_MAX_DOF], dl[MPB_MAX_DOF];
+        const float f = (dist > a.radius) ? a.radius / dist : 1.0f;
+#pragma unroll
+        for (int k = 0; k < MPB_MAX_DOF; ++k) {
+            q1[k] = (k < DM && k < D) ? nd[(size_t)bi * L.Dp + k] : 0.f;
+            const float df = __fsub_rn(tq[k], q1[k]);
+            // (utils.py:7-8: the far end clamped to n_radius; the point count below is from the UNCLAMPED distance)
+            const float q2 = (dist > a.radius) ? __fadd_rn(q1[k], __fmul_rn(df, f)) : tq[k];
+            dl[k] = __fsub_rn(q2, q1[k]);
+        }
+        const float cntf = fminf(dist / a.step, (float)(RRT_MAX_PTS - 2));
+        const int n_pts = (int)cntf + 2;
+        const float lstep = 1.0f / (float)(n_pts - 1);
+        // linspace(0, 1, n_pts)[p] as ATen's CPU kernel evaluates it (from the near end of each half)
+        auto point = [&](int p, float (&q)[MPB_MAX_DOF]) {
+            const float al = (p < n_pts / 2) ? __fmul_rn(lstep, (float)p) : __fsub_rn(1.0f, __fmul_rn(lstep, (float)(n_pts - 1 - p)));
+#pragma unroll
+            for (int k = 0; k < MPB_MAX_DOF; ++k) q[k] = (k < DM) ? __fadd_rn(q1[k], __fmul_rn(dl[k], al)) : 0.f;
+        };
+        int first = -1;
+        for (int base = 0; base < n_pts; base += 64) {
+            const int p = base + lane;
+            float q[MPB_MAX_DOF];
+            point(min(p, n_pts - 1), q);
+            const float c = rrt_config_cost<MODEL>(a.geom, gridw, otab, staged, q);
+            const unsigned long long m = __ballot(p < n_pts && c > 0.f);
+            if (m != 0ull) {
+                first = base + (int)__builtin_ctzll(m);
+                break;
+            }
+        }
+        if (first == 0) return false;
+        point(first < 0 ? n_pts - 1 : first - 1, nq);
+        if (n >= a.max_nodes) {
+            status = MPB_RRT_TREE_FULL;
+            return false;
+        }
+        float* dst = nodes_b + ((size_t)t * a.max_nodes + n) * L.Dp;
+        float v = 0.f;
+#pragma unroll
+        for (int k = 0; k < DM; ++k) v = (lane == k) ? nq[k] : v;
+        if (lane < L.Dp) dst[lane] = v;
+        if (lane == 0) parents_b[(size_t)t * a.max_nodes + n] = bi;
+        cnt[t] = n + 1;
+        __syncthreads();                                   // the node is read back by the next nearest-node scan
+        return true;
+    };
+
+    int it = a.iter0;
+    const int it_end = min(a.iter0 + a.n_iters, a.total_iters);
+    for (; it < it_end && status == MPB_RRT_RUNNING; ++it) {
+        if (plen == 0) { status = MPB_RRT_POOL_EMPTY; break; }
+        bit ^= 1;                                          // rrt_connect.py:126-128
+        const int t1 = bit, t2 = bit ^ 1;
+        int idx;
+        if (a.sample_idx != nullptr) {
+            idx = a.sample_idx[(size_t)b * a.total_iters + it];
+            idx = min(max(idx, 0), plen - 1);
+        } else {
+            const uint4 r = philox4x32_10(make_uint4(a.problem_offset + (uint32_t)b, (uint32_t)it, RRT_MAGIC, 0u),
+                                          make_uint2(a.seed_lo, a.seed_hi));
+            idx = (int)__umulhi(r.x, (uint32_t)plen);
+        }
+        const float* trow = pre_b + (size_t)pool[idx] * D;
+        float tq[MPB_MAX_DOF];
+#pragma unroll
+        for (int k = 0; k < MPB_MAX_DOF; ++k) tq[k] = (k < DM && k < D) ? trow[k] : 0.f;
+        if (!extend(t1, tq)) continue;                     // :142-143 -- BEFORE the swap-back (Q15)
+        float n1[MPB_MAX_DOF];
+        bool reached = true;
+#pragma unroll
+        for (int k = 0; k < MPB_MAX_DOF; ++k) {
+            n1[k] = nq[k];
+            if (k < DM && k < D) reached = reached && rrt_close(n1[k], tq[k]);
+        }
+        if (reached) {                                     // :149-150, rrt_base.py:59-63: delete entry idx, keep the order
+            for (int base = idx; base < plen - 1; base += 64) {
+                const int i = base + lane;
+                const unsigned short v = pool[min(i + 1, plen - 1)];
+                __syncthreads();
+                if (i < plen - 1) pool[i] = v;
+                __syncthreads();
+            }
+            --plen;
+        }
+        if (!extend(t2, n1)) continue;                     // :161-162
+        bit ^= 1;                                          // :168-170
+        bool joined = true;
+#pragma unroll
+        for (int k = 0; k < MPB_MAX_DOF; ++k)
+            if (k < DM && k < D) joined = joined && rrt_close(n1[k], nq[k]);
+        if (!joined) continue;
+        // ---- :173-185: retrace(n2)[:-1] + reversed(retrace(n1)), then purge_duplicates_from_traj (utils.py:33-50)
+        const float* ndA = nodes_b + (size_t)t2 * a.max_nodes * L.Dp;
+        const float* ndB = nodes_b + (size_t)t1 * a.max_nodes * L.Dp;
+        const int* paA = parents_b + (size_t)t2 * a.max_nodes;
+        const int* paB = parents_b + (size_t)t1 * a.max_nodes;
+        int lenA = 0, lenB = 0;
+        for (int j = paA[cnt[t2] - 1]; j >= 0 && lenA < cnt[t2]; j = paA[j]) ++lenA;
+        for (int j = cnt[t1] - 1; j >= 0 && lenB < cnt[t1]; j = paB[j]) ++lenB;
+        const int Lraw = lenA + lenB;
+        ++it;
+        if (Lraw > a.Lmax) { status = MPB_RRT_PATH_TOO_LONG; break; }
+        {
+            int pos = lenA - 1;
+            for (int j = paA[cnt[t2] - 1]; j >= 0 && pos >= 0; j = paA[j], --pos)
+                if (lane < D) path_b[(size_t)pos * D + lane] = ndA[(size_t)j * L.Dp + lane];
+            pos = lenA;
+            for (int j = cnt[t1] - 1; j >= 0 && pos < Lraw; j = paB[j], ++pos)
+                if (lane < D) path_b[(size_t)pos * D + lane] = ndB[(size_t)j * L.Dp + lane];
+        }
+        __syncthreads();
+        int len = Lraw;
+        if (Lraw > 2) {
+            const bool on = lane < D;
+            const float row0 = on ? path_b[lane] : 0.f;
+            const float last = on ? path_b[(size_t)(Lraw - 1) * D + lane] : 0.f;
+            float cur = row0, lastsel = row0;
+            int out = 0;
+            bool any_sel = false;
+            for (int j = 0; j + 1 < Lraw; ++j) {
+                const float nxt = on ? path_b[(size_t)(j + 1) * D + lane] : 0.f;
+                if (__ballot(on && fabsf(nxt - cur) > 1e-6f) != 0ull) {   // row j differs from row j + 1: selected
+                    if (!any_sel) {
+                        any_sel = true;
+                        if (j > 0 && __ballot(on && !rrt_close(cur, row0)) != 0ull) {
+                            if (on) path_b[(size_t)out * D + lane] = row0;
+                            ++out;
+                        }
+                    }
+                    if (on) path_b[(size_t)out * D + lane] = cur;
+                    ++out;
+                    lastsel = cur;
+                }
+                cur = nxt;
+            }
+            if (!any_sel) {                                 // (every row equals its successor: the first row stands for all)
+                if (on) path_b[lane] = row0;
+                out = 1;
+            }
+            if (__ballot(on && !rrt_close(lastsel, last)) != 0ull) {
+                if (on) path_b[(size_t)out * D + lane] = last;
+                ++out;
+            }
+            len = out;
+        }
+        if (lane == 0) a.lengths[b] = len;
+        status = MPB_RRT_FOUND;
+        break;
+    }
+    if (status == MPB_RRT_RUNNING && it >= a.total_iters) status = MPB_RRT_EXHAUSTED_ITERS;
+    __syncthreads();
+    for (int i = lane; i < plen; i += 64) pool_g[i] = pool[i];
+    if (lane == 0) {
+        H[0] = status; H[1] = it; H[2] = cnt[0]; H[3] = cnt[1]; H[4] = bit; H[5] = plen;
+        a.status[b] = status;
+    }
+}
+
+// ---- host side ------------------------------------------------------------------------------------------------------
+static int rrt_shape_check(const char* who, int B, int max_nodes, int n_pre, int D) {
+    if (n_pre > RRT_MAX_PRE) return mpb_failf(MPB_E_UNSUPPORTED, "%s: n_pre = %d exceeds the %d pool entries the kernel keeps in LDS", who, n_pre, RRT_MAX_PRE);
+    if (D > MPB_MAX_DOF) return mpb_failf(MPB_E_UNSUPPORTED, "%s: D = %d exceeds MPB_MAX_DOF = %d", who, D, MPB_MAX_DOF);
+    if (B < 0 || max_nodes < 2 || n_pre < 1 || D < 1) return mpb_failf(MPB_E_INVALID, "%s: bad shape (B %d, max_nodes %d, n_pre %d, D %d)", who, B, max_nodes, n_pre, D);
+    if ((double)B * 2.0 * max_nodes * 16.0 > 2.0e9) return mpb_failf(MPB_E_UNSUPPORTED, "%s: B x max_nodes too large", who);
+    return MPB_OK;
+}
+
+extern "C" size_t mpb_rrt_connect_workspace_bytes(int B, int max_nodes, int n_pre, int D) {
+    if (rrt_shape_check("mpb_rrt_connect_workspace_bytes", B, max_nodes, n_pre, D) != MPB_OK) return 0;
+    return 4 * rrt_layout(B, max_nodes, n_pre, D).total;
+}
+
+static bool rrt_use_model(int geom_flags, int D) {
+    return (geom_flags & 0xFF) == PandaModel::ID && (geom_flags & 0x100) && D == PandaModel::N_DOF;
+}
+
+extern "C" int mpb_rrt_connect_init(void* workspace, size_t workspace_bytes, const float* start, const float* goal,
+                                    const float* geom, int geom_flags, int B, int max_nodes, int n_pre, int D, void* stream) {
+    const int rc = rrt_shape_check("mpb_rrt_connect_init", B, max_nodes, n_pre, D);
+    if (rc != MPB_OK) return rc;
+    if (!workspace || !start || !goal || !geom) return mpb_fail(MPB_E_INVALID, "mpb_rrt_connect_init: null pointer");
+    if (mpb_misaligned16(workspace, geom)) return mpb_fail(MPB_E_INVALID, "mpb_rrt_connect_init: workspace and geom must be 16-byte aligned");
+    const size_t need = 4 * rrt_layout(B, max_nodes, n_pre, D).total;
+    if (workspace_bytes < need) return mpb_failf(MPB_E_INVALID, "mpb_rrt_connect_init: workspace of %zu bytes, %zu needed", workspace_bytes, need);
+    if (B == 0) return MPB_OK;
+    if (rrt_use_model(geom_flags, D))
+        hipLaunchKernelGGL(rrt_init_kernel<PandaModel::ID>, dim3(B), dim3(64), 0, (hipStream_t)stream, (int*)workspace, start, goal, geom, B, max_nodes, n_pre, D);
+    else
+        hipLaunchKernelGGL(rrt_init_kernel<0>, dim3(B), dim3(64), 0, (hipStream_t)stream, (int*)workspace, start, goal, geom, B, max_nodes, n_pre, D);
+    return mpb_check_launch("mpb_rrt_connect_init");
+}
+
+extern "C" int mpb_rrt_connect_run(void* workspace, size_t workspace_bytes, const float* geom, int geom_flags,
+                                   const float* pre_samples, size_t pre_stride, const int* sample_idx, float* paths,
+                                   int* lengths, int* status, int B, int max_nodes, int n_pre, int D, int Lmax, int iter0,
+                                   int n_iters, int total_iters, float step_size, float n_radius, uint64_t seed,
+                                   uint32_t problem_offset, void* stream) {
+    const int rc = rrt_shape_check("mpb_rrt_connect_run", B, max_nodes, n_pre, D);
+    if (rc != MPB_OK) return rc;
+    if (!workspace || !geom || !pre_samples || !paths || !lengths || !status) return mpb_fail(MPB_E_INVALID, "mpb_rrt_connect_run: null pointer");
+    if (mpb_misaligned16(workspace, geom)) return mpb_fail(MPB_E_INVALID, "mpb_rrt_connect_run: workspace and geom must be 16-byte aligned");
+    const size_t need = 4 * rrt_layout(B, max_nodes, n_pre, D).total;
+    if (workspace_bytes < need) return mpb_failf(MPB_E_INVALID, "mpb_rrt_connect_run: workspace of %zu bytes, %zu needed", workspace_bytes, need);
+    if (Lmax < 2 || iter0 < 0 || n_iters < 0 || total_iters < 0 || iter0 > total_iters)
+        return mpb_fail(MPB_E_INVALID, "mpb_rrt_connect_run: bad Lmax / iteration range / pre_stride");
+    if (!(step_size > 0.f) || !(n_radius > 0.f)) return mpb_fail(MPB_E_INVALID, "mpb_rrt_connect_run: step_size and n_radius must be positive");
+    if (B == 0) return MPB_OK;
+    const RrtArgs a = {(int*)workspace, geom, pre_samples, pre_stride, sample_idx, paths, lengths, status, B, D, max_nodes, n_pre, Lmax,
+                       iter0, n_iters, total_iters, step_size, n_radius, (uint32_t)seed, (uint32_t)(seed >> 32), problem_offset};
+    const hipStream_t s = (hipStream_t)stream;
+    if (rrt_use_model(geom_flags, D)) hipLaunchKernelGGL((rrt_connect_kernel<7, PandaModel::ID>), dim3(B), dim3(64), 0, s, a);
+    else if (D == 2) hipLaunchKernelGGL((rrt_connect_kernel<2, 0>), dim3(B), dim3(64), 0, s, a);
+    else if (D == 3) hipLaunchKernelGGL((rrt_connect_kernel<3, 0>), dim3(B), dim3(64), 0, s, a);
+    else if (D == 7) hipLaunchKernelGGL((rrt_connect_kernel<7, 0>), dim3(B), dim3(64), 0, s, a);
+    else hipLaunchKernelGGL((rrt_connect_kernel<0, 0>), dim3(B), dim3(64), 0, s, a);
+    return mpb_check_launch("mpb_rrt_connect_run");
+}
+
+extern "C" int mpb_collision_check(const float* q, const float* geom, int geom_flags, unsigned char* in_collision, float* gap,
+                                   int N, int D, void* stream) {
+    if (D > MPB_MAX_DOF) return mpb_failf(MPB_E_UNSUPPORTED, "mpb_collision_check: D = %d exceeds MPB_MAX_DOF = %d", D, MPB_MAX_DOF);
+    if (N < 0 || D < 1) return mpb_fail(MPB_E_INVALID, "mpb_collision_check: bad shape");
+    if (N == 0) return MPB_OK;
+    if (!q || !geom || !in_collision) return mpb_fail(MPB_E_INVALID, "mpb_collision_check: null pointer");
+    if (mpb_misaligned16(geom)) return mpb_fail(MPB_E_INVALID, "mpb_collision_check: geom must be 16-byte aligned");
+    const dim3 grid((N + 255) / 256);
+    if (rrt_use_model(geom_flags, D))
+        hipLaunchKernelGGL(collision_check_kernel<PandaModel::ID>, grid, dim3(256), 0, (hipStream_t)stream, q, geom, in_collision, gap, N, D);
+    else
+        hipLaunchKernelGGL(collision_check_kernel<0>, grid, dim3(256), 0, (hipStream_t)stream, q, geom, in_collision, gap, N, D);
+    return mpb_check_launch("mpb_collision_check");
+}

@@ -996,3 +996,98 @@ def debug_mt19937_uniforms(n, n_calls, device, generator=None):
             _ptr(tb.idx), _ptr(tb.cnt), tb.stride, _ptr(tb.segs), tb.n_segs, _ptr(_mt_work(tb, out.device)), _stream()),
             'mpb_debug_mt19937_uniforms')
     return out, MT.state_after(host, tb.total, st_out.cpu().numpy().view(np.uint32))
+
+
+# ---- collision predicate and batched RRT-Connect (csrc/mpb_rrt_connect.hip) -------------------------------------------
+RRT_RUNNING, RRT_FOUND, RRT_EXHAUSTED_ITERS, RRT_START_OR_GOAL_IN_COLLISION, RRT_POOL_EMPTY, RRT_TREE_FULL, \
+    RRT_PATH_TOO_LONG = range(7)                                  # include/mpb.h MPB_RRT_*
+RRT_STATUS_NAMES = ('RUNNING', 'FOUND', 'EXHAUSTED_ITERS', 'START_OR_GOAL_IN_COLLISION', 'POOL_EMPTY', 'TREE_FULL',
+                    'PATH_TOO_LONG')
+RRT_MAX_PRE_SAMPLES = 16384
+
+
+@_on_tensor_device
+def collision_check(q, geom, with_gap=False):
+    """(N, D) configurations -> bool (N,): the collision cost of the configuration is positive (mpb_collision_check);
+    with_gap also returns that cost (the hinge sum)."""
+    N, D = q.shape
+    _chk(q, (N, D), 'q')
+    if D != geom.n_dof:
+        raise ValueError(f'q has {D} columns, the geometry {geom.n_dof} degrees of freedom')
+    flag = torch.empty(N, device=q.device, dtype=torch.bool)
+    gap = torch.empty(N, device=q.device, dtype=torch.float32) if with_gap else None
+    _lib.check(_lib.lib().mpb_collision_check(_ptr(q), _ptr(geom.buf), int(geom.flags), _ptr(flag), _ptr(gap), N, D, _stream()),
+               'mpb_collision_check')
+    return (flag, gap) if with_gap else flag
+
+
+class RRTWorkspace:
+    """The caller-allocated state of a batch of RRT-Connect problems: trees, pool lists, status words (layout: include/mpb.h)."""
+
+    def __init__(self, B, max_nodes, n_pre, D, device):
+        nbytes = int(_lib.lib().mpb_rrt_connect_workspace_bytes(int(B), int(max_nodes), int(n_pre), int(D)))
+        if nbytes == 0:
+            msg = _lib.lib().mpb_last_error()
+            raise _lib.MPBError(f'mpb_rrt_connect_workspace_bytes: {msg.decode() if msg else "?"}')
+        self.B, self.max_nodes, self.n_pre, self.D = int(B), int(max_nodes), int(n_pre), int(D)
+        self.nbytes = nbytes
+        self.buf = torch.zeros(nbytes // 4, device=device, dtype=torch.int32)
+
+
+@_on_tensor_device
+def rrt_connect_init(ws_buf, ws, start, goal, geom):
+    """Roots, counts, pool lists, status words and the start / goal collision check of every problem (mpb_rrt_connect_init).
+    `ws_buf` is ws.buf (passed so that the launch lands on its device)."""
+    _chk(start, (ws.B, ws.D), 'start')
+    _chk(goal, (ws.B, ws.D), 'goal')
+    if ws.D != geom.n_dof:
+        raise ValueError(f'the problems have {ws.D} columns, the geometry {geom.n_dof} degrees of freedom')
+    _lib.check(_lib.lib().mpb_rrt_connect_init(_ptr(ws_buf), ws.nbytes, _ptr(start), _ptr(goal), _ptr(geom.buf), int(geom.flags),
+                                              ws.B, ws.max_nodes, ws.n_pre, ws.D, _stream()), 'mpb_rrt_connect_init')
+
+
+@_on_tensor_device
+def rrt_connect_run(ws_buf, ws, geom, pre_samples, sample_idx, paths, lengths, status, iter0, n_iters, total_iters, step_size,
+                    n_radius, seed=0, problem_offset=0):
+    """Iterations iter0 .. min(iter0 + n_iters, total_iters) - 1 of every problem still RUNNING (mpb_rrt_connect_run).
+    pre_samples (n_pre, D) shared or (B, n_pre, D) one pool per problem; sample_idx None (device Philox) or (B, total_iters) int32."""
+    B, D = ws.B, ws.D
+    if pre_samples.ndim == 2:
+        _chk(pre_samples, (ws.n_pre, D), 'pre_samples')
+        stride = 0
+    else:
+        _chk(pre_samples, (B, ws.n_pre, D), 'pre_samples')
+        stride = ws.n_pre * D
+    _chk(sample_idx, (B, total_iters), 'sample_idx', allow_none=True, dtype=torch.int32)
+    Lmax = paths.shape[1]
+    _chk(paths, (B, Lmax, D), 'paths')
+    _chk(lengths, (B,), 'lengths', dtype=torch.int32)
+    _chk(status, (B,), 'status', dtype=torch.int32)
+    _lib.check(_lib.lib().mpb_rrt_connect_run(
+        _ptr(ws_buf), ws.nbytes, _ptr(geom.buf), int(geom.flags), _ptr(pre_samples), stride, _ptr(sample_idx), _ptr(paths),
+        _ptr(lengths), _ptr(status), B, ws.max_nodes, ws.n_pre, D, Lmax, int(iter0), int(n_iters), int(total_iters),
+        float(step_size), float(n_radius), _seed64(seed), int(problem_offset) & 0xFFFFFFFF, _stream()), 'mpb_rrt_connect_run')
+
+
+def rrt_connect_trees(ws):
+    """The trees of a workspace, for tests and rendering: dict of `nodes` (B, 2, max_nodes, D) fp32, `parents`
+    (B, 2, max_nodes) int32 (-1: root), `counts` (B, 2), `iters` (B,) iterations used, `status` (B,), `swap` (B,) and
+    `pool_len` (B,), `pool` (B, n_pre) int32 (entries beyond pool_len are stale).  Tree 0 is rooted at the start, tree 1 at the goal."""
+    B, M, D = ws.B, ws.max_nodes, ws.D
+    Dp = (D + 3) // 4 * 4
+    w = ws.buf
+    glob = w[:6].tolist()
+    if glob[0] != 0x52525443 or glob[1:5] != [B, M, ws.n_pre, D]:
+        raise ValueError('the workspace was not initialised for these shapes (rrt_connect_init)')
+    o = 16
+    hdr = w[o:o + 16 * B].reshape(B, 16)
+    o += 16 * B
+    nodes = w[o:o + B * 2 * M * Dp].view(torch.float32).reshape(B, 2, M, Dp)[..., :D]
+    o += B * 2 * M * Dp
+    parents = w[o:o + B * 2 * M].reshape(B, 2, M)
+    o += B * 2 * M
+    pw = (ws.n_pre + 1) // 2
+    pool = w[o:o + B * pw].reshape(B, pw)
+    pool = torch.stack((pool & 0xFFFF, (pool >> 16) & 0xFFFF), dim=-1).reshape(B, 2 * pw)[:, :ws.n_pre]
+    return dict(nodes=nodes, parents=parents, counts=hdr[:, 2:4], iters=hdr[:, 1], status=hdr[:, 0], swap=hdr[:, 4],
+                pool_len=hdr[:, 5], pool=pool)

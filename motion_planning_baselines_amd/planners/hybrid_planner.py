@@ -7,9 +7,15 @@ handed to an optimisation-based planner (GPMP2 / StochGPMP of this package) that
 The reference converts the paths with torch_robotics' ``smoothen_trajectory`` / ``tensor_linspace_v1``
 (external, CPU, one path at a time in a Python loop: hybrid_planner.py:44-59).  Here ALL paths are converted
 by one launch of mpb_traj_resample (arc-length-uniform linear resampling, average velocity on the interior
-points -- build-defined); the sample-based planner itself is the caller's (duck-typed:
-``optimize(refill_samples_buffer=True, ...) -> list of (n_i, D) tensors or None``, ``start_state_pos``,
-``goal_state_pos``) -- RRT is outside this build's scope.
+points -- build-defined).
+
+The sample-based half is served by this package: RRTConnect / MultiSampleBasedPlanner (planners/rrt_connect.py,
+planners/multi_sample_based_planner.py) grow all tree pairs in one batched launch on the GPU.  A sample-based planner
+that offers ``optimize_batched() -> (paths (N, Lmax, D), lengths (N,), status (N,))`` device tensors is fed straight
+into mpb_traj_resample -- no host round trip, no padding loop; a problem without a path gets the straight line
+start -> goal, written on the device (hybrid_planner.py:47-51).  Any other sample-based planner stays the caller's
+(duck-typed: ``optimize(refill_samples_buffer=True, ...) -> list of (n_i, D) tensors or None``, ``start_state_pos``,
+``goal_state_pos``) and takes the list path below.  RRTStar / InfRRTStar (rewiring) are outside this build's scope.
 """
 import torch
 
@@ -47,9 +53,30 @@ class HybridPlanner(MPPlanner):
         out = ops.traj_resample(padded.to(self.device), lengths.to(self.device), H, dt)
         return out.unsqueeze(0)                                   # 'n h d -> 1 n h d' (:64)
 
+    def batched_paths_to_initial_means(self, paths, lengths):
+        """(paths (N, Lmax, D), lengths (N,)) device tensors of optimize_batched -> (1, N, H, 2D) initial particle means;
+        lengths[n] == 0 (no path) becomes the straight line start -> goal, on the device."""
+        sp = self.sample_based_planner
+        N, D = paths.shape[0], paths.shape[-1]
+        starts, goals = sp.starts.reshape(-1, D), sp.goals.reshape(-1, D)
+        if starts.shape[0] != N:                                  # one start / goal pair for all copies
+            starts, goals = starts.expand(N, D), goals.expand(N, D)
+        missing = lengths == 0
+        paths = paths.clone()
+        paths[:, 0] = torch.where(missing[:, None], starts, paths[:, 0])
+        paths[:, 1] = torch.where(missing[:, None], goals, paths[:, 1])
+        lengths = torch.where(missing, torch.full_like(lengths, 2), lengths)
+        H, dt = self.opt_based_planner.n_support_points, self.opt_based_planner.dt
+        return ops.traj_resample(paths.contiguous(), lengths.contiguous(), H, dt).unsqueeze(0)
+
     def optimize(self, debug=False, print_times=False, return_iterations=False, **kwargs):
-        traj_l = self.sample_based_planner.optimize(refill_samples_buffer=True, debug=debug, **kwargs)
-        self.opt_based_planner.reset(initial_particle_means=self.paths_to_initial_means(traj_l))
+        if hasattr(self.sample_based_planner, 'optimize_batched'):
+            paths, lengths, _ = self.sample_based_planner.optimize_batched(**kwargs)
+            means = self.batched_paths_to_initial_means(paths, lengths)
+        else:
+            traj_l = self.sample_based_planner.optimize(refill_samples_buffer=True, debug=debug, **kwargs)
+            means = self.paths_to_initial_means(traj_l)
+        self.opt_based_planner.reset(initial_particle_means=means)
         trajs_0 = self.opt_based_planner.get_traj()
         n = self.opt_based_planner.opt_iters
         trajs_iters = torch.empty((n + 1, *trajs_0.shape), device=trajs_0.device, dtype=trajs_0.dtype)

@@ -86,3 +86,53 @@ def device_robot_field(robot, field, device):
     """(DeviceRobot, DeviceField) for one robot / collision field pair (geometry.Robot*, geometry.CollisionField)."""
     geom = ops.DeviceGeometry(robot, field, device, keep_all_links=True)
     return DeviceRobot(robot, geom, device), DeviceField(field, geom)
+
+
+class PlanningTask:
+    """The slice of torch_robotics' planning task that the reference's sample-based planners call (rrt_base.py:56-57,
+    :100-110): compute_collision, random_coll_free_q, random_q, distance_q -- on the GPU.
+
+    The collision predicate is build-defined (torch_robotics is absent): a configuration is in collision iff the
+    package's per-waypoint collision cost  sum_f s_f sum_l relu(margin + r_l - min_o sdf_o(x_l))  is positive
+    (mpb_collision_check; the same evaluators as every cost kernel).  `field` may be a list of up to four fields."""
+
+    def __init__(self, robot, field, tensor_args=None, seed=0):
+        from .planners.base import require_cuda
+        self.tensor_args = tensor_args
+        self.device = require_cuda(tensor_args)
+        self.robot, self.field = robot, field
+        self.geom = ops.DeviceGeometry(robot, field, self.device)
+        self.q_dim = robot.q_dim
+        self.q_min = robot.q_min.to(self.device)
+        self.q_max = robot.q_max.to(self.device)
+        self._gen = torch.Generator(device=self.device)
+        self._gen.manual_seed(int(seed))
+
+    def compute_collision(self, qs, **kwargs):
+        """(..., D) configurations -> bool (...): in collision."""
+        q2 = torch.as_tensor(qs, dtype=torch.float32, device=self.device).reshape(-1, self.q_dim).contiguous()
+        return ops.collision_check(q2, self.geom).reshape(qs.shape[:-1])
+
+    def random_q(self, n_samples=1):
+        """n_samples configurations uniform within the joint limits, (n_samples, D)."""
+        u = torch.rand(int(n_samples), self.q_dim, device=self.device, dtype=torch.float32, generator=self._gen)
+        return self.q_min + (self.q_max - self.q_min) * u
+
+    def random_coll_free_q(self, n_samples=1, max_samples=1000, max_tries=1000):
+        """n_samples collision-free configurations (n_samples, D), drawn max_samples at a time (at least n_samples) and
+        filtered by mpb_collision_check; raises when max_tries rounds do not yield them."""
+        n_samples = int(n_samples)
+        if n_samples <= 0:
+            return torch.empty(0, self.q_dim, device=self.device, dtype=torch.float32)
+        found, have = [], 0
+        for _ in range(int(max_tries)):
+            q = self.random_q(max(int(max_samples), n_samples)).contiguous()
+            free = q[~ops.collision_check(q, self.geom)]
+            found.append(free)
+            have += free.shape[0]
+            if have >= n_samples:
+                return torch.cat(found)[:n_samples].contiguous()
+        raise RuntimeError(f'random_coll_free_q: {have} of {n_samples} collision-free configurations after {max_tries} rounds')
+
+    def distance_q(self, q1, q2):
+        return torch.linalg.norm(q1 - q2, dim=-1)
