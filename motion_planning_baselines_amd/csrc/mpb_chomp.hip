@@ -401,7 +401,7 @@ extern "C" int mpb_chomp_step(float* means, const float* R, const float* geom, i
     if (D <= 3)
         hipLaunchKernelGGL(chomp_lean_kernel, dim3(B_local), dim3(threads), (size_t)H * d * 4, (hipStream_t)stream, means,
                            R, geom, costs_out, B_global, H, d, D, k_sigma, weight, w_prior, lr, grad_clip, n_iters);
-    else if ((geom_flags & 0xFF) == PandaModel::ID && (geom_flags & 0x100) && D == PandaModel::N_DOF)
+    else if (mpb_flags_model_on_grids(geom_flags, PandaModel::ID) && D == PandaModel::N_DOF)
         hipLaunchKernelGGL(chomp_kernel<PandaModel::ID>, dim3(B_local), dim3(threads), (size_t)H * d * 4, (hipStream_t)stream, means,
                            R, geom, costs_out, B_global, H, d, D, k_sigma, weight, w_prior, lr, grad_clip, n_iters);
     else

@@ -19,23 +19,6 @@
 // ds_bpermute shuffles through the LDS crossbar: four dependent full-rate instructions bring every 16-lane row to its
 // row total, the four row totals are read with v_readlane.  Callers are wave-uniform (all 64 lanes active).
 //   quad_perm [1,0,3,2] = 0xB1, quad_perm [2,3,0,1] = 0x4E, row_half_mirror = 0x141, row_mirror = 0x140
-#ifdef MPB_SHFL_REDUCE   // the former butterfly, kept for A/B measurements
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-__device__ __forceinline__ float wave_sum_f32(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-__device__ __forceinline__ float wave_max_f32(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
-    return v;
-}
-#else
 // debug builds (-DMPB_DEBUG): the DPP reductions read neighbouring lanes' registers directly, so every lane of the wave
 // must be active at the call site (a disabled lane contributes a stale register, not a neutral element)
 #ifdef MPB_DEBUG
@@ -157,13 +140,11 @@ __device__ __forceinline__ double wave_sum_f64(double v) {
     }
     return (r[0] + r[1]) + (r[2] + r[3]);
 }
-#endif
 
 // wave_sum_f32 for callers that need the total in ONE lane only: valid in LANE 63.  The four row totals meet through DPP row_bcast:15
 // (lane 15 of a row into the next row; rows 1 and 3 take it) and row_bcast:31 (lane 31 into rows 2 and 3; row 3 takes it): (r2 + r3) +
 // (r0 + r1) -- the association of wave_sum_f32, hence the same bits -- in two vector instructions where the four row totals cost four
 // v_readlane, each a round trip through a scalar register the adds then wait for.
-#ifndef MPB_SHFL_REDUCE
 __device__ __forceinline__ float wave_sum_f32_lane63(float v) {
     MPB_ASSERT_FULL_WAVE();
     v += dpp_f32<0xB1>(v);
@@ -174,9 +155,6 @@ __device__ __forceinline__ float wave_sum_f32_lane63(float v) {
     v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x143, 0xC, 0xF, false));   // row_bcast:31 -> rows 2, 3
     return v;
 }
-#else
-__device__ __forceinline__ float wave_sum_f32_lane63(float v) { return wave_sum_f32(v); }
-#endif
 
 // A kernel argument RE-READ from the kernarg segment at its point of use (one s_load on the scalar-memory pipe) instead of being held in
 // scalar registers from the kernel's entry on.  The big kernels of this library carry 20-30 arguments; the ones a phase touches once per

@@ -41,17 +41,10 @@
 #define MPB_KIND_CHAIN 1
 #define MPB_MAX_DOF 12
 #define MPB_MAX_TF (MPB_MAX_DOF + 1)
-// collision spheres processed together (VGPR resident) by the exhaustive obstacle loop: 4.  (The cost-only path ran 8 at
+// collision spheres processed together (VGPR resident) by every evaluator: 4.  (The cost-only exhaustive path ran 8 at
 // a time in round 1; that evaluator is now the cold path -- fields without a usable broad-phase grid -- and at 8 it alone
 // pushed STOMP kernel A, which also holds the grid evaluator, over its 128 registers: 64 B / lane of scratch.)
-#ifndef MPB_LCH_COST
-#define MPB_LCH_COST 4
-#endif
-#define MPB_LCH_OF(GRAD) ((GRAD) ? 4 : MPB_LCH_COST)
-// conservative-test policy: 0 = adaptive (default), 1 = never test, 2 = always test (tuning builds only)
-#ifndef MPB_CULL_MODE
-#define MPB_CULL_MODE 0
-#endif
+#define MPB_GROUP 4
 
 struct GeomView {
     int kind, n_dof, n_tf, n_links, n_sph, n_box;
@@ -124,25 +117,9 @@ __device__ __forceinline__ GeomView geom_view(const float* __restrict__ g) {
 // mantissa bits).  21 VALU instructions for both values, none of them a compare / select (the pi/2 form with the cephes
 // polynomials on [-pi/4, pi/4] took 29, eight of them half-rate compares, selects and converts: 7 x 8 per waypoint).
 // Max abs error against fp64 over |x| <= 20: sin 1.16e-7, cos 1.28e-7 (rms 2.1e-8 / 3.2e-8; the pi/2 form: 9.1e-8 / 9.2e-8,
-// rms 2.1e-8 -- one ulp either way; emulated in scripts/sincos_fit.py, measured on the device by scripts/sincos_accuracy.hip).
+// rms 2.1e-8 -- one ulp either way; emulated in scripts/sincos_fit.py, measured on the device by scripts/sincos_accuracy.hip,
+// which carries the pi/2 form for that comparison).
 // ocml sinf + cosf cost ~4x that because of their huge-argument path.  Joint angles are bounded by the limits plus STOMP noise.
-#ifdef MPB_SINCOS_PI2   // the former pi/2 form, kept for A/B measurements (scripts/ab_k20.sh)
-__device__ __forceinline__ void fast_sincos(float x, float& sn, float& cs) {
-    const float k = rintf(x * 0.6366197466850281f);
-    float r = fmaf(-k, 1.5707963705062866f, x);
-    r = fmaf(-k, -4.371138828673793e-08f, r);
-    r = fmaf(-k, -1.7763568394002505e-15f, r);
-    const float r2 = r * r;
-    const float s = fmaf(r * r2, fmaf(r2, fmaf(r2, -1.9515295891e-4f, 8.3321608736e-3f), -1.6666654611e-1f), r);
-    const float c = fmaf(r2 * r2, fmaf(r2, fmaf(r2, 2.443315711809948e-5f, -1.388731625493765e-3f), 4.166664568298827e-2f),
-                         fmaf(-0.5f, r2, 1.0f));
-    const int q = (int)k;
-    const float a = (q & 1) ? c : s;
-    const float b = (q & 1) ? s : c;
-    sn = (q & 2) ? -a : a;
-    cs = ((q + 1) & 2) ? -b : b;
-}
-#else
 __device__ __forceinline__ void fast_sincos(float x, float& sn, float& cs) {
     const float t = fmaf(x, 0.3183098861837907f, 12582912.0f);        // 1.5 * 2^23 + rint(x / pi): valid for |x| < 1e6
     const float k = t - 12582912.0f;
@@ -158,7 +135,6 @@ __device__ __forceinline__ void fast_sincos(float x, float& sn, float& cs) {
     sn = __uint_as_float(__float_as_uint(s) ^ sg);
     cs = __uint_as_float(__float_as_uint(c) ^ sg);
 }
-#endif
 
 // v_sqrt_f32: 1 ulp, one quarter-rate instruction (the IEEE-correct expansion hipcc emits for sqrtf is
 // ~20 VALU instructions).  Arguments are squared distances, far inside the range that needs no scaling.
@@ -167,10 +143,23 @@ __device__ __forceinline__ float fast_sqrt(float x) { return __builtin_amdgcn_sq
 // State of N collision spheres (VGPR resident) while the obstacle set streams past them in SGPRs.
 template <bool GRAD>
 struct LinkChunk {
-    static constexpr int N = MPB_LCH_OF(GRAD);
+    static constexpr int N = MPB_GROUP;
     float x[N], y[N], z[N], xx[N], best[N];
     float vx[GRAD ? N : 1], vy[GRAD ? N : 1], vz[GRAD ? N : 1], vn[GRAD ? N : 1];
 };
+
+// Signed distance of the point (x,y,z) to one obstacle, cost-only: every evaluator that needs no direction uses these two, so
+// their hinges agree bit for bit.
+__device__ __forceinline__ float sphere_sd(float x, float y, float z, const float4 s) {
+    const float dx = x - s.x, dy = y - s.y, dz = z - s.z;
+    return fast_sqrt(dx * dx + dy * dy + dz * dz) - s.w;
+}
+__device__ __forceinline__ float box_sd(float x, float y, float z, const float4 c, const float4 h) {
+    const float px = x - c.x, py = y - c.y, pz = z - c.z;
+    const float ax = fabsf(px) - h.x, ay = fabsf(py) - h.y, az = fabsf(pz) - h.z;
+    const float qx = fmaxf(ax, 0.f), qy = fmaxf(ay, 0.f), qz = fmaxf(az, 0.f);
+    return fast_sqrt(qx * qx + qy * qy + qz * qz) + fminf(fmaxf(ax, fmaxf(ay, az)), 0.f);
+}
 
 // exact signed distance of sphere obstacle (cx,cy,cz,r) at slot I; keeps the running minimum (and for GRAD
 // the un-normalised direction v and its norm vn with grad sdf = v / vn)
@@ -272,11 +261,11 @@ __device__ __forceinline__ void chunk_vs_obstacles(const GeomView& G, LinkChunk<
         float4 k[8];
 #pragma unroll
         for (int i = 0; i < 8; ++i) k[i] = cu[2 * ob + i];
-        if (MPB_CULL_MODE != 1 && cs.on) {
+        if (cs.on) {
             const bool any = block_may_touch<GRAD>(C, k);
             cs.tested += 1;
             cs.hit += any ? 1 : 0;
-            if (MPB_CULL_MODE == 0) cs.on = (cs.tested < 8) || (2 * cs.hit <= cs.tested);
+            cs.on = (cs.tested < 8) || (2 * cs.hit <= cs.tested);
             if (!any) continue;
         }
         block_exact<GRAD>(C, k);
@@ -319,6 +308,14 @@ struct FKState {
     float zx[GRAD ? MPB_MAX_DOF : 1], zy[GRAD ? MPB_MAX_DOF : 1], zz[GRAD ? MPB_MAX_DOF : 1];
     float px[GRAD ? MPB_MAX_DOF : 1], py[GRAD ? MPB_MAX_DOF : 1], pz[GRAD ? MPB_MAX_DOF : 1];
 };
+
+// the chain's start for either kind of state (FKState, ModelFK): the identity frame.  (The joint tables of a gradient state are
+// zeroed by its owner: through a helper the compiler numbers the registers of the gradient kernels differently.)
+template <class FK>
+__device__ __forceinline__ void fk_identity(FK& F) {
+    F.r00 = 1.f; F.r01 = 0.f; F.r02 = 0.f; F.r10 = 0.f; F.r11 = 1.f; F.r12 = 0.f; F.r20 = 0.f; F.r21 = 0.f; F.r22 = 1.f;
+    F.tx = F.ty = F.tz = 0.f;
+}
 
 // frame_{j+1} = frame_j * P_j * Rz(q_j); q_j and the joint-array slot are picked with selects, never by a
 // runtime register index
@@ -420,6 +417,24 @@ __device__ __forceinline__ float point_cost(const GeomView& G, float x, float y,
     return h;
 }
 
+// The collision sphere at (x,y,z) on frame `fr` (table-driven walks) with hinge h and nearest-obstacle direction v / vn: where
+// some lane of the wave is in contact, the force -v / vn pulled back through the chain, dq += J^T f over the joints upstream
+// of the sphere's frame.
+__device__ __forceinline__ void hinge_jtf(const GeomView& G, const FKState<true>& F, float x, float y, float z, float h, float vx,
+                                          float vy, float vz, float vn, int fr, float (&dq)[MPB_MAX_DOF]) {
+    if (__any(h > 0.f)) {
+        const float s = (h > 0.f) ? -1.0f / vn : 0.f;
+        const float fx = vx * s, fy = vy * s, fz = vz * s;
+#pragma unroll
+        for (int ii = 0; ii < MPB_MAX_DOF; ++ii) {
+            if (ii < fr && ii < G.n_dof) {
+                // d x / d q_ii = z_ii x (x - p_ii) for every joint upstream of the sphere's frame
+                dq[ii] += joint_term(F.zx[ii], F.zy[ii], F.zz[ii], F.px[ii], F.py[ii], F.pz[ii], x, y, z, fx, fy, fz);
+            }
+        }
+    }
+}
+
 // Collision cost of one waypoint q[0..D) (sum over the robot's collision spheres); for GRAD
 // dq[i] = d cost / d q_i (i < D).  q / dq are register arrays indexed only with compile-time indices.
 template <bool GRAD>
@@ -440,15 +455,14 @@ __device__ __forceinline__ float waypoint_cost(const GeomView& G, const float (&
     LinkChunk<GRAD> C;
     CullStats cs = {0, 0, true};
     FKState<GRAD> F;
-    F.r00 = 1.f; F.r01 = 0.f; F.r02 = 0.f; F.r10 = 0.f; F.r11 = 1.f; F.r12 = 0.f; F.r20 = 0.f; F.r21 = 0.f; F.r22 = 1.f;
-    F.tx = F.ty = F.tz = 0.f;
+    fk_identity(F);
     F.frame = 0;
     if (GRAD) {
 #pragma unroll
         for (int i = 0; i < MPB_MAX_DOF; ++i) { F.zx[i] = F.zy[i] = F.zz[i] = F.px[i] = F.py[i] = F.pz[i] = 0.f; }
     }
-    const bool point = (G.kind == MPB_KIND_POINT);
-    float cost = 0.f;
+    const bool point = (G.kind == MPB_KIND_POINT);   // false here (point robots returned above); its use below is dead code the
+    float cost = 0.f;                                // register numbering of collision_cost_kernel<true, 0> hangs on: left in
     // chunks of N consecutive collision spheres; the kinematic chain advances inside the slot loop so
     // that every chunk is full whatever the spheres-per-frame distribution is
     for (int l0 = 0; l0 < G.n_links; l0 += N) {
@@ -486,25 +500,7 @@ __device__ __forceinline__ float waypoint_cost(const GeomView& G, const float (&
         for (int i = 0; i < N; ++i) {
             const float h = fmaxf(G.margin + rl[i] - C.best[i], 0.f);  // parked slots: best = 3e38 -> 0
             cost += h;
-            if (GRAD) {
-                if (__any(h > 0.f)) {
-                    const float s = (h > 0.f) ? -1.0f / C.vn[i] : 0.f;
-                    const float fx = C.vx[i] * s, fy = C.vy[i] * s, fz = C.vz[i] * s;
-                    if (point) {
-                        dq[0] += fx; dq[1] += fy;
-                        if (G.n_dof > 2) dq[2] += fz;
-                    } else {
-#pragma unroll
-                        for (int ii = 0; ii < MPB_MAX_DOF; ++ii) {
-                            if (ii < fr[i] && ii < G.n_dof) {
-                                // d x / d q_ii = z_ii x (x - p_ii) for every joint upstream of the sphere's frame
-                                dq[ii] += joint_term(F.zx[ii], F.zy[ii], F.zz[ii], F.px[ii], F.py[ii], F.pz[ii], C.x[i], C.y[i],
-                                                     C.z[i], fx, fy, fz);
-                            }
-                        }
-                    }
-                }
-            }
+            if constexpr (GRAD) hinge_jtf(G, F, C.x[i], C.y[i], C.z[i], h, C.vx[i], C.vy[i], C.vz[i], C.vn[i], fr[i], dq);
         }
     }
     return cost;
@@ -541,31 +537,25 @@ __device__ __forceinline__ float waypoint_cost_chain(const float* __restrict__ g
 }
 
 // issue priority of a wave with r groups of the chain walk still to come after the current one (see model_group_positions)
-#ifndef MPB_COST_PRIO
-#define MPB_COST_PRIO(r) ((r) < 3 ? (r) : 3)
-#endif
+constexpr int cost_prio(int r) { return r < 3 ? r : 3; }
 __device__ __forceinline__ bool grid_usable(const GeomView& G) {
     return G.version == MPB_GEOM_VERSION && G.n_cells > 0 && G.n_cells <= MPB_GRID_MAX_CELLS && G.n_sph <= MPB_GRID_MAX_SPH;
 }
 
-// clamped cell of a point, all in fp32: 3 fma + 3 floor + 3 med3 + 2 fma + 1 cvt (the integer formulation needs
-// floor-convert + min + max per axis and two integer mads, one of them quarter rate).  Cell coordinates and the
-// cell count stay below 2^24, so the float index arithmetic is exact; fma(x, inv, -lo * inv) differs from the
-// host's (x - lo) * inv by ~1e-6 cells, inside the 1e-5 m the host adds to the candidate radius for exactly this
-// (geometry.py build_grid).  NaN / inf coordinates land in some valid cell.
-// FP32 = false keeps the integer formulation: the gradient evaluators are register-bound, and the eight uniform float
-// constants of the fp32 form cost them more than the shorter index arithmetic saves (cost+grad +5 %, measured).
-template <bool FP32>
+// clamped cell of a point: nine instructions -- the cell coordinate and v_cvt_flr_i32_f32 per axis, two v_mad_u32_u24, ONE clamp
+// of the linear index.  No per-axis clamp: a point inside the box gets its own cell; a point outside it (or on its upper
+// faces) lands in SOME valid cell, and whatever that cell lists gives hinge 0 exactly -- and therefore gradient 0 -- (the box
+// bounds the inflated obstacles: see spheres_hinge_grid).  Saturated converts (parked slots at 1e9, inf) and NaN (-> 0) included.
+// FMA: the coordinate as fma(x, inv, -lo * inv), one instruction per axis; it differs from the host's (x - lo) * inv by ~1e-6
+// cells, inside the 1e-5 m the host adds to the candidate radius for exactly this (geometry.py build_grid).
+// FMA = false keeps (x - lo) * inv: the gradient evaluators are register-bound, and the extra uniform float constants of the
+// fma form cost them more than the shorter arithmetic saves (cost+grad +5 %, measured).  (An all-float index -- floor, med3
+// per axis, two fma, one convert -- was twelve instructions.)  The two forms stay written out one after the other: the order
+// of their statements is the order the scheduler sees.
+template <bool FMA>
 __device__ __forceinline__ unsigned grid_cell(const GeomView& G, float x, float y, float z) {
-    if (!FP32) {
+    if (!FMA) {
         const float fx = (x - G.glx) * G.gix, fy = (y - G.gly) * G.giy, fz = (z - G.glz) * G.giz;
-#ifdef MPB_GRID_CELL_FP32
-        const int ix = min(max((int)floorf(fx), 0), G.gnx - 1), iy = min(max((int)floorf(fy), 0), G.gny - 1),
-                  iz = min(max((int)floorf(fz), 0), G.gnz - 1);
-        return (unsigned)(__mul24(__mul24(iz, G.gny) + iy, G.gnx) + ix);
-#else
-        // (one clamp of the linear index instead of two per axis: see below -- a point outside the box has hinge 0 and
-        // therefore gradient 0 whatever candidates it is given)
         int ix, iy, iz;
         asm("v_cvt_flr_i32_f32 %0, %1" : "=v"(ix) : "v"(fx));
         asm("v_cvt_flr_i32_f32 %0, %1" : "=v"(iy) : "v"(fy));
@@ -574,18 +564,7 @@ __device__ __forceinline__ unsigned grid_cell(const GeomView& G, float x, float 
         asm("v_mad_u32_u24 %0, %1, %2, %3" : "=v"(t) : "v"(iz), "s"(G.gny), "v"(iy));
         asm("v_mad_u32_u24 %0, %1, %2, %3" : "=v"(idx) : "v"(t), "s"(G.gnx), "v"(ix));
         return min(idx, (unsigned)(G.n_cells - 1));
-#endif
     }
-#ifdef MPB_GRID_CELL_FP32
-    const float fx = __builtin_amdgcn_fmed3f(floorf(fmaf(x, G.gix, -G.glx * G.gix)), 0.f, (float)(G.gnx - 1));
-    const float fy = __builtin_amdgcn_fmed3f(floorf(fmaf(y, G.giy, -G.gly * G.giy)), 0.f, (float)(G.gny - 1));
-    const float fz = __builtin_amdgcn_fmed3f(floorf(fmaf(z, G.giz, -G.glz * G.giz)), 0.f, (float)(G.gnz - 1));
-    return (unsigned)fmaf(fmaf(fz, (float)G.gny, fy), (float)G.gnx, fx);
-#else
-    // nine instructions instead of twelve: fma + v_cvt_flr_i32_f32 per axis, two v_mad_u32_u24, ONE clamp of the linear
-    // index.  No per-axis clamp: a point inside the box gets the cell it always got; a point outside it (or on its upper
-    // faces) lands in SOME valid cell, and whatever that cell lists gives hinge 0 exactly (the box bounds the inflated
-    // obstacles: see spheres_hinge_grid).  Saturated converts (parked slots at 1e9, inf) and NaN (-> 0) included.
     int ix, iy, iz;
     asm("v_cvt_flr_i32_f32 %0, %1" : "=v"(ix) : "v"(fmaf(x, G.gix, -G.glx * G.gix)));
     asm("v_cvt_flr_i32_f32 %0, %1" : "=v"(iy) : "v"(fmaf(y, G.giy, -G.gly * G.giy)));
@@ -594,7 +573,6 @@ __device__ __forceinline__ unsigned grid_cell(const GeomView& G, float x, float 
     asm("v_mad_u32_u24 %0, %1, %2, %3" : "=v"(t) : "v"(iz), "s"(G.gny), "v"(iy));
     asm("v_mad_u32_u24 %0, %1, %2, %3" : "=v"(idx) : "v"(t), "s"(G.gnx), "v"(ix));
     return min(idx, (unsigned)(G.n_cells - 1));
-#endif
 }
 
 // BYTE OFFSET of a point's grid word (persistent STOMP kernels, MPPI; geometry version 6), clamped to the grid.  The cells
@@ -712,6 +690,7 @@ __device__ __forceinline__ void spheres_hinge_grid(const GeomView& G, const unsi
         for (int i = 1; i < N; ++i) comb |= w[i];
 #pragma unroll
         for (int i = 0; i < N; ++i) {
+            // (sphere_sd, written out: called here it changes the schedule of the persistent STOMP kernels)
             const float dx = x[i] - s0[i].x, dy = y[i] - s0[i].y, dz = z[i] - s0[i].z;
             best[i] = fast_sqrt(dx * dx + dy * dy + dz * dz) - s0[i].w;
         }
@@ -721,10 +700,7 @@ __device__ __forceinline__ void spheres_hinge_grid(const GeomView& G, const unsi
                 for (int o = 0; o < G.n_sph; ++o) {
                     const float4 s = otab[o];
 #pragma unroll
-                    for (int i = 0; i < N; ++i) {
-                        const float dx = x[i] - s.x, dy = y[i] - s.y, dz = z[i] - s.z;
-                        best[i] = fminf(best[i], fast_sqrt(dx * dx + dy * dy + dz * dz) - s.w);
-                    }
+                    for (int i = 0; i < N; ++i) best[i] = fminf(best[i], sphere_sd(x[i], y[i], z[i], s));
                 }
             } else {
                 // (measured and dropped, twice: the later slots sphere by sphere, each behind its own wave-uniform test -- +1.5 %)
@@ -735,10 +711,7 @@ __device__ __forceinline__ void spheres_hinge_grid(const GeomView& G, const unsi
 #pragma unroll
                     for (int i = 0; i < N; ++i) s[i] = *reinterpret_cast<const float4*>(ob + ((w[i] >> (10 * k)) & 0x3FFu));
 #pragma unroll
-                    for (int i = 0; i < N; ++i) {
-                        const float dx = x[i] - s[i].x, dy = y[i] - s[i].y, dz = z[i] - s[i].z;
-                        best[i] = fminf(best[i], fast_sqrt(dx * dx + dy * dy + dz * dz) - s[i].w);
-                    }
+                    for (int i = 0; i < N; ++i) best[i] = fminf(best[i], sphere_sd(x[i], y[i], z[i], s[i]));
                 }
             }
         }
@@ -758,10 +731,7 @@ __device__ __forceinline__ void spheres_hinge_grid(const GeomView& G, const unsi
         for (int o = 0; o < G.n_sph; ++o) {
             const float4 s = otab[o];
 #pragma unroll
-            for (int i = 0; i < N; ++i) {
-                const float dx = x[i] - s.x, dy = y[i] - s.y, dz = z[i] - s.z;
-                best[i] = fminf(best[i], fast_sqrt(dx * dx + dy * dy + dz * dz) - s.w);
-            }
+            for (int i = 0; i < N; ++i) best[i] = fminf(best[i], sphere_sd(x[i], y[i], z[i], s));
         }
     } else {
         // candidate slot k of every sphere of the group at once (an unused slot holds n_sph, the far dummy of the
@@ -782,8 +752,7 @@ __device__ __forceinline__ void spheres_hinge_grid(const GeomView& G, const unsi
             for (int i = 0; i < N; ++i) s[i] = otab[(w[i] >> (8 * k)) & 0xFFu];
 #pragma unroll
             for (int i = 0; i < N; ++i) {
-                const float dx = x[i] - s[i].x, dy = y[i] - s[i].y, dz = z[i] - s[i].z;
-                const float dist = fast_sqrt(dx * dx + dy * dy + dz * dz) - s[i].w;
+                const float dist = sphere_sd(x[i], y[i], z[i], s[i]);
                 // (slot 0 is always evaluated: min(3e38, dist) is dist -- v_min_f32 issues at half the rate of v_sub_f32 on
                 // gfx950, profiles/r03_microbench_rates.txt)
                 best[i] = (k == 0) ? dist : fminf(best[i], dist);
@@ -796,13 +765,7 @@ __device__ __forceinline__ void spheres_hinge_grid(const GeomView& G, const unsi
     for (int o = 0; o < G.n_box; ++o) {
         const float4 c = bp[2 * o], h = bp[2 * o + 1];
 #pragma unroll
-        for (int i = 0; i < N; ++i) {
-            const float px = x[i] - c.x, py = y[i] - c.y, pz = z[i] - c.z;
-            const float ax = fabsf(px) - h.x, ay = fabsf(py) - h.y, az = fabsf(pz) - h.z;
-            const float qx = fmaxf(ax, 0.f), qy = fmaxf(ay, 0.f), qz = fmaxf(az, 0.f);
-            const float sd = fast_sqrt(qx * qx + qy * qy + qz * qz) + fminf(fmaxf(ax, fmaxf(ay, az)), 0.f);
-            best[i] = fminf(best[i], sd);
-        }
+        for (int i = 0; i < N; ++i) best[i] = fminf(best[i], box_sd(x[i], y[i], z[i], c, h));
     }
 #pragma unroll
     for (int i = 0; i < N; ++i) {                                                 // parked slots: best = 3e38 / 1e9 -> +0
@@ -855,17 +818,8 @@ __device__ __forceinline__ void spheres_hinge_list(const GeomView& G, const List
         best[i] = 3.0e38f;
         comb |= w[i];
     }
-    auto sphere = [&](int i, const float4 s) {
-        const float dx = x[i] - s.x, dy = y[i] - s.y, dz = z[i] - s.z;
-        best[i] = fminf(best[i], fast_sqrt(dx * dx + dy * dy + dz * dz) - s.w);
-    };
-    auto box = [&](int i, const float4 c, const float4 h) {
-        const float px = x[i] - c.x, py = y[i] - c.y, pz = z[i] - c.z;
-        const float ax = fabsf(px) - h.x, ay = fabsf(py) - h.y, az = fabsf(pz) - h.z;
-        const float qx = fmaxf(ax, 0.f), qy = fmaxf(ay, 0.f), qz = fmaxf(az, 0.f);
-        const float sd = fast_sqrt(qx * qx + qy * qy + qz * qz) + fminf(fmaxf(ax, fmaxf(ay, az)), 0.f);
-        best[i] = fminf(best[i], sd);
-    };
+    auto sphere = [&](int i, const float4 s) { best[i] = fminf(best[i], sphere_sd(x[i], y[i], z[i], s)); };
+    auto box = [&](int i, const float4 c, const float4 h) { best[i] = fminf(best[i], box_sd(x[i], y[i], z[i], c, h)); };
     if (__builtin_expect(__ballot((int)comb < 0) != 0ull, 0)) {
         // some lane sits in a cell that overflows a count field: every obstacle for this group (rare)
         for (int o = 0; o < G.n_sph; ++o) {
@@ -929,28 +883,22 @@ __device__ __forceinline__ float waypoint_cost_grid(const GeomView& G, const uns
         else spheres_hinge_grid<1, OFFS>(G, gridw, otab, x, y, z, rl, c, OFFS ? grid_addr(G) : GridAddr{});
         return c;
     }
-#ifndef MPB_GRID_N
-#define MPB_GRID_N 4
-#endif
-    constexpr int N = MPB_GRID_N;
+    constexpr int N = MPB_GROUP;
     constexpr float FAR = 1.0e9f;  // parked slot: outside the grid, no candidates
     FKState<false> F;
-    F.r00 = 1.f; F.r01 = 0.f; F.r02 = 0.f; F.r10 = 0.f; F.r11 = 1.f; F.r12 = 0.f; F.r20 = 0.f; F.r21 = 0.f; F.r22 = 1.f;
-    F.tx = F.ty = F.tz = 0.f;
+    fk_identity(F);
     F.frame = 0;
     float cost = 0.f;
     const GridAddr GA = (OFFS || LIST) ? grid_addr(G) : GridAddr{};
     for (int l0 = 0; l0 < G.n_links; l0 += N) {
         const int nl = min(N, G.n_links - l0);
-#ifndef MPB_NO_COST_PRIO
         // issue priority by the groups still to come (wave-uniform; see model_group_positions)
         switch ((G.n_links - l0 - 1) / N) {
-            case 0: __builtin_amdgcn_s_setprio(MPB_COST_PRIO(0)); break;
-            case 1: __builtin_amdgcn_s_setprio(MPB_COST_PRIO(1)); break;
-            case 2: __builtin_amdgcn_s_setprio(MPB_COST_PRIO(2)); break;
-            default: __builtin_amdgcn_s_setprio(MPB_COST_PRIO(3)); break;
+            case 0: __builtin_amdgcn_s_setprio(cost_prio(0)); break;
+            case 1: __builtin_amdgcn_s_setprio(cost_prio(1)); break;
+            case 2: __builtin_amdgcn_s_setprio(cost_prio(2)); break;
+            default: __builtin_amdgcn_s_setprio(cost_prio(3)); break;
         }
-#endif
         float x[N], y[N], z[N], rl[N];
         // the N link records of the group are fetched together, so the scalar-load latency is paid once per group
         // instead of once per sphere.  Records past n_links (last group) are read but never used: the words behind
@@ -978,9 +926,7 @@ __device__ __forceinline__ float waypoint_cost_grid(const GeomView& G, const uns
         if constexpr (LIST) spheres_hinge_list<N>(G, *LV, x, y, z, rl, cost, GA);
         else spheres_hinge_grid<N, OFFS>(G, gridw, otab, x, y, z, rl, cost, GA);
     }
-#ifndef MPB_NO_COST_PRIO
     __builtin_amdgcn_s_setprio(0);
-#endif
     return cost;
 }
 
@@ -995,12 +941,28 @@ __device__ __forceinline__ float waypoint_cost_grid(const GeomView& G, const uns
 //   keep_mask: spheres riding on frame 1 that static pruning dropped are parked (their hinge is exactly 0); a group of
 //   frame-1 spheres with no survivor is skipped.
 // ------------------------------------------------------------------------------------------------
+// GRAD: the state also keeps every joint's axis z_j and origin p_j in the base frame (model_group_jtf)
+template <class M, bool GRAD>
 struct ModelFK {
     float r00, r01, r02, r10, r11, r12, r20, r21, r22, tx, ty, tz;
+    float zx[GRAD ? M::N_DOF : 1], zy[GRAD ? M::N_DOF : 1], zz[GRAD ? M::N_DOF : 1];
+    float px[GRAD ? M::N_DOF : 1], py[GRAD ? M::N_DOF : 1], pz[GRAD ? M::N_DOF : 1];
 };
 
-template <class M, int J>
-__device__ __forceinline__ void model_fk_advance(ModelFK& F, const float (&q)[MPB_MAX_DOF]) {
+// The groups of (up to four) collision spheres the model walks: the spheres on frame 1 first (the only ones static pruning
+// can drop), then the rest, four at a time.  Group GRP holds the spheres [lo, hi).
+template <class M, int GRP = 0>
+struct ModelGroup {
+    static constexpr int G1 = (M::N_FRAME1 + 3) / 4;
+    static constexpr int NG = G1 + (M::N_LINKS - M::N_FRAME1 + 3) / 4;
+    static constexpr bool first = GRP < G1;
+    static constexpr int lo = first ? 4 * GRP : M::N_FRAME1 + 4 * (GRP - G1);
+    static constexpr int part_end = first ? M::N_FRAME1 : M::N_LINKS;
+    static constexpr int hi = (lo + 4 < part_end) ? lo + 4 : part_end;
+};
+
+template <class M, int J, bool GRAD>
+__device__ __forceinline__ void model_fk_advance(ModelFK<M, GRAD>& F, const float (&q)[MPB_MAX_DOF]) {
     constexpr float p0x = M::TF[J][0], p0y = M::TF[J][1], p0z = M::TF[J][2], p0w = M::TF[J][3];
     constexpr float p1x = M::TF[J][4], p1y = M::TF[J][5], p1z = M::TF[J][6], p1w = M::TF[J][7];
     constexpr float p2x = M::TF[J][8], p2y = M::TF[J][9], p2z = M::TF[J][10], p2w = M::TF[J][11];
@@ -1021,31 +983,28 @@ __device__ __forceinline__ void model_fk_advance(ModelFK& F, const float (&q)[MP
         const float n10 = fmaf(a11, sn, a10 * cs), n11 = fmaf(-a10, sn, a11 * cs);
         const float n20 = fmaf(a21, sn, a20 * cs), n21 = fmaf(-a20, sn, a21 * cs);
         a00 = n00; a01 = n01; a10 = n10; a11 = n11; a20 = n20; a21 = n21;
+        if constexpr (GRAD) {
+            F.zx[J] = a02; F.zy[J] = a12; F.zz[J] = a22;          // joint axis and origin in the base frame
+            F.px[J] = F.tx; F.py[J] = F.ty; F.pz[J] = F.tz;
+        }
     }
     F.r00 = a00; F.r01 = a01; F.r02 = a02; F.r10 = a10; F.r11 = a11; F.r12 = a12;
     F.r20 = a20; F.r21 = a21; F.r22 = a22;
 }
 
-// positions of the (up to four) collision spheres of group GRP, advancing the chain as far as they need.  Groups:
-// the spheres on frame 1 first (the only ones static pruning can drop), then the rest, four at a time.
-template <class M, int GRP>
-__device__ __forceinline__ bool model_group_positions(ModelFK& F, const float (&q)[MPB_MAX_DOF], unsigned keep,
+// positions of the collision spheres of group GRP, advancing the chain as far as they need; false: a frame-1 group with no
+// survivor, to be skipped.  RLM: rl[] gets margin + r_l (spheres_hinge_grid, RLM) instead of r_l.
+template <class M, int GRP, bool RLM, bool GRAD>
+__device__ __forceinline__ bool model_group_positions(ModelFK<M, GRAD>& F, const float (&q)[MPB_MAX_DOF], unsigned keep,
                                                       float (&x)[4], float (&y)[4], float (&z)[4], float (&rl)[4], float mrg) {
     constexpr float FAR = 1.0e9f;   // parked slot: outside the grid, no candidates
-    constexpr int G1 = (M::N_FRAME1 + 3) / 4;
-    constexpr bool first = GRP < G1;
-    constexpr int lo = first ? 4 * GRP : M::N_FRAME1 + 4 * (GRP - G1);
-    constexpr int part_end = first ? M::N_FRAME1 : M::N_LINKS;
-    constexpr int hi = (lo + 4 < part_end) ? lo + 4 : part_end;
-#ifndef MPB_NO_COST_PRIO
+    using GR = ModelGroup<M, GRP>;
+    constexpr bool first = GR::first;
+    constexpr int lo = GR::lo, hi = GR::hi;
     // issue priority by progress: the SIMD arbiter serves its oldest wave first, so without this the waves of a SIMD
     // finish one after the other and the last one runs alone, latency-bound, at a fraction of the issue rate.  A wave
     // that is behind (earlier group) outranks the ones ahead of it, which keeps all of them in flight to the end.
-    {
-        constexpr int NG_ = (M::N_FRAME1 + 3) / 4 + (M::N_LINKS - M::N_FRAME1 + 3) / 4;
-        __builtin_amdgcn_s_setprio(MPB_COST_PRIO(NG_ - 1 - GRP));
-    }
-#endif
+    __builtin_amdgcn_s_setprio(cost_prio(GR::NG - 1 - GRP));
     static_for<lo, hi>([&](auto lc) {
         constexpr int l = decltype(lc)::value;
         constexpr int f = M::LINK_FRAME[l];
@@ -1056,11 +1015,12 @@ __device__ __forceinline__ bool model_group_positions(ModelFK& F, const float (&
         const float px = mad3(F.r00, ox, F.r01, oy, F.r02, oz, F.tx);
         const float py = mad3(F.r10, ox, F.r11, oy, F.r12, oz, F.ty);
         const float pz = mad3(F.r20, ox, F.r21, oy, F.r22, oz, F.tz);
+        const float r = RLM ? mrg + rad : rad;
         if constexpr (first) {
             const bool on = (keep >> l) & 1u;                // wave-uniform
-            x[slot] = on ? px : FAR; y[slot] = on ? py : FAR; z[slot] = on ? pz : FAR; rl[slot] = on ? mrg + rad : 0.f;
+            x[slot] = on ? px : FAR; y[slot] = on ? py : FAR; z[slot] = on ? pz : FAR; rl[slot] = on ? r : 0.f;
         } else {
-            x[slot] = px; y[slot] = py; z[slot] = pz; rl[slot] = mrg + rad;     // (margin + r_l: spheres_hinge_grid, RLM)
+            x[slot] = px; y[slot] = py; z[slot] = pz; rl[slot] = r;
         }
     });
 #pragma unroll
@@ -1072,24 +1032,23 @@ __device__ __forceinline__ bool model_group_positions(ModelFK& F, const float (&
     return true;
 }
 
-template <class M, int... GRPS>
-__device__ __forceinline__ bool model_group_dispatch(int grp, ModelFK& F, const float (&q)[MPB_MAX_DOF], unsigned keep,
+template <class M, bool RLM, bool GRAD, int... GRPS>
+__device__ __forceinline__ bool model_group_dispatch(int grp, ModelFK<M, GRAD>& F, const float (&q)[MPB_MAX_DOF], unsigned keep,
                                                      float (&x)[4], float (&y)[4], float (&z)[4], float (&rl)[4], float mrg,
                                                      std::integer_sequence<int, GRPS...>) {
     bool run = false;
     // one arm per group, selected by the wave-uniform group counter (scalar compares / branches)
     // (a switch over the group index -- a jump table or a compare tree instead of the compare chain -- measured +1 %, round 5)
-    ((grp == GRPS ? (void)(run = model_group_positions<M, GRPS>(F, q, keep, x, y, z, rl, mrg)) : (void)0), ...);
+    ((grp == GRPS ? (void)(run = model_group_positions<M, GRPS, RLM>(F, q, keep, x, y, z, rl, mrg)) : (void)0), ...);
     return run;
 }
 
 template <class M, bool OFFS = false, bool LIST = false>
 __device__ __forceinline__ float waypoint_cost_grid_model(const GeomView& G, const unsigned* gridw, const float4* otab,
                                                           const float (&q)[MPB_MAX_DOF], const ListView* LV = nullptr) {
-    constexpr int NG = (M::N_FRAME1 + 3) / 4 + (M::N_LINKS - M::N_FRAME1 + 3) / 4;
-    ModelFK F;
-    F.r00 = 1.f; F.r01 = 0.f; F.r02 = 0.f; F.r10 = 0.f; F.r11 = 1.f; F.r12 = 0.f; F.r20 = 0.f; F.r21 = 0.f; F.r22 = 1.f;
-    F.tx = F.ty = F.tz = 0.f;
+    constexpr int NG = ModelGroup<M>::NG;
+    ModelFK<M, false> F;
+    fk_identity(F);
     float cost = 0.f;
     const unsigned keep = G.keep_mask;
     const GridAddr GA = (OFFS || LIST) ? grid_addr(G) : GridAddr{};
@@ -1099,16 +1058,14 @@ __device__ __forceinline__ float waypoint_cost_grid_model(const GeomView& G, con
 #pragma nounroll
     for (int grp = 0; grp < NG; ++grp) {
         float x[4], y[4], z[4], rl[4];
-        const bool run = model_group_dispatch<M>(grp, F, q, keep, x, y, z, rl, mrg, std::make_integer_sequence<int, NG>{});
+        const bool run = model_group_dispatch<M, true>(grp, F, q, keep, x, y, z, rl, mrg, std::make_integer_sequence<int, NG>{});
         if constexpr (LIST) {
             if (run) spheres_hinge_list<4, true, true>(G, *LV, x, y, z, rl, cost, GA);
         } else {
             if (run) spheres_hinge_grid<4, OFFS, true, true>(G, gridw, otab, x, y, z, rl, cost, GA);
         }
     }
-#ifndef MPB_NO_COST_PRIO
     __builtin_amdgcn_s_setprio(0);
-#endif
     return cost;
 }
 
@@ -1223,23 +1180,20 @@ __device__ __forceinline__ float waypoint_cost_grid_grad(const GeomView& G, cons
     constexpr int N = 4;
     constexpr float FAR = 1.0e9f;
     FKState<true> F;
-    F.r00 = 1.f; F.r01 = 0.f; F.r02 = 0.f; F.r10 = 0.f; F.r11 = 1.f; F.r12 = 0.f; F.r20 = 0.f; F.r21 = 0.f; F.r22 = 1.f;
-    F.tx = F.ty = F.tz = 0.f;
+    fk_identity(F);
     F.frame = 0;
 #pragma unroll
     for (int i = 0; i < MPB_MAX_DOF; ++i) { F.zx[i] = F.zy[i] = F.zz[i] = F.px[i] = F.py[i] = F.pz[i] = 0.f; }
     float cost = 0.f;
     for (int l0 = 0; l0 < G.n_links; l0 += N) {
         const int nl = min(N, G.n_links - l0);
-#ifndef MPB_NO_COST_PRIO
         // issue priority by the groups still to come (wave-uniform; see model_group_positions)
         switch ((G.n_links - l0 - 1) / N) {
-            case 0: __builtin_amdgcn_s_setprio(MPB_COST_PRIO(0)); break;
-            case 1: __builtin_amdgcn_s_setprio(MPB_COST_PRIO(1)); break;
-            case 2: __builtin_amdgcn_s_setprio(MPB_COST_PRIO(2)); break;
-            default: __builtin_amdgcn_s_setprio(MPB_COST_PRIO(3)); break;
+            case 0: __builtin_amdgcn_s_setprio(cost_prio(0)); break;
+            case 1: __builtin_amdgcn_s_setprio(cost_prio(1)); break;
+            case 2: __builtin_amdgcn_s_setprio(cost_prio(2)); break;
+            default: __builtin_amdgcn_s_setprio(cost_prio(3)); break;
         }
-#endif
         float x[N], y[N], z[N], rl[N];
         int fr[N];
         float4 lkv[N];
@@ -1270,22 +1224,10 @@ __device__ __forceinline__ float waypoint_cost_grid_grad(const GeomView& G, cons
         for (int i = 0; i < N; ++i) {
             const float h = fmaxf(G.margin + rl[i] - best[i], 0.f);   // parked slots: best = 3e38 -> 0
             cost += h;
-            if (__any(h > 0.f)) {
-                const float sc = (h > 0.f) ? -1.0f / vn[i] : 0.f;
-                const float fx = vx[i] * sc, fy = vy[i] * sc, fz = vz[i] * sc;
-#pragma unroll
-                for (int ii = 0; ii < MPB_MAX_DOF; ++ii) {
-                    if (ii < fr[i] && ii < G.n_dof) {
-                        // d x / d q_ii = z_ii x (x - p_ii) for every joint upstream of the sphere's frame
-                        dq[ii] += joint_term(F.zx[ii], F.zy[ii], F.zz[ii], F.px[ii], F.py[ii], F.pz[ii], x[i], y[i], z[i], fx, fy, fz);
-                    }
-                }
-            }
+            hinge_jtf(G, F, x[i], y[i], z[i], h, vx[i], vy[i], vz[i], vn[i], fr[i], dq);
         }
     }
-#ifndef MPB_NO_COST_PRIO
     __builtin_amdgcn_s_setprio(0);
-#endif
     return cost;
 }
 
@@ -1298,94 +1240,14 @@ __device__ __forceinline__ float waypoint_cost_grid_grad(const GeomView& G, cons
 // besides the folded arithmetic: no scalar loads on the chain, no `joint < frame` predicates (a sphere's frame is a
 // constant: its joint loop is exactly as long as its chain), no select chains for q_j and for the joint tables.
 // ------------------------------------------------------------------------------------------------
-template <class M>
-struct ModelFKGrad : ModelFK {
-    float zx[M::N_DOF], zy[M::N_DOF], zz[M::N_DOF], px[M::N_DOF], py[M::N_DOF], pz[M::N_DOF];
-};
-
-template <class M, int J>
-__device__ __forceinline__ void model_fk_advance_grad(ModelFKGrad<M>& F, const float (&q)[MPB_MAX_DOF]) {
-    constexpr float p0x = M::TF[J][0], p0y = M::TF[J][1], p0z = M::TF[J][2], p0w = M::TF[J][3];
-    constexpr float p1x = M::TF[J][4], p1y = M::TF[J][5], p1z = M::TF[J][6], p1w = M::TF[J][7];
-    constexpr float p2x = M::TF[J][8], p2y = M::TF[J][9], p2z = M::TF[J][10], p2w = M::TF[J][11];
-    const float ntx = mad3(F.r00, p0w, F.r01, p1w, F.r02, p2w, F.tx);
-    const float nty = mad3(F.r10, p0w, F.r11, p1w, F.r12, p2w, F.ty);
-    const float ntz = mad3(F.r20, p0w, F.r21, p1w, F.r22, p2w, F.tz);
-    F.tx = ntx; F.ty = nty; F.tz = ntz;
-    float a00 = dot3(F.r00, p0x, F.r01, p1x, F.r02, p2x), a01 = dot3(F.r00, p0y, F.r01, p1y, F.r02, p2y),
-          a02 = dot3(F.r00, p0z, F.r01, p1z, F.r02, p2z);
-    float a10 = dot3(F.r10, p0x, F.r11, p1x, F.r12, p2x), a11 = dot3(F.r10, p0y, F.r11, p1y, F.r12, p2y),
-          a12 = dot3(F.r10, p0z, F.r11, p1z, F.r12, p2z);
-    float a20 = dot3(F.r20, p0x, F.r21, p1x, F.r22, p2x), a21 = dot3(F.r20, p0y, F.r21, p1y, F.r22, p2y),
-          a22 = dot3(F.r20, p0z, F.r21, p1z, F.r22, p2z);
-    if constexpr (J < M::N_DOF) {
-        float sn, cs;
-        fast_sincos(q[J], sn, cs);
-        const float n00 = fmaf(a01, sn, a00 * cs), n01 = fmaf(-a00, sn, a01 * cs);
-        const float n10 = fmaf(a11, sn, a10 * cs), n11 = fmaf(-a10, sn, a11 * cs);
-        const float n20 = fmaf(a21, sn, a20 * cs), n21 = fmaf(-a20, sn, a21 * cs);
-        a00 = n00; a01 = n01; a10 = n10; a11 = n11; a20 = n20; a21 = n21;
-        F.zx[J] = a02; F.zy[J] = a12; F.zz[J] = a22;          // joint axis and origin in the base frame
-        F.px[J] = F.tx; F.py[J] = F.ty; F.pz[J] = F.tz;
-    }
-    F.r00 = a00; F.r01 = a01; F.r02 = a02; F.r10 = a10; F.r11 = a11; F.r12 = a12;
-    F.r20 = a20; F.r21 = a21; F.r22 = a22;
-}
-
-// positions of the collision spheres of group GRP (model_group_positions with the gradient state)
-template <class M, int GRP>
-__device__ __forceinline__ bool model_group_positions_grad(ModelFKGrad<M>& F, const float (&q)[MPB_MAX_DOF], unsigned keep,
-                                                           float (&x)[4], float (&y)[4], float (&z)[4], float (&rl)[4]) {
-    constexpr float FAR = 1.0e9f;
-    constexpr int G1 = (M::N_FRAME1 + 3) / 4;
-    constexpr bool first = GRP < G1;
-    constexpr int lo = first ? 4 * GRP : M::N_FRAME1 + 4 * (GRP - G1);
-    constexpr int part_end = first ? M::N_FRAME1 : M::N_LINKS;
-    constexpr int hi = (lo + 4 < part_end) ? lo + 4 : part_end;
-#ifndef MPB_NO_COST_PRIO
-    {
-        constexpr int NG_ = (M::N_FRAME1 + 3) / 4 + (M::N_LINKS - M::N_FRAME1 + 3) / 4;
-        __builtin_amdgcn_s_setprio(MPB_COST_PRIO(NG_ - 1 - GRP));
-    }
-#endif
-    static_for<lo, hi>([&](auto lc) {
-        constexpr int l = decltype(lc)::value;
-        constexpr int f = M::LINK_FRAME[l];
-        constexpr int fprev = (l == 0) ? 0 : M::LINK_FRAME[l > 0 ? l - 1 : 0];
-        static_for<fprev, f>([&](auto jc) { model_fk_advance_grad<M, decltype(jc)::value>(F, q); });
-        constexpr int slot = l - lo;
-        constexpr float ox = M::LINK[l][0], oy = M::LINK[l][1], oz = M::LINK[l][2], rad = M::LINK[l][3];
-        const float px = mad3(F.r00, ox, F.r01, oy, F.r02, oz, F.tx);
-        const float py = mad3(F.r10, ox, F.r11, oy, F.r12, oz, F.ty);
-        const float pz = mad3(F.r20, ox, F.r21, oy, F.r22, oz, F.tz);
-        if constexpr (first) {
-            const bool on = (keep >> l) & 1u;                // wave-uniform
-            x[slot] = on ? px : FAR; y[slot] = on ? py : FAR; z[slot] = on ? pz : FAR; rl[slot] = on ? rad : 0.f;
-        } else {
-            x[slot] = px; y[slot] = py; z[slot] = pz; rl[slot] = rad;
-        }
-    });
-#pragma unroll
-    for (int i = hi - lo; i < 4; ++i) { x[i] = y[i] = z[i] = FAR; rl[i] = 0.f; }
-    if constexpr (first) {
-        constexpr unsigned gmask = ((hi >= 32) ? 0xFFFFFFFFu : ((1u << hi) - 1u)) & ~((1u << lo) - 1u);
-        return (keep & gmask) != 0u;
-    }
-    return true;
-}
-
 // J^T f of the spheres of group GRP: slot i (sphere lo + i, on frame LINK_FRAME) pulls on the joints 0 .. frame - 1
 template <class M, int GRP>
-__device__ __forceinline__ void model_group_jtf(const ModelFKGrad<M>& F, const GeomView& G, const float (&x)[4],
+__device__ __forceinline__ void model_group_jtf(const ModelFK<M, true>& F, const GeomView& G, const float (&x)[4],
                                                 const float (&y)[4], const float (&z)[4], const float (&rl)[4],
                                                 const float (&best)[4], const float (&vx)[4], const float (&vy)[4],
                                                 const float (&vz)[4], const float (&vn)[4], float& cost,
                                                 float (&dq)[MPB_MAX_DOF]) {
-    constexpr int G1 = (M::N_FRAME1 + 3) / 4;
-    constexpr bool first = GRP < G1;
-    constexpr int lo = first ? 4 * GRP : M::N_FRAME1 + 4 * (GRP - G1);
-    constexpr int part_end = first ? M::N_FRAME1 : M::N_LINKS;
-    constexpr int hi = (lo + 4 < part_end) ? lo + 4 : part_end;
+    constexpr int lo = ModelGroup<M, GRP>::lo, hi = ModelGroup<M, GRP>::hi;
     static_for<0, 4>([&](auto ic) {
         constexpr int i = decltype(ic)::value;
         const float h = fmaxf(G.margin + rl[i] - best[i], 0.f);   // parked slots: best = 3e38 -> 0
@@ -1406,15 +1268,7 @@ __device__ __forceinline__ void model_group_jtf(const ModelFKGrad<M>& F, const G
 }
 
 template <class M, int... GRPS>
-__device__ __forceinline__ bool model_group_dispatch_grad(int grp, ModelFKGrad<M>& F, const float (&q)[MPB_MAX_DOF], unsigned keep,
-                                                          float (&x)[4], float (&y)[4], float (&z)[4], float (&rl)[4],
-                                                          std::integer_sequence<int, GRPS...>) {
-    bool run = false;
-    ((grp == GRPS ? (void)(run = model_group_positions_grad<M, GRPS>(F, q, keep, x, y, z, rl)) : (void)0), ...);
-    return run;
-}
-template <class M, int... GRPS>
-__device__ __forceinline__ void model_group_dispatch_jtf(int grp, const ModelFKGrad<M>& F, const GeomView& G, const float (&x)[4],
+__device__ __forceinline__ void model_group_dispatch_jtf(int grp, const ModelFK<M, true>& F, const GeomView& G, const float (&x)[4],
                                                          const float (&y)[4], const float (&z)[4], const float (&rl)[4],
                                                          const float (&best)[4], const float (&vx)[4], const float (&vy)[4],
                                                          const float (&vz)[4], const float (&vn)[4], float& cost,
@@ -1425,12 +1279,11 @@ __device__ __forceinline__ void model_group_dispatch_jtf(int grp, const ModelFKG
 template <class M>
 __device__ __forceinline__ float waypoint_cost_grid_grad_model(const GeomView& G, const unsigned* gridw, const float4* otab,
                                                                const float (&q)[MPB_MAX_DOF], float (&dq)[MPB_MAX_DOF]) {
-    constexpr int NG = (M::N_FRAME1 + 3) / 4 + (M::N_LINKS - M::N_FRAME1 + 3) / 4;
+    constexpr int NG = ModelGroup<M>::NG;
 #pragma unroll
     for (int i = 0; i < MPB_MAX_DOF; ++i) dq[i] = 0.f;
-    ModelFKGrad<M> F;
-    F.r00 = 1.f; F.r01 = 0.f; F.r02 = 0.f; F.r10 = 0.f; F.r11 = 1.f; F.r12 = 0.f; F.r20 = 0.f; F.r21 = 0.f; F.r22 = 1.f;
-    F.tx = F.ty = F.tz = 0.f;
+    ModelFK<M, true> F;
+    fk_identity(F);
 #pragma unroll
     for (int i = 0; i < M::N_DOF; ++i) { F.zx[i] = F.zy[i] = F.zz[i] = F.px[i] = F.py[i] = F.pz[i] = 0.f; }
     float cost = 0.f;
@@ -1438,22 +1291,30 @@ __device__ __forceinline__ float waypoint_cost_grid_grad_model(const GeomView& G
 #pragma nounroll
     for (int grp = 0; grp < NG; ++grp) {
         float x[4], y[4], z[4], rl[4];
-        const bool run = model_group_dispatch_grad<M>(grp, F, q, keep, x, y, z, rl, std::make_integer_sequence<int, NG>{});
+        const bool run = model_group_dispatch<M, false>(grp, F, q, keep, x, y, z, rl, 0.f, std::make_integer_sequence<int, NG>{});
         if (run) {
             float best[4], vx[4], vy[4], vz[4], vn[4];
             spheres_nearest_grid<4>(G, gridw, otab, x, y, z, best, vx, vy, vz, vn);
             model_group_dispatch_jtf<M>(grp, F, G, x, y, z, rl, best, vx, vy, vz, vn, cost, dq, std::make_integer_sequence<int, NG>{});
         }
     }
-#ifndef MPB_NO_COST_PRIO
     __builtin_amdgcn_s_setprio(0);
-#endif
     return cost;
 }
 
-// the gradient evaluator a kernel should call for this field: the compile-time model when the buffer carries its id
-__device__ __forceinline__ float waypoint_cost_grid_grad_any(const GeomView& G, const unsigned* gridw, const float4* otab,
-                                                             const float (&q)[MPB_MAX_DOF], float (&dq)[MPB_MAX_DOF]) {
-    if (G.model == PandaModel::ID) return waypoint_cost_grid_grad_model<PandaModel>(G, gridw, otab, q, dq);   // wave-uniform
-    return waypoint_cost_grid_grad(G, gridw, otab, q, dq);
+// The gradient evaluator that serves a field.  `ug`: the field's compact grid is staged in LDS as gridw / otab (grid_usable_grad,
+// decided by the kernel, which also stages it); otherwise the exhaustive walk runs.  MODEL: the compile-time robot model whose
+// gradient walk the kernel was instantiated for (0: the table-driven walks).  The launcher picks it from geom_flags; the
+// buffer's own tag is re-checked here, and a mismatch poisons cost and gradient (NaN) instead of mis-reading the buffer.
+// (gpmp2_linearize_kernel calls it; chomp_kernel and collision_cost_kernel spell the same choice out around their own scaling.)
+template <int MODEL>
+__device__ __forceinline__ float waypoint_cost_grad_any(const GeomView& G, bool ug, const unsigned* gridw, const float4* otab,
+                                                        const float (&q)[MPB_MAX_DOF], float (&dq)[MPB_MAX_DOF]) {
+    if (MODEL == PandaModel::ID) {
+        if (G.model == PandaModel::ID && ug) return waypoint_cost_grid_grad_model<PandaModel>(G, gridw, otab, q, dq);
+#pragma unroll
+        for (int i = 0; i < MPB_MAX_DOF; ++i) dq[i] = __uint_as_float(0x7FC00000u);
+        return __uint_as_float(0x7FC00000u);
+    }
+    return ug ? waypoint_cost_grid_grad(G, gridw, otab, q, dq) : waypoint_cost<true>(G, q, dq);
 }

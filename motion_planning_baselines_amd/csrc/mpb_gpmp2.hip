@@ -39,20 +39,7 @@ typedef double f64x4 __attribute__((ext_vector_type(4)));
 // linearisation of the collision factor: jac[b][t][0..D) = h_t = -d c_t/d q, jac[b][t][D] = c_t
 // (t = 0 is excluded from the collision factor: traj_range [1, None]).  One wave per particle, lane = waypoint.
 // ------------------------------------------------------------------------------------------------
-// MODEL: compile-time robot model whose gradient walk the kernel runs (0: the table-driven walk); the geometry's tag is
-// re-checked on the device and a mismatch poisons the rows (NaN) instead of mis-reading the buffer.
-template <int MODEL>
-__device__ __forceinline__ float gp_point_grad(const GeomView& G, bool ug, const unsigned* gridw, const float4* otab,
-                                               const float (&q)[MPB_MAX_DOF], float (&dq)[MPB_MAX_DOF]) {
-    if (MODEL == PandaModel::ID) {
-        if (G.model == PandaModel::ID && ug) return waypoint_cost_grid_grad_model<PandaModel>(G, gridw, otab, q, dq);
-#pragma unroll
-        for (int i = 0; i < MPB_MAX_DOF; ++i) dq[i] = __uint_as_float(0x7FC00000u);
-        return __uint_as_float(0x7FC00000u);
-    }
-    return ug ? waypoint_cost_grid_grad(G, gridw, otab, q, dq) : waypoint_cost<true>(G, q, dq);
-}
-
+// MODEL: compile-time robot model whose gradient walk the kernel runs (0: the table-driven walk): waypoint_cost_grad_any.
 // INTERP: the interpolated-Jacobian path exists in the instantiation (its arrays cost ~40 registers the plain
 // linearisation does not need); WPE: waves per SIMD the register allocation aims at.
 template <int MODEL, bool INTERP, int WPE>
@@ -98,7 +85,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE))) void
                 gnext[i] = 0.f;
             }
             float c = 0.f;
-            if (active && t >= 1) c = gp_point_grad<MODEL>(G, ug, gridw, otab, q, dq);
+            if (active && t >= 1) c = waypoint_cost_grad_any<MODEL>(G, ug, gridw, otab, q, dq);
             if (n_interp > 0) {
                 if (active && t + 1 < H) {
                     float qn[MPB_MAX_DOF];
@@ -109,7 +96,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE))) void
                         float qi[MPB_MAX_DOF], dqi[MPB_MAX_DOF];
 #pragma unroll
                         for (int i = 0; i < MPB_MAX_DOF; ++i) qi[i] = q[i] + al * (qn[i] - q[i]);
-                        gp_point_grad<MODEL>(G, ug, gridw, otab, qi, dqi);
+                        waypoint_cost_grad_any<MODEL>(G, ug, gridw, otab, qi, dqi);
 #pragma unroll
                         for (int i = 0; i < MPB_MAX_DOF; ++i) {
                             dq[i] = fmaf(1.f - al, dqi[i], dq[i]);
@@ -796,7 +783,7 @@ extern "C" int mpb_gpmp2_linearize(const float* x, const float* geom, int geom_f
 #ifndef GP_LIN_WPE
 #define GP_LIN_WPE 3
 #endif
-    const bool model = (geom_flags & 0xFF) == PandaModel::ID && (geom_flags & 0x100) && D == PandaModel::N_DOF;
+    const bool model = mpb_flags_model_on_grids(geom_flags, PandaModel::ID) && D == PandaModel::N_DOF;
 #define GP_LIN(MODEL, INTERP, WPE)                                                                                           \
     hipLaunchKernelGGL((gpmp2_linearize_kernel<MODEL, INTERP, WPE>), dim3((B + 3) / 4), dim3(256), 0, (hipStream_t)stream, x, \
                        geom, w.jac, B, H, D, n_interp)

@@ -34,6 +34,9 @@ static inline bool mpb_misaligned16(const void* a, const void* b = nullptr, cons
                                     const void* e = nullptr, const void* f = nullptr) {
     return ((((uintptr_t)a) | ((uintptr_t)b) | ((uintptr_t)c) | ((uintptr_t)d) | ((uintptr_t)e) | ((uintptr_t)f)) & 15u) != 0;
 }
+// do the geom_flags of mpb_geom_flags name the compile-time robot model `model_id` (low byte) AND report every chained field
+// backed by a compact grid (bit 8)?  Only then may a launcher pick the kernel instantiated for that model.
+static inline bool mpb_flags_model_on_grids(int geom_flags, int model_id) { return (geom_flags & 0xFF) == model_id && (geom_flags & 0x100); }
 // the shapes and LDS budget mpb_stomp_update takes (defined beside the update kernels in mpb_kernels.hip): MPB_OK, or the code and
 // message (under the name `who`) of the refusal -- for callers that enqueue the update behind other stages and must refuse before
 // the first launch

@@ -755,7 +755,7 @@ extern "C" int mpb_cost_collision_grad(const float* trajs, const float* geom, in
     if (B == 0) return MPB_OK;
     if (!trajs || !geom || !out || !grad) return mpb_failf(MPB_E_INVALID, "%s: null pointer", __func__);
     if (B < 0 || H < 1 || d < 1 || d > 2 * MPB_MAX_DOF || h_begin < 0) return mpb_failf(MPB_E_INVALID, "%s: bad shape", __func__);   // (rows of any width up to positions + velocities of 12 joints; the first n_dof channels are read)
-    if ((geom_flags & 0xFF) == PandaModel::ID && (geom_flags & 0x100))
+    if (mpb_flags_model_on_grids(geom_flags, PandaModel::ID))
         hipLaunchKernelGGL((collision_cost_kernel<true, PandaModel::ID>), dim3((B + 3) / 4), dim3(256), 0, (hipStream_t)stream, trajs,
                            geom, out, (float*)nullptr, grad, B, H, d, h_begin, k_sigma, weight);
     else
@@ -821,7 +821,7 @@ static void launch_sample(const StompCall& c, const float* eps, uint32_t iter, h
         return;
     // (bit 8: every field COMPACT-grid-backed -- since round 6 the model byte is also set for list-grid scenes, which this kernel
     // serves through the exhaustive walk)
-    if (H == 64 && WITH_COST && (c.geom_flags & 0xFF) == PandaModel::ID && (c.geom_flags & 0x100)) {   // the Panda's channel counts (pos_only / not)
+    if (H == 64 && WITH_COST && mpb_flags_model_on_grids(c.geom_flags, PandaModel::ID)) {   // the Panda's channel counts (pos_only / not)
         switch (d) {
             MPB_A_CASE(7, (WITH_COST ? PandaModel::ID : 0)) MPB_A_CASE(14, (WITH_COST ? PandaModel::ID : 0))
             default: break;

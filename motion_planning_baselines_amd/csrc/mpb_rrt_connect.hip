@@ -392,7 +392,7 @@ extern "C" size_t mpb_rrt_connect_workspace_bytes(int B, int max_nodes, int n_pr
 }
 
 static bool rrt_use_model(int geom_flags, int D) {
-    return (geom_flags & 0xFF) == PandaModel::ID && (geom_flags & 0x100) && D == PandaModel::N_DOF;
+    return mpb_flags_model_on_grids(geom_flags, PandaModel::ID) && D == PandaModel::N_DOF;
 }
 
 extern "C" int mpb_rrt_connect_init(void* workspace, size_t workspace_bytes, const float* start, const float* goal,

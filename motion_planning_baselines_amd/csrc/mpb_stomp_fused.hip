@@ -727,7 +727,7 @@ int mpb_fused_launch(const StompCall& c, const StompLaunch& l, const StompFusedG
     const bool two_batches = g.nb == 2;
     const dim3 grid(two_batches ? c.P : c.P * g.nc), block(FUSED_THREADS);
     const int nc_k = two_batches ? 1 : g.nc;
-    const int model = c.geom_flags & 0xFF, d = c.d;
+    const int model = mpb_flags_model_on_grids(c.geom_flags, PandaModel::ID) ? PandaModel::ID : 0, d = c.d;   // (bit 8: fused_plan)
     const uint32_t lo = (uint32_t)c.seed, hi = (uint32_t)(c.seed >> 32);
 #define MPB_F_LAUNCH_(DCH, MODEL, NB, INJ, CHAIN)                                                                                       \
     MPB_LAUNCH(l.events, (stomp_fused_kernel<DCH, MODEL, NB, INJ, CHAIN>), grid, block, 0, l.stream, c.means, c.eps, c.samples, c.costs, \
