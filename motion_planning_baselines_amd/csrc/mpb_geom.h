@@ -1043,7 +1043,15 @@ __device__ __forceinline__ bool model_group_dispatch(int grp, ModelFK<M, GRAD>& 
     return run;
 }
 
-template <class M, bool OFFS = false, bool LIST = false>
+// UNROLLED: the group loop is unrolled at compile time -- one straight-line block per group, each with its own copy of the
+// grid look-up -- instead of a real loop with one arm per group and ONE look-up.  Same calls in the same group order, same
+// s_setprio per group, hinges added sphere by sphere in the same order: the same bits.  What the rolled form pays for its
+// single look-up is loop-carried state: the chain frame (12 floats) and the group's x / y / z / rl (16) must sit in the same
+// registers at the end of every arm, the identity frame is run-time data (joint 0 is rotated in full against it), and every
+// trip goes through the compare chain.  Unrolled, the headline kernel stomp_fused_kernel<14, 1, 1, false, false> is 33.2 KB of
+// code instead of 19.3 KB, at 124 VGPRs and 0 B of scratch; the persistent kernel's chained-field forms spill 180-288 B with it
+// and keep the loop, like every other caller (registers, code sizes and timings of both forms).
+template <class M, bool OFFS = false, bool LIST = false, bool UNROLLED = false>
 __device__ __forceinline__ float waypoint_cost_grid_model(const GeomView& G, const unsigned* gridw, const float4* otab,
                                                           const float (&q)[MPB_MAX_DOF], const ListView* LV = nullptr) {
     constexpr int NG = ModelGroup<M>::NG;
@@ -1054,15 +1062,34 @@ __device__ __forceinline__ float waypoint_cost_grid_model(const GeomView& G, con
     const GridAddr GA = (OFFS || LIST) ? grid_addr(G) : GridAddr{};
     float mrg = G.margin;                    // in a VECTOR register: v_add takes the literal radius plus one register
     asm volatile("" : "+v"(mrg));
-    // a real loop over the groups with ONE instance of the grid look-up (unrolling it per group is 60 KB of code)
+    if constexpr (UNROLLED) {
+        static_for<0, NG>([&](auto gc) {
+            float x[4], y[4], z[4], rl[4];
+            using GR = ModelGroup<M, decltype(gc)::value>;
+            const bool run = model_group_positions<M, decltype(gc)::value, true>(F, q, keep, x, y, z, rl, mrg);
+            // The sphere centres reach the look-up as opaque registers, as they do through the loop-carried registers of the rolled
+            // form.  Where the frame's translation is a compile-time zero (frames 1 and 2 of the Panda) a centre folds to a bare
+            // product, which the compiler would contract with the look-up's `x - s.x` into ONE fma -- one rounding instead of
+            // two, and no longer the bits of fmaf(r, o, t) that every other evaluator computes.
+#pragma unroll
+            for (int i = 0; i < GR::hi - GR::lo; ++i) asm("" : "+v"(x[i]), "+v"(y[i]), "+v"(z[i]));
+            if constexpr (LIST) {
+                if (run) spheres_hinge_list<4, true, true>(G, *LV, x, y, z, rl, cost, GA);
+            } else {
+                if (run) spheres_hinge_grid<4, OFFS, true, true>(G, gridw, otab, x, y, z, rl, cost, GA);
+            }
+        });
+    } else {
+        // a real loop over the groups with ONE instance of the grid look-up
 #pragma nounroll
-    for (int grp = 0; grp < NG; ++grp) {
-        float x[4], y[4], z[4], rl[4];
-        const bool run = model_group_dispatch<M, true>(grp, F, q, keep, x, y, z, rl, mrg, std::make_integer_sequence<int, NG>{});
-        if constexpr (LIST) {
-            if (run) spheres_hinge_list<4, true, true>(G, *LV, x, y, z, rl, cost, GA);
-        } else {
-            if (run) spheres_hinge_grid<4, OFFS, true, true>(G, gridw, otab, x, y, z, rl, cost, GA);
+        for (int grp = 0; grp < NG; ++grp) {
+            float x[4], y[4], z[4], rl[4];
+            const bool run = model_group_dispatch<M, true>(grp, F, q, keep, x, y, z, rl, mrg, std::make_integer_sequence<int, NG>{});
+            if constexpr (LIST) {
+                if (run) spheres_hinge_list<4, true, true>(G, *LV, x, y, z, rl, cost, GA);
+            } else {
+                if (run) spheres_hinge_grid<4, OFFS, true, true>(G, gridw, otab, x, y, z, rl, cost, GA);
+            }
         }
     }
     __builtin_amdgcn_s_setprio(0);

@@ -358,7 +358,9 @@ __global__ __launch_bounds__(FUSED_THREADS, 4) void stomp_fused_kernel(
                 if (live && h >= 1) {
 #endif
                     if (MODEL == PandaModel::ID) {
-                        if (G.model == PandaModel::ID) c = fmaf(G.fscale, waypoint_cost_grid_model<PandaModel, true>(G, gridw, otab, q), c);
+                        // (one field: the walk's groups unrolled -- 0 B scratch in all eight such forms; unrolled, the chained
+                        // forms spill 180-288 B and keep the loop: mpb_geom.h, waypoint_cost_grid_model)
+                        if (G.model == PandaModel::ID) c = fmaf(G.fscale, waypoint_cost_grid_model<PandaModel, true, false, !CHAIN>(G, gridw, otab, q), c);
                     } else {
                         c = fmaf(G.fscale, waypoint_cost_grid<true>(G, gridw, otab, q), c);
                     }

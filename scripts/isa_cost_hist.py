@@ -15,6 +15,12 @@ instruction where the full rate is 2.  This script prices the loop body by opcod
          one group of four collision spheres, each arm once per iteration); the block with the v_sqrt_f32 and the ds_read of the
          grid word is the group's SLOT-0 body (once per group that runs); blocks starting with v_bfe_u32 are the LATER candidate
          slots; the depth-4 loops are the exhaustive / box loops (never at C3);
+       * the one-field instantiations take the walk UNROLLED (waypoint_cost_grid_model<..., UNROLLED = true>): there is no group
+         loop, the walk is straight-line code of the iteration loop itself.  Per group: ONE block that holds the arm and the
+         SLOT-0 body (four v_sqrt_f32 and the v_mad_u32_u24 of the cell index; once per iteration, the frame-1 groups by the
+         share of them that runs), behind it -- up to the label its closing branch skips to -- the LATER slots (blocks starting
+         with v_bfe_u32) and their glue (the slot-1 trips of the group), and a depth-2 exhaustive loop (never at C3).  The
+         crowded-cell code LLVM moves behind the loop's latch is cold (never);
        * the number of group bodies and later-slot trips per iteration is not static (frame-1 groups can be skipped, later
          slots run while any lane has a candidate): it is SOLVED from the PMC pass's SQ_INSTS_VALU_TRANS_F32 (v_sqrt: four per
          trip, everything else that is transcendental is static), and the split of the later slots between slot 1 and slot 2 from
@@ -195,6 +201,7 @@ def main():
     grp_loop, inner4 = find_grp(3)
     if grp_loop is None:
         grp_loop, inner4 = find_grp(2)
+    unrolled = grp_loop is None          # no group loop: the walk is straight-line code of the iteration loop
 
     def in_iteration_loop(b):
         if depth_of(b) == 0:
@@ -211,8 +218,31 @@ def main():
     # ---- phases by position (the kernel's source order survives: A sample, B cost, C partial, D Sigma product, noise draw, poll, E update)
     loop_blocks = [b for b in blocks if in_iteration_loop(b)]
     idx = {id(b): i for i, b in enumerate(loop_blocks)}
-    first_grp = min(idx[id(b)] for b in loop_blocks if header_of(b) == grp_loop or header_of(b) in inner4)
-    last_grp = max(idx[id(b)] for b in loop_blocks if header_of(b) == grp_loop or header_of(b) in inner4)
+    nsqrt = lambda b: sum(1 for x in b['ins'] if x.startswith('v_sqrt_f32'))
+    body_of, cold_from = {}, len(loop_blocks)
+    if unrolled:
+        # group blocks: depth 1, the four distances of slot 0 and the cell index arithmetic (the Box-Muller blocks of the draw have
+        # square roots too, and no v_mad_u32_u24)
+        bodies_u = [i for i, b in enumerate(loop_blocks) if header_of(b) == it_loop and nsqrt(b) and
+                    sum(1 for x in b['ins'] if x.startswith('v_mad_u32_u24')) >= 4]
+        # the later-slot region of a group: from its block to the label the block's closing branch skips to
+        label_at = {name_of(b): i for i, b in enumerate(loop_blocks)}
+        for i in bodies_u:
+            m = re.match(r's_cbranch_\w+\s+\.L(BB\d+_\d+)', loop_blocks[i]['ins'][-1])
+            end = label_at.get(m.group(1), i + 1) if m else i + 1
+            for j in range(i + 1, end):
+                body_of[j] = i
+        # cold code behind the latch: the blocks of the loop laid out in front of its header are the latch's targets, the last block
+        # that branches to one of them closes the hot part
+        hdr_pos = next(i for i, b in enumerate(blocks) if name_of(b) == it_loop)
+        front = set(name_of(b) for b in blocks[:hdr_pos] if in_iteration_loop(b))
+        latch = [i for i, b in enumerate(loop_blocks) if b['ins'] and b['ins'][-1].startswith(('s_branch', 's_cbranch')) and
+                 b['ins'][-1].split()[-1].replace('.L', '') in front]
+        cold_from = max(latch) + 1 if latch else len(loop_blocks)
+        first_grp, last_grp = min(bodies_u), max(max(body_of, default=0), max(bodies_u))
+    else:
+        first_grp = min(idx[id(b)] for b in loop_blocks if header_of(b) == grp_loop or header_of(b) in inner4)
+        last_grp = max(idx[id(b)] for b in loop_blocks if header_of(b) == grp_loop or header_of(b) in inner4)
     # the block in front of the field loop that carries the first joints of the chain (fmamk-heavy) belongs to the cost phase
     chain_prefix = max((i for i in range(first_grp) if sum(1 for x in loop_blocks[i]['ins'] if x.startswith('v_')) > 100), default=None)
     noise_blocks = [i for i, b in enumerate(loop_blocks) if any(x.startswith('v_mfma_f32_16x16x32') for x in b['ins']) or
@@ -224,6 +254,8 @@ def main():
 
     def phase(i, b):
         h = header_of(b)
+        if unrolled and (first_grp <= i <= last_grp + 3 or i >= cold_from):
+            return 'B cost'
         if h == grp_loop or h in inner4 or (chain_prefix is not None and chain_prefix <= i <= last_grp + 3 and i >= chain_prefix):
             if i <= last_grp + 3:
                 return 'B cost'
@@ -240,7 +272,7 @@ def main():
         return 'E combine / update'
 
     # the field loop (depth 2, parent of the group loop) and the poll loop (depth 2 with s_sleep / s_memrealtime)
-    field_loop = next((p for p, d in hdr_block[grp_loop]['parents'] if d == 2 and hdr_block[grp_loop]['hdr'] == 3), None)
+    field_loop = None if unrolled else next((p for p, d in hdr_block[grp_loop]['parents'] if d == 2 and hdr_block[grp_loop]['hdr'] == 3), None)
     poll_loops = set()
     for b in loop_blocks:
         if any('s_sleep' in x or 's_memrealtime' in x for x in b['ins']) and header_of(b) not in (it_loop, None):
@@ -266,8 +298,14 @@ def main():
         first = b['ins'][0].split()[0] if b['ins'] else ''
         nsq = sum(1 for x in b['ins'] if x.startswith('v_sqrt_f32'))
         other_loop = h is not None and h not in (it_loop, grp_loop, field_loop) and h not in poll_loops
-        if h in inner4 or other_loop:
+        if h in inner4 or other_loop or i >= cold_from:
             kinds[i] = 'never'                                   # exhaustive overflow / box loops, grid re-staging of chained fields: not at C3
+        elif unrolled and i in bodies_u:
+            kinds[i] = 'group'                                   # arm + slot-0 body of one group
+            body_sqrt = nsq
+        elif unrolled and i in body_of:
+            kinds[i] = 'later' if nsq and any(x.startswith('v_bfe_u32') for x in b['ins'][:4]) else 'later-glue'
+            later_sqrt = max(later_sqrt, nsq)
         elif any(x.startswith('global_load_dwordx4') for x in b['ins']) and i > last_grp:
             kinds[i] = 'never'                                   # injected-eps loads: the timed path draws its noise
         elif i in injected_variants:
@@ -288,17 +326,19 @@ def main():
     for i, b in enumerate(loop_blocks):
         if kinds[i] in ('once', 'arm'):
             trans_static += sum(1 for x in b['ins'] if re.sub(r'_(e32|e64)$', '', x.split()[0]) in TRANS)
+        elif kinds[i] == 'group':                                # (what a group block holds besides its four square roots)
+            trans_static += sum(1 for x in b['ins'] if re.sub(r'_(e32|e64)$', '', x.split()[0]) in TRANS and not x.startswith('v_sqrt_f32'))
     trans_pmc = pmc['SQ_INSTS_VALU_TRANS_F32_per_wave_iteration']
     later_blocks = [i for i in kinds if kinds[i] == 'later']
-    NG = sum(1 for i in kinds if kinds[i] == 'arm')
+    NG = sum(1 for i in kinds if kinds[i] in ('arm', 'group'))
     # the arms come in two rotated copies of the dispatch chain when LLVM rotates the loop: every group has ONE arm that runs
     arm_groups = collections.Counter()
     return_blocks = (blocks, loop_blocks, kinds)
-    return pmc, pmc_file, loop_blocks, kinds, phase, trans_static, trans_pmc, body_sqrt, later_sqrt, NG, args, it_loop, grp_loop
+    return pmc, pmc_file, loop_blocks, kinds, phase, trans_static, trans_pmc, body_sqrt, later_sqrt, NG, args, it_loop, grp_loop, body_of
 
 
 def report():
-    pmc, pmc_file, loop_blocks, kinds, phase, trans_static, trans_pmc, body_sqrt, later_sqrt, n_arm_blocks, args, it_loop, grp_loop = main()
+    pmc, pmc_file, loop_blocks, kinds, phase, trans_static, trans_pmc, body_sqrt, later_sqrt, n_arm_blocks, args, it_loop, grp_loop, body_of = main()
     # groups: the model has (N_FRAME1 + 3) / 4 + (N_LINKS - N_FRAME1 + 3) / 4 groups; LLVM may duplicate arms (loop rotation), the
     # number of DISTINCT groups is what runs: read it from the model header
     hdr = open(os.path.join(ROOT, 'motion_planning_baselines_amd', 'csrc', 'mpb_model_panda.h')).read()
@@ -314,10 +354,27 @@ def report():
     later = trips - bodies
     n_later_blocks = sum(1 for k in kinds.values() if k == 'later')
     mult = {}
+    # unrolled walk: one block per group.  The later groups always run; of the frame-1 groups (the first (N_FRAME1 + 3) / 4 blocks)
+    # what the trip budget leaves over them.  A group's later slots (and their glue) by the group's share of the bodies
+    group_blocks = sorted(i for i in kinds if kinds[i] == 'group')
+    g1 = (n_f1 + 3) // 4
+    f1_share = min(max(bodies - (len(group_blocks) - g1), 0.0), float(g1)) / g1 if group_blocks else 0.0
+    group_mult = {i: (f1_share if n < g1 else 1.0) for n, i in enumerate(group_blocks)}
+    group_sum = sum(group_mult.values()) or 1.0
+    if group_blocks:
+        bodies = group_sum                                       # (structural here: what is left of the trip budget are later slots)
+        later = max(trips - bodies, 0.0)
     for i, b in enumerate(loop_blocks):
         k = kinds[i]
         if k == 'never':
             mult[i] = 0.0
+        elif k == 'group':
+            mult[i] = group_mult[i]
+        elif k in ('later', 'later-glue') and i in body_of:
+            g = body_of[i]
+            order = sorted(j for j in body_of if body_of[j] == g and kinds[j] == 'later')
+            slot2 = k == 'later' and order.index(i) > 0
+            mult[i] = later * (args.slot2_share if slot2 else 1.0 - args.slot2_share) * group_mult[g] / group_sum
         elif k == 'arm':
             mult[i] = arm_mult
         elif k == 'body':
@@ -370,10 +427,18 @@ def report():
     P('# Instruction-cost histogram of `%s` -- one iteration of the persistent loop, per wave' % args.kernel)
     P('')
     P('Made by `scripts/isa_cost_hist.py` (rules and prices: its docstring) from the assembly of the product build and `%s`.' % os.path.relpath(pmc_file, ROOT))
-    P('Multiplicities: %d groups of four collision spheres (arms: %d blocks, %.2f executions each); from TRANS_F32 = %.1f per wave-iteration' %
-      (NG, n_arm_blocks, arm_mult, trans_pmc))
-    P('(static transcendental instructions: %.0f) -> %.2f distance trips of 4 sqrt = %.2f group bodies x 1.39 trips (scripts/grid_stats.py).' %
-      (trans_static, trips, bodies))
+    if group_blocks:
+        P('Multiplicities: %d groups of four collision spheres, the walk unrolled (one block per group: %s executions); from TRANS_F32 = %.1f per wave-iteration' %
+          (NG, ' / '.join('%.2f' % group_mult[i] for i in group_blocks), trans_pmc))
+    else:
+        P('Multiplicities: %d groups of four collision spheres (arms: %d blocks, %.2f executions each); from TRANS_F32 = %.1f per wave-iteration' %
+          (NG, n_arm_blocks, arm_mult, trans_pmc))
+    if group_blocks:
+        P('(static transcendental instructions: %.0f) -> %.2f distance trips of 4 sqrt = %.2f group bodies + %.2f later-slot trips.' %
+          (trans_static, trips, bodies, later))
+    else:
+        P('(static transcendental instructions: %.0f) -> %.2f distance trips of 4 sqrt = %.2f group bodies x 1.39 trips (scripts/grid_stats.py).' %
+          (trans_static, trips, bodies))
     P('')
     P('## Reconciliation with the PMC pass')
     P('')
