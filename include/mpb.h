@@ -18,8 +18,8 @@
  *   - shapes: P particles, S samples per particle, B = P*S rollouts, H support points (horizon),
  *     D degrees of freedom, d = optimised state width (D if pos_only else 2D).
  *   - `geom` is the packed geometry word buffer (motion_planning_baselines_amd/geometry.py
- *     pack_geometry; layout in csrc/mpb_geom.h): robot kinematics + collision spheres + obstacle
- *     spheres / boxes + hinge margin.  It stands in for the reference's external robot / field objects
+ *     pack_geometry; layout: the table at the top of that module, in C as mpb_geom_layout.h): robot
+ *     kinematics + collision spheres + obstacle spheres / boxes + hinge margin.  It stands in for the reference's external robot / field objects
  *     (cost_functions.py:50-52 robot.fk_map_collision, field_factor.py:39 field.compute_cost).
  */
 #ifndef MPB_H
@@ -27,6 +27,10 @@
 
 #include <stddef.h>
 #include <stdint.h>
+
+/* the packed geometry buffer in numbers (generated from geometry.py): header word indices MPB_GW_*, geometry versions, robot
+ * kinds, MPB_MAX_DOF / MPB_MAX_FIELDS and the grid limits, the cell-word fields, MPB_GEOM_FLAG_* */
+#include "mpb_geom_layout.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -38,7 +42,6 @@ extern "C" {
 #define MPB_E_HIP 3         /* a HIP runtime call failed; see mpb_last_error() */
 
 #define MPB_MAX_H 256
-#define MPB_MAX_DOF 12
 
 /* ABI version in the low 16 bits (MPB_ABI_VERSION: bumped whenever a signature of this header changes positionally or a call that
  * used to be accepted is now refused; a binding must refuse a library that reports another number); bit 30 set = a tuning build
@@ -64,18 +67,30 @@ const char *mpb_last_error(void);
 /* Validate a packed geometry buffer held in HOST memory (n_words 32-bit words). */
 int mpb_geom_check(const float *geom_host, int n_words);
 /* Properties of a (valid) packed geometry buffer, read from its HOST copy, that let a launcher pick a kernel
- * instantiation without touching device memory.  *flags: bits 0-7 = id of the compile-time robot model
- * (csrc/mpb_model_*.h) every chained field is tagged with AND whose cost-only kernels can run (every field has a
- * usable broad-phase grid); 0 = generic table-driven kernels; bit 8 = every chained field has a usable broad-phase
- * grid (what the persistent STOMP kernel needs); bit 9 = point robot with ONE field of at most 32 spheres and 8 boxes
- * (CHOMP's four-lanes-per-waypoint kernel keeps such an obstacle set in registers); bit 10 = point robot; bit 12 = ONE field (no chain: MPPI's LDS grid, the persistent STOMP kernels' one-field instantiations); bits 16-28 = cells of the largest
- * broad-phase grid of the chain when bit 8 or bit 13 is set (what a kernel that stages the grid in LDS has to reserve); bit 13 (round 6) = every
- * chained field carries a LIST grid (geometry version 7: a field with more than 63 obstacle spheres -- up to 255 spheres + 127 boxes, any number
- * of candidates per cell, boxes culled like spheres; bit 8 is then clear): the generalised persistent STOMP kernel takes such a geometry up to
- * H = 64 (csrc/mpb_stomp_fused_hx.hip, LIST), every other kernel walks such a field exhaustively; the model byte is also set for it, and
- * consumers other than that kernel require bit 8 beside it.  Entry points that take `geom_flags` expect the value
- * computed from the host copy of the very buffer `geom` points to (0 is always valid); a kernel re-checks the tag
- * and the one-field promise against the device header and writes NaN costs if they disagree. */
+ * instantiation without touching device memory.  *flags is built from MPB_GEOM_FLAG_* of mpb_geom_layout.h (the values
+ * are what they have been since the bits were introduced; bit 11 is unused):
+ *   & MPB_GEOM_FLAG_MODEL_MASK   id of the compile-time robot model (csrc/mpb_model_*.h) EVERY chained field is tagged with
+ *                                and every field has a usable grid of either format; 0 = generic table-driven kernels.
+ *                                Only the generalised persistent STOMP kernel runs the model on list grids: every other
+ *                                consumer requires MPB_GEOM_FLAG_ALL_GRIDS beside it;
+ *   MPB_GEOM_FLAG_ALL_GRIDS      every chained field has a usable COMPACT broad-phase grid (geometry version 6, at most
+ *                                MPB_GRID_MAX_SPH obstacle spheres): what the persistent STOMP kernels and the cost-only
+ *                                model kernels need;
+ *   MPB_GEOM_FLAG_POINT_SMALL    point robot with ONE field of at most 32 spheres and 8 boxes (CHOMP's
+ *                                four-lanes-per-waypoint kernel keeps such an obstacle set in registers);
+ *   MPB_GEOM_FLAG_POINT          point robot;
+ *   MPB_GEOM_FLAG_ONE_FIELD      ONE field, no chain (MPPI's LDS grid, the persistent STOMP kernels' one-field instantiations);
+ *   MPB_GEOM_FLAG_ALL_LISTS      (round 6) every chained field carries a LIST grid (geometry version 7: a field with more
+ *                                obstacle spheres than a compact grid serves -- up to MPB_LIST_MAX_SPH spheres +
+ *                                MPB_LIST_MAX_BOX boxes, any number of candidates per cell, boxes culled like spheres;
+ *                                MPB_GEOM_FLAG_ALL_GRIDS is then clear): the generalised persistent STOMP kernel takes such a
+ *                                geometry up to H = 64 (csrc/mpb_stomp_fused_hx.hip, LIST), every other kernel walks such a
+ *                                field exhaustively;
+ *   >> MPB_GEOM_FLAG_CELLS_SHIFT & MPB_GEOM_FLAG_CELLS_MASK   cells of the largest broad-phase grid of the chain when ALL_GRIDS or
+ *                                ALL_LISTS is set (what a kernel that stages the grid in LDS has to reserve).
+ * Entry points that take `geom_flags` expect the value computed from the host copy of the very buffer `geom` points to
+ * (0 is always valid); a kernel re-checks the tag and the one-field promise against the device header and writes NaN
+ * costs if they disagree. */
 int mpb_geom_flags(const float *geom_host, int n_words, int *flags);
 
 /* ---------------------------------------------------------------------------------------------

@@ -51,14 +51,15 @@ def parse_resource_remarks(text):
 
 # which sources define the kernels a counter summary (profiles/*_pmc_*.json) was taken for: the summary carries the SHA-1 of these
 # files as they were when the passes ran (scripts/pmc_summary.py), bench.py recomputes it and says when the kernel has changed since
+_LAYOUT = '../../include/mpb_geom_layout.h'     # (relative to csrc: the limits and cell-word fields mpb_geom.h compiles in)
 PMC_SOURCES = {
-    'stomp': ['mpb_stomp_fused.hip', 'mpb_stomp_fused.h', 'mpb_stomp_noise.h', 'mpb_geom.h', 'mpb_common.h', 'mpb_model_panda.h'],
-    'stomp_c5': ['mpb_stomp_fused.hip', 'mpb_stomp_fused.h', 'mpb_stomp_noise.h', 'mpb_geom.h', 'mpb_common.h', 'mpb_model_panda.h'],
-    'stomp_h128': ['mpb_stomp_fused_hx.hip', 'mpb_stomp_fused.h', 'mpb_stomp_noise.h', 'mpb_geom.h', 'mpb_common.h', 'mpb_model_panda.h'],
-    'kernelA': ['mpb_kernels.hip', 'mpb_stomp_noise.h', 'mpb_geom.h', 'mpb_common.h', 'mpb_model_panda.h'],
-    'solve': ['mpb_gpmp2.hip', 'mpb_gpmp2_lr.hip', 'mpb_gpmp2.h', 'mpb_geom.h', 'mpb_common.h'],
-    'chomp': ['mpb_chomp.hip', 'mpb_geom.h', 'mpb_common.h', 'mpb_model_panda.h'],
-    'mppi': ['mpb_mppi.hip', 'mpb_geom.h', 'mpb_common.h'],
+    'stomp': ['mpb_stomp_fused.hip', 'mpb_stomp_fused.h', 'mpb_stomp_noise.h', 'mpb_geom.h', _LAYOUT, 'mpb_common.h', 'mpb_model_panda.h'],
+    'stomp_c5': ['mpb_stomp_fused.hip', 'mpb_stomp_fused.h', 'mpb_stomp_noise.h', 'mpb_geom.h', _LAYOUT, 'mpb_common.h', 'mpb_model_panda.h'],
+    'stomp_h128': ['mpb_stomp_fused_hx.hip', 'mpb_stomp_fused.h', 'mpb_stomp_noise.h', 'mpb_geom.h', _LAYOUT, 'mpb_common.h', 'mpb_model_panda.h'],
+    'kernelA': ['mpb_kernels.hip', 'mpb_stomp_noise.h', 'mpb_geom.h', _LAYOUT, 'mpb_common.h', 'mpb_model_panda.h'],
+    'solve': ['mpb_gpmp2.hip', 'mpb_gpmp2_lr.hip', 'mpb_gpmp2.h', 'mpb_geom.h', _LAYOUT, 'mpb_common.h'],
+    'chomp': ['mpb_chomp.hip', 'mpb_geom.h', _LAYOUT, 'mpb_common.h', 'mpb_model_panda.h'],
+    'mppi': ['mpb_mppi.hip', 'mpb_geom.h', _LAYOUT, 'mpb_common.h'],
 }
 
 
@@ -83,7 +84,7 @@ def _stale():
         return True
     t = min(os.path.getmtime(OUT), os.path.getmtime(DEBUG_OUT))
     deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(('.hip', '.h'))]
-    deps += [os.path.join(os.path.dirname(HERE), 'include', h) for h in ('mpb.h', 'mpb_debug.h')]
+    deps += [os.path.join(os.path.dirname(HERE), 'include', h) for h in ('mpb.h', 'mpb_geom_layout.h', 'mpb_debug.h')]
     return any(os.path.getmtime(d) > t for d in deps)
 
 
@@ -115,9 +116,9 @@ def build_variant(out, extra_flags, verbose=False):
 def build(force=False, verbose=True):
     """The product library.  Compiles with FLAGS + the per-file scheduling flags only: extra defines (HIPCC_FLAGS-style
     environment hooks do not exist here) cannot reach it, and a tuning build is refused outright."""
-    # the compile-time robot models (csrc/mpb_model_*.h) are generated from geometry.py, the single source of the numbers.
-    # They are rewritten only when a build is going to run; on the fast path the committed header is only compared
-    # (ranks starting together must not write into the package, and it may be installed read-only)
+    # the compile-time robot models (csrc/mpb_model_*.h) and the packed-geometry layout (include/mpb_geom_layout.h) are generated
+    # from geometry.py, the single source of the numbers.  They are rewritten only when a build is going to run; on the fast path
+    # the committed header is only compared (ranks starting together must not write into the package, and it may be installed read-only)
     from . import model_gen
     stale = force or _stale() or bool(model_gen.stale_headers())
     if not stale:

@@ -393,7 +393,7 @@ extern "C" int mpb_chomp_step(float* means, const float* R, const float* geom, i
     if (B_local == 0 || n_iters == 0) return MPB_OK;
     const int threads = (H + 63) & ~63;
     static const bool no_p4 = getenv("MPB_CHOMP_LEAN") != nullptr;    // A/B aid
-    if ((geom_flags & 0x200) && D <= 3 && 4 * H <= 1024 && !no_p4) {  // point robot, one field, <= 32 spheres + 8 boxes
+    if (mpb_flags_point_small(geom_flags) && D <= 3 && 4 * H <= 1024 && !no_p4) {  // point robot, one field, <= 32 spheres + 8 boxes
         hipLaunchKernelGGL(chomp_point4_kernel, dim3(B_local), dim3((4 * H + 63) & ~63), (size_t)H * d * 4, (hipStream_t)stream, means,
                            R, geom, costs_out, B_global, H, d, D, k_sigma, weight, w_prior, lr, grad_clip, n_iters);
         return mpb_check_launch("mpb_chomp_step");

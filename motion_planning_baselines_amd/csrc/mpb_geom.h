@@ -22,24 +22,10 @@
 #include <utility>
 
 #include "mpb_model_panda.h"
+// the packed buffer in numbers -- header word indices MPB_GW_*, versions, kinds, limits, cell-word fields, geom_flags: generated from
+// geometry.py, the one definition of the layout
+#include "../../include/mpb_geom_layout.h"
 
-#define MPB_GEOM_MAGIC 0x4D504247
-#define MPB_GEOM_VERSION 6
-#define MPB_GEOM_VERSION_LIST 7  // a field whose grid section is a LIST grid (round 6: scenes beyond the compact grid's 63 spheres; geometry.py build_list_grid)
-#define MPB_LIST_MAX_SPH 255     // the list evaluators' sphere table (LDS): 255 + the far dummy
-#define MPB_LIST_MAX_BOX 127     // ... and box table: 127 + the far dummy
-#define MPB_LIST_MAX_CAND 16384  // bytes of candidate indices (LDS)
-#define MPB_LIST_CELL_MAX_SPH 126
-#define MPB_LIST_CELL_MAX_BOX 62
-#define MPB_MAX_FIELDS 4   // collision fields chained in one buffer (header word 27 = words to the next one)
-#define MPB_GEOM_HEADER_WORDS 32
-#define MPB_GRID_MAX_CELLS 4096
-#define MPB_GRID_PAD 1024        // the grid section of a buffer is padded to a multiple of this many words
-#define MPB_GRID_MAX_SPH 63      // obstacle table in LDS: 63 spheres + one far-away dummy
-#define MPB_GRID_OVERFLOW 0xFFFFFFFEu   // a cell word packs four 8-bit obstacle indices; an unused slot holds n_sph (the far dummy)
-#define MPB_KIND_POINT 0
-#define MPB_KIND_CHAIN 1
-#define MPB_MAX_DOF 12
 #define MPB_MAX_TF (MPB_MAX_DOF + 1)
 // collision spheres processed together (VGPR resident) by every evaluator: 4.  (The cost-only exhaustive path ran 8 at
 // a time in round 1; that evaluator is now the cold path -- fields without a usable broad-phase grid -- and at 8 it alone
@@ -71,42 +57,42 @@ struct GeomView {
 
 // next field of the chain (the reference sums one CostCollision per field), nullptr after the last one
 __device__ __forceinline__ const float* geom_next(const float* __restrict__ g) {
-    const int off = reinterpret_cast<const int*>(g)[27];
+    const int off = reinterpret_cast<const int*>(g)[MPB_GW_NEXT];
     return off ? g + off : nullptr;
 }
 
 __device__ __forceinline__ GeomView geom_view(const float* __restrict__ g) {
     const int* gi = reinterpret_cast<const int*>(g);
     GeomView v;
-    v.kind = gi[2];
-    v.n_dof = gi[3];
-    v.n_tf = gi[4];
-    v.n_links = gi[5];
-    v.n_sph = gi[6];
-    v.n_box = gi[7];
-    v.margin = g[8];
-    v.tf = g + gi[9];
-    v.links = g + gi[10];
-    v.sph = g + gi[11];
-    v.box = g + gi[12];
-    v.cull = g + gi[14];
-    v.fstart = gi + gi[15];
-    v.grid = reinterpret_cast<const unsigned*>(g) + gi[16];
-    v.gnx = gi[17]; v.gny = gi[18]; v.gnz = gi[19];
-    v.glx = g[20]; v.gly = g[21]; v.glz = g[22];
-    v.gix = g[23]; v.giy = g[24]; v.giz = g[25];
-    v.n_cells = gi[26];
-    v.version = gi[1];
+    v.kind = gi[MPB_GW_KIND];
+    v.n_dof = gi[MPB_GW_N_DOF];
+    v.n_tf = gi[MPB_GW_N_TF];
+    v.n_links = gi[MPB_GW_N_LINKS];
+    v.n_sph = gi[MPB_GW_N_SPH];
+    v.n_box = gi[MPB_GW_N_BOX];
+    v.margin = g[MPB_GW_MARGIN];
+    v.tf = g + gi[MPB_GW_OFF_TF];
+    v.links = g + gi[MPB_GW_OFF_LINKS];
+    v.sph = g + gi[MPB_GW_OFF_SPH];
+    v.box = g + gi[MPB_GW_OFF_BOX];
+    v.cull = g + gi[MPB_GW_OFF_CULL];
+    v.fstart = gi + gi[MPB_GW_OFF_FS];
+    v.grid = reinterpret_cast<const unsigned*>(g) + gi[MPB_GW_OFF_GRID];
+    v.gnx = gi[MPB_GW_GRID_DIMS]; v.gny = gi[MPB_GW_GRID_DIMS + 1]; v.gnz = gi[MPB_GW_GRID_DIMS + 2];
+    v.glx = g[MPB_GW_GRID_LO]; v.gly = g[MPB_GW_GRID_LO + 1]; v.glz = g[MPB_GW_GRID_LO + 2];
+    v.gix = g[MPB_GW_GRID_INV]; v.giy = g[MPB_GW_GRID_INV + 1]; v.giz = g[MPB_GW_GRID_INV + 2];
+    v.n_cells = gi[MPB_GW_N_CELLS];
+    v.version = gi[MPB_GW_VERSION];
     {
-        const int off_cand = gi[16] + (gi[26] + MPB_GRID_PAD - 1) / MPB_GRID_PAD * MPB_GRID_PAD;
+        const int off_cand = gi[MPB_GW_OFF_GRID] + (gi[MPB_GW_N_CELLS] + MPB_GRID_PAD - 1) / MPB_GRID_PAD * MPB_GRID_PAD;
         v.cand = reinterpret_cast<const unsigned char*>(g + off_cand);
-        v.n_cand = 4 * (gi[13] - off_cand);
+        v.n_cand = 4 * (gi[MPB_GW_TOTAL] - off_cand);
     }
-    v.k_lin = gi[31];
-    v.fscale = g[28];
-    v.next = gi[27];
-    v.model = gi[29];
-    v.keep_mask = (unsigned)gi[30];
+    v.k_lin = gi[MPB_GW_K_LIN];
+    v.fscale = g[MPB_GW_FSCALE];
+    v.next = gi[MPB_GW_NEXT];
+    v.model = gi[MPB_GW_MODEL];
+    v.keep_mask = (unsigned)gi[MPB_GW_KEEP_MASK];
     return v;
 }
 
@@ -837,7 +823,7 @@ __device__ __forceinline__ void spheres_hinge_list(const GeomView& G, const List
         unsigned mns = 0u, mnb = 0u;
 #pragma unroll
         for (int i = 0; i < N; ++i) {
-            st[i] = w[i] & 0x7FFFu; ns[i] = (w[i] >> 15) & 0x7Fu; nb[i] = (w[i] >> 22) & 0x3Fu;
+            st[i] = w[i] & MPB_LIST_START_MASK; ns[i] = (w[i] >> MPB_LIST_NSPH_SHIFT) & MPB_LIST_NSPH_MASK; nb[i] = (w[i] >> MPB_LIST_NBOX_SHIFT) & MPB_LIST_NBOX_MASK;
             mns = max(mns, ns[i]); mnb = max(mnb, nb[i]);
         }
         // as many trips as the longest sphere / box range among the wave's ACTIVE lanes (a ballot per trip: the callers run this

@@ -3,8 +3,6 @@
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 
-#define MPB_GP_MAX_FIELDS 4      // = MPB_MAX_FIELDS of mpb_geom.h (asserted in mpb_gpmp2.hip): collision fields chained in one buffer
-
 // precisions 1 / sigma^2 of the factors, damping and step of one Gauss-Newton iteration (gpmp2.py:308-368)
 struct GpConst {
     double dt, ks, kgp, kg, kc, delta, step;

@@ -28,7 +28,6 @@
 #include "mpb_host.h"
 #include "mpb_geom.h"
 #include "mpb_gpmp2.h"
-static_assert(MPB_GP_MAX_FIELDS == MPB_MAX_FIELDS, "mpb_gpmp2.h mirrors mpb_geom.h");
 
 typedef double f64x4 __attribute__((ext_vector_type(4)));
 #define GP_N 16            // padded block size (2D <= 16)
@@ -778,8 +777,8 @@ extern "C" int mpb_gpmp2_linearize(const float* x, const float* geom, int geom_f
     if (!gp_shape_ok(B, H, D) || n_interp < 0 || n_interp > 64) return mpb_fail(MPB_E_INVALID, "mpb_gpmp2_linearize: bad shape");
     if (B == 0) return MPB_OK;
     GpWork w = gp_carve(workspace, B, H, D);
-    // geom_flags (mpb_geom_flags of the host copy): low byte = compile-time robot model of EVERY chained field, bit 8 = all
-    // of them grid-backed -- the model kernel needs both
+    // geom_flags (mpb_geom_flags of the host copy): the compile-time robot model of EVERY chained field, and all of them backed by
+    // compact grids -- the model kernel needs both
 #ifndef GP_LIN_WPE
 #define GP_LIN_WPE 3
 #endif

@@ -964,7 +964,7 @@ bool mpb_gpmp2_lr_ok(int H, int D, int n_fields) { return H >= 2 && D >= 1 && D 
 // doubles of workspace: shared tables (cyclic-reduction coefficients, G) + per-batch arrays (the steps, w, the GP cost, g_rest / u0, the order)
 size_t mpb_gpmp2_lr_ws_doubles(int B, int H, int D) {
     const size_t NL = (size_t)B * D;
-    return 2 * (size_t)D * pcr_coef_entries(H) + (size_t)D * H * H + (size_t)H * NL + (size_t)MPB_GP_MAX_FIELDS * B * H + (size_t)B + 64 +
+    return 2 * (size_t)D * pcr_coef_entries(H) + (size_t)D * H * H + (size_t)H * NL + (size_t)MPB_MAX_FIELDS * B * H + (size_t)B + 64 +
            (size_t)B * H * 2 * D +         // ... and g_rest
            (size_t)B + 1;                  // ... and the size class of every particle + the launch order of the capacitance systems (2 B ints)
 }
@@ -978,7 +978,7 @@ int mpb_gpmp2_lr_launch(float* x, const float* start, const float* goal, const f
     double* G = coef + 2 * (size_t)D * n_coef;
     double* dth = G + (size_t)D * H * H;                                 // the steps of the particles with collision rows: (D, B, H) float pairs
     double* wdense = dth + (size_t)H * NL;
-    double* gpcost = wdense + (size_t)MPB_GP_MAX_FIELDS * B * H;
+    double* gpcost = wdense + (size_t)MPB_MAX_FIELDS * B * H;
     double* grest = gpcost + B + 64;
     int* ord = reinterpret_cast<int*>(grest + (size_t)B * H * 2 * D);        // [0, B): size class of particle b; [B, 2 B): the particles, largest class first
     static const int n_cu = [] {

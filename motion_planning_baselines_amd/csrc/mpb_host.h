@@ -34,9 +34,24 @@ static inline bool mpb_misaligned16(const void* a, const void* b = nullptr, cons
                                     const void* e = nullptr, const void* f = nullptr) {
     return ((((uintptr_t)a) | ((uintptr_t)b) | ((uintptr_t)c) | ((uintptr_t)d) | ((uintptr_t)e) | ((uintptr_t)f)) & 15u) != 0;
 }
-// do the geom_flags of mpb_geom_flags name the compile-time robot model `model_id` (low byte) AND report every chained field
-// backed by a compact grid (bit 8)?  Only then may a launcher pick the kernel instantiated for that model.
-static inline bool mpb_flags_model_on_grids(int geom_flags, int model_id) { return (geom_flags & 0xFF) == model_id && (geom_flags & 0x100); }
+// what the geom_flags of mpb_geom_flags (MPB_GEOM_FLAG_* of include/mpb_geom_layout.h; include/mpb.h says what each promises) tell a
+// launcher: the compile-time robot model every chained field is tagged with (0: none) ...
+static inline int mpb_flags_model(int geom_flags) { return geom_flags & MPB_GEOM_FLAG_MODEL_MASK; }
+// ... every chained field backed by a compact grid / by a list grid; ONE field; a point robot with a small obstacle set in one field
+static inline bool mpb_flags_all_grids(int geom_flags) { return (geom_flags & MPB_GEOM_FLAG_ALL_GRIDS) != 0; }
+static inline bool mpb_flags_all_lists(int geom_flags) { return (geom_flags & MPB_GEOM_FLAG_ALL_LISTS) != 0; }
+static inline bool mpb_flags_one_field(int geom_flags) { return (geom_flags & MPB_GEOM_FLAG_ONE_FIELD) != 0; }
+static inline bool mpb_flags_point_small(int geom_flags) { return (geom_flags & MPB_GEOM_FLAG_POINT_SMALL) != 0; }
+// ... a point robot in ONE field that has a compact grid, and the cells of the chain's largest grid (what staging it in LDS takes)
+static inline bool mpb_flags_point_on_one_grid(int geom_flags) {
+    const int need = MPB_GEOM_FLAG_POINT | MPB_GEOM_FLAG_ONE_FIELD | MPB_GEOM_FLAG_ALL_GRIDS;
+    return (geom_flags & need) == need;
+}
+static inline int mpb_flags_cells(int geom_flags) { return (geom_flags >> MPB_GEOM_FLAG_CELLS_SHIFT) & MPB_GEOM_FLAG_CELLS_MASK; }
+// ... the model `model_id` AND compact grids throughout: only then may a launcher pick the kernel instantiated for that model
+static inline bool mpb_flags_model_on_grids(int geom_flags, int model_id) {
+    return mpb_flags_model(geom_flags) == model_id && mpb_flags_all_grids(geom_flags);
+}
 // the shapes and LDS budget mpb_stomp_update takes (defined beside the update kernels in mpb_kernels.hip): MPB_OK, or the code and
 // message (under the name `who`) of the refusal -- for callers that enqueue the update behind other stages and must refuse before
 // the first launch

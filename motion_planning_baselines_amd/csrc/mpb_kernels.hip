@@ -819,7 +819,7 @@ static void launch_sample(const StompCall& c, const float* eps, uint32_t iter, h
                    dim3(64 * MPB_A_WPB), 0, st, (const float*)c.means, eps, c.samples, c.costs, c.L, c.geom, P, S,     \
                    c.k_sigma, c.weight, lo, hi, iter, c.particle_offset);                                              \
         return;
-    // (bit 8: every field COMPACT-grid-backed -- since round 6 the model byte is also set for list-grid scenes, which this kernel
+    // (MPB_GEOM_FLAG_ALL_GRIDS: every field COMPACT-grid-backed -- since round 6 the model byte is also set for list-grid scenes, which this kernel
     // serves through the exhaustive walk)
     if (H == 64 && WITH_COST && mpb_flags_model_on_grids(c.geom_flags, PandaModel::ID)) {   // the Panda's channel counts (pos_only / not)
         switch (d) {

@@ -582,12 +582,12 @@ extern "C" int mpb_mppi_step(float* mean, const float* eps, const float* scale_t
     if (force_mode == MPPI_NOISE_GLOBAL) noise_mode = MPPI_NOISE_GLOBAL;
     if (force_mode == MPPI_NOISE_LDS && with_tril <= budget) noise_mode = MPPI_NOISE_LDS;
     size_t lds_words = noise_mode == MPPI_NOISE_MATRIX ? with_matrix : noise_mode == MPPI_NOISE_LDS ? with_tril : base;
-    // ONE grid-backed collision field (geom_flags bit 8, bits 16-28 = its cells): the grid + obstacle table ride in LDS when
+    // ONE grid-backed collision field (geom_flags also carry its cells): the grid + obstacle table ride in LDS when
     // they fit next to the rest (and, with two workgroups per CU, leave room for the second one)
     int grid_words = 0;
     static const int no_grid = getenv("MPB_MPPI_NO_GRID") ? atoi(getenv("MPB_MPPI_NO_GRID")) : 0;           // tuning / tests
-    if (geom && (geom_flags & 0x1500) == 0x1500 && !no_grid) {     // ONE grid-backed field, point robot
-        const int cells = (geom_flags >> 16) & 0x1FFF;
+    if (geom && mpb_flags_point_on_one_grid(geom_flags) && !no_grid) {     // ONE grid-backed field, point robot
+        const int cells = mpb_flags_cells(geom_flags);
         const size_t extra = 4 + (size_t)((cells + 3) & ~3) + 4 * (MPB_GRID_MAX_SPH + 1);
         const size_t cap = (nw <= 8 ? 78 : 150) * 1024 / sizeof(float);
         if (cells > 0 && lds_words + extra <= cap) {

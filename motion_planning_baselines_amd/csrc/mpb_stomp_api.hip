@@ -184,7 +184,7 @@ static FusedPlan fused_plan(int geom_flags, int P, int S, int H, int d) {
     // MPB_STOMP_HX = 1 sends every shape to the generalised kernel (a test aid: it is compared with the H = 64 kernel)
     const char* hx_env = getenv("MPB_STOMP_HX");
     const int force_hx = hx_env ? atoi(hx_env) : 0;
-    const bool v1 = !force_hx && H == 64 && S <= FUSED_WAVES * FUSED_MAX_CHUNKS && (geom_flags & 0x100) &&
+    const bool v1 = !force_hx && H == 64 && S <= FUSED_WAVES * FUSED_MAX_CHUNKS && mpb_flags_all_grids(geom_flags) &&
                     (d == 2 || d == 3 || d == 4 || d == 6 || d == 7 || d == 14);
     if (!v1) {
         if (!mpb_fused_hx_plan(geom_flags, n_cu, P, S, H, d, &f.nc, &f.nb, &f.ws_bytes)) return f;
@@ -211,10 +211,10 @@ extern "C" size_t mpb_stomp_workspace_bytes(int P, int S, int H, int d) {
     if (P < 1 || S < 1) return 0;
     // what the layout the launcher will pick needs (grid-backed fields assumed; a call the persistent kernel cannot
     // serve needs none): the exchange area only when partner workgroups exchange partials, else just the header
-    const FusedPlan f = fused_plan(0x100, P, S, H, d);
-    // (a scene packed with LIST grids -- geometry version 7, flag bit 13 -- goes to the generalised kernel even at H = 64, whose
+    const FusedPlan f = fused_plan(MPB_GEOM_FLAG_ALL_GRIDS, P, S, H, d);
+    // (a scene packed with LIST grids -- geometry version 7, MPB_GEOM_FLAG_ALL_LISTS -- goes to the generalised kernel even at H = 64, whose
     // exchange slots are larger: the workspace serves whichever of the two the geometry will select)
-    const FusedPlan fl = fused_plan(0x2000, P, S, H, d);
+    const FusedPlan fl = fused_plan(MPB_GEOM_FLAG_ALL_LISTS, P, S, H, d);
     size_t b = f.path == MPB_STOMP_PATH_TWO_KERNEL ? FUSED_HDR_WORDS * sizeof(float) : f.ws_bytes;
     if (fl.path != MPB_STOMP_PATH_TWO_KERNEL && fl.ws_bytes > b) b = fl.ws_bytes;
     return b;

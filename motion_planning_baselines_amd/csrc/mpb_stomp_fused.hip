@@ -115,7 +115,7 @@ struct FusedSmem {
 //         batches' partials in registers -- no exchange, five instead of six block barriers per particle and iteration, one
 //         update instead of two.  For loads with at least as many particles as CUs (C5); the partials are combined with
 //         the very expressions of the exchange path, so both layouts produce the same bits.
-// CHAIN = false: ONE collision field by construction (geom_flags bit 12; only instantiated for the compile-time robot models): the
+// CHAIN = false: ONE collision field by construction (geom_flags MPB_GEOM_FLAG_ONE_FIELD; only instantiated for the compile-time robot models): the
 // loop over chained fields and its second GeomView are gone -- 7 / 16 SGPR spills less, c5 -1.9 %, C3 -0.4 % (round 5).
 template <int DCH, int MODEL, int NB, bool INJ, bool CHAIN>
 __global__ __launch_bounds__(FUSED_THREADS, 4) void stomp_fused_kernel(
@@ -366,7 +366,7 @@ __global__ __launch_bounds__(FUSED_THREADS, 4) void stomp_fused_kernel(
                     }
                 }
                 if (MODEL != 0 && G.model != MODEL) bad = true;    // (wave-uniform: lane 0 -- waypoint 0, outside the walk -- writes the cost)
-                if (!CHAIN) break;            // (one field by construction: the launcher read geom_flags bit 12)
+                if (!CHAIN) break;            // (one field by construction: the launcher read MPB_GEOM_FLAG_ONE_FIELD)
                 if (G.next == 0) break;
                 gp += G.next;
                 G = geom_view(gp);
@@ -729,13 +729,13 @@ int mpb_fused_launch(const StompCall& c, const StompLaunch& l, const StompFusedG
     const bool two_batches = g.nb == 2;
     const dim3 grid(two_batches ? c.P : c.P * g.nc), block(FUSED_THREADS);
     const int nc_k = two_batches ? 1 : g.nc;
-    const int model = mpb_flags_model_on_grids(c.geom_flags, PandaModel::ID) ? PandaModel::ID : 0, d = c.d;   // (bit 8: fused_plan)
+    const int model = mpb_flags_model_on_grids(c.geom_flags, PandaModel::ID) ? PandaModel::ID : 0, d = c.d;   // (compact grids: fused_plan)
     const uint32_t lo = (uint32_t)c.seed, hi = (uint32_t)(c.seed >> 32);
 #define MPB_F_LAUNCH_(DCH, MODEL, NB, INJ, CHAIN)                                                                                       \
     MPB_LAUNCH(l.events, (stomp_fused_kernel<DCH, MODEL, NB, INJ, CHAIN>), grid, block, 0, l.stream, c.means, c.eps, c.samples, c.costs, \
                c.weights, c.L, c.Sigma, c.geom, g.workspace, c.P, c.S, nc_k, c.k_sigma, c.weight, c.lr, c.temperature, l.n_iters, lo,   \
                hi, l.iter0, c.particle_offset, g.tag0, g.timeout, g.status_dev, l.means_copy)
-    const bool one_field = (c.geom_flags & 0x1000) != 0;
+    const bool one_field = mpb_flags_one_field(c.geom_flags);
 #define MPB_F_LAUNCH(DCH, MODEL, NB, INJ)                                              \
     do {                                                                               \
         if ((MODEL) != 0 && one_field) MPB_F_LAUNCH_(DCH, MODEL, NB, INJ, (MODEL) == 0); \

@@ -584,9 +584,9 @@ __global__ __launch_bounds__(FUSED_THREADS, 4) void stomp_fused_hx_kernel(
 // ------------------------------------------------------------------------------------------------
 // can this kernel serve the shape, and with which split of the S samples over workgroups (nc) and passes (nb)?
 bool mpb_fused_hx_plan(int geom_flags, int n_cu, int P, int S, int H, int d, int* nc_out, int* nb_out, size_t* ws_bytes) {
-    // every field grid-backed: compact grids (flag bit 8) at any horizon, list grids (bit 13, round 6) up to 64 support points
+    // every field grid-backed: compact grids at any horizon, list grids (round 6) up to 64 support points
     if (P < 1 || S < 1 || S > 128 || H < 3 || H > 128 || d < 1 || d > 16) return false;
-    if (!(geom_flags & 0x100) && !((geom_flags & 0x2000) && H <= 64)) return false;
+    if (!mpb_flags_all_grids(geom_flags) && !(mpb_flags_all_lists(geom_flags) && H <= 64)) return false;
     const int HC = H > 64 ? 2 : 1, RB = FUSED_WAVES / HC;
     const int passes = (S + RB - 1) / RB;                 // passes of RB rollouts a particle needs per iteration
     // few particles: as many workgroups per particle as fit the chip in one round (and the exchange allows); many
@@ -609,7 +609,7 @@ bool mpb_fused_hx_plan(int geom_flags, int n_cu, int P, int S, int H, int d, int
 
 int mpb_fused_hx_launch(const StompCall& c, const StompLaunch& l, const StompFusedGrid& g) {
     const dim3 grid(c.P * g.nc), block(FUSED_THREADS);
-    const int model = c.geom_flags & 0xFF, H = c.H, d = c.d;
+    const int model = mpb_flags_model(c.geom_flags), H = c.H, d = c.d;
     const uint32_t lo = (uint32_t)c.seed, hi = (uint32_t)(c.seed >> 32);
 #define MPB_HX_LAUNCH_(DCH, MODEL, HC, INJ, LIST)                                                                                        \
     MPB_LAUNCH(l.events, (stomp_fused_hx_kernel<DCH, MODEL, HC, INJ, LIST>), grid, block, 0, l.stream, c.means, c.eps, c.samples, c.costs, \
@@ -625,7 +625,7 @@ int mpb_fused_hx_launch(const StompCall& c, const StompLaunch& l, const StompFus
         if (c.eps) MPB_HX_LAUNCH_(DCH, MODEL, 1, true, true);      \
         else MPB_HX_LAUNCH_(DCH, MODEL, 1, false, true);           \
     } while (0)
-    if (!(c.geom_flags & 0x100)) {            // list grids (mpb_fused_hx_plan admitted them: H <= 64)
+    if (!mpb_flags_all_grids(c.geom_flags)) {            // list grids (mpb_fused_hx_plan admitted them: H <= 64)
         if (model == PandaModel::ID && d == 7) MPB_HX_LAUNCH_LIST(7, PandaModel::ID);
         else if (model == PandaModel::ID && d == 14) MPB_HX_LAUNCH_LIST(14, PandaModel::ID);
         else MPB_HX_LAUNCH_LIST(0, 0);

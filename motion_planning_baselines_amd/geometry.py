@@ -26,31 +26,144 @@ import os
 import numpy as np
 import torch
 
+# ----------------------------------------------------------------------------------------------
+# The packed-geometry contract.  This block is its ONLY definition: model_gen.py emits include/mpb_geom_layout.h from it (C_LAYOUT
+# below names what goes there, as MPB_<name>), which include/mpb.h and csrc/mpb_geom.h include; tests/test_host_logic.py pins the
+# public numbers as literals so that an edit here cannot renumber the ABI unnoticed.
+# ----------------------------------------------------------------------------------------------
 GEOM_MAGIC = 0x4D504247  # 'MPBG'
-GEOM_VERSION = 6
-MAX_FIELDS = 4           # collision fields chained in one buffer (csrc/mpb_geom.h MPB_MAX_FIELDS)
-GEOM_HEADER_WORDS = 32
-GRID_MAX_DIM = 64       # cells per axis of the broad-phase grid
-GRID_MAX_CELLS = 4096   # = MPB_GRID_MAX_CELLS of csrc/mpb_geom.h: 16 KB of LDS
-GRID_CELL = 0.14        # coarsest target cell edge [m]; refined by GRID_REFINE steps down to GRID_CELL_MIN while the grid fits
-GRID_CELL_MIN = 0.05
-GRID_REFINE = 0.97
-GRID_PAD = 1024         # the grid section is padded to a multiple of this many words (one round of a 256-thread block's uint4 loads)
-GRID_OVERFLOW = 0xFFFFFFFE  # more than 4 candidates in the cell: the kernel tests every obstacle
-# geometry version 7 (round 6): fields whose obstacle set does not fit the compact grid (more than 63 spheres) carry a LIST grid --
-# a cell word holds (start, sphere count, box count) into a byte array of candidate indices that follows the cell words: any number of
-# candidates per cell, boxes culled like spheres (csrc/mpb_geom.h, spheres_hinge_list).  Limits = what the persistent kernel keeps in LDS
+GEOM_VERSION = 6         # the grid section is a COMPACT grid (or absent): cells on a lattice through the world origin
+# geometry version 7 (round 6): fields whose obstacle set does not fit the compact grid (more than GRID_MAX_SPH spheres) carry a LIST
+# grid -- a cell word holds (start, sphere count, box count) into a byte array of candidate indices that follows the cell words: any number
+# of candidates per cell, boxes culled like spheres (csrc/mpb_geom.h, spheres_hinge_list).  Limits = what the persistent kernel keeps in LDS
 GEOM_VERSION_LIST = 7
-LIST_MAX_SPH = 255        # 8-bit candidate indices; the kernels' sphere table holds 255 + the far dummy
-LIST_MAX_BOX = 127
-LIST_MAX_CAND = 16384     # bytes of candidate indices
-LIST_CELL_MAX_SPH = 126   # per cell (7-bit field; 127 marks an overflowing cell: exhaustive loop)
-LIST_CELL_MAX_BOX = 62    # per cell (6-bit field; 63 marks overflow)
-LIST_OVERFLOW = 0x80000000
 KIND_POINT = 0
 KIND_CHAIN = 1
 MAX_DOF = 12
+MAX_FIELDS = 4           # collision fields chained in one buffer
+GEOM_HEADER_WORDS = 32
+GRID_MAX_CELLS = 4096    # cell words of a grid: 16 KB of LDS
+GRID_PAD = 1024          # the grid section is padded to a multiple of this many words (one round of a 256-thread block's uint4 loads)
+GRID_MAX_SPH = 63        # obstacle spheres a compact grid serves: the kernels' table in LDS holds 63 + one far-away dummy
+LIST_MAX_SPH = 255       # 8-bit candidate indices; the kernels' sphere table holds 255 + the far dummy
+LIST_MAX_BOX = 127       # ... and the box table 127 + the far dummy
+LIST_MAX_CAND = 16384    # bytes of candidate indices (LDS)
+LIST_CELL_MAX_SPH = 126  # per cell (7-bit field; 127 marks an overflowing cell: exhaustive loop)
+LIST_CELL_MAX_BOX = 62   # per cell (6-bit field; 63 marks overflow)
+
+# The header: GEOM_HEADER_WORDS 32-bit words, in this order -- (name, type, words).  Ints are stored bit-exact in the fp32 buffer.
+HEADER_WORDS = (
+    ('magic', 'i4', 1),        # GEOM_MAGIC
+    ('version', 'i4', 1),      # GEOM_VERSION or GEOM_VERSION_LIST: the format of this field's grid section
+    ('kind', 'i4', 1),         # KIND_POINT / KIND_CHAIN
+    ('n_dof', 'i4', 1),
+    ('n_tf', 'i4', 1),         # joint transforms: 0 (point robot) or n_dof + 1
+    ('n_links', 'i4', 1),      # collision spheres of the robot in the link table
+    ('n_sph', 'i4', 1),        # obstacle spheres
+    ('n_box', 'i4', 1),        # obstacle boxes
+    ('margin', 'f4', 1),       # hinge margin
+    ('off_tf', 'i4', 1),       # word offsets of the sections from this header ...
+    ('off_links', 'i4', 1),
+    ('off_sph', 'i4', 1),
+    ('off_box', 'i4', 1),
+    ('total', 'i4', 1),        # words of this field, header included
+    ('off_cull', 'i4', 1),
+    ('off_fs', 'i4', 1),       # frame_start table
+    ('off_grid', 'i4', 1),
+    ('grid_dims', 'i4', 3),    # nx, ny, nz
+    ('grid_lo', 'f4', 3),      # origin: (K - 1/2) h per axis with integer K
+    ('grid_inv', 'f4', 3),     # 1 / cell size per axis
+    ('n_cells', 'i4', 1),      # nx * ny * nz (0: no grid)
+    ('next', 'i4', 1),         # words from this header to the next chained field (0: last)
+    ('fscale', 'f4', 1),       # s_f: this field's share in sum_f s_f * cost_f
+    ('model', 'i4', 1),        # compile-time robot model the tables equal bit for bit (model_gen.py; 0: none)
+    ('keep_mask', 'u4', 1),    # bit l: the MODEL's collision sphere l is in the link table (static pruning)
+    ('k_lin', 'i4', 1),        # linear index Kx + nx (Ky + ny Kz) of the lattice point the grid starts at
+)
+HEADER_DTYPE = np.dtype([(name, typ, (n,)) if n > 1 else (name, typ) for name, typ, n in HEADER_WORDS])
+assert HEADER_DTYPE.itemsize == 4 * GEOM_HEADER_WORDS
+
+# COMPACT grid cell word: GRID_SLOTS obstacle-sphere indices of GRID_SLOT_BITS each, filled from slot 0; an unused slot holds n_sph
+# (the far dummy the kernels append to their table)
+GRID_SLOTS = 4
+GRID_SLOT_BITS = 8
+GRID_SLOT_MASK = (1 << GRID_SLOT_BITS) - 1
+GRID_OVERFLOW = (1 << 32) - 2   # more than GRID_SLOTS candidates in the cell: the kernels test every obstacle
+# LIST grid cell word: start into the candidate bytes | sphere count | box count (a cell's boxes follow its spheres); bits 28-30 zero
+LIST_START_BITS = 15
+LIST_START_MASK = (1 << LIST_START_BITS) - 1
+LIST_NSPH_SHIFT = LIST_START_BITS
+LIST_NSPH_BITS = 7
+LIST_NSPH_MASK = (1 << LIST_NSPH_BITS) - 1
+LIST_NBOX_SHIFT = LIST_NSPH_SHIFT + LIST_NSPH_BITS
+LIST_NBOX_BITS = 6
+LIST_NBOX_MASK = (1 << LIST_NBOX_BITS) - 1
+LIST_OVERFLOW = 1 << 31         # the cell overflows a count field: the kernels test every obstacle
+LIST_RESERVED = LIST_OVERFLOW - (1 << (LIST_NBOX_SHIFT + LIST_NBOX_BITS))   # bits 28-30: must be zero
+
+# geom_flags (mpb_geom_flags: what a launcher picks its kernel instantiation by; include/mpb.h says what each promises).  Bit 11 is unused.
+GEOM_FLAG_MODEL_MASK = (1 << 8) - 1   # bits 0-7: compile-time robot model of EVERY chained field (0: table-driven kernels)
+GEOM_FLAG_ALL_GRIDS = 1 << 8          # every chained field has a usable compact grid
+GEOM_FLAG_POINT_SMALL = 1 << 9        # point robot, ONE field of at most 32 spheres and 8 boxes
+GEOM_FLAG_POINT = 1 << 10             # point robot
+GEOM_FLAG_ONE_FIELD = 1 << 12         # no chain
+GEOM_FLAG_ALL_LISTS = 1 << 13         # every chained field carries a list grid
+GEOM_FLAG_CELLS_SHIFT = 16            # bits 16-28: cells of the largest grid of the chain (with ALL_GRIDS or ALL_LISTS)
+GEOM_FLAG_CELLS_MASK = (1 << 13) - 1
+
+# what include/mpb_geom_layout.h carries besides the word indices: (heading, C literal form, names), each as MPB_<name>
+C_LAYOUT = (
+    ('magic, versions, robot kinds', '0x%X', ('GEOM_MAGIC',)),
+    (None, '%d', ('GEOM_VERSION', 'GEOM_VERSION_LIST', 'KIND_POINT', 'KIND_CHAIN')),
+    ('limits', '%d', ('MAX_DOF', 'MAX_FIELDS', 'GEOM_HEADER_WORDS', 'GRID_MAX_CELLS', 'GRID_PAD', 'GRID_MAX_SPH', 'LIST_MAX_SPH', 'LIST_MAX_BOX',
+                      'LIST_MAX_CAND', 'LIST_CELL_MAX_SPH', 'LIST_CELL_MAX_BOX')),
+    ('compact grid cell word', '%d', ('GRID_SLOTS', 'GRID_SLOT_BITS')),
+    (None, '0x%Xu', ('GRID_SLOT_MASK', 'GRID_OVERFLOW')),
+    ('list grid cell word', '%d', ('LIST_NSPH_SHIFT', 'LIST_NBOX_SHIFT')),
+    (None, '0x%Xu', ('LIST_START_MASK', 'LIST_NSPH_MASK', 'LIST_NBOX_MASK', 'LIST_OVERFLOW', 'LIST_RESERVED')),
+    ('geom_flags', '0x%X', ('GEOM_FLAG_MODEL_MASK', 'GEOM_FLAG_ALL_GRIDS', 'GEOM_FLAG_POINT_SMALL', 'GEOM_FLAG_POINT', 'GEOM_FLAG_ONE_FIELD',
+                            'GEOM_FLAG_ALL_LISTS')),
+    (None, '%d', ('GEOM_FLAG_CELLS_SHIFT',)),
+    (None, '0x%X', ('GEOM_FLAG_CELLS_MASK',)),
+)
+
+# the grid builders' own tuning (not part of the layout)
+GRID_MAX_DIM = 64       # cells per axis of the broad-phase grid
+GRID_CELL = 0.14        # coarsest target cell edge [m]; refined by GRID_REFINE steps down to GRID_CELL_MIN while the grid fits
+GRID_CELL_MIN = 0.05
+GRID_REFINE = 0.97
 BOX_2D_HALF_Z = 1.0e6  # 2-D boxes are 3-D boxes that are effectively infinite in z
+
+
+def header(buf, offset=0):
+    """The header of the field that starts at word `offset` of a packed buffer, as a numpy record over HEADER_WORDS: a VIEW -- reads
+    and writes by name go to the buffer's own words (h['n_sph'], h['grid_dims'][0], h['next'] = 0)."""
+    words = np.asarray(buf)[offset:offset + GEOM_HEADER_WORDS]
+    assert words.dtype.itemsize == 4 and words.size == GEOM_HEADER_WORDS, 'a packed geometry buffer is an array of 32-bit words'
+    return words.view(HEADER_DTYPE)[0]
+
+
+def fields(buf):
+    """The headers (as header() gives them) of the chained fields of a packed buffer, in order."""
+    off = 0
+    while True:
+        h = header(buf, off)
+        yield h
+        if h['next'] == 0:
+            return
+        off += int(h['next'])
+
+
+def grid_cell_slots(words):
+    """Compact-grid cell words (..., ) -> their GRID_SLOTS obstacle indices (..., GRID_SLOTS); meaningless where words == GRID_OVERFLOW."""
+    w = np.asarray(words, dtype=np.uint32)
+    return np.stack([(w >> (GRID_SLOT_BITS * k)) & GRID_SLOT_MASK for k in range(GRID_SLOTS)], -1)
+
+
+def list_cell_fields(words):
+    """List-grid cell words -> (start, sphere count, box count, overflows) as the kernels decode them."""
+    w = np.asarray(words, dtype=np.uint32)
+    return (w & LIST_START_MASK, (w >> LIST_NSPH_SHIFT) & LIST_NSPH_MASK, (w >> LIST_NBOX_SHIFT) & LIST_NBOX_MASK, (w & LIST_OVERFLOW) != 0)
 
 
 def _rot_x(a):
@@ -260,8 +373,8 @@ def _fit_axis(a, b, edge):
 def build_list_grid(spheres, boxes, a_max, slack=1e-4, planar=False):
     """Broad-phase LIST grid (geometry version 7) over the inflated obstacle spheres AND boxes, for scenes beyond the compact grid's 63
     spheres: per cell the indices of every sphere / box a collision sphere of radius <= a_max - margin centred in the cell could be
-    within its hinge threshold of (conservative, fp64).  Cell words: bits 0-14 start into the candidate bytes, 15-21 sphere count,
-    22-27 box count (boxes follow the spheres), bit 31 = the cell overflows a count field (the kernels then test every obstacle).
+    within its hinge threshold of (conservative, fp64).  Cell words: the LIST_* fields above (start into the candidate bytes, sphere
+    count, box count -- boxes follow the spheres --, LIST_OVERFLOW where the cell overflows a count field).
     The finest lattice cell (from GRID_CELL_MIN up) whose grid fits GRID_MAX_CELLS words and LIST_MAX_CAND candidate bytes.
     None when the scene does not fit the kernels' tables (LIST_MAX_SPH / LIST_MAX_BOX) or no cell size fits."""
     ns, nb = len(spheres), len(boxes)
@@ -307,7 +420,7 @@ def build_list_grid(spheres, boxes, a_max, slack=1e-4, planar=False):
                 cs, cb = hit_s.sum(-1), hit_b.sum(-1)
                 over = (cs > LIST_CELL_MAX_SPH) | (cb > LIST_CELL_MAX_BOX)
                 total = int((cs + cb)[~over].sum())
-                if total <= LIST_MAX_CAND and total < (1 << 15):
+                if total <= LIST_MAX_CAND and total <= LIST_START_MASK:
                     # cell words in x-fastest order, candidates in ascending index order (spheres, then boxes)
                     order = (2, 1, 0)
                     ncl = int(dims.prod())
@@ -322,7 +435,7 @@ def build_list_grid(spheres, boxes, a_max, slack=1e-4, planar=False):
                             words[i] = LIST_OVERFLOW
                             continue
                         si, bi = np.nonzero(hs[i])[0], np.nonzero(hbx[i])[0]
-                        words[i] = pos | (len(si) << 15) | (len(bi) << 22)
+                        words[i] = pos | (len(si) << LIST_NSPH_SHIFT) | (len(bi) << LIST_NBOX_SHIFT)
                         cand.extend(si.tolist())
                         cand.extend(bi.tolist())
                         pos += len(si) + len(bi)
@@ -410,22 +523,24 @@ def build_grid(spheres, a_max, slack=1e-4, planar=False):
     cmin = lo_s + np.stack([X, Y, Z], -1) * cell_eff          # (nx,ny,nz,3)
     cmax = cmin + cell_eff
     counts = np.zeros(dims, dtype=np.int64)
-    lists = np.full((*dims, 4), n, dtype=np.uint32)      # empty slot = n: the far dummy the kernels append to the table
+    lists = np.full((*dims, GRID_SLOTS), n, dtype=np.uint32)      # empty slot = n: the far dummy the kernels append to the table
     for o in range(n):
         d = np.maximum(np.maximum(cmin - c[o], c[o] - cmax), 0.0)
         hit = (d * d).sum(-1) < Rg[o] ** 2
         idx = np.nonzero(hit)
         k = counts[idx]
-        ok = k < 4
+        ok = k < GRID_SLOTS
         sel = tuple(a[ok] for a in idx)
         lists[sel + (k[ok],)] = o
         counts[idx] += 1
-    w = lists[..., 0] | (lists[..., 1] << 8) | (lists[..., 2] << 16) | (lists[..., 3] << 24)
-    w = np.where(counts > 4, np.uint32(GRID_OVERFLOW), w.astype(np.uint32))
+    w = lists[..., 0]
+    for k in range(1, GRID_SLOTS):
+        w = w | (lists[..., k] << (GRID_SLOT_BITS * k))
+    w = np.where(counts > GRID_SLOTS, np.uint32(GRID_OVERFLOW), w.astype(np.uint32))
     words = np.ascontiguousarray(w.transpose(2, 1, 0)).reshape(-1).astype(np.uint32)   # x fastest
-    k_lin = int(K[0] + dims[0] * (K[1] + dims[1] * K[2]))     # linear index of the lattice point (Kx, Ky, Kz): header word 31
+    k_lin = int(K[0] + dims[0] * (K[1] + dims[1] * K[2]))     # linear index of the lattice point (Kx, Ky, Kz): header word k_lin
     return dict(dims=dims.astype(np.int32), lo=lo32, inv=inv32, words=words, k_lin=k_lin, K=K,
-                stats=dict(mean=float(counts.mean()), max=int(counts.max()), overflow=int((counts > 4).sum())))
+                stats=dict(mean=float(counts.mean()), max=int(counts.max()), overflow=int((counts > GRID_SLOTS).sum())))
 
 
 def links_that_can_touch(rs, fs, slack=1e-4):
@@ -476,9 +591,9 @@ def hinge_bound(rs, fs):
 
 
 def field_needs_list_grid(field):
-    """The compact broad-phase grid (geometry version 6) serves up to 63 obstacle spheres (csrc/mpb_geom.h MPB_GRID_MAX_SPH); beyond
-    that a field takes the list grid of version 7 where it fits."""
-    return len(field.spec()['spheres']) > 63
+    """The compact broad-phase grid (geometry version 6) serves up to GRID_MAX_SPH obstacle spheres; beyond that a field takes the
+    list grid of version 7 where it fits."""
+    return len(field.spec()['spheres']) > GRID_MAX_SPH
 
 
 def pack_geometry(robot, field, scales=None, prune_static=True, use_model=True, list_grid=None):
@@ -492,20 +607,13 @@ def pack_geometry(robot, field, scales=None, prune_static=True, use_model=True, 
     the full table: pack with prune_static=False for them.
 
     `field` may be a list of up to MAX_FIELDS CollisionFields (the reference builds one CostCollision per field,
-    gpmp2.py:70-78, and sums them): the per-field buffers are chained, header word [27] of each holding the word
-    offset to the next one (0 = last) and word [28] a per-field scale s_f -- every kernel evaluates
+    gpmp2.py:70-78, and sums them): the per-field buffers are chained, header word `next` of each holding the word
+    offset to the next one (0 = last) and `fscale` a per-field scale s_f -- every kernel evaluates
     sum_f s_f * cost_f(q) (and its gradient) by walking the chain.
 
-    Layout (32-bit words; ints stored bit-exact), mirrored by csrc/mpb_geom.h:
-      [0] magic [1] version [2] kind [3] n_dof [4] n_frames_tf (0 or n_dof+1) [5] n_links
-      [6] n_spheres [7] n_boxes [8] margin(f32) [9] off_tf [10] off_links [11] off_spheres
-      [12] off_boxes [13] total_words [14] off_cull [15] off_frame_start
-      [16] off_grid [17..19] grid dims nx,ny,nz [20..22] grid origin (f32) [23..25] 1/cell size (f32)
-      [26] n_cells (0: no grid) [27] words to the next chained field (0: none) [28] field scale s_f (f32)
-      (version 7: the grid section is a LIST grid -- build_list_grid -- and n_cand_words = total_words - off_grid - pad1024(n_cells) words of
-      candidate bytes follow the padded cell words)
-      [29] compile-time robot model id (model_gen.py; 0: none -- set only when the robot's tables equal the model's
-      bit for bit) [30] keep mask over the MODEL's collision spheres (bit l: sphere l is in the link table) [31] reserved
+    Layout (32-bit words; ints stored bit-exact): the header is HEADER_WORDS at the top of this module (read one with header(), walk a
+    chain with fields(); the C side has the same words as MPB_GW_* of include/mpb_geom_layout.h, generated from that table), `model` set
+    only when the robot's tables equal the model's bit for bit.  The sections follow in this order:
       joint_tf    : n_frames_tf x 12   (row-major 3x4)
       links       : n_links x 8        (frame:int, ox, oy, oz, radius, 0, 0, 0)
       spheres     : n_spheres x 4      (cx, cy, cz, r)
@@ -515,11 +623,13 @@ def pack_geometry(robot, field, scales=None, prune_static=True, use_model=True, 
                     (3 fma + 1 compare per pair; the exact distance is evaluated only when a lane passes).
                     Padding entries never pass (rhs = -1e30).
       frame_start : n_frames + 1 ints (padded to 4): links [fs[j], fs[j+1]) ride on frame j+1
-      grid        : nx*ny*nz uint32 words, x fastest (section zero-padded to a multiple of 1024 words).  Broad phase for the obstacle spheres: a word packs up
-                    to four 8-bit obstacle indices (n_spheres = none: the far dummy) -- exactly the obstacles whose ball inflated
-                    by (margin + max_l r_l + slack) touches the cell; GRID_OVERFLOW when more than four do.
+      grid        : nx*ny*nz uint32 words, x fastest (section zero-padded to a multiple of GRID_PAD words).  Broad phase for the obstacle spheres: a
+                    word packs up to GRID_SLOTS obstacle indices (n_spheres = none: the far dummy) -- exactly the obstacles whose ball inflated
+                    by (margin + max_l r_l + slack) touches the cell; GRID_OVERFLOW when more do.
                     A collision sphere at x can only be within its hinge threshold of the obstacles listed
                     in the cell containing x (none outside the grid), so per-LANE culling is exact.
+                    version GEOM_VERSION_LIST: a LIST grid instead (build_list_grid), whose candidate bytes -- total - off_grid - the padded
+                    cell words, in words -- follow the padded cell words.
     """
     if isinstance(field, (list, tuple)):
         fields = list(field)
@@ -530,8 +640,8 @@ def pack_geometry(robot, field, scales=None, prune_static=True, use_model=True, 
         want_list = any(field_needs_list_grid(f) for f in fields) if list_grid is None else bool(list_grid)
         parts = [pack_geometry(robot, f, scales=[sc], prune_static=prune_static, use_model=use_model, list_grid=want_list)
                  for f, sc in zip(fields, scales)]
-        for i, part in enumerate(parts[:-1]):
-            part.view(np.int32)[27] = part.size
+        for part in parts[:-1]:
+            header(part)['next'] = part.size
         return np.concatenate(parts)
     rs, fs = robot.spec(), field.spec()
     from . import model_gen
@@ -581,15 +691,16 @@ def pack_geometry(robot, field, scales=None, prune_static=True, use_model=True, 
     total = off_cand + n_cand_words
     buf = np.zeros((total,), dtype=np.float32)
     ibuf = buf.view(np.int32)
-    ibuf[0:8] = [GEOM_MAGIC, version, rs['kind'], rs['n_dof'], n_tf, n_links, n_sph, n_box]
-    buf[8] = fs['margin']
-    ibuf[9:17] = [off_tf, off_links, off_sph, off_box, total, off_cull, off_fs, off_grid]
+    written = dict(magic=GEOM_MAGIC, version=version, kind=rs['kind'], n_dof=rs['n_dof'], n_tf=n_tf, n_links=n_links, n_sph=n_sph, n_box=n_box,
+                   margin=fs['margin'], off_tf=off_tf, off_links=off_links, off_sph=off_sph, off_box=off_box, total=total, off_cull=off_cull,
+                   off_fs=off_fs, off_grid=off_grid, next=0, fscale=1.0 if scales is None else float(scales[0]), model=model_id,
+                   keep_mask=keep_mask)
     if grid is not None:
-        ibuf[17:20] = grid['dims']
-        buf[20:23] = grid['lo']
-        buf[23:26] = grid['inv']
-        ibuf[26] = n_cells
-        ibuf[31] = grid['k_lin']
+        written.update(grid_dims=grid['dims'], grid_lo=grid['lo'], grid_inv=grid['inv'], n_cells=n_cells, k_lin=grid['k_lin'])
+    hdr = header(buf)
+    for name, value in written.items():
+        hdr[name] = value
+    if grid is not None:
         buf.view(np.uint32)[off_grid:off_grid + n_cells] = grid['words']
         if version == GEOM_VERSION_LIST:
             buf.view(np.uint8)[4 * off_cand:4 * off_cand + grid['cand'].size] = grid['cand']
@@ -632,21 +743,12 @@ def pack_geometry(robot, field, scales=None, prune_static=True, use_model=True, 
     else:
         fstart[0], fstart[1:] = 0, n_links
     ibuf[off_fs:off_grid] = fstart
-    ibuf[27] = 0
-    buf[28] = 1.0 if scales is None else float(scales[0])
-    ibuf[29] = model_id
-    buf.view(np.uint32)[30] = keep_mask
     return buf
 
 
 def count_fields(packed):
     """Number of chained fields in a packed geometry buffer."""
-    gi = np.asarray(packed).view(np.int32)
-    n, off = 1, 0
-    while gi[off + 27] != 0:
-        off += int(gi[off + 27])
-        n += 1
-    return n
+    return sum(1 for _ in fields(packed))
 
 
 # ----------------------------------------------------------------------------------------------

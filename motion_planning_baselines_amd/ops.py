@@ -10,7 +10,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from .geometry import count_fields, pack_geometry
+from .geometry import MAX_FIELDS, count_fields, pack_geometry
+from .geometry import header as geometry_header
 
 
 # the raw handle of a device's current stream: torch.cuda.current_stream(dev).cuda_stream builds a Stream object per call (~2.5 us,
@@ -83,29 +84,27 @@ class DeviceGeometry:
         fk_collision_points / field_cost_points); by default spheres that can never reach an obstacle of the field are
         left out of the link table (geometry.links_that_can_touch: exact, cost and gradient unchanged)."""
         self.robot, self.field = robot, field
-        host = pack_geometry(robot, field, scales=scales, prune_static=not keep_all_links, use_model=use_model)
-        self.all_links = int(host.view(np.int32)[5]) == len(robot.spec()['link_radius']) and (
+        self._adopt(pack_geometry(robot, field, scales=scales, prune_static=not keep_all_links, use_model=use_model), device)
+        self.all_links = self.n_links == len(robot.spec()['link_radius']) and (
             not isinstance(field, (list, tuple)) or keep_all_links or len(field) == 1)
-        _lib.geom_check(host)
-        self.flags = _lib.geom_flags(host)
-        self.host = host
-        self.n_dof = robot.q_dim
-        self.n_fields = count_fields(host)
-        self.buf = torch.from_numpy(host.copy()).to(device)
 
     @classmethod
     def from_packed(cls, packed, device):
         self = cls.__new__(cls)
-        host = np.ascontiguousarray(packed, dtype=np.float32)
+        self.robot = self.field = None
+        self._adopt(np.ascontiguousarray(packed, dtype=np.float32), device)
+        self.all_links = True
+        return self
+
+    def _adopt(self, host, device):
+        """Check the packed buffer, read what the entry points ask of its (first) header once, and put it on the device."""
         _lib.geom_check(host)
         self.flags = _lib.geom_flags(host)
-        self.robot = self.field = None
-        self.all_links = True
         self.host = host
-        self.n_dof = int(host.view(np.int32)[3])
+        hdr = geometry_header(host)
+        self.n_dof, self.n_links = int(hdr['n_dof']), int(hdr['n_links'])
         self.n_fields = count_fields(host)
         self.buf = torch.from_numpy(host.copy()).to(device)
-        return self
 
 
 @_on_tensor_device
@@ -203,7 +202,7 @@ def fk_collision_points(q, geom):
     B, H, d = q.shape
     _chk(q, (B, H, d), 'q')
     _need_all_links(geom)
-    L = int(geom.host.view(np.int32)[5])
+    L = geom.n_links
     pts = torch.empty(B, H, L, 3, device=q.device, dtype=torch.float32)
     _lib.check(_lib.lib().mpb_fk_collision_points(_ptr(q), _ptr(geom.buf), _ptr(pts), B, H, d, _stream()), 'mpb_fk_collision_points')
     return pts
@@ -213,7 +212,7 @@ def fk_collision_points(q, geom):
 def fk_collision_points_vjp(q, geom, grad_pts):
     B, H, d = q.shape
     _need_all_links(geom)
-    L = int(geom.host.view(np.int32)[5])
+    L = geom.n_links
     _chk(q, (B, H, d), 'q')
     _chk(grad_pts, (B, H, L, 3), 'grad_pts')
     gq = torch.empty(B, H, geom.n_dof, device=q.device, dtype=torch.float32)
@@ -227,7 +226,7 @@ def field_cost_points(pts, geom):
     """Collision-sphere positions (B,H,L,3) -> hinge cost per waypoint (B,H) (mpb_field_cost_points)."""
     B, H, L, _ = pts.shape
     _need_all_links(geom)
-    _chk(pts, (B, H, int(geom.host.view(np.int32)[5]), 3), 'pts')
+    _chk(pts, (B, H, geom.n_links, 3), 'pts')
     cost = torch.empty(B, H, device=pts.device, dtype=torch.float32)
     _lib.check(_lib.lib().mpb_field_cost_points(_ptr(pts), _ptr(geom.buf), _ptr(cost), B, H, _stream()), 'mpb_field_cost_points')
     return cost
@@ -237,7 +236,7 @@ def field_cost_points(pts, geom):
 def field_cost_points_vjp(pts, geom, grad_cost):
     B, H, L, _ = pts.shape
     _need_all_links(geom)
-    _chk(pts, (B, H, int(geom.host.view(np.int32)[5]), 3), 'pts')
+    _chk(pts, (B, H, geom.n_links, 3), 'pts')
     _chk(grad_cost, (B, H), 'grad_cost')
     gp = torch.empty_like(pts)
     _lib.check(_lib.lib().mpb_field_cost_points_vjp(_ptr(pts), _ptr(geom.buf), _ptr(grad_cost), _ptr(gp), B, H, _stream()),
@@ -657,8 +656,7 @@ def gpmp2_collision_rows(x, geom, n_interp=0):
     _chk(x, (B, H, dim), 'x')
     if _lib.lib().mpb_gpmp2_workspace_bytes(B, H, D) == 0:
         raise ValueError(f'unsupported GPMP2 shape B={B} H={H} D={D}')
-    MAX_FIELDS = 4                                   # MPB_MAX_FIELDS: the section is laid out for four fields
-    jac = torch.zeros(MAX_FIELDS, B, H, D + 1, device=x.device, dtype=torch.float32)
+    jac = torch.zeros(MAX_FIELDS, B, H, D + 1, device=x.device, dtype=torch.float32)     # (the section is laid out for MAX_FIELDS fields)
     _lib.check(_lib.lib().mpb_gpmp2_linearize(_ptr(x), _ptr(geom.buf), int(geom.flags), _ptr(jac), B, H, D, int(n_interp or 0), _stream()),
                'mpb_gpmp2_linearize')
     return jac[:geom.n_fields]

@@ -50,7 +50,7 @@ def stats(cell, maxdim, per_link=False):
     ijk = np.clip(np.floor((pos - lo) * inv), 0, dims - 1).astype(np.int64)
     w = words[(ijk[..., 2] * dims[1] + ijk[..., 1]) * dims[0] + ijk[..., 0]]
     n = len(sph)
-    cnt = sum((((w >> (8 * k)) & 0xFF) != n).astype(np.int64) for k in range(4))
+    cnt = (geometry.grid_cell_slots(w) != n).sum(-1)
     cnt = np.where(w == geometry.GRID_OVERFLOW, 9, cnt)
     cnt = cnt.reshape(P * S, H, 31)
     trips = []

@@ -350,18 +350,18 @@ def test_point_entry_points_edge_cases(gpu_device):
 
 def _rewrite_grid_words(host, fn):
     """A copy of a packed geometry buffer with every (non-overflow) word of its broad-phase grid rewritten by fn(slots, n_sph)
-    -> slots (lists of obstacle indices; pack_geometry header: [6] n_spheres, [16] off_grid, [26] n_cells)."""
+    -> slots (lists of obstacle indices)."""
+    from motion_planning_baselines_amd import geometry as G
     out = host.copy()
     w = out.view(np.uint32)
-    ns, off, n = int(w[6]), int(w[16]), int(w[26])
+    h = G.header(out)
+    ns, off, n = int(h['n_sph']), int(h['off_grid']), int(h['n_cells'])
     for i in range(off, off + n):
-        word = int(w[i])
-        if word == 0xFFFFFFFE:
+        if w[i] == G.GRID_OVERFLOW:
             continue
-        slots = [(word >> (8 * k)) & 0xFF for k in range(4)]
-        slots = fn([b for b in slots if b < ns], ns)
-        slots = (list(slots) + [ns] * 4)[:4]
-        w[i] = slots[0] | (slots[1] << 8) | (slots[2] << 16) | (slots[3] << 24)
+        slots = fn([int(b) for b in G.grid_cell_slots(w[i]) if b < ns], ns)
+        slots = (list(slots) + [ns] * G.GRID_SLOTS)[:G.GRID_SLOTS]
+        w[i] = sum(b << (G.GRID_SLOT_BITS * k) for k, b in enumerate(slots))
     return out
 
 

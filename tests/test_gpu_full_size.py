@@ -81,15 +81,15 @@ def test_panda_model_path_equals_generic_walk(gpu_device, keep_all):
     table-driven chain walk return the same bits: fused STOMP cost and stand-alone cost on 131072 waypoints incl.
     far-out-of-range angles, with the statically pruned link table and with the full one (frame-1 group live)."""
     import numpy as np
-    from motion_planning_baselines_amd import ops
+    from motion_planning_baselines_amd import geometry as G, ops
     dev = gpu_device
     P, S, H = 16, 32, 64
     wl, Sigma, L, _ = _c3(dev, P, S)
     gm = ops.DeviceGeometry(wl['robot'], wl['field'], dev, keep_all_links=keep_all)
     gg = ops.DeviceGeometry(wl['robot'], wl['field'], dev, keep_all_links=keep_all, use_model=False)
-    assert int(gm.host.view(np.int32)[29]) == 1 and int(gg.host.view(np.int32)[29]) == 0
-    n_kept = int(gm.host.view(np.int32)[5])
-    assert int(gm.host.view(np.uint32)[30]) == ((1 << 31) - 1 if keep_all else ((1 << 31) - 1) & ~((1 << (31 - n_kept)) - 1))
+    assert G.header(gm.host)['model'] == 1 and G.header(gg.host)['model'] == 0
+    n_kept = int(G.header(gm.host)['n_links'])
+    assert int(G.header(gm.host)['keep_mask']) == ((1 << 31) - 1 if keep_all else ((1 << 31) - 1) & ~((1 << (31 - n_kept)) - 1))
     d = wl['means0'].shape[-1]
     out = []
     for geom in (gm, gg):
@@ -113,12 +113,12 @@ def test_panda_model_gradient_walk_equals_generic_walk(gpu_device, keep_all):
     GPMP2's linearisation incl. interpolated points, CHOMP's loop) and the table-driven walk return the same bits:
     131072 waypoints incl. far-out-of-range angles, pruned and full link tables."""
     import numpy as np
-    from motion_planning_baselines_amd import ops
+    from motion_planning_baselines_amd import geometry as G, ops
     dev = gpu_device
     wl, _, _, _ = _c3(dev, 8, 4)
     gm = ops.DeviceGeometry(wl['robot'], wl['field'], dev, keep_all_links=keep_all)
     gg = ops.DeviceGeometry(wl['robot'], wl['field'], dev, keep_all_links=keep_all, use_model=False)
-    assert (gm.flags & 0xFF) == 1 and (gg.flags & 0xFF) == 0
+    assert (gm.flags & G.GEOM_FLAG_MODEL_MASK) == 1 and (gg.flags & G.GEOM_FLAG_MODEL_MASK) == 0
     g = torch.Generator().manual_seed(1)
     x = ((torch.rand(2048, 64, 14, generator=g) * 2 - 1) * 6.0).to(dev)
     x[:1024] *= 0.4                                          # half of them near the workspace centre: many contacts
@@ -161,20 +161,20 @@ def test_collision_cost_grid_equals_exhaustive_at_scale(gpu_device):
 
 def test_chomp_c2_quad_kernel_equals_lean_kernel(gpu_device):
     """C2 runs on the four-lanes-per-waypoint kernel (obstacles in registers, nearest combined over the quad by (signed
-    distance, obstacle index)); with the geometry's flag bit 9 cleared the same call takes the one-lane-per-waypoint
+    distance, obstacle index)); with the geometry's POINT_SMALL flag cleared the same call takes the one-lane-per-waypoint
     kernel with its exhaustive loop: same arithmetic per obstacle, same first-minimum rule."""
-    from motion_planning_baselines_amd import ops, workloads
+    from motion_planning_baselines_amd import geometry as G, ops, workloads
     from motion_planning_baselines_amd.planners.chomp import chomp_precision_matrix
     dev = gpu_device
     wl = workloads.pointmass_dense_chomp(1024, dev)
     R = chomp_precision_matrix(wl['params']['dt'], 64, dict(device='cpu', dtype=torch.float32)).to(dev).contiguous()
     geom = ops.DeviceGeometry(wl['robot'], wl['field'], dev)
-    assert geom.flags & 0x200
+    assert geom.flags & G.GEOM_FLAG_POINT_SMALL
     kw = dict(D=2, k_sigma=1.0, weight=10.0, w_prior=1e-4, lr=0.05, grad_clip=0.05)
     a, b = wl['means0'].clone(), wl['means0'].clone()
     ca, cb = torch.empty(1024, device=dev), torch.empty(1024, device=dev)
     ops.chomp_step(a, R, geom, n_iters=1, costs_out=ca, **kw)
-    geom.flags &= ~0x200
+    geom.flags &= ~G.GEOM_FLAG_POINT_SMALL
     ops.chomp_step(b, R, geom, n_iters=1, costs_out=cb, **kw)
     torch.cuda.synchronize()
     assert float(ca.max()) > 0 and not torch.equal(a, wl['means0'])
@@ -325,7 +325,7 @@ def test_static_link_pruning_changes_nothing(gpu_device):
     robot, field = G.RobotPanda(), G.env_spheres_3d(seed=0)
     full = ops.DeviceGeometry(robot, field, dev, keep_all_links=True)
     pruned = ops.DeviceGeometry(robot, field, dev)
-    assert int(full.host.view(np.int32)[5]) == 31 and int(pruned.host.view(np.int32)[5]) == 28
+    assert G.header(full.host)['n_links'] == 31 and G.header(pruned.host)['n_links'] == 28
     g = torch.Generator().manual_seed(4)
     lo, hi = torch.from_numpy(robot.q_min_np), torch.from_numpy(robot.q_max_np)
     q = (lo + (hi - lo) * torch.rand(4096, 64, 7, generator=g) + 0.5 * torch.randn(4096, 64, 7, generator=g)).to(dev)

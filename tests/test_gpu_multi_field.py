@@ -251,9 +251,9 @@ def test_gpmp2_two_fields_with_interpolation_vs_oracle(gpu_device):
 @pytest.mark.parametrize('P,S', [(3, 6), (70, 64)])
 def test_persistent_stomp_one_field_flag_is_rechecked_on_the_device(gpu_device, P, S):
     """The persistent STOMP kernel has a ONE-field instantiation (template flag CHAIN = false, csrc/mpb_stomp_fused.hip) the
-    launcher takes on geom_flags bit 12.  With two fields it must take the chained form (checked against the oracle); a caller
+    launcher takes on geom_flags ONE_FIELD.  With two fields it must take the chained form (checked against the oracle); a caller
     whose flags claim one field over a device buffer that chains two gets NaN costs, never the first field's costs alone."""
-    from motion_planning_baselines_amd import ops
+    from motion_planning_baselines_amd import geometry as G, ops
     from motion_planning_baselines_amd.planners.stomp import precision_to_scale_tril, stomp_precision_matrix
     from oracle import planners_ref as O
     from oracle.geometry_ref import make_ref_geometry
@@ -263,9 +263,9 @@ def test_persistent_stomp_one_field_flag_is_rechecked_on_the_device(gpu_device, 
     d = 2 * D
     scales = [1.0, 0.6]
     geom = ops.DeviceGeometry(robot, fields, dev, scales=scales)
-    assert not geom.flags & 0x1000 and geom.flags & 0x100
+    assert not geom.flags & G.GEOM_FLAG_ONE_FIELD and geom.flags & G.GEOM_FLAG_ALL_GRIDS
     one = ops.DeviceGeometry(robot, fields[:1], dev)
-    assert one.flags & 0x1000
+    assert one.flags & G.GEOM_FLAG_ONE_FIELD
     cpu = dict(device='cpu', dtype=torch.float32)
     R = stomp_precision_matrix(H, 0.05, 1.0, cpu)
     Sigma, L = torch.inverse(R).contiguous(), precision_to_scale_tril(R).contiguous()
@@ -317,7 +317,7 @@ def test_stomp_model_flag_is_rechecked_on_the_device(gpu_device, H):
     tagged = ops.DeviceGeometry(robot, [G.env_spheres_3d()], dev)
     big = G.CollisionField(spheres=np.array([[0.5, 0.5, 0.5, 0.9], [-0.6, 0.2, 0.4, 0.1]], np.float32), margin=0.05)
     plain = ops.DeviceGeometry(robot, [big], dev)
-    assert tagged.flags & 0xFF and not plain.flags & 0xFF and plain.flags & 0x100
+    assert tagged.flags & G.GEOM_FLAG_MODEL_MASK and not plain.flags & G.GEOM_FLAG_MODEL_MASK and plain.flags & G.GEOM_FLAG_ALL_GRIDS
 
     class Forged:
         buf, flags = plain.buf, tagged.flags

@@ -272,7 +272,8 @@ def test_mppi_bench_shape_vs_oracle(gpu_device):
     goal = torch.rand(NP, c, generator=gen) * 0.2 + 0.7
     robot, field = G.RobotPointMass(2, radius=0.01), G.env_grid_circles_2d()
     geom = ops.DeviceGeometry(robot, field, dev)
-    assert (geom.flags & 0x1500) == 0x1500                       # one grid-backed field, point robot: the grid instantiation
+    grid_instantiation = G.GEOM_FLAG_ALL_GRIDS | G.GEOM_FLAG_POINT | G.GEOM_FLAG_ONE_FIELD     # one grid-backed field, point robot
+    assert (geom.flags & grid_instantiation) == grid_instantiation
     rr, rf = make_ref_geometry(robot, field, ta)
     eps = torch.randn(n_it, NP, c, S, T, generator=gen)
     f = lambda t: t.contiguous().to(dev)

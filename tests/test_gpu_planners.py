@@ -229,7 +229,8 @@ def test_gpmp2_extra_collision_cost(gpu_device):
     # a different sigma on the extra cost changes the solution the way a scaled field does
     loose = CostCollision(robot, H, field=fields[1], sigma_coll=10.0 * sc, tensor_args=ta)
     pl, _, _ = _gpmp2_from_golden(g, dev, collision_fields=fields[:1], extra_costs=[loose])
-    assert abs(pl.geom.host[28 + int(pl.geom.host.view(np.int32)[27])] - 0.01) < 1e-8    # second field's share
+    from motion_planning_baselines_amd import geometry as G
+    assert abs(list(G.fields(pl.geom.host))[1]['fscale'] - 0.01) < 1e-8    # second field's share
     assert not torch.equal(pl.optimize(opt_iters=1), T(g['means'][0]).float().to(dev))
     with pytest.raises(NotImplementedError):
         _gpmp2_from_golden(g, dev, extra_costs=[CostGPTrajectory(robot, H, float(g['dt']), sigma_gp=1.0, tensor_args=ta)])

@@ -219,7 +219,7 @@ def test_lattice_grid_offset_equals_floor_form_on_shifted_scenes(gpu_device, shi
     sph = np.concatenate([rng.uniform(-1, 1, (14, 3)) + off, rng.uniform(0.05, 0.2, (14, 1))], 1).astype(np.float32)
     robot, field = G.RobotPointMass(3, radius=0.02), G.CollisionField(spheres=sph, margin=0.03)
     geom = ops.DeviceGeometry(robot, field, dev)
-    assert geom.flags & 0x100
+    assert geom.flags & G.GEOM_FLAG_ALL_GRIDS
     P, S, H, d = 6, 16, 64, 6
     a = torch.linspace(0, 1, H).reshape(1, H, 1)
     s0 = torch.tensor(rng.uniform(-1, 1, (P, 1, 3)) + off, dtype=torch.float32)

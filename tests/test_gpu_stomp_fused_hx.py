@@ -277,7 +277,8 @@ def test_list_grid_scene_on_the_persistent_path(gpu_device, robot_kind, P, S, H,
         robot, D = G.RobotPanda(), 7
     fields = [G.env_spheres_3d(seed=2), field] if robot_kind == 'panda2' else field
     geom = ops.DeviceGeometry(robot, fields, dev, use_model=use_model)
-    assert (geom.flags & 0x2100) == 0x2000 and bool(geom.flags & 0xFF) == use_model
+    assert (geom.flags & (G.GEOM_FLAG_ALL_LISTS | G.GEOM_FLAG_ALL_GRIDS)) == G.GEOM_FLAG_ALL_LISTS
+    assert bool(geom.flags & G.GEOM_FLAG_MODEL_MASK) == use_model
     d = D if pos_only else 2 * D
     means0 = trajs(D, P, H, d, seed=3).to(dev)
     Sigma, L = _constants(H, 0.05, 0.05, dev)

@@ -48,7 +48,7 @@ def _setup(name, dev):
     wl = workloads.panda_spheres_stomp(P, dev, H=H, S=S, pos_only=pos_only)
     if scene == 'list':
         geom = ops.DeviceGeometry(wl['robot'], G.env_spheres_boxes_3d(0, 200, 32, 0.04), dev)
-        assert (geom.flags & 0x2100) == 0x2000
+        assert (geom.flags & (G.GEOM_FLAG_ALL_LISTS | G.GEOM_FLAG_ALL_GRIDS)) == G.GEOM_FLAG_ALL_LISTS
         scal = (25.0, 1.0, 0.3, 2.0)              # k_sigma, weight, lr, temperature
     else:
         geom = ops.DeviceGeometry(wl['robot'], wl['field'], dev)
@@ -127,9 +127,9 @@ def check_poison(name, noise, dev):
     tagged = ops.DeviceGeometry(robot, [G.env_spheres_3d()], dev)
     big = G.CollisionField(spheres=np.array([[0.5, 0.5, 0.5, 0.9], [-0.6, 0.2, 0.4, 0.1]], np.float32), margin=0.05)
     plain = ops.DeviceGeometry(robot, [big], dev)
-    assert tagged.flags & 0xFF and not plain.flags & 0xFF and plain.flags & 0x100
+    assert tagged.flags & G.GEOM_FLAG_MODEL_MASK and not plain.flags & G.GEOM_FLAG_MODEL_MASK and plain.flags & G.GEOM_FLAG_ALL_GRIDS
     two = ops.DeviceGeometry(robot, [G.env_spheres_3d(), G.env_spheres_3d(seed=2)], dev)
-    assert tagged.flags & 0x1000 and not two.flags & 0x1000
+    assert tagged.flags & G.GEOM_FLAG_ONE_FIELD and not two.flags & G.GEOM_FLAG_ONE_FIELD
 
     class ForgedModel:
         buf, flags = plain.buf, tagged.flags

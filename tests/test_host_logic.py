@@ -59,11 +59,11 @@ def test_geometry_pack_validates_and_rejects_corruption():
         buf = G.pack_geometry(robot, field)
         _lib.geom_check(buf)
         bad = buf.copy()
-        bad.view(np.int32)[0] ^= 1
+        G.header(bad)['magic'] ^= 1
         with pytest.raises(_lib.MPBError):
             _lib.geom_check(bad)
         bad = buf.copy()
-        bad.view(np.int32)[13] += 4
+        G.header(bad)['total'] += 4
         with pytest.raises(_lib.MPBError):
             _lib.geom_check(bad)
         with pytest.raises(_lib.MPBError):
@@ -75,9 +75,9 @@ def test_cull_table_is_conservative():
     from motion_planning_baselines_amd import geometry as G
     robot, field = G.RobotPanda(), G.env_spheres_3d()
     buf = G.pack_geometry(robot, field)
-    i = buf.view(np.int32)
-    n_sph = i[6]
-    cull = buf[i[14]:i[14] + 8 * ((n_sph + 3) // 4 * 4)].reshape(-1, 8)
+    h = G.header(buf)
+    n_sph = h['n_sph']
+    cull = buf[h['off_cull']:h['off_cull'] + 8 * ((n_sph + 3) // 4 * 4)].reshape(-1, 8)
     rng = np.random.RandomState(0)
     T = field.margin + robot.link_radius.max() + field.spheres[:, 3]
     for o in range(n_sph):
@@ -123,8 +123,8 @@ def test_product_geometry_round_trip():
     robot, field = product_geometry_from_golden(g)
     from motion_planning_baselines_amd import geometry as G
     buf = G.pack_geometry(robot, field, prune_static=False)
-    i = buf.view(np.int32)
-    assert i[5] == len(g['link_radius']) and i[6] == len(g['spheres'])
+    h = G.header(buf)
+    assert h['n_links'] == len(g['link_radius']) and h['n_sph'] == len(g['spheres'])
 
 
 def test_static_link_pruning_is_conservative():
@@ -150,7 +150,7 @@ def test_static_link_pruning_is_conservative():
         worst = hinge.max(0).values.numpy()
         assert (worst[~keep] == 0).all(), worst[~keep]
         buf = G.pack_geometry(robot, field)
-        assert buf.view(np.int32)[5] == int(keep.sum())
+        assert G.header(buf)['n_links'] == int(keep.sum())
     # the synthetic C3 scene keeps obstacles off the base axis: the three base-link spheres go
     assert int(G.links_that_can_touch(robot.spec(), G.env_spheres_3d(seed=0).spec()).sum()) == 28
 
@@ -210,7 +210,7 @@ def test_oracle_trajectory_utilities():
 
 
 def test_chained_geometry_buffers():
-    """Several collision fields in one buffer: header word 27 links them, word 28 carries the per-field scale;
+    """Several collision fields in one buffer: header word `next` links them, `fscale` carries the per-field scale;
     the C-ABI validator walks the chain."""
     from motion_planning_baselines_amd import geometry as G
     from motion_planning_baselines_amd import _lib
@@ -220,16 +220,18 @@ def test_chained_geometry_buffers():
     one = G.pack_geometry(robot, f1)
     two = G.pack_geometry(robot, [f1, f2], scales=[1.0, 0.25])
     assert G.count_fields(one) == 1 and G.count_fields(two) == 2
-    assert np.array_equal(two[:one.size].view(np.int32)[:27], one.view(np.int32)[:27])
-    assert two.view(np.int32)[27] == one.size and two[one.size + 28] == np.float32(0.25) and two[28] == 1.0
+    first, second = G.fields(two)
+    assert all(np.array_equal(first[name], G.header(one)[name]) for name in G.HEADER_DTYPE.names if name != 'next')
+    assert first['next'] == one.size and second['fscale'] == np.float32(0.25) and first['fscale'] == 1.0
+    assert second.tobytes() == two[one.size:one.size + G.GEOM_HEADER_WORDS].tobytes()
     _lib.geom_check(one)
     _lib.geom_check(two)
     bad = two.copy()
-    bad.view(np.int32)[27] = one.size - 4          # next header inside the first field
+    G.header(bad)['next'] = one.size - 4           # next header inside the first field
     with pytest.raises(MPBError):
         _lib.geom_check(bad)
     bad = two.copy()
-    bad[one.size + 28] = -1.0                      # negative scale
+    G.header(bad, one.size)['fscale'] = -1.0       # negative scale
     with pytest.raises(MPBError):
         _lib.geom_check(bad)
     with pytest.raises(MPBError):                  # second field for a different robot
@@ -240,7 +242,8 @@ def test_chained_geometry_buffers():
 
 def _link(buf):
     b = buf.copy()
-    b.view(np.int32)[27] = b.size
+    from motion_planning_baselines_amd import geometry as G
+    G.header(b)['next'] = b.size
     return b
 
 
@@ -301,38 +304,45 @@ def test_geometry_model_tag_and_flags():
     from motion_planning_baselines_amd import _lib, geometry as G
     robot, field = G.RobotPanda(), G.env_spheres_3d()
     buf = G.pack_geometry(robot, field)
-    gi = buf.view(np.int32)
-    assert gi[29] == 1 and int(buf.view(np.uint32)[30]) == ((1 << 31) - 1) & ~0b111      # the three base spheres are pruned here
+    h = G.header(buf)
+    assert h['model'] == 1 and int(h['keep_mask']) == ((1 << 31) - 1) & ~0b111      # the three base spheres are pruned here
     _lib.geom_check(buf)
-    # (bit 12: one field; bits 16-28: the cells of its broad-phase grid)
-    n_cells = int(gi[26])
-    assert _lib.geom_flags(buf) == (1 | 0x100 | 0x1000 | n_cells << 16)
-    assert _lib.geom_flags(G.pack_geometry(robot, field, use_model=False)) == (0x100 | 0x1000 | n_cells << 16)
+    # (one field; the cells of its broad-phase grid)
+    n_cells = int(h['n_cells'])
+    grids_one, cells = G.GEOM_FLAG_ALL_GRIDS | G.GEOM_FLAG_ONE_FIELD, n_cells << G.GEOM_FLAG_CELLS_SHIFT
+    assert _lib.geom_flags(buf) == (1 | grids_one | cells)
+    assert _lib.geom_flags(G.pack_geometry(robot, field, use_model=False)) == (grids_one | cells)
     full = G.pack_geometry(robot, field, prune_static=False)
-    assert int(full.view(np.uint32)[30]) == (1 << 31) - 1 and _lib.geom_flags(full) == (1 | 0x100 | 0x1000 | n_cells << 16)
+    assert int(G.header(full)['keep_mask']) == (1 << 31) - 1 and _lib.geom_flags(full) == (1 | grids_one | cells)
     two = G.pack_geometry(robot, [field, G.env_spheres_3d(seed=5)])
-    assert not (_lib.geom_flags(two) & 0x1000) and (_lib.geom_flags(two) & 0x1FF) == (1 | 0x100)
+    assert not (_lib.geom_flags(two) & G.GEOM_FLAG_ONE_FIELD)
+    assert (_lib.geom_flags(two) & (G.GEOM_FLAG_MODEL_MASK | G.GEOM_FLAG_ALL_GRIDS)) == (1 | G.GEOM_FLAG_ALL_GRIDS)
     # a robot that is not the Panda bit for bit is not tagged
     other = G.RobotPanda()
     other.link_offset[5, 1] += 1e-4
-    assert G.pack_geometry(other, field).view(np.int32)[29] == 0
+    assert G.header(G.pack_geometry(other, field))['model'] == 0
     # a forged tag on that buffer is refused
     forged = G.pack_geometry(other, field, prune_static=False)
-    forged.view(np.int32)[29] = 1
-    forged.view(np.uint32)[30] = (1 << 31) - 1
+    G.header(forged)['model'] = 1
+    G.header(forged)['keep_mask'] = (1 << 31) - 1
     with pytest.raises(_lib.MPBError):
         _lib.geom_check(forged)
     # point robot: no model, grid usable; box-only field: no grid at all
     pm = G.pack_geometry(G.RobotPointMass(2, radius=0.01), G.env_grid_circles_2d())
-    assert (_lib.geom_flags(pm) & 0xFFFF) == (0x100 | 0x400 | 0x1000)          # 49 circles: too many for the in-register CHOMP kernel (bit 9)
-    assert _lib.geom_flags(pm) >> 16 == int(pm.view(np.int32)[26])
-    assert (_lib.geom_flags(G.pack_geometry(G.RobotPointMass(2, radius=0.01), G.env_dense_2d())) & 0xFFFF) == (0x100 | 0x200 | 0x400 | 0x1000)
+    below_cells = (1 << G.GEOM_FLAG_CELLS_SHIFT) - 1
+    point_one = G.GEOM_FLAG_POINT | G.GEOM_FLAG_ONE_FIELD
+    # 49 circles: too many for the in-register CHOMP kernel (POINT_SMALL)
+    assert (_lib.geom_flags(pm) & below_cells) == (G.GEOM_FLAG_ALL_GRIDS | point_one)
+    assert _lib.geom_flags(pm) >> G.GEOM_FLAG_CELLS_SHIFT == int(G.header(pm)['n_cells'])
+    assert (_lib.geom_flags(G.pack_geometry(G.RobotPointMass(2, radius=0.01), G.env_dense_2d())) & below_cells) == (
+        G.GEOM_FLAG_ALL_GRIDS | G.GEOM_FLAG_POINT_SMALL | point_one)
     boxes = G.CollisionField(boxes=np.array([[0.2, 0.2, 0.1, 0.1]], np.float32), margin=0.01)
-    assert _lib.geom_flags(G.pack_geometry(G.RobotPointMass(2, radius=0.01), boxes)) == (0x200 | 0x400 | 0x1000)
+    assert _lib.geom_flags(G.pack_geometry(G.RobotPointMass(2, radius=0.01), boxes)) == (G.GEOM_FLAG_POINT_SMALL | point_one)
 
 
 def test_stomp_workspace_size():
     from motion_planning_baselines_amd import _lib
+    from motion_planning_baselines_amd.geometry import GEOM_FLAG_ALL_GRIDS as GRIDS, GEOM_FLAG_ALL_LISTS as LISTS
     f = _lib.lib().mpb_stomp_workspace_bytes
     # header + 8-byte {value, tag} granules, two parities: the H = 64 kernel's exchange slots hold 912 granules, the generalised
     # kernel's 2064 -- which also serves H = 64 when the geometry carries list grids (round 6): the workspace fits either
@@ -343,14 +353,14 @@ def test_stomp_workspace_size():
     assert f(8, 32, 200, 14) == 4 * 320                                     # a shape no persistent kernel serves (H > 128)
     # which path a call takes is a pure host-side function of the shape, the geometry flags and the workspace size
     path = _lib.lib().mpb_stomp_run_path
-    assert path(0x100 | 1, f(128, 32, 64, 14), 128, 32, 64, 14) == 1       # exchange layout
-    assert path(0x100 | 1, 4 * 320 + 8 * (2 * 128 * 2 * 912), 128, 32, 64, 14) == 1    # ... which needs the smaller slots only
-    assert path(0x2000 | 1, f(128, 32, 64, 14), 128, 32, 64, 14) == 1 and path(0x2000 | 1, 1 << 30, 128, 32, 100, 14) == 0   # list grids: H <= 64
-    assert path(0x100 | 1, 64, 128, 32, 64, 14) == 0                       # workspace too small: two-kernel loop
-    assert path(0x100, 1280, 4096, 32, 64, 14) == 2 and path(0x100, 1280, 8, 16, 64, 7) == 2      # the header alone (MPB_STOMP_WS_HEADER_BYTES)
-    assert path(0, 1 << 30, 128, 32, 64, 14) == 0 and path(0x100, 1 << 30, 128, 32, 200, 14) == 0
-    assert path(0x100, 1 << 30, 128, 32, 128, 14) == 1 and path(0x100, 1280, 300, 32, 128, 14) == 2   # H = 128: generalised kernel
-    assert path(0x100, 1 << 30, 2, 128, 32, 7) == 1 and path(0x100, 1 << 30, 128, 32, 64, 5) == 1  # S = 128; d = 5
+    assert path(GRIDS | 1, f(128, 32, 64, 14), 128, 32, 64, 14) == 1       # exchange layout
+    assert path(GRIDS | 1, 4 * 320 + 8 * (2 * 128 * 2 * 912), 128, 32, 64, 14) == 1    # ... which needs the smaller slots only
+    assert path(LISTS | 1, f(128, 32, 64, 14), 128, 32, 64, 14) == 1 and path(LISTS | 1, 1 << 30, 128, 32, 100, 14) == 0   # list grids: H <= 64
+    assert path(GRIDS | 1, 64, 128, 32, 64, 14) == 0                       # workspace too small: two-kernel loop
+    assert path(GRIDS, 1280, 4096, 32, 64, 14) == 2 and path(GRIDS, 1280, 8, 16, 64, 7) == 2      # the header alone (MPB_STOMP_WS_HEADER_BYTES)
+    assert path(0, 1 << 30, 128, 32, 64, 14) == 0 and path(GRIDS, 1 << 30, 128, 32, 200, 14) == 0
+    assert path(GRIDS, 1 << 30, 128, 32, 128, 14) == 1 and path(GRIDS, 1280, 300, 32, 128, 14) == 2   # H = 128: generalised kernel
+    assert path(GRIDS, 1 << 30, 2, 128, 32, 7) == 1 and path(GRIDS, 1 << 30, 128, 32, 64, 5) == 1  # S = 128; d = 5
 
 
 @pytest.mark.parametrize('scene', ['spheres_3d', 'dense_2d', 'grid_circles_2d', 'large_3d'])
@@ -404,7 +414,7 @@ def test_broad_phase_grid_is_conservative_and_fits(scene):
     assert (np.abs(idx2[ins & inside] - idx[ins & inside]) <= dims[0] * dims[1] + dims[0] + 1).all()
     for which, ii in (('floor', idx), ('lattice', idx2)):
         ww = words[ii]
-        lst = np.stack([(ww >> (8 * s_)) & 0xFF for s_ in range(4)], 1)
+        lst = G.grid_cell_slots(ww)
         d_ = np.linalg.norm(p[:, None, :3].astype(np.float64) - sph[None, :, :3].astype(np.float64), axis=2)
         near_ = d_ < (sph[None, :, 3].astype(np.float64) + a_max)
         for i in np.nonzero(near_.any(1))[0]:
@@ -413,7 +423,7 @@ def test_broad_phase_grid_is_conservative_and_fits(scene):
             need = set(np.nonzero(near_[i])[0].tolist())
             assert need <= set(lst[i].tolist()), (scene, which, i, need, lst[i])
     w = words[idx]
-    listed = np.stack([(w >> (8 * s)) & 0xFF for s in range(4)], 1)
+    listed = G.grid_cell_slots(w)
     d = np.linalg.norm(p[:, None, :3].astype(np.float64) - sph[None, :, :3].astype(np.float64), axis=2)
     near = d < (sph[None, :, 3].astype(np.float64) + a_max)                       # obstacles that can matter at p
     assert not near[~inside].any()                           # outside the grid box nothing is within reach by construction
@@ -573,41 +583,41 @@ def test_model_tag_requires_hinges_below_one():
     from motion_planning_baselines_amd import geometry as G, _lib
     robot = G.RobotPanda()
     ok = G.pack_geometry(robot, G.env_spheres_3d())
-    assert ok.view(np.int32)[29] != 0
+    assert G.header(ok)['model'] != 0
     _lib.geom_check(ok)
     big = G.CollisionField(spheres=np.array([[0.5, 0.5, 0.5, 0.9], [-0.6, 0.2, 0.4, 0.1]], np.float32), margin=0.05)
     buf = G.pack_geometry(robot, big)
-    assert buf.view(np.int32)[29] == 0                       # 0.05 + 0.08 + 0.9 >= 1: no model tag
+    assert G.header(buf)['model'] == 0                       # 0.05 + 0.08 + 0.9 >= 1: no model tag
     _lib.geom_check(buf)
     forged = buf.copy()
-    forged.view(np.int32)[29] = ok.view(np.int32)[29]
-    forged.view(np.uint32)[30] = ok.view(np.uint32)[30]
+    G.header(forged)['model'] = G.header(ok)['model']
+    G.header(forged)['keep_mask'] = G.header(ok)['keep_mask']
     with pytest.raises(_lib.MPBError):
         _lib.geom_check(forged)
 
 
 def test_grid_lattice_far_and_negative_scenes():
     """Geometry version 6: the grid's origin sits on the lattice lo = (K - 1/2) h for scenes anywhere near the origin (negative K
-    included) and mpb_geom_check verifies header word 31 against it; a scene too far away for fp32 to resolve its cells gets no grid."""
+    included) and mpb_geom_check verifies header word k_lin against it; a scene too far away for fp32 to resolve its cells gets no grid."""
     from motion_planning_baselines_amd import geometry as G, _lib
     robot = G.RobotPointMass(3, radius=0.02)
     rng = np.random.default_rng(1)
     for shift in ([0, 0, 0], [-7.3, 2.1, -0.4], [55.0, -31.0, 12.0]):
         sph = np.concatenate([rng.uniform(-1, 1, (12, 3)) + np.array(shift), rng.uniform(0.05, 0.2, (12, 1))], 1).astype(np.float32)
         buf = G.pack_geometry(robot, G.CollisionField(spheres=sph, margin=0.03))
-        gi = buf.view(np.int32)
-        assert gi[26] > 0
+        h = G.header(buf)
+        assert h['n_cells'] > 0
         _lib.geom_check(buf)
-        lo, inv = buf[20:23].astype(np.float64), buf[23:26].astype(np.float64)
+        lo, inv, dims = h['grid_lo'].astype(np.float64), h['grid_inv'].astype(np.float64), h['grid_dims']
         K = np.rint(lo * inv + 0.5)
-        assert np.abs(lo * inv + 0.5 - K).max() < 1e-3 and gi[31] == int(K[0] + gi[17] * (K[1] + gi[18] * K[2]))
+        assert np.abs(lo * inv + 0.5 - K).max() < 1e-3 and h['k_lin'] == int(K[0] + dims[0] * (K[1] + dims[1] * K[2]))
         bad = buf.copy()
-        bad.view(np.int32)[31] += 1
+        G.header(bad)['k_lin'] += 1
         with pytest.raises(_lib.MPBError):
             _lib.geom_check(bad)
     far = np.array([[1.0e6, -1.0e6, 3.0e5, 0.1]], np.float32)
     buf = G.pack_geometry(robot, G.CollisionField(spheres=far, margin=0.03))
-    assert buf.view(np.int32)[26] == 0 and not (_lib.geom_flags(buf) & 0x100)
+    assert G.header(buf)['n_cells'] == 0 and not (_lib.geom_flags(buf) & G.GEOM_FLAG_ALL_GRIDS)
     _lib.geom_check(buf)
 
 
@@ -657,47 +667,48 @@ def _big_scene(seed=0, n_sph=200, n_box=32):
 def test_list_grid_pack_check_flags_and_candidate_sets():
     """Geometry version 7 (round 6): a field with more than 63 obstacle spheres carries a LIST grid -- any number of candidates per
     cell, boxes culled like spheres.  pack_geometry builds it, mpb_geom_check accepts it (and refuses forged ranges), mpb_geom_flags
-    reports bit 13 (and not bit 8: the compact-grid kernels must not take it), the persistent launcher takes it up to H = 64; and the
+    reports ALL_LISTS (and not ALL_GRIDS: the compact-grid kernels must not take it), the persistent launcher takes it up to H = 64; and the
     candidate sets are CONSERVATIVE: for random query points every sphere / box within (margin + largest collision sphere) of the
     point is listed in the point's cell, found the way the kernels find it (cell = round(x / h) - K on the lattice)."""
     from motion_planning_baselines_amd import geometry as G, _lib
     robot, field = G.RobotPanda(), _big_scene()
     buf = G.pack_geometry(robot, field)
-    gi = buf.view(np.int32)
-    assert gi[1] == G.GEOM_VERSION_LIST and gi[6] == 200 and gi[7] == 32
+    h = G.header(buf)
+    assert h['version'] == G.GEOM_VERSION_LIST and h['n_sph'] == 200 and h['n_box'] == 32
     _lib.geom_check(buf)
     fl = _lib.geom_flags(buf)
-    assert (fl & 0x2000) and not (fl & 0x100) and (fl >> 16) == gi[26]
+    assert (fl & G.GEOM_FLAG_ALL_LISTS) and not (fl & G.GEOM_FLAG_ALL_GRIDS) and (fl >> G.GEOM_FLAG_CELLS_SHIFT) == h['n_cells']
     lib = _lib.lib()
     assert lib.mpb_stomp_run_path(fl, 1 << 30, 128, 32, 64, 14) != 0 and lib.mpb_stomp_run_path(fl, 1 << 30, 128, 32, 48, 7) != 0
     assert lib.mpb_stomp_run_path(fl, 1 << 30, 128, 32, 128, 14) == 0           # two horizon chunks leave no LDS for the tables
     # a compact-grid scene is untouched; two fields: one needs the list grid -> both take it
     small = G.env_spheres_3d()
-    assert G.pack_geometry(robot, small).view(np.int32)[1] == G.GEOM_VERSION
+    assert G.header(G.pack_geometry(robot, small))['version'] == G.GEOM_VERSION
     two = G.pack_geometry(robot, [small, field])
-    assert two.view(np.int32)[1] == G.GEOM_VERSION_LIST and (_lib.geom_flags(two) & 0x2100) == 0x2000
+    assert G.header(two)['version'] == G.GEOM_VERSION_LIST
+    assert (_lib.geom_flags(two) & (G.GEOM_FLAG_ALL_LISTS | G.GEOM_FLAG_ALL_GRIDS)) == G.GEOM_FLAG_ALL_LISTS
     _lib.geom_check(two)
     # forged ranges are refused
-    off_grid, n_cells, total = int(gi[16]), int(gi[26]), int(gi[13])
-    off_cand = off_grid + (n_cells + 1023) // 1024 * 1024
+    off_grid, n_cells, total = int(h['off_grid']), int(h['n_cells']), int(h['total'])
+    off_cand = off_grid + (n_cells + G.GRID_PAD - 1) // G.GRID_PAD * G.GRID_PAD
     bad = buf.copy()
     w = bad.view(np.uint32)
-    i = int(np.argmax((w[off_grid:off_grid + n_cells] >> 15) & 0x7F))
-    w[off_grid + i] = (4 * (total - off_cand) - 1) | (5 << 15)                  # range runs past the candidate bytes
+    i = int(np.argmax(G.list_cell_fields(w[off_grid:off_grid + n_cells])[1]))
+    w[off_grid + i] = (4 * (total - off_cand) - 1) | (5 << G.LIST_NSPH_SHIFT)   # range runs past the candidate bytes
     with pytest.raises(_lib.MPBError):
         _lib.geom_check(bad)
     bad = buf.copy()
     bad.view(np.uint8)[4 * off_cand] = 250                                       # a sphere index that does not exist
     w = bad.view(np.uint32)
-    w[off_grid] = 0 | (1 << 15)
+    w[off_grid] = 0 | (1 << G.LIST_NSPH_SHIFT)
     with pytest.raises(_lib.MPBError):
         _lib.geom_check(bad)
     # ---- conservative candidate sets
     fs, rs = field.spec(), robot.spec()
     a_max = float(fs['margin']) + float(np.max(rs['link_radius']))
-    inv = buf[23:26].astype(np.float64)
-    dims = gi[17:20].astype(np.int64)
-    lo = buf[20:23].astype(np.float64)
+    inv = h['grid_inv'].astype(np.float64)
+    dims = h['grid_dims'].astype(np.int64)
+    lo = h['grid_lo'].astype(np.float64)
     K = np.rint(lo * inv + 0.5).astype(np.int64)
     words = buf.view(np.uint32)[off_grid:off_grid + n_cells]
     cand = buf.view(np.uint8)[4 * off_cand:]
@@ -714,10 +725,9 @@ def test_list_grid_pack_check_flags_and_candidate_sets():
         if np.any(cell < 0) or np.any(cell >= dims):
             assert not near_s and not near_b, 'a point outside the grid must be beyond every threshold'
             continue
-        wd = int(words[cell[0] + dims[0] * (cell[1] + dims[1] * cell[2])])
-        if wd & 0x80000000:
+        st, ns, nb, overflows = G.list_cell_fields(words[cell[0] + dims[0] * (cell[1] + dims[1] * cell[2])])
+        if overflows:
             continue
-        st, ns, nb = wd & 0x7FFF, (wd >> 15) & 0x7F, (wd >> 22) & 0x3F
         assert near_s <= set(cand[st:st + ns].tolist()), (p, near_s)
         assert near_b <= set(cand[st + ns:st + ns + nb].tolist()), (p, near_b)
         checked += bool(near_s or near_b)
@@ -737,8 +747,96 @@ def test_scene_far_from_the_origin_packs_and_checks(offset_m):
     field = G.CollisionField(spheres=sph, margin=base.margin)
     buf = G.pack_geometry(G.RobotPanda(), field)
     _lib.geom_check(buf)                                   # must not raise
-    n_cells = int(buf.view(np.int32)[26])
+    n_cells = int(G.header(buf)['n_cells'])
     if offset_m <= 5000.0:
-        assert n_cells > 0 and (_lib.geom_flags(buf) & 0x100)
+        assert n_cells > 0 and (_lib.geom_flags(buf) & G.GEOM_FLAG_ALL_GRIDS)
     else:
-        assert n_cells == 0 and not (_lib.geom_flags(buf) & 0x100)      # too far for the fp32 cell index: the exhaustive evaluators serve it
+        assert n_cells == 0 and not (_lib.geom_flags(buf) & G.GEOM_FLAG_ALL_GRIDS)      # too far for the fp32 cell index: the exhaustive evaluators serve it
+
+
+def test_geometry_layout_header_is_generated_from_geometry():
+    """include/mpb_geom_layout.h (header word indices, limits, versions, kinds, cell-word fields, geom_flags: what the C side compiles
+    in) is exactly what model_gen emits from the table in geometry.py."""
+    from motion_planning_baselines_amd import model_gen
+    assert model_gen.LAYOUT_HEADER == os.path.join(ROOT, 'include', 'mpb_geom_layout.h')
+    assert open(model_gen.LAYOUT_HEADER).read() == model_gen.layout_header_text()
+    assert not model_gen.stale_headers()
+
+
+def test_geometry_header_table_is_32_distinct_words():
+    from motion_planning_baselines_amd import geometry as G
+    names = [name for name, _, _ in G.HEADER_WORDS]
+    assert sum(n for _, _, n in G.HEADER_WORDS) == 32 == G.GEOM_HEADER_WORDS
+    assert G.HEADER_DTYPE.itemsize == 128 and len(set(names)) == len(names) and tuple(names) == G.HEADER_DTYPE.names
+    assert {typ for _, typ, _ in G.HEADER_WORDS} <= {'i4', 'u4', 'f4'}
+    # the record is a view: writes by name land in the buffer's own words, at the field's offset
+    buf = np.zeros(100, np.float32)
+    G.header(buf, 40)['n_sph'] = 9
+    G.header(buf, 40)['grid_inv'] = [1.0, 2.0, 3.0]
+    assert buf.view(np.int32)[46] == 9 and list(buf[63:66]) == [1.0, 2.0, 3.0] and np.count_nonzero(buf) == 4
+
+
+def test_geometry_layout_public_numbers_are_pinned():
+    """The packed-geometry layout has ONE definition (the table in geometry.py, emitted as include/mpb_geom_layout.h): these literals
+    -- the only ones outside that header -- keep an edit of the table from renumbering the ABI unnoticed."""
+    from motion_planning_baselines_amd import geometry as G, model_gen
+    words = ['magic', 'version', 'kind', 'n_dof', 'n_tf', 'n_links', 'n_sph', 'n_box', 'margin', 'off_tf', 'off_links', 'off_sph', 'off_box',
+             'total', 'off_cull', 'off_fs', 'off_grid', 'grid_dims', 'grid_dims', 'grid_dims', 'grid_lo', 'grid_lo', 'grid_lo', 'grid_inv',
+             'grid_inv', 'grid_inv', 'n_cells', 'next', 'fscale', 'model', 'keep_mask', 'k_lin']
+    assert [name for name, _, n in G.HEADER_WORDS for _ in range(n)] == words
+    assert [G.HEADER_DTYPE.fields[name][1] // 4 for name in words] == [words.index(name) for name in words]
+    floats = {'margin', 'grid_lo', 'grid_inv', 'fscale'}
+    assert {name: typ for name, typ, _ in G.HEADER_WORDS} == {name: 'f4' if name in floats else 'u4' if name == 'keep_mask' else 'i4'
+                                                               for name in words}
+    assert (G.GEOM_FLAG_MODEL_MASK, G.GEOM_FLAG_ALL_GRIDS, G.GEOM_FLAG_POINT_SMALL, G.GEOM_FLAG_POINT, G.GEOM_FLAG_ONE_FIELD,
+            G.GEOM_FLAG_ALL_LISTS, G.GEOM_FLAG_CELLS_SHIFT, G.GEOM_FLAG_CELLS_MASK) == (0xFF, 0x100, 0x200, 0x400, 0x1000, 0x2000, 16, 0x1FFF)
+    assert (G.GEOM_MAGIC, G.GEOM_VERSION, G.GEOM_VERSION_LIST, G.KIND_POINT, G.KIND_CHAIN) == (0x4D504247, 6, 7, 0, 1)
+    assert (G.MAX_FIELDS, G.MAX_DOF, G.GEOM_HEADER_WORDS) == (4, 12, 32)
+    assert (G.GRID_MAX_CELLS, G.GRID_PAD, G.GRID_MAX_SPH) == (4096, 1024, 63)
+    assert (G.LIST_MAX_SPH, G.LIST_MAX_BOX, G.LIST_MAX_CAND, G.LIST_CELL_MAX_SPH, G.LIST_CELL_MAX_BOX) == (255, 127, 16384, 126, 62)
+    assert (G.GRID_SLOTS, G.GRID_SLOT_BITS, G.GRID_SLOT_MASK, G.GRID_OVERFLOW) == (4, 8, 0xFF, 0xFFFFFFFE)
+    assert (G.LIST_START_MASK, G.LIST_NSPH_SHIFT, G.LIST_NSPH_MASK, G.LIST_NBOX_SHIFT, G.LIST_NBOX_MASK) == ((1 << 15) - 1, 15, (1 << 7) - 1, 22, (1 << 6) - 1)
+    assert (G.LIST_OVERFLOW, G.LIST_RESERVED) == (1 << 31, 0b111 << 28)
+    # ... and the C side gets those very numbers
+    hdr = model_gen.layout_header_text()
+    for i, name in enumerate(words):
+        if words.index(name) == i:
+            assert re.search(r'^    MPB_GW_%s = %d,$' % (name.upper(), i), hdr, flags=re.M), name
+    for line in ('#define MPB_GEOM_FLAG_ALL_LISTS 0x2000', '#define MPB_GEOM_FLAG_CELLS_MASK 0x1FFF', '#define MPB_GRID_OVERFLOW 0xFFFFFFFEu',
+                 '#define MPB_LIST_RESERVED 0x70000000u', '#define MPB_GRID_MAX_SPH 63', '#define MPB_MAX_DOF 12', '#define MPB_GEOM_VERSION_LIST 7'):
+        assert line in hdr.splitlines(), line
+
+
+def test_list_grid_cell_words_round_trip_by_name():
+    """Every cell word of the packed crowded scene, decoded with the named fields, gives back the candidate set build_list_grid made for
+    the cell; mpb_geom_check accepts the buffer and refuses it once one reserved bit of a cell word is set."""
+    from motion_planning_baselines_amd import geometry as G, _lib
+    robot, field = G.RobotPanda(), _big_scene()
+    buf = G.pack_geometry(robot, field)
+    h = G.header(buf)
+    fs, rs = field.spec(), robot.spec()
+    grid = G.build_list_grid(fs['spheres'].reshape(-1, 4), fs['boxes'].reshape(-1, 6), float(fs['margin']) + float(np.max(rs['link_radius'])))
+    n_cells, off_grid = int(h['n_cells']), int(h['off_grid'])
+    assert h['version'] == G.GEOM_VERSION_LIST and n_cells == grid['words'].size and list(h['grid_dims']) == list(grid['dims'])
+    off_cand = off_grid + (n_cells + G.GRID_PAD - 1) // G.GRID_PAD * G.GRID_PAD
+    words = buf.view(np.uint32)[off_grid:off_grid + n_cells]
+    cand = buf.view(np.uint8)[4 * off_cand:4 * int(h['total'])]
+    assert np.array_equal(words, grid['words']) and np.array_equal(cand, grid['cand'])
+    assert not (words & G.LIST_RESERVED).any()
+    # the sets the builder lists per cell, recomputed the way it defines them: spheres, then boxes, each in ascending index order,
+    # ranges back to back from byte 0
+    start, n_sph, n_box, overflows = G.list_cell_fields(words)
+    assert not overflows.any() and n_sph.max() <= G.LIST_CELL_MAX_SPH and n_box.max() <= G.LIST_CELL_MAX_BOX
+    ends = np.cumsum(n_sph.astype(np.int64) + n_box)
+    assert np.array_equal(start, ends - n_sph - n_box) and ends[-1] == grid['stats']['cand_bytes'] <= cand.size
+    assert int(n_sph.max()) == grid['stats']['max_sph'] and int(n_box.max()) == grid['stats']['max_box']
+    for i in range(n_cells):
+        s, b = cand[start[i]:start[i] + n_sph[i]], cand[start[i] + n_sph[i]:start[i] + n_sph[i] + n_box[i]]
+        assert (np.diff(s.astype(np.int64)) > 0).all() and (np.diff(b.astype(np.int64)) > 0).all()
+        assert (s < h['n_sph']).all() and (b < h['n_box']).all()
+    _lib.geom_check(buf)
+    reserved_bit = G.LIST_RESERVED & -G.LIST_RESERVED
+    bad = buf.copy()
+    bad.view(np.uint32)[off_grid + n_cells // 2] |= reserved_bit
+    with pytest.raises(_lib.MPBError, match='list-grid cell out of range'):
+        _lib.geom_check(bad)
