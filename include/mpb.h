@@ -58,7 +58,8 @@ extern "C" {
  *                        geometry buffers of version 7 (LIST broad-phase grid, per field) are accepted next to version 6;
  *                        MPB_MAX_DOF 8 -> 12; mpb_gpmp2_solve takes the low-rank form wherever n_fields (H - 1) <= 127 (same
  *                        results to the solver's fp64 rounding);
- *           7            batched RRT-Connect (mpb_rrt_connect_*) and mpb_collision_check added; nothing else changed. */
+ *           7            batched RRT-Connect (mpb_rrt_connect_*) and mpb_collision_check added; nothing else changed.  ABI 7 now
+ *                        also carries batched RRT* / informed RRT* (mpb_rrt_star_*): additive, no existing signature moved. */
 #define MPB_ABI_VERSION 7
 #define MPB_VERSION_TUNING_BUILD 0x40000000
 int mpb_version(void);
@@ -587,6 +588,70 @@ int mpb_rrt_connect_run(void *workspace, size_t workspace_bytes, const float *ge
                         int *lengths, int *status, int B, int max_nodes, int n_pre, int D, int Lmax, int iter0,
                         int n_iters, int total_iters, float step_size, float n_radius, uint64_t seed,
                         uint32_t problem_offset, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Batched RRT* and informed RRT* -- replaces RRTStar._run_optimization (rrt_star.py:133-261) with OptimalNode's cost
+ * bookkeeping (:16-61), RRTBase.get_pre_sample / remove_last_pre_sample / get_nearest_node (rrt_base.py:59-63, :94-98,
+ * :115-119), extend_path, safe_path and purge_duplicates_from_traj (utils.py:4-50), for B independent problems at once.
+ * One persistent launch, one single-wave workgroup per problem; workgroups never wait on each other.  Only the radius
+ * neighbourhood (n_knn == 0) is served.
+ *
+ * workspace: mpb_rrt_star_workspace_bytes(B, max_nodes, n_pre, D) bytes, 16-byte aligned (0 = shape refused, see
+ *   mpb_last_error).  Layout in 32-bit words: 16 words (magic, B, max_nodes, n_pre, D, Dp = D rounded up to 4);
+ *   B x 32 words per problem: 0 status, 1 loop bodies started (the reference's final `iteration` + 1), 2 node count,
+ *   3 goal node index (-1: none), 4 pool length, 5 stop_reason (MPB_RRT_STOP_*), 6 best_cost_iters,
+ *   7 iters_after_first_success, 8 best_cost_eps (fp32 bits; 3e38 before the first success), 9 accepted rewires,
+ *   10 informed rejections, 11 goal cost at the first success (fp32 bits), 12 iteration of the first success (-1: none),
+ *   13 node count at the first success (nodes from this index on were created after the goal node);
+ *   goal configurations (B, Dp) fp32; ONE tree per problem, rooted at the start: node configurations (B, max_nodes, Dp)
+ *   fp32, zero padded; parents (B, max_nodes) int32 (-1: root; after a rewire a parent may follow its child); d
+ *   (B, max_nodes) fp32, the length of the edge to the parent; cost (B, max_nodes) fp32 with
+ *   cost[i] == fl32(cost[parent[i]] + d[i]) bitwise, root 0; neighbour scratch (B, 3, max_nodes) (rewire candidates of
+ *   the current iteration: index, d, edge verdict); pool lists (B, (n_pre + 1) / 2) words of two uint16 indices.
+ * mpb_rrt_star_init: root, goal, counters, the full pool list 0 .. n_pre - 1, and the start / goal collision check
+ *   (rrt_star.py:143-144: status START_OR_GOAL_IN_COLLISION, no path).  start, goal (B,D).
+ * mpb_rrt_star_run: loop bodies iter0 .. min(iter0 + n_iters, total_iters) - 1 of every problem still RUNNING, resumed
+ *   from the workspace (call in chunks with iter0 advancing; total_iters = the reference's n_iters + 1).  Per body, in
+ *   the reference's order: (:167-168) best_cost_iters >= max_best_cost_iters stops (COST_CONVERGED); (:169-174) with a
+ *   goal node, goal cost < best_cost_eps - cost_eps (fp32) resets best_cost_iters, else counts it; (:176-182)
+ *   iters_after_first_success > n_iters_after_success stops (AFTER_SUCCESS; n_iters_after_success < 0 = None);
+ *   (:185) goal draw iff no goal node exists and (iteration == 0 or uniform < goal_prob), else a pool entry;
+ *   (:197-199) informed != 0 and a goal node exists and d(start, s) + d(s, goal) >= goal cost: the entry is deleted,
+ *   the body ends; (:202-208) nearest node, extend_path, safe_path as in mpb_rrt_connect_run; (:210-211) a sample the
+ *   extension reached (allclose) is deleted; (:213-222) the new node with d and cost, the goal node iff this was a goal
+ *   draw and d(new, goal) < eps; (:225-251) every node within n_radius whose cost the new node lowers and whose edge
+ *   from the new node is free up to eps is rewired in index order, the costs of its subtree following before the next
+ *   neighbour is tested.
+ *   pre_samples, pre_stride as in mpb_rrt_connect_run.  sample_idx, goal_draw: both NULL -> one Philox4x32-10 call per
+ *   (problem, iteration) (counter = (problem_offset + b, iteration, tag, 0), key = seed): .x gives the pool index by
+ *   mulhi with the pool length, the top 24 bits of .y the uniform compared with goal_prob in fp32; else both
+ *   (B, total_iters) int32: goal_draw 1 = goal, 0 = sample (iteration 0 always aims at the goal; ignored once a goal
+ *   node exists), sample_idx the recorded torch.randperm(len(pool))[0], clamped, ignored where the goal is drawn.
+ *   At the end of EVERY launch a problem that has a goal node gets its current retrace root -> goal through
+ *   purge_duplicates_from_traj in paths (B,Lmax,D) / lengths (B) and the goal's cost in costs (B), so a run cut between
+ *   chunks still returns its best path.  status (B): copy of the status words: FOUND iff a goal node exists when the
+ *   problem stops (why it stopped: stop_reason), else EXHAUSTED_ITERS (also for the two early stops without a goal
+ *   node), POOL_EMPTY (a sample was needed from an empty list), TREE_FULL (max_nodes >= total_iters + 1 cannot),
+ *   PATH_TOO_LONG (the un-purged retrace has more than Lmax nodes; lengths 0).
+ * Refusals: n_pre > MPB_RRT_MAX_PRE_SAMPLES, D > MPB_MAX_DOF, B x max_nodes beyond 32-bit indexing: MPB_E_UNSUPPORTED;
+ *   null pointers (sample_idx / goal_draw given one without the other included), misaligned workspace / geom, a short
+ *   workspace, Lmax < 2, a bad iteration range, non-positive step_size / n_radius: MPB_E_INVALID.
+ * ------------------------------------------------------------------------------------------- */
+#define MPB_RRT_STOP_RUNNING 0
+#define MPB_RRT_STOP_ITERS 1          /* the n_iters + 1 loop bodies are used up */
+#define MPB_RRT_STOP_COST_CONVERGED 2 /* best_cost_iters >= max_best_cost_iters */
+#define MPB_RRT_STOP_AFTER_SUCCESS 3  /* iters_after_first_success > n_iters_after_success */
+#define MPB_RRT_STOP_TREE_FULL 4      /* a FOUND problem whose tree reached max_nodes */
+#define MPB_RRT_STOP_POOL_EMPTY 5     /* a FOUND problem whose pool list ran empty */
+size_t mpb_rrt_star_workspace_bytes(int B, int max_nodes, int n_pre, int D);
+int mpb_rrt_star_init(void *workspace, size_t workspace_bytes, const float *start, const float *goal,
+                      const float *geom, int geom_flags, int B, int max_nodes, int n_pre, int D, void *stream);
+int mpb_rrt_star_run(void *workspace, size_t workspace_bytes, const float *geom, int geom_flags,
+                     const float *pre_samples, size_t pre_stride, const int *sample_idx, const int *goal_draw,
+                     float *paths, int *lengths, float *costs, int *status, int B, int max_nodes, int n_pre, int D,
+                     int Lmax, int iter0, int n_iters, int total_iters, int max_best_cost_iters,
+                     int n_iters_after_success, int informed, float step_size, float n_radius, float goal_prob,
+                     float cost_eps, float eps, uint64_t seed, uint32_t problem_offset, void *stream);
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,117 @@
+// mpb_rrt.h -- the pieces the sample-based planner kernels share (mpb_rrt_connect.hip, mpb_rrt_star.hip): the collision
+// cost of one configuration per lane, torch.allclose, extend_path's linspace point (utils.py:4-14), safe_path's scan for
+// the first point in collision (utils.py:17-30), purge_duplicates_from_traj (utils.py:33-50) and the order-preserving
+// deletion of a pool entry (rrt_base.py:59-63).  Every function is block-uniform: all 64 lanes of the single-wave
+// workgroup call it.
+#pragma once
+#include "mpb_common.h"
+#include "mpb_geom.h"
+#include "mpb_model_panda.h"
+
+#define RRT_MAX_PRE 16384
+#define RRT_MAX_PTS (1 << 20)    // points of one extension (dist / step_size + 2): far beyond any sane step size
+
+// Collision cost of one configuration per lane, chained fields in turn.  Block-uniform control flow: every thread of the
+// block calls it (a lane without work passes any valid configuration).  `staged` is the field whose grid sits in LDS.
+template <int MODEL>
+__device__ __forceinline__ float rrt_config_cost(const float* __restrict__ geom, unsigned* gridw, float4* otab,
+                                                 const float*& staged, const float (&q)[MPB_MAX_DOF]) {
+    float c = 0.f;
+    for (const float* gp = geom; gp != nullptr; gp = geom_next(gp)) {
+        const GeomView G = geom_view(gp);
+        if (grid_usable(G)) {
+            if (staged != gp) {
+                __syncthreads();
+                grid_stage(G, gridw, otab, threadIdx.x, blockDim.x);
+                __syncthreads();
+                staged = gp;
+            }
+            if (MODEL == PandaModel::ID && G.model == PandaModel::ID)
+                c = fmaf(G.fscale, waypoint_cost_grid_model<PandaModel>(G, gridw, otab, q), c);
+            else
+                c = fmaf(G.fscale, waypoint_cost_grid(G, gridw, otab, q), c);
+        } else {
+            float dq[MPB_MAX_DOF];
+            c = fmaf(G.fscale, waypoint_cost<false>(G, q, dq), c);
+        }
+    }
+    return c;
+}
+
+// torch.allclose(a, b) element: |a - b| <= atol + rtol |b| with the defaults rtol 1e-5, atol 1e-8
+__device__ __forceinline__ bool rrt_close(float a, float b) { return fabsf(a - b) <= 1e-8f + 1e-5f * fabsf(b); }
+
+// point p of  q1 + dl * linspace(0, 1, n_pts)  as ATen's CPU kernel evaluates the linspace (from the near end of each
+// half); lstep = 1 / (n_pts - 1)
+template <int DM>
+__device__ __forceinline__ void rrt_linspace_point(const float (&q1)[MPB_MAX_DOF], const float (&dl)[MPB_MAX_DOF], int n_pts,
+                                                   float lstep, int p, float (&q)[MPB_MAX_DOF]) {
+    const float al = (p < n_pts / 2) ? __fmul_rn(lstep, (float)p) : __fsub_rn(1.0f, __fmul_rn(lstep, (float)(n_pts - 1 - p)));
+#pragma unroll
+    for (int k = 0; k < MPB_MAX_DOF; ++k) q[k] = (k < DM) ? __fadd_rn(q1[k], __fmul_rn(dl[k], al)) : 0.f;
+}
+
+// safe_path's scan: the index of the first of the n_pts points of an extension that is in collision, -1 when none is;
+// one lane per point, 64 points per trip, and the trips after the first hit are never evaluated
+template <int DM, int MODEL>
+__device__ __forceinline__ int rrt_first_collision(const float* __restrict__ geom, unsigned* gridw, float4* otab,
+                                                   const float*& staged, const float (&q1)[MPB_MAX_DOF],
+                                                   const float (&dl)[MPB_MAX_DOF], int n_pts, float lstep, int lane) {
+    for (int base = 0; base < n_pts; base += 64) {
+        const int p = base + lane;
+        float q[MPB_MAX_DOF];
+        rrt_linspace_point<DM>(q1, dl, n_pts, lstep, min(p, n_pts - 1), q);
+        const float c = rrt_config_cost<MODEL>(geom, gridw, otab, staged, q);
+        const unsigned long long m = __ballot(p < n_pts && c > 0.f);
+        if (m != 0ull) return base + (int)__builtin_ctzll(m);
+    }
+    return -1;
+}
+
+// rrt_base.py:59-63: delete entry idx of the LDS pool list of plen entries, keeping the order (a parallel shift)
+__device__ __forceinline__ void rrt_pool_delete(unsigned short* pool, int idx, int plen, int lane) {
+    for (int base = idx; base < plen - 1; base += 64) {
+        const int i = base + lane;
+        const unsigned short v = pool[min(i + 1, plen - 1)];
+        __syncthreads();
+        if (i < plen - 1) pool[i] = v;
+        __syncthreads();
+    }
+}
+
+// purge_duplicates_from_traj (utils.py:33-50) in place on the Lraw rows of path_b (row-major, D columns; lane k owns
+// column k): returns the number of rows kept
+__device__ __forceinline__ int rrt_purge(float* path_b, int Lraw, int D, int lane) {
+    if (Lraw <= 2) return Lraw;
+    const bool on = lane < D;
+    const float row0 = on ? path_b[lane] : 0.f;
+    const float last = on ? path_b[(size_t)(Lraw - 1) * D + lane] : 0.f;
+    float cur = row0, lastsel = row0;
+    int out = 0;
+    bool any_sel = false;
+    for (int j = 0; j + 1 < Lraw; ++j) {
+        const float nxt = on ? path_b[(size_t)(j + 1) * D + lane] : 0.f;
+        if (__ballot(on && fabsf(nxt - cur) > 1e-6f) != 0ull) {   // row j differs from row j + 1: selected
+            if (!any_sel) {
+                any_sel = true;
+                if (j > 0 && __ballot(on && !rrt_close(cur, row0)) != 0ull) {
+                    if (on) path_b[(size_t)out * D + lane] = row0;
+                    ++out;
+                }
+            }
+            if (on) path_b[(size_t)out * D + lane] = cur;
+            ++out;
+            lastsel = cur;
+        }
+        cur = nxt;
+    }
+    if (!any_sel) {                                 // (every row equals its successor: the first row stands for all)
+        if (on) path_b[lane] = row0;
+        out = 1;
+    }
+    if (__ballot(on && !rrt_close(lastsel, last)) != 0ull) {
+        if (on) path_b[(size_t)out * D + lane] = last;
+        ++out;
+    }
+    return out;
+}

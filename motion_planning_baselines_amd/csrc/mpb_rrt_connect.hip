@@ -22,14 +22,11 @@
 // allows, the exhaustive walk otherwise; chained fields in turn).
 #include "mpb_common.h"
 #include "mpb_host.h"
-#include "mpb_geom.h"
-#include "mpb_model_panda.h"
+#include "mpb_rrt.h"
 
 #define RRT_MAGIC 0x52525443
 #define RRT_GLOBAL_WORDS 16      // workspace header: magic, B, max_nodes, n_pre, D, Dp
 #define RRT_HDR_WORDS 16         // per problem: status, iterations used, count 0, count 1, swap bit, pool length
-#define RRT_MAX_PRE 16384
-#define RRT_MAX_PTS (1 << 20)    // points of one extension (dist / step_size + 2): far beyond any sane step size
 
 struct RrtLayout {
     size_t hdr, nodes, parents, pool, total;   // offsets in 32-bit words
@@ -47,36 +44,6 @@ __host__ __device__ static inline RrtLayout rrt_layout(int B, int max_nodes, int
     L.total = L.pool + (size_t)B * L.pool_words;
     return L;
 }
-
-// Collision cost of one configuration per lane, chained fields in turn.  Block-uniform control flow: every thread of the
-// block calls it (a lane without work passes any valid configuration).  `staged` is the field whose grid sits in LDS.
-template <int MODEL>
-__device__ __forceinline__ float rrt_config_cost(const float* __restrict__ geom, unsigned* gridw, float4* otab,
-                                                 const float*& staged, const float (&q)[MPB_MAX_DOF]) {
-    float c = 0.f;
-    for (const float* gp = geom; gp != nullptr; gp = geom_next(gp)) {
-        const GeomView G = geom_view(gp);
-        if (grid_usable(G)) {
-            if (staged != gp) {
-                __syncthreads();
-                grid_stage(G, gridw, otab, threadIdx.x, blockDim.x);
-                __syncthreads();
-                staged = gp;
-            }
-            if (MODEL == PandaModel::ID && G.model == PandaModel::ID)
-                c = fmaf(G.fscale, waypoint_cost_grid_model<PandaModel>(G, gridw, otab, q), c);
-            else
-                c = fmaf(G.fscale, waypoint_cost_grid(G, gridw, otab, q), c);
-        } else {
-            float dq[MPB_MAX_DOF];
-            c = fmaf(G.fscale, waypoint_cost<false>(G, q, dq), c);
-        }
-    }
-    return c;
-}
-
-// torch.allclose(a, b) element: |a - b| <= atol + rtol |b| with the defaults rtol 1e-5, atol 1e-8
-__device__ __forceinline__ bool rrt_close(float a, float b) { return fabsf(a - b) <= 1e-8f + 1e-5f * fabsf(b); }
 
 // ---- stand-alone predicate: N configurations (N, D) -> flag (N) [and the hinge sum] --------------------------------
 template <int MODEL>
@@ -231,26 +198,9 @@ __global__ __launch_bounds__(64) void rrt_connect_kernel(const RrtArgs a) {
         const float cntf = fminf(dist / a.step, (float)(RRT_MAX_PTS - 2));
         const int n_pts = (int)cntf + 2;
         const float lstep = 1.0f / (float)(n_pts - 1);
-        // linspace(0, 1, n_pts)[p] as ATen's CPU kernel evaluates it (from the near end of each half)
-        auto point = [&](int p, float (&q)[MPB_MAX_DOF]) {
-            const float al = (p < n_pts / 2) ? __fmul_rn(lstep, (float)p) : __fsub_rn(1.0f, __fmul_rn(lstep, (float)(n_pts - 1 - p)));
-#pragma unroll
-            for (int k = 0; k < MPB_MAX_DOF; ++k) q[k] = (k < DM) ? __fadd_rn(q1[k], __fmul_rn(dl[k], al)) : 0.f;
-        };
-        int first = -1;
-        for (int base = 0; base < n_pts; base += 64) {
-            const int p = base + lane;
-            float q[MPB_MAX_DOF];
-            point(min(p, n_pts - 1), q);
-            const float c = rrt_config_cost<MODEL>(a.geom, gridw, otab, staged, q);
-            const unsigned long long m = __ballot(p < n_pts && c > 0.f);
-            if (m != 0ull) {
-                first = base + (int)__builtin_ctzll(m);
-                break;
-            }
-        }
+        const int first = rrt_first_collision<DM, MODEL>(a.geom, gridw, otab, staged, q1, dl, n_pts, lstep, lane);
         if (first == 0) return false;
-        point(first < 0 ? n_pts - 1 : first - 1, nq);
+        rrt_linspace_point<DM>(q1, dl, n_pts, lstep, first < 0 ? n_pts - 1 : first - 1, nq);
         if (n >= a.max_nodes) {
             status = MPB_RRT_TREE_FULL;
             return false;
@@ -294,13 +244,7 @@ __global__ __launch_bounds__(64) void rrt_connect_kernel(const RrtArgs a) {
             if (k < DM && k < D) reached = reached && rrt_close(n1[k], tq[k]);
         }
         if (reached) {                                     // :149-150, rrt_base.py:59-63: delete entry idx, keep the order
-            for (int base = idx; base < plen - 1; base += 64) {
-                const int i = base + lane;
-                const unsigned short v = pool[min(i + 1, plen - 1)];
-                __syncthreads();
-                if (i < plen - 1) pool[i] = v;
-                __syncthreads();
-            }
+            rrt_pool_delete(pool, idx, plen, lane);
             --plen;
         }
         if (!extend(t2, n1)) continue;                     // :161-162
@@ -330,40 +274,7 @@ __global__ __launch_bounds__(64) void rrt_connect_kernel(const RrtArgs a) {
                 if (lane < D) path_b[(size_t)pos * D + lane] = ndB[(size_t)j * L.Dp + lane];
         }
         __syncthreads();
-        int len = Lraw;
-        if (Lraw > 2) {
-            const bool on = lane < D;
-            const float row0 = on ? path_b[lane] : 0.f;
-            const float last = on ? path_b[(size_t)(Lraw - 1) * D + lane] : 0.f;
-            float cur = row0, lastsel = row0;
-            int out = 0;
-            bool any_sel = false;
-            for (int j = 0; j + 1 < Lraw; ++j) {
-                const float nxt = on ? path_b[(size_t)(j + 1) * D + lane] : 0.f;
-                if (__ballot(on && fabsf(nxt - cur) > 1e-6f) != 0ull) {   // row j differs from row j + 1: selected
-                    if (!any_sel) {
-                        any_sel = true;
-                        if (j > 0 && __ballot(on && !rrt_close(cur, row0)) != 0ull) {
-                            if (on) path_b[(size_t)out * D + lane] = row0;
-                            ++out;
-                        }
-                    }
-                    if (on) path_b[(size_t)out * D + lane] = cur;
-                    ++out;
-                    lastsel = cur;
-                }
-                cur = nxt;
-            }
-            if (!any_sel) {                                 // (every row equals its successor: the first row stands for all)
-                if (on) path_b[lane] = row0;
-                out = 1;
-            }
-            if (__ballot(on && !rrt_close(lastsel, last)) != 0ull) {
-                if (on) path_b[(size_t)out * D + lane] = last;
-                ++out;
-            }
-            len = out;
-        }
+        const int len = rrt_purge(path_b, Lraw, D, lane);
         if (lane == 0) a.lengths[b] = len;
         status = MPB_RRT_FOUND;
         break;

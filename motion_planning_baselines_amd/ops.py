@@ -1089,3 +1089,98 @@ def rrt_connect_trees(ws):
     pool = torch.stack((pool & 0xFFFF, (pool >> 16) & 0xFFFF), dim=-1).reshape(B, 2 * pw)[:, :ws.n_pre]
     return dict(nodes=nodes, parents=parents, counts=hdr[:, 2:4], iters=hdr[:, 1], status=hdr[:, 0], swap=hdr[:, 4],
                 pool_len=hdr[:, 5], pool=pool)
+
+
+# ---- batched RRT* / informed RRT* (csrc/mpb_rrt_star.hip) ----------------------------------------------------------------
+RRT_STOP_RUNNING, RRT_STOP_ITERS, RRT_STOP_COST_CONVERGED, RRT_STOP_AFTER_SUCCESS, RRT_STOP_TREE_FULL, \
+    RRT_STOP_POOL_EMPTY = range(6)                                # include/mpb.h MPB_RRT_STOP_*
+RRT_STOP_NAMES = ('RUNNING', 'ITERS', 'COST_CONVERGED', 'AFTER_SUCCESS', 'TREE_FULL', 'POOL_EMPTY')
+
+
+class RRTStarWorkspace:
+    """The caller-allocated state of a batch of RRT* problems: one tree per problem with parents, d and cost, the
+    neighbour scratch, pool lists and the per-problem header of counters (layout: include/mpb.h)."""
+
+    def __init__(self, B, max_nodes, n_pre, D, device):
+        nbytes = int(_lib.lib().mpb_rrt_star_workspace_bytes(int(B), int(max_nodes), int(n_pre), int(D)))
+        if nbytes == 0:
+            msg = _lib.lib().mpb_last_error()
+            raise _lib.MPBError(f'mpb_rrt_star_workspace_bytes: {msg.decode() if msg else "?"}')
+        self.B, self.max_nodes, self.n_pre, self.D = int(B), int(max_nodes), int(n_pre), int(D)
+        self.nbytes = nbytes
+        self.buf = torch.zeros(nbytes // 4, device=device, dtype=torch.int32)
+
+
+@_on_tensor_device
+def rrt_star_init(ws_buf, ws, start, goal, geom):
+    """Root, goal, counters, pool list and the start / goal collision check of every problem (mpb_rrt_star_init).
+    `ws_buf` is ws.buf (passed so that the launch lands on its device)."""
+    _chk(start, (ws.B, ws.D), 'start')
+    _chk(goal, (ws.B, ws.D), 'goal')
+    if ws.D != geom.n_dof:
+        raise ValueError(f'the problems have {ws.D} columns, the geometry {geom.n_dof} degrees of freedom')
+    _lib.check(_lib.lib().mpb_rrt_star_init(_ptr(ws_buf), ws.nbytes, _ptr(start), _ptr(goal), _ptr(geom.buf), int(geom.flags),
+                                           ws.B, ws.max_nodes, ws.n_pre, ws.D, _stream()), 'mpb_rrt_star_init')
+
+
+@_on_tensor_device
+def rrt_star_run(ws_buf, ws, geom, pre_samples, sample_idx, goal_draw, paths, lengths, costs, status, iter0, n_iters, total_iters,
+                 step_size, n_radius, max_best_cost_iters=1000, n_iters_after_success=None, informed=False, goal_prob=0.1,
+                 cost_eps=1e-2, eps=1e-6, seed=0, problem_offset=0):
+    """Loop bodies iter0 .. min(iter0 + n_iters, total_iters) - 1 of every problem still RUNNING (mpb_rrt_star_run).
+    pre_samples (n_pre, D) shared or (B, n_pre, D); sample_idx and goal_draw both None (device Philox) or both
+    (B, total_iters) int32.  paths / lengths / costs hold the current best path of every problem with a goal node after
+    every call."""
+    B, D = ws.B, ws.D
+    if pre_samples.ndim == 2:
+        _chk(pre_samples, (ws.n_pre, D), 'pre_samples')
+        stride = 0
+    else:
+        _chk(pre_samples, (B, ws.n_pre, D), 'pre_samples')
+        stride = ws.n_pre * D
+    if (sample_idx is None) != (goal_draw is None):
+        raise ValueError('sample_idx and goal_draw are given together or not at all')
+    _chk(sample_idx, (B, total_iters), 'sample_idx', allow_none=True, dtype=torch.int32)
+    _chk(goal_draw, (B, total_iters), 'goal_draw', allow_none=True, dtype=torch.int32)
+    Lmax = paths.shape[1]
+    _chk(paths, (B, Lmax, D), 'paths')
+    _chk(lengths, (B,), 'lengths', dtype=torch.int32)
+    _chk(costs, (B,), 'costs')
+    _chk(status, (B,), 'status', dtype=torch.int32)
+    _lib.check(_lib.lib().mpb_rrt_star_run(
+        _ptr(ws_buf), ws.nbytes, _ptr(geom.buf), int(geom.flags), _ptr(pre_samples), stride, _ptr(sample_idx), _ptr(goal_draw),
+        _ptr(paths), _ptr(lengths), _ptr(costs), _ptr(status), B, ws.max_nodes, ws.n_pre, D, Lmax, int(iter0), int(n_iters),
+        int(total_iters), int(max_best_cost_iters), -1 if n_iters_after_success is None else int(n_iters_after_success),
+        1 if informed else 0, float(step_size), float(n_radius), float(goal_prob), float(cost_eps), float(eps), _seed64(seed),
+        int(problem_offset) & 0xFFFFFFFF, _stream()), 'mpb_rrt_star_run')
+
+
+def rrt_star_tree(ws):
+    """The trees of an RRT* workspace, for tests and rendering: dict of `nodes` (B, max_nodes, D) fp32, `parents`
+    (B, max_nodes) int32 (-1: root), `d`, `cost` (B, max_nodes) fp32, `count`, `goal` (index, -1: none), `status`,
+    `stop_reason`, `iters` (loop bodies started), `pool` (B, n_pre) int32 (entries beyond pool_len are stale), `pool_len`,
+    `rewires`, `informed_rejections`, and the first success: `first_cost`, `first_iter`, `first_count` (all (B,))."""
+    B, M, D = ws.B, ws.max_nodes, ws.D
+    Dp = (D + 3) // 4 * 4
+    w = ws.buf
+    glob = w[:6].tolist()
+    if glob[0] != 0x52525453 or glob[1:5] != [B, M, ws.n_pre, D]:
+        raise ValueError('the workspace was not initialised for these shapes (rrt_star_init)')
+    o = 16
+    hdr = w[o:o + 32 * B].reshape(B, 32)
+    o += 32 * B + B * Dp
+    nodes = w[o:o + B * M * Dp].view(torch.float32).reshape(B, M, Dp)[..., :D]
+    o += B * M * Dp
+    parents = w[o:o + B * M].reshape(B, M)
+    o += B * M
+    d = w[o:o + B * M].view(torch.float32).reshape(B, M)
+    o += B * M
+    cost = w[o:o + B * M].view(torch.float32).reshape(B, M)
+    o += B * M + 3 * B * M
+    pw = (ws.n_pre + 1) // 2
+    pool = w[o:o + B * pw].reshape(B, pw)
+    pool = torch.stack((pool & 0xFFFF, (pool >> 16) & 0xFFFF), dim=-1).reshape(B, 2 * pw)[:, :ws.n_pre]
+    return dict(nodes=nodes, parents=parents, d=d, cost=cost, count=hdr[:, 2], goal=hdr[:, 3], status=hdr[:, 0],
+                stop_reason=hdr[:, 5], iters=hdr[:, 1], pool=pool, pool_len=hdr[:, 4], rewires=hdr[:, 9],
+                informed_rejections=hdr[:, 10], first_cost=hdr[:, 11].view(torch.float32), first_iter=hdr[:, 12],
+                first_count=hdr[:, 13], best_cost_iters=hdr[:, 6], iters_after_first_success=hdr[:, 7])

@@ -1,0 +1,1 @@
+from .rrt_star import InfRRTStar, RRTStar  # noqa: F401

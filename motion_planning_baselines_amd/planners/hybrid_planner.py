@@ -9,13 +9,14 @@ The reference converts the paths with torch_robotics' ``smoothen_trajectory`` / 
 by one launch of mpb_traj_resample (arc-length-uniform linear resampling, average velocity on the interior
 points -- build-defined).
 
-The sample-based half is served by this package: RRTConnect / MultiSampleBasedPlanner (planners/rrt_connect.py,
-planners/multi_sample_based_planner.py) grow all tree pairs in one batched launch on the GPU.  A sample-based planner
+The sample-based half is served by this package: RRTConnect, RRTStar / InfRRTStar and MultiSampleBasedPlanner
+(planners/rrt_connect.py, planners/rrt_star.py, planners/multi_sample_based_planner.py) grow all trees in one batched
+launch sequence on the GPU.  A sample-based planner
 that offers ``optimize_batched() -> (paths (N, Lmax, D), lengths (N,), status (N,))`` device tensors is fed straight
 into mpb_traj_resample -- no host round trip, no padding loop; a problem without a path gets the straight line
 start -> goal, written on the device (hybrid_planner.py:47-51).  Any other sample-based planner stays the caller's
 (duck-typed: ``optimize(refill_samples_buffer=True, ...) -> list of (n_i, D) tensors or None``, ``start_state_pos``,
-``goal_state_pos``) and takes the list path below.  RRTStar / InfRRTStar (rewiring) are outside this build's scope.
+``goal_state_pos``) and takes the list path below.
 """
 import torch
 

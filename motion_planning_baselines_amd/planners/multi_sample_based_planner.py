@@ -2,7 +2,7 @@
 
 The reference copies the planner n_trajectories times and runs the copies in a forkserver process pool.  Independent
 copies are batch-parallel: here they are the problems of ONE batched launch sequence of the planner's kernel
-(RRTConnect.optimize_batched), copy c drawing its pool indices from a Philox stream of its own.  The pool keyword
+(RRTConnect.optimize_batched, RRTStar.optimize_batched), copy c drawing its pool indices from a Philox stream of its own.  The pool keyword
 arguments of the reference (`optimize_sequentially`, MultiProcessor's) are accepted and ignored.
 """
 from .rrt_connect import paths_to_list
@@ -12,7 +12,7 @@ class MultiSampleBasedPlanner:
 
     def __init__(self, planner, n_trajectories=2, optimize_sequentially=False, **kwargs):
         if not hasattr(planner, 'optimize_batched'):
-            raise TypeError('MultiSampleBasedPlanner needs a planner with optimize_batched (RRTConnect of this package)')
+            raise TypeError('MultiSampleBasedPlanner needs a planner with optimize_batched (RRTConnect, RRTStar or InfRRTStar of this package)')
         self.planner = planner
         self.n_trajectories = int(n_trajectories)
 
