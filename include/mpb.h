@@ -31,6 +31,7 @@
 /* the packed geometry buffer in numbers (generated from geometry.py): header word indices MPB_GW_*, geometry versions, robot
  * kinds, MPB_MAX_DOF / MPB_MAX_FIELDS and the grid limits, the cell-word fields, MPB_GEOM_FLAG_* */
 #include "mpb_geom_layout.h"
+#include "mpb_rrt_layout.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -552,8 +553,11 @@ int mpb_collision_check(const float *q, const float *geom, int geom_flags, unsig
  * over a process pool).  One persistent launch, one workgroup per problem; workgroups never wait on each other.
  *
  * workspace: mpb_rrt_connect_workspace_bytes(B, max_nodes, n_pre, D) bytes, 16-byte aligned (0 = shape refused, see
- *   mpb_last_error).  Layout in 32-bit words: 16 words (magic, B, max_nodes, n_pre, D, Dp = D rounded up to 4);
- *   B x 16 words per problem (status, iterations used, nodes of tree 0, nodes of tree 1, swap bit, pool length);
+ *   mpb_last_error).  The layout in numbers is mpb_rrt_layout.h (generated from rrt_layout.py, the one definition); in
+ *   32-bit words: MPB_RRT_GLOBAL_WORDS words, of which MPB_RRTG_MAGIC (MPB_RRT_CONNECT_MAGIC), _B, _MAX_NODES, _N_PRE,
+ *   _D and _DP (D rounded up to 4) are used; B x MPB_RRT_CONNECT_HDR_WORDS words per problem, of which
+ *   MPB_RRTC_STATUS (MPB_RRT_*), _ITERS (iterations used), _COUNTS (two words: nodes of tree 0, nodes of tree 1), _SWAP
+ *   (the swap bit) and _POOL_LEN are used;
  *   node configurations (B, 2, max_nodes, Dp) fp32, zero padded; parents (B, 2, max_nodes) int32 (-1: root);
  *   pool lists (B, (n_pre + 1) / 2) words of two uint16 indices into pre_samples.  Tree 0 is rooted at the start, tree 1
  *   at the goal; the reference's name swap is the swap bit (`continue` leaves an iteration before the swap-back, so a
@@ -572,14 +576,7 @@ int mpb_collision_check(const float *q, const float *geom, int geom_flags, unsig
  *   takes); PATH_TOO_LONG when the un-purged path has more than Lmax nodes.  status (B): copy of the status words.
  *   A tree that would exceed max_nodes ends with TREE_FULL (max_nodes >= total_iters + 1 cannot).
  * ------------------------------------------------------------------------------------------- */
-#define MPB_RRT_RUNNING 0
-#define MPB_RRT_FOUND 1
-#define MPB_RRT_EXHAUSTED_ITERS 2
-#define MPB_RRT_START_OR_GOAL_IN_COLLISION 3
-#define MPB_RRT_POOL_EMPTY 4
-#define MPB_RRT_TREE_FULL 5
-#define MPB_RRT_PATH_TOO_LONG 6
-#define MPB_RRT_MAX_PRE_SAMPLES 16384
+/* MPB_RRT_* (the status values) and MPB_RRT_MAX_PRE_SAMPLES: mpb_rrt_layout.h */
 size_t mpb_rrt_connect_workspace_bytes(int B, int max_nodes, int n_pre, int D);
 int mpb_rrt_connect_init(void *workspace, size_t workspace_bytes, const float *start, const float *goal,
                          const float *geom, int geom_flags, int B, int max_nodes, int n_pre, int D, void *stream);
@@ -597,12 +594,13 @@ int mpb_rrt_connect_run(void *workspace, size_t workspace_bytes, const float *ge
  * neighbourhood (n_knn == 0) is served.
  *
  * workspace: mpb_rrt_star_workspace_bytes(B, max_nodes, n_pre, D) bytes, 16-byte aligned (0 = shape refused, see
- *   mpb_last_error).  Layout in 32-bit words: 16 words (magic, B, max_nodes, n_pre, D, Dp = D rounded up to 4);
- *   B x 32 words per problem: 0 status, 1 loop bodies started (the reference's final `iteration` + 1), 2 node count,
- *   3 goal node index (-1: none), 4 pool length, 5 stop_reason (MPB_RRT_STOP_*), 6 best_cost_iters,
- *   7 iters_after_first_success, 8 best_cost_eps (fp32 bits; 3e38 before the first success), 9 accepted rewires,
- *   10 informed rejections, 11 goal cost at the first success (fp32 bits), 12 iteration of the first success (-1: none),
- *   13 node count at the first success (nodes from this index on were created after the goal node);
+ *   mpb_last_error).  In 32-bit words: the MPB_RRT_GLOBAL_WORDS words of mpb_rrt_connect's workspace with
+ *   MPB_RRT_STAR_MAGIC; B x MPB_RRT_STAR_HDR_WORDS words per problem, of which these are used: MPB_RRTS_STATUS,
+ *   _ITERS (loop bodies started: the reference's final `iteration` + 1), _COUNT (nodes), _GOAL (index of the goal node,
+ *   -1: none), _POOL_LEN, _STOP_REASON (MPB_RRT_STOP_*), _BEST_COST_ITERS, _ITERS_AFTER_FIRST_SUCCESS, _BEST_COST_EPS
+ *   (fp32 bits; 3e38 before the first success), _REWIRES (accepted), _INFORMED_REJECTIONS, _FIRST_COST (goal cost at the
+ *   first success, fp32 bits), _FIRST_ITER (iteration of the first success, -1: none), _FIRST_COUNT (node count at the
+ *   first success: nodes from this index on were created after the goal node);
  *   goal configurations (B, Dp) fp32; ONE tree per problem, rooted at the start: node configurations (B, max_nodes, Dp)
  *   fp32, zero padded; parents (B, max_nodes) int32 (-1: root; after a rewire a parent may follow its child); d
  *   (B, max_nodes) fp32, the length of the edge to the parent; cost (B, max_nodes) fp32 with
@@ -637,12 +635,10 @@ int mpb_rrt_connect_run(void *workspace, size_t workspace_bytes, const float *ge
  *   null pointers (sample_idx / goal_draw given one without the other included), misaligned workspace / geom, a short
  *   workspace, Lmax < 2, a bad iteration range, non-positive step_size / n_radius: MPB_E_INVALID.
  * ------------------------------------------------------------------------------------------- */
-#define MPB_RRT_STOP_RUNNING 0
-#define MPB_RRT_STOP_ITERS 1          /* the n_iters + 1 loop bodies are used up */
-#define MPB_RRT_STOP_COST_CONVERGED 2 /* best_cost_iters >= max_best_cost_iters */
-#define MPB_RRT_STOP_AFTER_SUCCESS 3  /* iters_after_first_success > n_iters_after_success */
-#define MPB_RRT_STOP_TREE_FULL 4      /* a FOUND problem whose tree reached max_nodes */
-#define MPB_RRT_STOP_POOL_EMPTY 5     /* a FOUND problem whose pool list ran empty */
+/* stop_reason (MPB_RRT_STOP_* of mpb_rrt_layout.h): RUNNING; ITERS, the n_iters + 1 loop bodies are used up;
+ * COST_CONVERGED, best_cost_iters >= max_best_cost_iters; AFTER_SUCCESS, iters_after_first_success >
+ * n_iters_after_success; TREE_FULL, a FOUND problem whose tree reached max_nodes; POOL_EMPTY, a FOUND problem whose
+ * pool list ran empty */
 size_t mpb_rrt_star_workspace_bytes(int B, int max_nodes, int n_pre, int D);
 int mpb_rrt_star_init(void *workspace, size_t workspace_bytes, const float *start, const float *goal,
                       const float *geom, int geom_flags, int B, int max_nodes, int n_pre, int D, void *stream);

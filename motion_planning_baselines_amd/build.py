@@ -84,7 +84,7 @@ def _stale():
         return True
     t = min(os.path.getmtime(OUT), os.path.getmtime(DEBUG_OUT))
     deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(('.hip', '.h'))]
-    deps += [os.path.join(os.path.dirname(HERE), 'include', h) for h in ('mpb.h', 'mpb_geom_layout.h', 'mpb_debug.h')]
+    deps += [os.path.join(os.path.dirname(HERE), 'include', h) for h in ('mpb.h', 'mpb_geom_layout.h', 'mpb_rrt_layout.h', 'mpb_debug.h')]
     return any(os.path.getmtime(d) > t for d in deps)
 
 
@@ -117,7 +117,7 @@ def build(force=False, verbose=True):
     """The product library.  Compiles with FLAGS + the per-file scheduling flags only: extra defines (HIPCC_FLAGS-style
     environment hooks do not exist here) cannot reach it, and a tuning build is refused outright."""
     # the compile-time robot models (csrc/mpb_model_*.h) and the packed-geometry layout (include/mpb_geom_layout.h) are generated
-    # from geometry.py, the single source of the numbers.  They are rewritten only when a build is going to run; on the fast path
+    # from geometry.py, the RRT workspace layout (include/mpb_rrt_layout.h) from rrt_layout.py: the single sources of the numbers.  They are rewritten only when a build is going to run; on the fast path
     # the committed header is only compared (ranks starting together must not write into the package, and it may be installed read-only)
     from . import model_gen
     stale = force or _stale() or bool(model_gen.stale_headers())

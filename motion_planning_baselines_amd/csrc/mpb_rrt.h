@@ -1,14 +1,15 @@
 // mpb_rrt.h -- the pieces the sample-based planner kernels share (mpb_rrt_connect.hip, mpb_rrt_star.hip): the collision
 // cost of one configuration per lane, torch.allclose, extend_path's linspace point (utils.py:4-14), safe_path's scan for
 // the first point in collision (utils.py:17-30), purge_duplicates_from_traj (utils.py:33-50) and the order-preserving
-// deletion of a pool entry (rrt_base.py:59-63).  Every function is block-uniform: all 64 lanes of the single-wave
-// workgroup call it.
+// deletion of a pool entry (rrt_base.py:59-63), and what the two init kernels have in common.  Every function is
+// block-uniform: all 64 lanes of the single-wave workgroup call it.  The workspace in numbers (status values, header word
+// indices, the pool limit MPB_RRT_MAX_PRE_SAMPLES) is include/mpb_rrt_layout.h, generated from rrt_layout.py.
 #pragma once
+#include "../../include/mpb_rrt_layout.h"
 #include "mpb_common.h"
 #include "mpb_geom.h"
 #include "mpb_model_panda.h"
 
-#define RRT_MAX_PRE 16384
 #define RRT_MAX_PTS (1 << 20)    // points of one extension (dist / step_size + 2): far beyond any sane step size
 
 // Collision cost of one configuration per lane, chained fields in turn.  Block-uniform control flow: every thread of the
@@ -114,4 +115,34 @@ __device__ __forceinline__ int rrt_purge(float* path_b, int Lraw, int D, int lan
         ++out;
     }
     return out;
+}
+
+// What the init kernels of both planners do alike, for problem b: the global words (block 0), the full pool list
+// 0 .. n_pre - 1 at `pool`, and the collision check of the start (lane 0) and the goal (every other lane).  Returns the
+// problem's first status word.
+template <int MODEL>
+__device__ __forceinline__ int rrt_init_shared(int* __restrict__ ws, int magic, int B, int max_nodes, int n_pre, int D, int Dp,
+                                               unsigned* __restrict__ pool, int pool_words, const float* __restrict__ start,
+                                               const float* __restrict__ goal, const float* __restrict__ geom, unsigned* gridw,
+                                               float4* otab, int b, int lane) {
+    if (b == 0 && lane < MPB_RRT_GLOBAL_WORDS) {
+        int v = 0;
+        if (lane == MPB_RRTG_MAGIC) v = magic;
+        if (lane == MPB_RRTG_B) v = B;
+        if (lane == MPB_RRTG_MAX_NODES) v = max_nodes;
+        if (lane == MPB_RRTG_N_PRE) v = n_pre;
+        if (lane == MPB_RRTG_D) v = D;
+        if (lane == MPB_RRTG_DP) v = Dp;
+        ws[lane] = v;
+    }
+    const float* row = (lane == 0 ? start : goal) + (size_t)b * D;
+    float q[MPB_MAX_DOF];
+#pragma unroll
+    for (int k = 0; k < MPB_MAX_DOF; ++k) q[k] = (k < D) ? row[k] : 0.f;
+    const float* staged = nullptr;
+    const float c = rrt_config_cost<MODEL>(geom, gridw, otab, staged, q);
+    const bool hit = __ballot(c > 0.f) != 0ull;
+    for (int w = lane; w < pool_words; w += 64)
+        pool[w] = (unsigned)(2 * w) | ((unsigned)(2 * w + 1) << MPB_RRT_POOL_INDEX_BITS);
+    return hit ? MPB_RRT_START_OR_GOAL_IN_COLLISION : MPB_RRT_RUNNING;
 }

@@ -21,12 +21,10 @@
 // evaluators of mpb_geom.h (broad-phase grid where the field has one, the compile-time Panda model where geom_flags
 // allows, the exhaustive walk otherwise; chained fields in turn).
 #include "mpb_common.h"
-#include "mpb_host.h"
 #include "mpb_rrt.h"
+#include "mpb_rrt_host.h"
 
-#define RRT_MAGIC 0x52525443
-#define RRT_GLOBAL_WORDS 16      // workspace header: magic, B, max_nodes, n_pre, D, Dp
-#define RRT_HDR_WORDS 16         // per problem: status, iterations used, count 0, count 1, swap bit, pool length
+#define RRT_WORDS_PER_NODE 32.0  // the size bound of rrt_shape_check: two trees, 16 words per node
 
 struct RrtLayout {
     size_t hdr, nodes, parents, pool, total;   // offsets in 32-bit words
@@ -37,8 +35,8 @@ __host__ __device__ static inline RrtLayout rrt_layout(int B, int max_nodes, int
     RrtLayout L;
     L.Dp = (D + 3) & ~3;
     L.pool_words = (n_pre + 1) / 2;
-    L.hdr = RRT_GLOBAL_WORDS;
-    L.nodes = L.hdr + (size_t)B * RRT_HDR_WORDS;
+    L.hdr = MPB_RRT_GLOBAL_WORDS;
+    L.nodes = L.hdr + (size_t)B * MPB_RRT_CONNECT_HDR_WORDS;
     L.parents = L.nodes + (size_t)B * 2 * max_nodes * L.Dp;
     L.pool = L.parents + (size_t)B * 2 * max_nodes;
     L.total = L.pool + (size_t)B * L.pool_words;
@@ -74,21 +72,9 @@ __global__ __launch_bounds__(64) void rrt_init_kernel(int* __restrict__ ws, cons
     __shared__ float4 otab[MPB_GRID_MAX_SPH + 1];
     const int b = blockIdx.x, lane = threadIdx.x;
     const RrtLayout L = rrt_layout(B, max_nodes, n_pre, D);
-    if (b == 0 && lane < RRT_GLOBAL_WORDS) {
-        const int g[6] = {RRT_MAGIC, B, max_nodes, n_pre, D, L.Dp};
-        int v = 0;
-#pragma unroll
-        for (int k = 0; k < 6; ++k) v = (lane == k) ? g[k] : v;
-        ws[lane] = v;
-    }
-    // lane 0 checks the start, every other lane the goal
-    const float* row = (lane == 0 ? start : goal) + (size_t)b * D;
-    float q[MPB_MAX_DOF];
-#pragma unroll
-    for (int k = 0; k < MPB_MAX_DOF; ++k) q[k] = (k < D) ? row[k] : 0.f;
-    const float* staged = nullptr;
-    const float c = rrt_config_cost<MODEL>(geom, gridw, otab, staged, q);
-    const bool hit = __ballot(c > 0.f) != 0ull;
+    unsigned* pool = reinterpret_cast<unsigned*>(ws) + L.pool + (size_t)b * L.pool_words;
+    const int status = rrt_init_shared<MODEL>(ws, MPB_RRT_CONNECT_MAGIC, B, max_nodes, n_pre, D, L.Dp, pool, L.pool_words, start, goal,
+                                              geom, gridw, otab, b, lane);
     float* nodes = reinterpret_cast<float*>(ws) + L.nodes + (size_t)b * 2 * max_nodes * L.Dp;
     int* parents = ws + L.parents + (size_t)b * 2 * max_nodes;
     if (lane < L.Dp) {
@@ -96,14 +82,12 @@ __global__ __launch_bounds__(64) void rrt_init_kernel(int* __restrict__ ws, cons
         nodes[(size_t)max_nodes * L.Dp + lane] = (lane < D) ? goal[(size_t)b * D + lane] : 0.f;
     }
     if (lane < 2) parents[(size_t)lane * max_nodes] = -1;
-    unsigned* pool = reinterpret_cast<unsigned*>(ws) + L.pool + (size_t)b * L.pool_words;
-    for (int w = lane; w < L.pool_words; w += 64) pool[w] = (unsigned)(2 * w) | ((unsigned)(2 * w + 1) << 16);
-    if (lane < RRT_HDR_WORDS) {
-        int* H = ws + L.hdr + (size_t)b * RRT_HDR_WORDS;
+    if (lane < MPB_RRT_CONNECT_HDR_WORDS) {
+        int* H = ws + L.hdr + (size_t)b * MPB_RRT_CONNECT_HDR_WORDS;
         int v = 0;
-        if (lane == 0) v = hit ? MPB_RRT_START_OR_GOAL_IN_COLLISION : MPB_RRT_RUNNING;
-        if (lane == 2 || lane == 3) v = 1;
-        if (lane == 5) v = n_pre;
+        if (lane == MPB_RRTC_STATUS) v = status;
+        if (lane == MPB_RRTC_COUNTS || lane == MPB_RRTC_COUNTS + 1) v = 1;
+        if (lane == MPB_RRTC_POOL_LEN) v = n_pre;
         H[lane] = v;
     }
 }
@@ -127,20 +111,20 @@ template <int DT, int MODEL>
 __global__ __launch_bounds__(64) void rrt_connect_kernel(const RrtArgs a) {
     __shared__ unsigned gridw[MPB_GRID_MAX_CELLS];
     __shared__ float4 otab[MPB_GRID_MAX_SPH + 1];
-    __shared__ unsigned short pool[RRT_MAX_PRE];
+    __shared__ unsigned short pool[MPB_RRT_MAX_PRE_SAMPLES];
     constexpr int DM = DT ? DT : MPB_MAX_DOF;
     constexpr int DM4 = (DM + 3) / 4;
     const int D = DT ? DT : a.D;
     const int b = blockIdx.x, lane = threadIdx.x;
     const RrtLayout L = rrt_layout(a.B, a.max_nodes, a.n_pre, D);
-    int* H = a.ws + L.hdr + (size_t)b * RRT_HDR_WORDS;
-    int status = H[0];
+    int* H = a.ws + L.hdr + (size_t)b * MPB_RRT_CONNECT_HDR_WORDS;
+    int status = H[MPB_RRTC_STATUS];
     if (status != MPB_RRT_RUNNING) {                       // block-uniform: a finished problem costs nothing
         if (lane == 0) a.status[b] = status;
         return;
     }
-    int cnt[2] = {H[2], H[3]};
-    int bit = H[4], plen = H[5];
+    int cnt[2] = {H[MPB_RRTC_COUNTS], H[MPB_RRTC_COUNTS + 1]};
+    int bit = H[MPB_RRTC_SWAP], plen = H[MPB_RRTC_POOL_LEN];
     float* nodes_b = reinterpret_cast<float*>(a.ws) + L.nodes + (size_t)b * 2 * a.max_nodes * L.Dp;
     int* parents_b = a.ws + L.parents + (size_t)b * 2 * a.max_nodes;
     unsigned short* pool_g = reinterpret_cast<unsigned short*>(a.ws + L.pool + (size_t)b * L.pool_words);
@@ -227,7 +211,7 @@ __global__ __launch_bounds__(64) void rrt_connect_kernel(const RrtArgs a) {
             idx = a.sample_idx[(size_t)b * a.total_iters + it];
             idx = min(max(idx, 0), plen - 1);
         } else {
-            const uint4 r = philox4x32_10(make_uint4(a.problem_offset + (uint32_t)b, (uint32_t)it, RRT_MAGIC, 0u),
+            const uint4 r = philox4x32_10(make_uint4(a.problem_offset + (uint32_t)b, (uint32_t)it, MPB_RRT_CONNECT_MAGIC, 0u),
                                           make_uint2(a.seed_lo, a.seed_hi));
             idx = (int)__umulhi(r.x, (uint32_t)plen);
         }
@@ -283,38 +267,23 @@ __global__ __launch_bounds__(64) void rrt_connect_kernel(const RrtArgs a) {
     __syncthreads();
     for (int i = lane; i < plen; i += 64) pool_g[i] = pool[i];
     if (lane == 0) {
-        H[0] = status; H[1] = it; H[2] = cnt[0]; H[3] = cnt[1]; H[4] = bit; H[5] = plen;
+        H[MPB_RRTC_STATUS] = status; H[MPB_RRTC_ITERS] = it; H[MPB_RRTC_COUNTS] = cnt[0]; H[MPB_RRTC_COUNTS + 1] = cnt[1];
+        H[MPB_RRTC_SWAP] = bit; H[MPB_RRTC_POOL_LEN] = plen;
         a.status[b] = status;
     }
 }
 
-// ---- host side ------------------------------------------------------------------------------------------------------
-static int rrt_shape_check(const char* who, int B, int max_nodes, int n_pre, int D) {
-    if (n_pre > RRT_MAX_PRE) return mpb_failf(MPB_E_UNSUPPORTED, "%s: n_pre = %d exceeds the %d pool entries the kernel keeps in LDS", who, n_pre, RRT_MAX_PRE);
-    if (D > MPB_MAX_DOF) return mpb_failf(MPB_E_UNSUPPORTED, "%s: D = %d exceeds MPB_MAX_DOF = %d", who, D, MPB_MAX_DOF);
-    if (B < 0 || max_nodes < 2 || n_pre < 1 || D < 1) return mpb_failf(MPB_E_INVALID, "%s: bad shape (B %d, max_nodes %d, n_pre %d, D %d)", who, B, max_nodes, n_pre, D);
-    if ((double)B * 2.0 * max_nodes * 16.0 > 2.0e9) return mpb_failf(MPB_E_UNSUPPORTED, "%s: B x max_nodes too large", who);
-    return MPB_OK;
-}
-
+// ---- host side (the checks: mpb_rrt_host.h) -------------------------------------------------------------------------
 extern "C" size_t mpb_rrt_connect_workspace_bytes(int B, int max_nodes, int n_pre, int D) {
-    if (rrt_shape_check("mpb_rrt_connect_workspace_bytes", B, max_nodes, n_pre, D) != MPB_OK) return 0;
+    if (rrt_shape_check("mpb_rrt_connect_workspace_bytes", RRT_WORDS_PER_NODE, B, max_nodes, n_pre, D) != MPB_OK) return 0;
     return 4 * rrt_layout(B, max_nodes, n_pre, D).total;
-}
-
-static bool rrt_use_model(int geom_flags, int D) {
-    return mpb_flags_model_on_grids(geom_flags, PandaModel::ID) && D == PandaModel::N_DOF;
 }
 
 extern "C" int mpb_rrt_connect_init(void* workspace, size_t workspace_bytes, const float* start, const float* goal,
                                     const float* geom, int geom_flags, int B, int max_nodes, int n_pre, int D, void* stream) {
-    const int rc = rrt_shape_check("mpb_rrt_connect_init", B, max_nodes, n_pre, D);
-    if (rc != MPB_OK) return rc;
-    if (!workspace || !start || !goal || !geom) return mpb_fail(MPB_E_INVALID, "mpb_rrt_connect_init: null pointer");
-    if (mpb_misaligned16(workspace, geom)) return mpb_fail(MPB_E_INVALID, "mpb_rrt_connect_init: workspace and geom must be 16-byte aligned");
-    const size_t need = 4 * rrt_layout(B, max_nodes, n_pre, D).total;
-    if (workspace_bytes < need) return mpb_failf(MPB_E_INVALID, "mpb_rrt_connect_init: workspace of %zu bytes, %zu needed", workspace_bytes, need);
-    if (B == 0) return MPB_OK;
+    const int rc = rrt_init_check("mpb_rrt_connect_init", RRT_WORDS_PER_NODE, B, max_nodes, n_pre, D, !workspace || !start || !goal || !geom, false,
+                                  workspace, geom, workspace_bytes, 4 * rrt_layout(B, max_nodes, n_pre, D).total);
+    if (rc != MPB_OK || B == 0) return rc;
     if (rrt_use_model(geom_flags, D))
         hipLaunchKernelGGL(rrt_init_kernel<PandaModel::ID>, dim3(B), dim3(64), 0, (hipStream_t)stream, (int*)workspace, start, goal, geom, B, max_nodes, n_pre, D);
     else
@@ -327,16 +296,10 @@ extern "C" int mpb_rrt_connect_run(void* workspace, size_t workspace_bytes, cons
                                    int* lengths, int* status, int B, int max_nodes, int n_pre, int D, int Lmax, int iter0,
                                    int n_iters, int total_iters, float step_size, float n_radius, uint64_t seed,
                                    uint32_t problem_offset, void* stream) {
-    const int rc = rrt_shape_check("mpb_rrt_connect_run", B, max_nodes, n_pre, D);
-    if (rc != MPB_OK) return rc;
-    if (!workspace || !geom || !pre_samples || !paths || !lengths || !status) return mpb_fail(MPB_E_INVALID, "mpb_rrt_connect_run: null pointer");
-    if (mpb_misaligned16(workspace, geom)) return mpb_fail(MPB_E_INVALID, "mpb_rrt_connect_run: workspace and geom must be 16-byte aligned");
-    const size_t need = 4 * rrt_layout(B, max_nodes, n_pre, D).total;
-    if (workspace_bytes < need) return mpb_failf(MPB_E_INVALID, "mpb_rrt_connect_run: workspace of %zu bytes, %zu needed", workspace_bytes, need);
-    if (Lmax < 2 || iter0 < 0 || n_iters < 0 || total_iters < 0 || iter0 > total_iters)
-        return mpb_fail(MPB_E_INVALID, "mpb_rrt_connect_run: bad Lmax / iteration range / pre_stride");
-    if (!(step_size > 0.f) || !(n_radius > 0.f)) return mpb_fail(MPB_E_INVALID, "mpb_rrt_connect_run: step_size and n_radius must be positive");
-    if (B == 0) return MPB_OK;
+    int rc = rrt_init_check("mpb_rrt_connect_run", RRT_WORDS_PER_NODE, B, max_nodes, n_pre, D, !workspace || !geom || !pre_samples || !paths || !lengths || !status,
+                            false, workspace, geom, workspace_bytes, 4 * rrt_layout(B, max_nodes, n_pre, D).total);
+    if (rc == MPB_OK) rc = rrt_run_check("mpb_rrt_connect_run", Lmax, iter0, n_iters, total_iters, true, step_size, n_radius);
+    if (rc != MPB_OK || B == 0) return rc;
     const RrtArgs a = {(int*)workspace, geom, pre_samples, pre_stride, sample_idx, paths, lengths, status, B, D, max_nodes, n_pre, Lmax,
                        iter0, n_iters, total_iters, step_size, n_radius, (uint32_t)seed, (uint32_t)(seed >> 32), problem_offset};
     const hipStream_t s = (hipStream_t)stream;

@@ -20,16 +20,11 @@
 // ONE distance routine (rrt_dist) serves nearest node, extension, neighbours, rewire, goal and informed tests: a distance
 // between the same two bit patterns is the same number wherever it is computed, which is what resolves the reference's
 // exact ties (new.cost + d == n.cost when the new node duplicates its parent) the way the reference does.
-#include "mpb_host.h"
 #include "mpb_rrt.h"
+#include "mpb_rrt_host.h"
 
-#define RRS_MAGIC 0x52525453
-#define RRS_GLOBAL_WORDS 16      // workspace header: magic, B, max_nodes, n_pre, D, Dp
-#define RRS_HDR_WORDS 32         // per problem, see include/mpb.h
+#define RRS_WORDS_PER_NODE 18.0  // the size bound of rrt_shape_check: the padded row, parent, d, cost, three of scratch
 #define RRS_NO_BEST 3.0e38f      // best_cost_eps before the first success (the reference's torch.inf)
-
-enum { H_STATUS, H_ITERS, H_COUNT, H_GOAL, H_PLEN, H_STOP, H_BCI, H_IAFS, H_BEST, H_REWIRES, H_REJECTED, H_FIRST_COST,
-       H_FIRST_ITER, H_FIRST_COUNT };
 
 struct RrsLayout {
     size_t hdr, goalq, nodes, parents, d, cost, cand, pool, total;   // offsets in 32-bit words
@@ -40,8 +35,8 @@ __host__ __device__ static inline RrsLayout rrs_layout(int B, int max_nodes, int
     RrsLayout L;
     L.Dp = (D + 3) & ~3;
     L.pool_words = (n_pre + 1) / 2;
-    L.hdr = RRS_GLOBAL_WORDS;
-    L.goalq = L.hdr + (size_t)B * RRS_HDR_WORDS;
+    L.hdr = MPB_RRT_GLOBAL_WORDS;
+    L.goalq = L.hdr + (size_t)B * MPB_RRT_STAR_HDR_WORDS;
     L.nodes = L.goalq + (size_t)B * L.Dp;
     L.parents = L.nodes + (size_t)B * max_nodes * L.Dp;
     L.d = L.parents + (size_t)B * max_nodes;
@@ -94,21 +89,9 @@ __global__ __launch_bounds__(64) void rrs_init_kernel(int* __restrict__ ws, cons
     __shared__ float4 otab[MPB_GRID_MAX_SPH + 1];
     const int b = blockIdx.x, lane = threadIdx.x;
     const RrsLayout L = rrs_layout(B, max_nodes, n_pre, D);
-    if (b == 0 && lane < RRS_GLOBAL_WORDS) {
-        const int g[6] = {RRS_MAGIC, B, max_nodes, n_pre, D, L.Dp};
-        int v = 0;
-#pragma unroll
-        for (int k = 0; k < 6; ++k) v = (lane == k) ? g[k] : v;
-        ws[lane] = v;
-    }
-    // lane 0 checks the start, every other lane the goal
-    const float* row = (lane == 0 ? start : goal) + (size_t)b * D;
-    float q[MPB_MAX_DOF];
-#pragma unroll
-    for (int k = 0; k < MPB_MAX_DOF; ++k) q[k] = (k < D) ? row[k] : 0.f;
-    const float* staged = nullptr;
-    const float c = rrt_config_cost<MODEL>(geom, gridw, otab, staged, q);
-    const bool hit = __ballot(c > 0.f) != 0ull;
+    unsigned* pool = reinterpret_cast<unsigned*>(ws) + L.pool + (size_t)b * L.pool_words;
+    const int status = rrt_init_shared<MODEL>(ws, MPB_RRT_STAR_MAGIC, B, max_nodes, n_pre, D, L.Dp, pool, L.pool_words, start, goal, geom,
+                                              gridw, otab, b, lane);
     float* wf = reinterpret_cast<float*>(ws);
     if (lane < L.Dp) {
         wf[L.nodes + (size_t)b * max_nodes * L.Dp + lane] = (lane < D) ? start[(size_t)b * D + lane] : 0.f;
@@ -119,16 +102,14 @@ __global__ __launch_bounds__(64) void rrs_init_kernel(int* __restrict__ ws, cons
         wf[L.d + (size_t)b * max_nodes] = 0.f;
         wf[L.cost + (size_t)b * max_nodes] = 0.f;
     }
-    unsigned* pool = reinterpret_cast<unsigned*>(ws) + L.pool + (size_t)b * L.pool_words;
-    for (int w = lane; w < L.pool_words; w += 64) pool[w] = (unsigned)(2 * w) | ((unsigned)(2 * w + 1) << 16);
-    if (lane < RRS_HDR_WORDS) {
+    if (lane < MPB_RRT_STAR_HDR_WORDS) {
         int v = 0;
-        if (lane == H_STATUS) v = hit ? MPB_RRT_START_OR_GOAL_IN_COLLISION : MPB_RRT_RUNNING;
-        if (lane == H_COUNT) v = 1;
-        if (lane == H_GOAL || lane == H_FIRST_ITER) v = -1;
-        if (lane == H_PLEN) v = n_pre;
-        if (lane == H_BEST) v = __float_as_int(RRS_NO_BEST);
-        ws[L.hdr + (size_t)b * RRS_HDR_WORDS + lane] = v;
+        if (lane == MPB_RRTS_STATUS) v = status;
+        if (lane == MPB_RRTS_COUNT) v = 1;
+        if (lane == MPB_RRTS_GOAL || lane == MPB_RRTS_FIRST_ITER) v = -1;
+        if (lane == MPB_RRTS_POOL_LEN) v = n_pre;
+        if (lane == MPB_RRTS_BEST_COST_EPS) v = __float_as_int(RRS_NO_BEST);
+        ws[L.hdr + (size_t)b * MPB_RRT_STAR_HDR_WORDS + lane] = v;
     }
 }
 
@@ -153,21 +134,22 @@ template <int DT, int MODEL>
 __global__ __launch_bounds__(64) void rrt_star_kernel(const RrsArgs a) {
     __shared__ unsigned gridw[MPB_GRID_MAX_CELLS];
     __shared__ float4 otab[MPB_GRID_MAX_SPH + 1];
-    __shared__ unsigned short pool[RRT_MAX_PRE];
+    __shared__ unsigned short pool[MPB_RRT_MAX_PRE_SAMPLES];
     __shared__ int s_excl[64], s_first[64];
     constexpr int DM = DT ? DT : MPB_MAX_DOF;
     const int D = DT ? DT : a.D;
     const int b = blockIdx.x, lane = threadIdx.x;
     const RrsLayout L = rrs_layout(a.B, a.max_nodes, a.n_pre, D);
-    int* H = a.ws + L.hdr + (size_t)b * RRS_HDR_WORDS;
-    int status = H[H_STATUS];
+    int* H = a.ws + L.hdr + (size_t)b * MPB_RRT_STAR_HDR_WORDS;
+    int status = H[MPB_RRTS_STATUS];
     if (status != MPB_RRT_RUNNING) {                       // block-uniform: a finished problem costs nothing
         if (lane == 0) a.status[b] = status;
         return;
     }
-    int it = H[H_ITERS], cnt = H[H_COUNT], goal = H[H_GOAL], plen = H[H_PLEN], stop = MPB_RRT_STOP_RUNNING;
-    int bci = H[H_BCI], iafs = H[H_IAFS], rewires = H[H_REWIRES], rejected = H[H_REJECTED];
-    float best = __int_as_float(H[H_BEST]);
+    int it = H[MPB_RRTS_ITERS], cnt = H[MPB_RRTS_COUNT], goal = H[MPB_RRTS_GOAL], plen = H[MPB_RRTS_POOL_LEN];
+    int stop = MPB_RRT_STOP_RUNNING, bci = H[MPB_RRTS_BEST_COST_ITERS], iafs = H[MPB_RRTS_ITERS_AFTER_FIRST_SUCCESS];
+    int rewires = H[MPB_RRTS_REWIRES], rejected = H[MPB_RRTS_INFORMED_REJECTIONS];
+    float best = __int_as_float(H[MPB_RRTS_BEST_COST_EPS]);
     float* wf = reinterpret_cast<float*>(a.ws);
     float* nodes_b = wf + L.nodes + (size_t)b * a.max_nodes * L.Dp;
     int* parents_b = a.ws + L.parents + (size_t)b * a.max_nodes;
@@ -205,7 +187,7 @@ __global__ __launch_bounds__(64) void rrt_star_kernel(const RrsArgs a) {
             idx = a.sample_idx[(size_t)b * a.total_iters + it];
             idx = min(max(idx, 0), max(plen - 1, 0));
         } else {
-            const uint4 r = philox4x32_10(make_uint4(a.problem_offset + (uint32_t)b, (uint32_t)it, RRS_MAGIC, 0u),
+            const uint4 r = philox4x32_10(make_uint4(a.problem_offset + (uint32_t)b, (uint32_t)it, MPB_RRT_STAR_MAGIC, 0u),
                                           make_uint2(a.seed_lo, a.seed_hi));
             idx = (int)__umulhi(r.x, (uint32_t)plen);
             do_goal = goal < 0 && (it == 0 || (float)(r.y >> 8) * (1.0f / 16777216.0f) < a.goal_prob);
@@ -286,7 +268,9 @@ __global__ __launch_bounds__(64) void rrt_star_kernel(const RrsArgs a) {
         }
         if (do_goal && rrt_dist<DM>(nq, gq) < a.eps) {       // :216
             goal = n;
-            if (lane == 0) { H[H_FIRST_COST] = __float_as_int(cn); H[H_FIRST_ITER] = it; H[H_FIRST_COUNT] = n + 1; }
+            if (lane == 0) {
+                H[MPB_RRTS_FIRST_COST] = __float_as_int(cn); H[MPB_RRTS_FIRST_ITER] = it; H[MPB_RRTS_FIRST_COUNT] = n + 1;
+            }
         }
         cnt = n + 1;
         __syncthreads();
@@ -404,40 +388,26 @@ __global__ __launch_bounds__(64) void rrt_star_kernel(const RrsArgs a) {
     }
     for (int i = lane; i < plen; i += 64) pool_g[i] = pool[i];
     if (lane == 0) {
-        H[H_STATUS] = status; H[H_ITERS] = it; H[H_COUNT] = cnt; H[H_GOAL] = goal; H[H_PLEN] = plen; H[H_STOP] = stop;
-        H[H_BCI] = bci; H[H_IAFS] = iafs; H[H_BEST] = __float_as_int(best); H[H_REWIRES] = rewires; H[H_REJECTED] = rejected;
+        H[MPB_RRTS_STATUS] = status; H[MPB_RRTS_ITERS] = it; H[MPB_RRTS_COUNT] = cnt; H[MPB_RRTS_GOAL] = goal;
+        H[MPB_RRTS_POOL_LEN] = plen; H[MPB_RRTS_STOP_REASON] = stop; H[MPB_RRTS_BEST_COST_ITERS] = bci;
+        H[MPB_RRTS_ITERS_AFTER_FIRST_SUCCESS] = iafs; H[MPB_RRTS_BEST_COST_EPS] = __float_as_int(best);
+        H[MPB_RRTS_REWIRES] = rewires; H[MPB_RRTS_INFORMED_REJECTIONS] = rejected;
         a.status[b] = status;
     }
 }
 
-// ---- host side ------------------------------------------------------------------------------------------------------
-static int rrs_shape_check(const char* who, int B, int max_nodes, int n_pre, int D) {
-    if (n_pre > RRT_MAX_PRE) return mpb_failf(MPB_E_UNSUPPORTED, "%s: n_pre = %d exceeds the %d pool entries the kernel keeps in LDS", who, n_pre, RRT_MAX_PRE);
-    if (D > MPB_MAX_DOF) return mpb_failf(MPB_E_UNSUPPORTED, "%s: D = %d exceeds MPB_MAX_DOF = %d", who, D, MPB_MAX_DOF);
-    if (B < 0 || max_nodes < 2 || n_pre < 1 || D < 1) return mpb_failf(MPB_E_INVALID, "%s: bad shape (B %d, max_nodes %d, n_pre %d, D %d)", who, B, max_nodes, n_pre, D);
-    if ((double)B * max_nodes * 18.0 > 2.0e9) return mpb_failf(MPB_E_UNSUPPORTED, "%s: B x max_nodes too large", who);
-    return MPB_OK;
-}
-
+// ---- host side (the checks: mpb_rrt_host.h) -------------------------------------------------------------------------
 extern "C" size_t mpb_rrt_star_workspace_bytes(int B, int max_nodes, int n_pre, int D) {
-    if (rrs_shape_check("mpb_rrt_star_workspace_bytes", B, max_nodes, n_pre, D) != MPB_OK) return 0;
+    if (rrt_shape_check("mpb_rrt_star_workspace_bytes", RRS_WORDS_PER_NODE, B, max_nodes, n_pre, D) != MPB_OK) return 0;
     return 4 * rrs_layout(B, max_nodes, n_pre, D).total;
-}
-
-static bool rrs_use_model(int geom_flags, int D) {
-    return mpb_flags_model_on_grids(geom_flags, PandaModel::ID) && D == PandaModel::N_DOF;
 }
 
 extern "C" int mpb_rrt_star_init(void* workspace, size_t workspace_bytes, const float* start, const float* goal,
                                  const float* geom, int geom_flags, int B, int max_nodes, int n_pre, int D, void* stream) {
-    const int rc = rrs_shape_check("mpb_rrt_star_init", B, max_nodes, n_pre, D);
-    if (rc != MPB_OK) return rc;
-    if (!workspace || !start || !goal || !geom) return mpb_fail(MPB_E_INVALID, "mpb_rrt_star_init: null pointer");
-    if (mpb_misaligned16(workspace, geom)) return mpb_fail(MPB_E_INVALID, "mpb_rrt_star_init: workspace and geom must be 16-byte aligned");
-    const size_t need = 4 * rrs_layout(B, max_nodes, n_pre, D).total;
-    if (workspace_bytes < need) return mpb_failf(MPB_E_INVALID, "mpb_rrt_star_init: workspace of %zu bytes, %zu needed", workspace_bytes, need);
-    if (B == 0) return MPB_OK;
-    if (rrs_use_model(geom_flags, D))
+    const int rc = rrt_init_check("mpb_rrt_star_init", RRS_WORDS_PER_NODE, B, max_nodes, n_pre, D, !workspace || !start || !goal || !geom, false,
+                                  workspace, geom, workspace_bytes, 4 * rrs_layout(B, max_nodes, n_pre, D).total);
+    if (rc != MPB_OK || B == 0) return rc;
+    if (rrt_use_model(geom_flags, D))
         hipLaunchKernelGGL(rrs_init_kernel<PandaModel::ID>, dim3(B), dim3(64), 0, (hipStream_t)stream, (int*)workspace, start, goal, geom, B, max_nodes, n_pre, D);
     else
         hipLaunchKernelGGL(rrs_init_kernel<0>, dim3(B), dim3(64), 0, (hipStream_t)stream, (int*)workspace, start, goal, geom, B, max_nodes, n_pre, D);
@@ -450,22 +420,15 @@ extern "C" int mpb_rrt_star_run(void* workspace, size_t workspace_bytes, const f
                                 int Lmax, int iter0, int n_iters, int total_iters, int max_best_cost_iters,
                                 int n_iters_after_success, int informed, float step_size, float n_radius, float goal_prob,
                                 float cost_eps, float eps, uint64_t seed, uint32_t problem_offset, void* stream) {
-    const int rc = rrs_shape_check("mpb_rrt_star_run", B, max_nodes, n_pre, D);
-    if (rc != MPB_OK) return rc;
-    if (!workspace || !geom || !pre_samples || !paths || !lengths || !costs || !status) return mpb_fail(MPB_E_INVALID, "mpb_rrt_star_run: null pointer");
-    if ((sample_idx == nullptr) != (goal_draw == nullptr)) return mpb_fail(MPB_E_INVALID, "mpb_rrt_star_run: sample_idx and goal_draw are given together or not at all");
-    if (mpb_misaligned16(workspace, geom)) return mpb_fail(MPB_E_INVALID, "mpb_rrt_star_run: workspace and geom must be 16-byte aligned");
-    const size_t need = 4 * rrs_layout(B, max_nodes, n_pre, D).total;
-    if (workspace_bytes < need) return mpb_failf(MPB_E_INVALID, "mpb_rrt_star_run: workspace of %zu bytes, %zu needed", workspace_bytes, need);
-    if (Lmax < 2 || iter0 < 0 || n_iters < 0 || total_iters < 0 || iter0 > total_iters || max_best_cost_iters < 0)
-        return mpb_fail(MPB_E_INVALID, "mpb_rrt_star_run: bad Lmax / iteration range / max_best_cost_iters");
-    if (!(step_size > 0.f) || !(n_radius > 0.f)) return mpb_fail(MPB_E_INVALID, "mpb_rrt_star_run: step_size and n_radius must be positive");
-    if (B == 0) return MPB_OK;
+    int rc = rrt_init_check("mpb_rrt_star_run", RRS_WORDS_PER_NODE, B, max_nodes, n_pre, D, !workspace || !geom || !pre_samples || !paths || !lengths || !costs || !status,
+                            (sample_idx == nullptr) != (goal_draw == nullptr), workspace, geom, workspace_bytes, 4 * rrs_layout(B, max_nodes, n_pre, D).total);
+    if (rc == MPB_OK) rc = rrt_run_check("mpb_rrt_star_run", Lmax, iter0, n_iters, total_iters, max_best_cost_iters >= 0, step_size, n_radius);
+    if (rc != MPB_OK || B == 0) return rc;
     const RrsArgs a = {(int*)workspace, geom, pre_samples, pre_stride, sample_idx, goal_draw, paths, lengths, costs, status,
                        B, D, max_nodes, n_pre, Lmax, iter0, n_iters, total_iters, max_best_cost_iters, n_iters_after_success,
                        informed, step_size, n_radius, goal_prob, cost_eps, eps, (uint32_t)seed, (uint32_t)(seed >> 32), problem_offset};
     const hipStream_t s = (hipStream_t)stream;
-    if (rrs_use_model(geom_flags, D)) hipLaunchKernelGGL((rrt_star_kernel<7, PandaModel::ID>), dim3(B), dim3(64), 0, s, a);
+    if (rrt_use_model(geom_flags, D)) hipLaunchKernelGGL((rrt_star_kernel<7, PandaModel::ID>), dim3(B), dim3(64), 0, s, a);
     else if (D == 2) hipLaunchKernelGGL((rrt_star_kernel<2, 0>), dim3(B), dim3(64), 0, s, a);
     else if (D == 7) hipLaunchKernelGGL((rrt_star_kernel<7, 0>), dim3(B), dim3(64), 0, s, a);
     else hipLaunchKernelGGL((rrt_star_kernel<0, 0>), dim3(B), dim3(64), 0, s, a);

@@ -5,11 +5,12 @@ launching (a kernel that faults can reset the whole GPU host).
 """
 import ctypes
 import functools
+import math
 
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, rrt_layout
 from .geometry import MAX_FIELDS, count_fields, pack_geometry
 from .geometry import header as geometry_header
 
@@ -996,12 +997,14 @@ def debug_mt19937_uniforms(n, n_calls, device, generator=None):
     return out, MT.state_after(host, tb.total, st_out.cpu().numpy().view(np.uint32))
 
 
-# ---- collision predicate and batched RRT-Connect (csrc/mpb_rrt_connect.hip) -------------------------------------------
-RRT_RUNNING, RRT_FOUND, RRT_EXHAUSTED_ITERS, RRT_START_OR_GOAL_IN_COLLISION, RRT_POOL_EMPTY, RRT_TREE_FULL, \
-    RRT_PATH_TOO_LONG = range(7)                                  # include/mpb.h MPB_RRT_*
-RRT_STATUS_NAMES = ('RUNNING', 'FOUND', 'EXHAUSTED_ITERS', 'START_OR_GOAL_IN_COLLISION', 'POOL_EMPTY', 'TREE_FULL',
-                    'PATH_TOO_LONG')
-RRT_MAX_PRE_SAMPLES = 16384
+# ---- collision predicate, batched RRT-Connect (csrc/mpb_rrt_connect.hip), batched RRT* / informed RRT* (csrc/mpb_rrt_star.hip) ---
+# statuses, stop reasons, the pool limit and the layout of the two workspaces: rrt_layout.py, their one definition
+RRT_STATUS_NAMES, RRT_STOP_NAMES, RRT_MAX_PRE_SAMPLES = rrt_layout.STATUS, rrt_layout.STOP, rrt_layout.MAX_PRE_SAMPLES
+(RRT_RUNNING, RRT_FOUND, RRT_EXHAUSTED_ITERS, RRT_START_OR_GOAL_IN_COLLISION, RRT_POOL_EMPTY, RRT_TREE_FULL,
+ RRT_PATH_TOO_LONG) = map(RRT_STATUS_NAMES.index, ('RUNNING', 'FOUND', 'EXHAUSTED_ITERS', 'START_OR_GOAL_IN_COLLISION', 'POOL_EMPTY',
+                                                   'TREE_FULL', 'PATH_TOO_LONG'))
+(RRT_STOP_RUNNING, RRT_STOP_ITERS, RRT_STOP_COST_CONVERGED, RRT_STOP_AFTER_SUCCESS, RRT_STOP_TREE_FULL,
+ RRT_STOP_POOL_EMPTY) = map(RRT_STOP_NAMES.index, ('RUNNING', 'ITERS', 'COST_CONVERGED', 'AFTER_SUCCESS', 'TREE_FULL', 'POOL_EMPTY'))
 
 
 @_on_tensor_device
@@ -1020,28 +1023,55 @@ def collision_check(q, geom, with_gap=False):
 
 
 class RRTWorkspace:
-    """The caller-allocated state of a batch of RRT-Connect problems: trees, pool lists, status words (layout: include/mpb.h)."""
+    """The caller-allocated state of a batch of RRT-Connect problems: trees, pool lists, status words (layout: rrt_layout.py)."""
+    kind = 'connect'
 
     def __init__(self, B, max_nodes, n_pre, D, device):
-        nbytes = int(_lib.lib().mpb_rrt_connect_workspace_bytes(int(B), int(max_nodes), int(n_pre), int(D)))
+        sym = f'mpb_rrt_{self.kind}_workspace_bytes'
+        nbytes = int(getattr(_lib.lib(), sym)(int(B), int(max_nodes), int(n_pre), int(D)))
         if nbytes == 0:
             msg = _lib.lib().mpb_last_error()
-            raise _lib.MPBError(f'mpb_rrt_connect_workspace_bytes: {msg.decode() if msg else "?"}')
+            raise _lib.MPBError(f'{sym}: {msg.decode() if msg else "?"}')
         self.B, self.max_nodes, self.n_pre, self.D = int(B), int(max_nodes), int(n_pre), int(D)
         self.nbytes = nbytes
         self.buf = torch.zeros(nbytes // 4, device=device, dtype=torch.int32)
 
 
+class RRTStarWorkspace(RRTWorkspace):
+    """The caller-allocated state of a batch of RRT* problems: one tree per problem with parents, d and cost, the
+    neighbour scratch, pool lists and the per-problem header of counters (layout: rrt_layout.py)."""
+    kind = 'star'
+
+
 @_on_tensor_device
-def rrt_connect_init(ws_buf, ws, start, goal, geom):
-    """Roots, counts, pool lists, status words and the start / goal collision check of every problem (mpb_rrt_connect_init).
-    `ws_buf` is ws.buf (passed so that the launch lands on its device)."""
+def rrt_init(ws_buf, ws, start, goal, geom):
+    """Roots (RRT*: the root and the goal), counts, pool lists, status words and the start / goal collision check of every problem, by
+    the workspace's kind (mpb_rrt_connect_init, mpb_rrt_star_init).  `ws_buf` is ws.buf (passed so that the launch lands on its device)."""
     _chk(start, (ws.B, ws.D), 'start')
     _chk(goal, (ws.B, ws.D), 'goal')
     if ws.D != geom.n_dof:
         raise ValueError(f'the problems have {ws.D} columns, the geometry {geom.n_dof} degrees of freedom')
-    _lib.check(_lib.lib().mpb_rrt_connect_init(_ptr(ws_buf), ws.nbytes, _ptr(start), _ptr(goal), _ptr(geom.buf), int(geom.flags),
-                                              ws.B, ws.max_nodes, ws.n_pre, ws.D, _stream()), 'mpb_rrt_connect_init')
+    sym = f'mpb_rrt_{ws.kind}_init'
+    _lib.check(getattr(_lib.lib(), sym)(_ptr(ws_buf), ws.nbytes, _ptr(start), _ptr(goal), _ptr(geom.buf), int(geom.flags), ws.B,
+                                        ws.max_nodes, ws.n_pre, ws.D, _stream()), sym)
+
+
+rrt_connect_init = rrt_star_init = rrt_init
+
+
+def _rrt_run_shapes(ws, pre_samples, paths, lengths, status):
+    """The checks both *_run wrappers make of the pool and of the outputs: (pre_stride, Lmax)."""
+    if pre_samples.ndim == 2:
+        _chk(pre_samples, (ws.n_pre, ws.D), 'pre_samples')
+        stride = 0
+    else:
+        _chk(pre_samples, (ws.B, ws.n_pre, ws.D), 'pre_samples')
+        stride = ws.n_pre * ws.D
+    Lmax = paths.shape[1]
+    _chk(paths, (ws.B, Lmax, ws.D), 'paths')
+    _chk(lengths, (ws.B,), 'lengths', dtype=torch.int32)
+    _chk(status, (ws.B,), 'status', dtype=torch.int32)
+    return stride, Lmax
 
 
 @_on_tensor_device
@@ -1050,77 +1080,12 @@ def rrt_connect_run(ws_buf, ws, geom, pre_samples, sample_idx, paths, lengths, s
     """Iterations iter0 .. min(iter0 + n_iters, total_iters) - 1 of every problem still RUNNING (mpb_rrt_connect_run).
     pre_samples (n_pre, D) shared or (B, n_pre, D) one pool per problem; sample_idx None (device Philox) or (B, total_iters) int32."""
     B, D = ws.B, ws.D
-    if pre_samples.ndim == 2:
-        _chk(pre_samples, (ws.n_pre, D), 'pre_samples')
-        stride = 0
-    else:
-        _chk(pre_samples, (B, ws.n_pre, D), 'pre_samples')
-        stride = ws.n_pre * D
+    stride, Lmax = _rrt_run_shapes(ws, pre_samples, paths, lengths, status)
     _chk(sample_idx, (B, total_iters), 'sample_idx', allow_none=True, dtype=torch.int32)
-    Lmax = paths.shape[1]
-    _chk(paths, (B, Lmax, D), 'paths')
-    _chk(lengths, (B,), 'lengths', dtype=torch.int32)
-    _chk(status, (B,), 'status', dtype=torch.int32)
     _lib.check(_lib.lib().mpb_rrt_connect_run(
         _ptr(ws_buf), ws.nbytes, _ptr(geom.buf), int(geom.flags), _ptr(pre_samples), stride, _ptr(sample_idx), _ptr(paths),
         _ptr(lengths), _ptr(status), B, ws.max_nodes, ws.n_pre, D, Lmax, int(iter0), int(n_iters), int(total_iters),
         float(step_size), float(n_radius), _seed64(seed), int(problem_offset) & 0xFFFFFFFF, _stream()), 'mpb_rrt_connect_run')
-
-
-def rrt_connect_trees(ws):
-    """The trees of a workspace, for tests and rendering: dict of `nodes` (B, 2, max_nodes, D) fp32, `parents`
-    (B, 2, max_nodes) int32 (-1: root), `counts` (B, 2), `iters` (B,) iterations used, `status` (B,), `swap` (B,) and
-    `pool_len` (B,), `pool` (B, n_pre) int32 (entries beyond pool_len are stale).  Tree 0 is rooted at the start, tree 1 at the goal."""
-    B, M, D = ws.B, ws.max_nodes, ws.D
-    Dp = (D + 3) // 4 * 4
-    w = ws.buf
-    glob = w[:6].tolist()
-    if glob[0] != 0x52525443 or glob[1:5] != [B, M, ws.n_pre, D]:
-        raise ValueError('the workspace was not initialised for these shapes (rrt_connect_init)')
-    o = 16
-    hdr = w[o:o + 16 * B].reshape(B, 16)
-    o += 16 * B
-    nodes = w[o:o + B * 2 * M * Dp].view(torch.float32).reshape(B, 2, M, Dp)[..., :D]
-    o += B * 2 * M * Dp
-    parents = w[o:o + B * 2 * M].reshape(B, 2, M)
-    o += B * 2 * M
-    pw = (ws.n_pre + 1) // 2
-    pool = w[o:o + B * pw].reshape(B, pw)
-    pool = torch.stack((pool & 0xFFFF, (pool >> 16) & 0xFFFF), dim=-1).reshape(B, 2 * pw)[:, :ws.n_pre]
-    return dict(nodes=nodes, parents=parents, counts=hdr[:, 2:4], iters=hdr[:, 1], status=hdr[:, 0], swap=hdr[:, 4],
-                pool_len=hdr[:, 5], pool=pool)
-
-
-# ---- batched RRT* / informed RRT* (csrc/mpb_rrt_star.hip) ----------------------------------------------------------------
-RRT_STOP_RUNNING, RRT_STOP_ITERS, RRT_STOP_COST_CONVERGED, RRT_STOP_AFTER_SUCCESS, RRT_STOP_TREE_FULL, \
-    RRT_STOP_POOL_EMPTY = range(6)                                # include/mpb.h MPB_RRT_STOP_*
-RRT_STOP_NAMES = ('RUNNING', 'ITERS', 'COST_CONVERGED', 'AFTER_SUCCESS', 'TREE_FULL', 'POOL_EMPTY')
-
-
-class RRTStarWorkspace:
-    """The caller-allocated state of a batch of RRT* problems: one tree per problem with parents, d and cost, the
-    neighbour scratch, pool lists and the per-problem header of counters (layout: include/mpb.h)."""
-
-    def __init__(self, B, max_nodes, n_pre, D, device):
-        nbytes = int(_lib.lib().mpb_rrt_star_workspace_bytes(int(B), int(max_nodes), int(n_pre), int(D)))
-        if nbytes == 0:
-            msg = _lib.lib().mpb_last_error()
-            raise _lib.MPBError(f'mpb_rrt_star_workspace_bytes: {msg.decode() if msg else "?"}')
-        self.B, self.max_nodes, self.n_pre, self.D = int(B), int(max_nodes), int(n_pre), int(D)
-        self.nbytes = nbytes
-        self.buf = torch.zeros(nbytes // 4, device=device, dtype=torch.int32)
-
-
-@_on_tensor_device
-def rrt_star_init(ws_buf, ws, start, goal, geom):
-    """Root, goal, counters, pool list and the start / goal collision check of every problem (mpb_rrt_star_init).
-    `ws_buf` is ws.buf (passed so that the launch lands on its device)."""
-    _chk(start, (ws.B, ws.D), 'start')
-    _chk(goal, (ws.B, ws.D), 'goal')
-    if ws.D != geom.n_dof:
-        raise ValueError(f'the problems have {ws.D} columns, the geometry {geom.n_dof} degrees of freedom')
-    _lib.check(_lib.lib().mpb_rrt_star_init(_ptr(ws_buf), ws.nbytes, _ptr(start), _ptr(goal), _ptr(geom.buf), int(geom.flags),
-                                           ws.B, ws.max_nodes, ws.n_pre, ws.D, _stream()), 'mpb_rrt_star_init')
 
 
 @_on_tensor_device
@@ -1132,21 +1097,12 @@ def rrt_star_run(ws_buf, ws, geom, pre_samples, sample_idx, goal_draw, paths, le
     (B, total_iters) int32.  paths / lengths / costs hold the current best path of every problem with a goal node after
     every call."""
     B, D = ws.B, ws.D
-    if pre_samples.ndim == 2:
-        _chk(pre_samples, (ws.n_pre, D), 'pre_samples')
-        stride = 0
-    else:
-        _chk(pre_samples, (B, ws.n_pre, D), 'pre_samples')
-        stride = ws.n_pre * D
+    stride, Lmax = _rrt_run_shapes(ws, pre_samples, paths, lengths, status)
     if (sample_idx is None) != (goal_draw is None):
         raise ValueError('sample_idx and goal_draw are given together or not at all')
     _chk(sample_idx, (B, total_iters), 'sample_idx', allow_none=True, dtype=torch.int32)
     _chk(goal_draw, (B, total_iters), 'goal_draw', allow_none=True, dtype=torch.int32)
-    Lmax = paths.shape[1]
-    _chk(paths, (B, Lmax, D), 'paths')
-    _chk(lengths, (B,), 'lengths', dtype=torch.int32)
     _chk(costs, (B,), 'costs')
-    _chk(status, (B,), 'status', dtype=torch.int32)
     _lib.check(_lib.lib().mpb_rrt_star_run(
         _ptr(ws_buf), ws.nbytes, _ptr(geom.buf), int(geom.flags), _ptr(pre_samples), stride, _ptr(sample_idx), _ptr(goal_draw),
         _ptr(paths), _ptr(lengths), _ptr(costs), _ptr(status), B, ws.max_nodes, ws.n_pre, D, Lmax, int(iter0), int(n_iters),
@@ -1155,32 +1111,41 @@ def rrt_star_run(ws_buf, ws, geom, pre_samples, sample_idx, goal_draw, paths, le
         int(problem_offset) & 0xFFFFFFFF, _stream()), 'mpb_rrt_star_run')
 
 
+def _rrt_read(kind, ws, hidden=()):
+    """A workspace of `kind` as a dict of views, by walking rrt_layout's table: every header word and every section by its
+    name there (fp32 words viewed as fp32, node rows cut to D columns, the pool words unpacked to one index per entry),
+    less the names in `hidden`."""
+    K, lay = rrt_layout.KINDS[kind], rrt_layout.offsets(kind, ws.B, ws.max_nodes, ws.n_pre, ws.D)
+    w = ws.buf
+    glob = dict(zip(rrt_layout.GLOBAL, w[:len(rrt_layout.GLOBAL)].tolist()))
+    if glob != dict(magic=K.magic, B=ws.B, max_nodes=ws.max_nodes, n_pre=ws.n_pre, D=ws.D, Dp=lay.Dp):
+        raise ValueError(f'the workspace was not initialised for these shapes (rrt_{kind}_init)')
+    out = {}
+    for name, (o, typ, shape) in lay.sections.items():
+        t = w[o:o + math.prod(shape)]
+        out[name] = (t.view(torch.float32) if typ == 'f4' else t).reshape(shape)
+    hdr = out.pop('hdr')
+    for name, (i, typ, n) in rrt_layout.header_index(kind).items():
+        t = hdr[:, i:i + n] if n > 1 else hdr[:, i]
+        out[name] = t.view(torch.float32) if typ == 'f4' else t
+    out['nodes'] = out['nodes'][..., :ws.D]
+    per, mask = rrt_layout.POOL_PER_WORD, (1 << rrt_layout.POOL_INDEX_BITS) - 1
+    out['pool'] = torch.stack([(out['pool'] >> (rrt_layout.POOL_INDEX_BITS * k)) & mask for k in range(per)],
+                              dim=-1).reshape(ws.B, per * lay.pool_words)[:, :ws.n_pre]
+    return {name: t for name, t in out.items() if name not in hidden}
+
+
+def rrt_connect_trees(ws):
+    """The trees of a workspace, for tests and rendering: dict of `nodes` (B, 2, max_nodes, D) fp32, `parents`
+    (B, 2, max_nodes) int32 (-1: root), `counts` (B, 2), `iters` (B,) iterations used, `status` (B,), `swap` (B,) and
+    `pool_len` (B,), `pool` (B, n_pre) int32 (entries beyond pool_len are stale).  Tree 0 is rooted at the start, tree 1 at the goal."""
+    return _rrt_read('connect', ws)
+
+
 def rrt_star_tree(ws):
     """The trees of an RRT* workspace, for tests and rendering: dict of `nodes` (B, max_nodes, D) fp32, `parents`
     (B, max_nodes) int32 (-1: root), `d`, `cost` (B, max_nodes) fp32, `count`, `goal` (index, -1: none), `status`,
     `stop_reason`, `iters` (loop bodies started), `pool` (B, n_pre) int32 (entries beyond pool_len are stale), `pool_len`,
-    `rewires`, `informed_rejections`, and the first success: `first_cost`, `first_iter`, `first_count` (all (B,))."""
-    B, M, D = ws.B, ws.max_nodes, ws.D
-    Dp = (D + 3) // 4 * 4
-    w = ws.buf
-    glob = w[:6].tolist()
-    if glob[0] != 0x52525453 or glob[1:5] != [B, M, ws.n_pre, D]:
-        raise ValueError('the workspace was not initialised for these shapes (rrt_star_init)')
-    o = 16
-    hdr = w[o:o + 32 * B].reshape(B, 32)
-    o += 32 * B + B * Dp
-    nodes = w[o:o + B * M * Dp].view(torch.float32).reshape(B, M, Dp)[..., :D]
-    o += B * M * Dp
-    parents = w[o:o + B * M].reshape(B, M)
-    o += B * M
-    d = w[o:o + B * M].view(torch.float32).reshape(B, M)
-    o += B * M
-    cost = w[o:o + B * M].view(torch.float32).reshape(B, M)
-    o += B * M + 3 * B * M
-    pw = (ws.n_pre + 1) // 2
-    pool = w[o:o + B * pw].reshape(B, pw)
-    pool = torch.stack((pool & 0xFFFF, (pool >> 16) & 0xFFFF), dim=-1).reshape(B, 2 * pw)[:, :ws.n_pre]
-    return dict(nodes=nodes, parents=parents, d=d, cost=cost, count=hdr[:, 2], goal=hdr[:, 3], status=hdr[:, 0],
-                stop_reason=hdr[:, 5], iters=hdr[:, 1], pool=pool, pool_len=hdr[:, 4], rewires=hdr[:, 9],
-                informed_rejections=hdr[:, 10], first_cost=hdr[:, 11].view(torch.float32), first_iter=hdr[:, 12],
-                first_count=hdr[:, 13], best_cost_iters=hdr[:, 6], iters_after_first_success=hdr[:, 7])
+    `rewires`, `informed_rejections`, `best_cost_iters`, `iters_after_first_success`, and the first success: `first_cost`,
+    `first_iter`, `first_count` (all (B,))."""
+    return _rrt_read('star', ws, hidden=('goal_q', 'cand', 'best_cost_eps'))

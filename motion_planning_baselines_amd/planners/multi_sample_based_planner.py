@@ -5,7 +5,7 @@ copies are batch-parallel: here they are the problems of ONE batched launch sequ
 (RRTConnect.optimize_batched, RRTStar.optimize_batched), copy c drawing its pool indices from a Philox stream of its own.  The pool keyword
 arguments of the reference (`optimize_sequentially`, MultiProcessor's) are accepted and ignored.
 """
-from .rrt_connect import paths_to_list
+from .rrt_base import paths_to_list
 
 
 class MultiSampleBasedPlanner:

@@ -7,105 +7,24 @@ workgroup of ONE persistent launch of mpb_rrt_connect_run (csrc/mpb_rrt_connect.
 by line -- nearest node, extend_path, safe_path, the order-preserving deletion of a reached pre-sample, the tree-name
 swap with its `continue` quirk, the retrace and purge_duplicates_from_traj.
 
-Differences from the reference, all documented in DESIGN.md section 10:
-  - the loop runs n_iters + 1 iterations exactly like the reference's `while iteration < n_iters` does;
-  - `max_time` is honoured between launches of `chunk_iters` iterations (default 1024), not per iteration;
-  - an emptied pre-sample pool is not refilled on the device: the problem ends with status POOL_EMPTY (cannot happen
-    while n_pre_samples > n_iters: an iteration deletes at most one entry);
-  - a path of more than `max_path_nodes` tree nodes (before duplicates are purged) raises (status PATH_TOO_LONG);
-  - the pre-sample pool holds at most 16 384 configurations (the kernel keeps its index list in LDS).
+Differences from the reference: those every sample-based planner here shares (rrt_base.py), and the loop
+runs n_iters + 1 iterations exactly like the reference's `while iteration < n_iters` does.
 """
-import time
-
-import torch
-
 from .. import ops
-from .._lib import MPBError
-from .base import MPPlanner, require_cuda
+from .rrt_base import RRTBase, paths_to_list  # noqa: F401  (paths_to_list: callers outside the package import it from here)
 
 
-class RRTConnect(MPPlanner):
-
-    def __init__(self, task=None, n_iters=None, start_state_pos=None, step_size=0.1, n_radius=1., max_time=60.,
-                 goal_state_pos=None, tensor_args=None, n_pre_samples=10000, pre_samples=None, seed=0, chunk_iters=1024,
-                 max_nodes=None, max_path_nodes=512, **kwargs):
-        assert start_state_pos is not None and goal_state_pos is not None
-        super().__init__(name='RRTConnect', tensor_args=tensor_args)
-        self.device = require_cuda(tensor_args)
-        self.task = task
-        self.n_iters = int(n_iters)
-        self.step_size, self.n_radius, self.max_time = float(step_size), float(n_radius), float(max_time)
-        self.start_state_pos, self.goal_state_pos = start_state_pos, goal_state_pos
-        self.starts = torch.as_tensor(start_state_pos, dtype=torch.float32).reshape(-1, task.q_dim).to(self.device).contiguous()
-        self.goals = torch.as_tensor(goal_state_pos, dtype=torch.float32).reshape(-1, task.q_dim).to(self.device).contiguous()
-        if self.starts.shape != self.goals.shape:
-            raise ValueError('start_state_pos and goal_state_pos must have the same shape, (D,) or (B, D)')
-        self.n_pre_samples = int(n_pre_samples)
-        if not 1 <= self.n_pre_samples <= ops.RRT_MAX_PRE_SAMPLES:
-            raise ValueError(f'n_pre_samples must be in 1 .. {ops.RRT_MAX_PRE_SAMPLES} (the kernel keeps the pool list in LDS)')
-        self.pre_samples = None if pre_samples is None else torch.as_tensor(pre_samples, dtype=torch.float32).to(self.device)
-        self.seed = int(seed)
-        self.chunk_iters = max(1, int(chunk_iters))
-        self.total_iters = self.n_iters + 1                        # `while iteration < n_iters: iteration += 1` (rrt_connect.py:115-116)
-        self.max_nodes = int(max_nodes) if max_nodes is not None else self.total_iters + 1
-        self.max_path_nodes = int(max_path_nodes)
-        self.workspace = None
-        self.status = None
-        self.reset()
-
-    def reset(self):
-        """Top the pool up to n_pre_samples collision-free configurations (rrt_base.py:47-54)."""
-        have = 0 if self.pre_samples is None else self.pre_samples.shape[0]
-        if have > self.n_pre_samples:
-            raise ValueError(f'pre_samples holds {have} configurations, n_pre_samples is {self.n_pre_samples}')
-        fresh = self.task.random_coll_free_q(self.n_pre_samples - have, 1000)
-        self.pre_samples = (fresh if self.pre_samples is None else torch.cat((self.pre_samples, fresh), dim=0)).contiguous()
+class RRTConnect(RRTBase):
+    NAME, Workspace = 'RRTConnect', ops.RRTWorkspace
 
     def optimize_batched(self, sample_idx=None, n_copies=1, problem_offset=0, **observation):
         """All problems (every start / goal row, n_copies times, copy-major) in one launch sequence.
         sample_idx: None (device Philox; problem b draws from stream problem_offset + b) or (B, n_iters + 1) int32 recorded
         pool indices.  Returns (paths (B, max_path_nodes, D), lengths (B,) int32 -- 0 where no path --, status (B,) int32)
         as device tensors; the trees stay readable through ops.rrt_connect_trees(self.workspace)."""
-        n_copies = int(n_copies)
-        starts = self.starts.repeat(n_copies, 1) if n_copies > 1 else self.starts
-        goals = self.goals.repeat(n_copies, 1) if n_copies > 1 else self.goals
-        B, D = starts.shape
-        ws = ops.RRTWorkspace(B, self.max_nodes, self.n_pre_samples, D, self.device)
-        geom = self.task.geom
-        ops.rrt_connect_init(ws.buf, ws, starts, goals, geom)
-        paths = torch.zeros(B, self.max_path_nodes, D, device=self.device, dtype=torch.float32)
-        lengths = torch.zeros(B, device=self.device, dtype=torch.int32)
-        status = torch.zeros(B, device=self.device, dtype=torch.int32)
-        if sample_idx is not None:
-            sample_idx = torch.as_tensor(sample_idx, dtype=torch.int32).to(self.device).reshape(B, self.total_iters).contiguous()
-        t0 = time.perf_counter()
-        it = 0
-        while it < self.total_iters:
-            n = min(self.chunk_iters, self.total_iters - it)
-            ops.rrt_connect_run(ws.buf, ws, geom, self.pre_samples, sample_idx, paths, lengths, status, it, n, self.total_iters,
-                                self.step_size, self.n_radius, seed=self.seed, problem_offset=problem_offset)
-            it += n
-            if it < self.total_iters:
-                if not bool((status == ops.RRT_RUNNING).any().item()):
-                    break
-                if time.perf_counter() - t0 >= self.max_time:       # chunk granularity
-                    break
-        self.workspace, self.status = ws, status
-        if bool((status == ops.RRT_PATH_TOO_LONG).any().item()):
-            raise MPBError(f'RRTConnect: a path has more than max_path_nodes = {self.max_path_nodes} tree nodes (status '
-                           f'PATH_TOO_LONG); construct the planner with a larger max_path_nodes')
-        return paths, lengths, status
+        out = self._run_batched([sample_idx], n_copies, problem_offset)
+        return out['paths'], out['lengths'], out['status']
 
-    def optimize(self, opt_iters=None, **observation):
-        """One problem: the (n, D) path or None like the reference; several: a list of those."""
-        paths, lengths, status = self.optimize_batched(**observation)
-        out = paths_to_list(paths, lengths)
-        return out[0] if len(out) == 1 else out
-
-    def render(self, ax, **kwargs):
-        raise NotImplementedError
-
-
-def paths_to_list(paths, lengths):
-    """(paths (B, Lmax, D), lengths (B,)) -> list of (n_b, D) device tensors, None where lengths[b] == 0."""
-    return [paths[b, :n].clone() if n > 0 else None for b, n in enumerate(lengths.tolist())]
+    def _launch(self, ws, draws, out, it, n, problem_offset):
+        ops.rrt_connect_run(ws.buf, ws, self.task.geom, self.pre_samples, draws[0], out['paths'], out['lengths'], out['status'], it, n,
+                            self.total_iters, self.step_size, self.n_radius, seed=self.seed, problem_offset=problem_offset)

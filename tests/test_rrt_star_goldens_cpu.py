@@ -27,12 +27,13 @@ def _tolerances(g):
 
 @pytest.mark.parametrize('name', SCENES)
 def test_every_golden_passes_the_checker(name):
+    from motion_planning_baselines_amd import ops
     g, robot, field = _scene(name)
     assert int(g['n_problems']) >= 8
     assert int(g['n_iters']) == 400 and int(g['n_iters_after_success']) == 150
     for k in range(int(g['n_problems'])):
         check_rrt_star_result(robot, field, *golden_star_problem(g, k), float(g['step_size']), float(g['n_radius']), **_tolerances(g))
-        assert int(g['stop_reason'][k]) in (1, 3) and int(g['n_iterations'][k]) <= 401
+        assert int(g['stop_reason'][k]) in (ops.RRT_STOP_ITERS, ops.RRT_STOP_AFTER_SUCCESS) and int(g['n_iterations'][k]) <= 401
 
 
 @pytest.mark.parametrize('name', SCENES)
