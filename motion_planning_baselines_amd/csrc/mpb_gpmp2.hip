@@ -739,138 +739,91 @@ static bool gp_shape_ok(int B, int H, int D) { return B >= 0 && H >= 2 && H <= G
 // the block elimination keeps a 2D x 2D block in ONE 16 x 16 matrix-core tile: D <= 8; beyond that (D <= 12) only the low-rank form applies
 #define GP_BLOCK_MAX_DOF 8
 
-extern "C" size_t mpb_gpmp2_workspace_bytes(int B, int H, int D) {
-    if (!gp_shape_ok(B, H, D)) return 0;
-    const size_t jac = (size_t)MPB_MAX_FIELDS * B * H * (D + 1) * sizeof(float);   // one (h, c) set per chained field
-    const size_t diag = 2 * (size_t)H * 2 * D * sizeof(double);
+GpLayout gp_layout(int B, int H, int D) {
+    const size_t diag_sum = ((size_t)MPB_MAX_FIELDS * B * H * (D + 1) * sizeof(float) + 255) / 256 * 256;   // behind jac: (h, c) per chained field
+    const size_t vec = (size_t)H * 2 * D * sizeof(double), solve = diag_sum + (2 * vec + 255) / 256 * 256;   // (sections start at multiples of 256)
     // the elimination records of the block form -- or the tables and sweep records of the low-rank form (mpb_gpmp2_lr.hip), whichever is larger
-    size_t fz = (size_t)B * H * GP_WS_PER_T * sizeof(double);
-    const size_t lr = mpb_gpmp2_lr_ws_doubles(B, H, D) * sizeof(double);
-    if (fz < lr) fz = lr;
-    return ((jac + 255) / 256) * 256 + ((diag + 255) / 256) * 256 + fz;
+    const size_t block = (size_t)B * H * GP_WS_PER_T * sizeof(double), lr = mpb_gpmp2_lr_ws_doubles(B, H, D) * sizeof(double);
+    return {0, diag_sum, diag_sum + vec, solve, solve + (block < lr ? lr : block)};
 }
+extern "C" size_t mpb_gpmp2_workspace_bytes(int B, int H, int D) { return gp_shape_ok(B, H, D) ? gp_layout(B, H, D).total : 0; }
 
-struct GpWork {
-    float* jac;
-    double* diag_sum;
-    double* diag_mean;
-    double* fz;
-};
-static GpWork gp_carve(void* ws, int B, int H, int D) {
-    GpWork w;
-    char* p = (char*)ws;
-    w.jac = (float*)p;
-    p += (((size_t)MPB_MAX_FIELDS * B * H * (D + 1) * sizeof(float)) + 255) / 256 * 256;
-    w.diag_sum = (double*)p;
-    w.diag_mean = w.diag_sum + (size_t)H * 2 * D;
-    p += ((2 * (size_t)H * 2 * D * sizeof(double)) + 255) / 256 * 256;
-    w.fz = (double*)p;
-    return w;
-}
-
-extern "C" int mpb_gpmp2_linearize(const float* x, const float* geom, int geom_flags, void* workspace, int B, int H, int D,
-                                   int n_interp, void* stream) {
-    if (!x || !geom || !workspace) return mpb_fail(MPB_E_INVALID, "mpb_gpmp2_linearize: null pointer");
+// The argument check of every entry point, which says what it `need`s, in the order they always refused in.  A PASS ALSO CARVES THE WORKSPACE (c.at)
+enum { GP_X = 1, GP_ENDS = 2, GP_GEOM = 4, GP_ALIGNED = 8, GP_INTERP = 16, GP_FIELDS = 32 };
+static int gp_check(GpCall& c, const char* who, int need, int n_iters = 0) {
+    if (!c.workspace || (need & GP_X && !c.x) || (need & GP_ENDS && (!c.start || !c.goal)) || (need & GP_GEOM && !c.geom))
+        return mpb_failf(MPB_E_INVALID, "%s: null pointer", who);
     // (waypoint rows are read as 8-byte pieces, the Jacobian rows written as 16-byte pieces)
-    if (((uintptr_t)x & 15u) || ((uintptr_t)workspace & 255u) || ((uintptr_t)geom & 15u))
-        return mpb_fail(MPB_E_INVALID, "mpb_gpmp2_linearize: x / geom must be 16-byte aligned and the workspace 256-byte aligned");
-    if (!gp_shape_ok(B, H, D) || n_interp < 0 || n_interp > 64) return mpb_fail(MPB_E_INVALID, "mpb_gpmp2_linearize: bad shape");
-    if (B == 0) return MPB_OK;
-    GpWork w = gp_carve(workspace, B, H, D);
+    if (need & GP_ALIGNED && (mpb_misaligned16(c.x, need & GP_GEOM ? c.geom : nullptr) || mpb_misaligned256(c.workspace)))
+        return mpb_failf(MPB_E_INVALID, "%s: %s must be 16-byte aligned and the workspace 256-byte aligned", who, need & GP_GEOM ? "x / geom" : "x");
+    if (!gp_shape_ok(c.B, c.H, c.D) || n_iters < 0 || (need & GP_INTERP && (c.n_interp < 0 || c.n_interp > 64)) ||
+        (need & GP_FIELDS && (c.n_fields < 1 || c.n_fields > MPB_MAX_FIELDS)))
+        return mpb_failf(MPB_E_INVALID, "%s: bad shape", who);
+    c.at = gp_layout(c.B, c.H, c.D);
+    return MPB_OK;
+}
+
+// Which form solves a call.  The low-rank form (round 6, mpb_gpmp2_lr.hip: A0 shared by all particles and factored once per iteration,
+// a dense solve of the size of a particle's ACTIVE collision rows) wherever its LDS tile holds the rows (F (H - 1) <= 127);
+// the block elimination otherwise.  MPB_GPMP2_FORM = lr / block forces one (tests, A/B timing); MPB_GPMP2_SM set
+// (either value) means the block form, as before round 6.   (read per call: the tests switch within one process)
+struct GpPlan { int rc; bool low_rank, split, sm; };    // rc: a refusal; split (two waves per particle), sm (Sherman-Morrison): of the block form
+static GpPlan gp_plan(const GpCall& c, double sigma_gp_over_coll) {
+    const char* form_env = getenv("MPB_GPMP2_FORM");
+    const bool want_block = (form_env && !strcmp(form_env, "block")) || (!form_env && getenv("MPB_GPMP2_SM") != nullptr);
+    if (form_env && !strcmp(form_env, "lr") && !mpb_gpmp2_lr_ok(c.H, c.D, c.n_fields))
+        return {mpb_fail(MPB_E_UNSUPPORTED, "mpb_gpmp2_solve: MPB_GPMP2_FORM=lr, but n_fields * (H - 1) > 127")};
+    if (c.D > GP_BLOCK_MAX_DOF && (want_block || !mpb_gpmp2_lr_ok(c.H, c.D, c.n_fields)))
+        return {mpb_fail(MPB_E_UNSUPPORTED, "mpb_gpmp2_solve: more than 8 degrees of freedom need the low-rank form (n_fields * (H - 1) <= 127, H <= 128)")};
+    GpPlan p = {MPB_OK, !want_block && mpb_gpmp2_lr_ok(c.H, c.D, c.n_fields)};
+    if (p.low_rank) return p;
+    // two waves per particle (sweeps from both ends of the chain, see the kernel) halve the sequential chain: B = 256 -32 %; at B = 2048 the
+    // instruction throughput is the bound and both forms take the same time (measured).  The one-wave form remains for chains too short to split
+    static const int force_split = getenv("MPB_GPMP2_SPLIT") ? atoi(getenv("MPB_GPMP2_SPLIT")) : -1;   // tuning aid
+    p.split = (c.H >= 4) && (force_split >= 0 ? force_split != 0 : 1);
+    // Sherman-Morrison form of the collision factors (template flag SM, see the kernel): selected when the collision precision exceeds the GP
+    // precision by more than 1e7 (x the number of fields) -- below that the assembled form is accurate to <= 2e-6 of the step (tests) and C4 (ratio
+    // 1e6) keeps the kernel it was tuned with.  MPB_GPMP2_SM = 0 / 1 forces a form (A/B timing and the tests that run both on the same system).
+    const char* sm_env = getenv("MPB_GPMP2_SM");            // (read per call: the tests switch it within one process)
+    const int force_sm = sm_env ? atoi(sm_env) : -1;
+    p.sm = force_sm >= 0 ? force_sm != 0 : sigma_gp_over_coll * sigma_gp_over_coll * c.n_fields > 1e7;
+    return p;
+}
+
+static int gp_linearize(const GpCall& c) {
     // geom_flags (mpb_geom_flags of the host copy): the compile-time robot model of EVERY chained field, and all of them backed by
     // compact grids -- the model kernel needs both
-#ifndef GP_LIN_WPE
-#define GP_LIN_WPE 3
-#endif
-    const bool model = mpb_flags_model_on_grids(geom_flags, PandaModel::ID) && D == PandaModel::N_DOF;
-#define GP_LIN(MODEL, INTERP, WPE)                                                                                           \
-    hipLaunchKernelGGL((gpmp2_linearize_kernel<MODEL, INTERP, WPE>), dim3((B + 3) / 4), dim3(256), 0, (hipStream_t)stream, x, \
-                       geom, w.jac, B, H, D, n_interp)
-    if (model && n_interp == 0) GP_LIN(PandaModel::ID, false, GP_LIN_WPE);
+    const bool model = mpb_flags_model_on_grids(c.geom_flags, PandaModel::ID) && c.D == PandaModel::N_DOF;
+#define GP_LIN(MODEL, INTERP, WPE)                                                                                                     \
+    hipLaunchKernelGGL((gpmp2_linearize_kernel<MODEL, INTERP, WPE>), dim3((c.B + 3) / 4), dim3(256), 0, c.stream, (const float*)c.x, \
+                       c.geom, (float*)(c.workspace + c.at.jac), c.B, c.H, c.D, c.n_interp)
+    if (model && c.n_interp == 0) GP_LIN(PandaModel::ID, false, 3);
     else if (model) GP_LIN(PandaModel::ID, true, 2);
-    else if (n_interp == 0) GP_LIN(0, false, 2);
+    else if (c.n_interp == 0) GP_LIN(0, false, 2);
     else GP_LIN(0, true, 2);
 #undef GP_LIN
     return mpb_check_launch("mpb_gpmp2_linearize");
 }
-
-extern "C" int mpb_gpmp2_diag(void* workspace, double* diag_sum_out, int B, int H, int D, int n_fields, float dt,
-                              float sigma_start, float sigma_gp, float sigma_goal, float sigma_coll, void* stream) {
-    if (!workspace) return mpb_fail(MPB_E_INVALID, "mpb_gpmp2_diag: null pointer");
-    if (!gp_shape_ok(B, H, D) || n_fields < 1 || n_fields > MPB_MAX_FIELDS) return mpb_fail(MPB_E_INVALID, "mpb_gpmp2_diag: bad shape");
-    GpWork w = gp_carve(workspace, B, H, D);
-    double* out = diag_sum_out ? diag_sum_out : w.diag_sum;
-    // workspace mode (one GPU): the LOCAL mean goes to the workspace in the same pass (what mpb_gpmp2_solve reads when it is
-    // given no diag_mean); with diag_sum_out the host all-reduces the sums over the shards and passes the global mean itself
-    hipLaunchKernelGGL(gpmp2_diag_kernel, dim3(H), dim3(256), 0, (hipStream_t)stream, w.jac, out,
-                       diag_sum_out ? (double*)nullptr : w.diag_mean, B, H, D, n_fields, (double)dt,
-                       1.0 / ((double)sigma_start * sigma_start), 1.0 / ((double)sigma_gp * sigma_gp),
-                       (sigma_goal > 0.f ? 1.0 / ((double)sigma_goal * sigma_goal) : 0.0), 1.0 / ((double)sigma_coll * sigma_coll));
+// workspace mode (no diag_sum_out: one GPU): the LOCAL mean goes to the workspace in the same pass (what the solve reads when it is
+// given no diag_mean); with diag_sum_out the host all-reduces the sums over the shards and passes the global mean itself
+static int gp_diag(const GpCall& c, double* diag_sum_out) {
+    double *const sum = (double*)(c.workspace + c.at.diag_sum), *const mean = (double*)(c.workspace + c.at.diag_mean);
+    hipLaunchKernelGGL(gpmp2_diag_kernel, dim3(c.H), dim3(256), 0, c.stream, (float*)(c.workspace + c.at.jac), diag_sum_out ? diag_sum_out : sum,
+                       diag_sum_out ? (double*)nullptr : mean, c.B, c.H, c.D, c.n_fields, c.K.dt, c.K.ks, c.K.kgp, c.K.kg, c.K.kc);
     return mpb_check_launch("mpb_gpmp2_diag");
 }
-
-extern "C" int mpb_gpmp2_solve(float* x, const float* start, const float* goal, const double* diag_mean, void* workspace,
-                               float* costs_out, int B, int H, int D, int n_fields, float dt, float sigma_start,
-                               float sigma_gp, float sigma_goal, float sigma_coll, float delta, int trust_region,
-                               float step_size, void* stream) {
-    if (!x || !start || !goal || !workspace) return mpb_fail(MPB_E_INVALID, "mpb_gpmp2_solve: null pointer");
-    if (((uintptr_t)x & 15u) || ((uintptr_t)workspace & 255u))
-        return mpb_fail(MPB_E_INVALID, "mpb_gpmp2_solve: x must be 16-byte aligned and the workspace 256-byte aligned");
-    if (!gp_shape_ok(B, H, D) || n_fields < 1 || n_fields > MPB_MAX_FIELDS) return mpb_fail(MPB_E_INVALID, "mpb_gpmp2_solve: bad shape");
-    if (B == 0) return MPB_OK;
-    GpWork w = gp_carve(workspace, B, H, D);
-    GpConst K;
-    K.dt = dt;
-    K.ks = 1.0 / ((double)sigma_start * sigma_start);
-    K.kgp = 1.0 / ((double)sigma_gp * sigma_gp);
-    K.kg = (sigma_goal > 0.f ? 1.0 / ((double)sigma_goal * sigma_goal) : 0.0);
-    K.kc = 1.0 / ((double)sigma_coll * sigma_coll);
-    K.delta = delta;
-    K.step = step_size;
-    K.trust = trust_region;
-    const double* dm = trust_region ? (diag_mean ? diag_mean : w.diag_mean) : nullptr;
-    // ---- which form.  The low-rank form (round 6, mpb_gpmp2_lr.hip: A0 shared by all particles and factored once per iteration,
-    // a dense solve of the size of a particle's ACTIVE collision rows) wherever its LDS tile holds the rows (F (H - 1) <= 127);
-    // the block elimination below otherwise.  MPB_GPMP2_FORM = lr / block forces one (tests, A/B timing); MPB_GPMP2_SM set
-    // (either value) means the block form, as before round 6.   (read per call: the tests switch within one process)
-    {
-        const char* form_env = getenv("MPB_GPMP2_FORM");
-        const bool want_block = (form_env && !strcmp(form_env, "block")) || (!form_env && getenv("MPB_GPMP2_SM") != nullptr);
-        if (form_env && !strcmp(form_env, "lr") && !mpb_gpmp2_lr_ok(H, D, n_fields))
-            return mpb_fail(MPB_E_UNSUPPORTED, "mpb_gpmp2_solve: MPB_GPMP2_FORM=lr, but n_fields * (H - 1) > 127");
-        if (D > GP_BLOCK_MAX_DOF && (want_block || !mpb_gpmp2_lr_ok(H, D, n_fields)))
-            return mpb_fail(MPB_E_UNSUPPORTED, "mpb_gpmp2_solve: more than 8 degrees of freedom need the low-rank form (n_fields * (H - 1) <= 127, H <= 128)");
-        if (!want_block && mpb_gpmp2_lr_ok(H, D, n_fields)) {
-            int rc = mpb_gpmp2_lr_launch(x, start, goal, w.jac, dm, w.fz, costs_out, B, H, D, n_fields, K, (hipStream_t)stream);
-            if (rc) return rc;
-            return mpb_check_launch("mpb_gpmp2_solve (low-rank form)");
-        }
-    }
-    // two waves per particle (sweeps from both ends of the chain, see the kernel) halve the sequential chain: B = 256
-    // -32 %; at B = 2048 the instruction throughput is the bound and both forms take the same time (measured).  The
-    // one-wave form remains for chains too short to split
-    static const int force_split = getenv("MPB_GPMP2_SPLIT") ? atoi(getenv("MPB_GPMP2_SPLIT")) : -1;   // tuning aid
-    const int split = (H >= 4) && (force_split >= 0 ? force_split != 0 : 1);
-    // Sherman-Morrison form of the collision factors (template flag SM, see the kernel): selected when the collision precision
-    // exceeds the GP precision by more than 1e7 (x the number of fields) -- below that the assembled form is accurate to
-    // <= 2e-6 of the step (tests) and C4 (ratio 1e6) keeps the kernel it was tuned with.  MPB_GPMP2_SM = 0 / 1 forces a form
-    // (A/B timing and the tests that run both on the same system).
-    const char* sm_env = getenv("MPB_GPMP2_SM");            // (read per call: the tests switch it within one process)
-    const int force_sm = sm_env ? atoi(sm_env) : -1;
-    const double ratio = ((double)sigma_gp / (double)sigma_coll) * ((double)sigma_gp / (double)sigma_coll) * n_fields;
-    const bool sm = force_sm >= 0 ? force_sm != 0 : ratio > 1e7;
-#define GP_LAUNCH_(DT, MULTI, SM)                                                                                              \
-    hipLaunchKernelGGL((gpmp2_solve_kernel<DT, MULTI, SM>), dim3(B), dim3(split ? 128 : 64), 0, (hipStream_t)stream, x, start, \
-                       goal, w.jac, dm, w.fz, costs_out, B, H, D, n_fields, split, K)
-#define GP_LAUNCH(DT)                                      \
-    if (n_fields == 1) {                                   \
-        if (sm) GP_LAUNCH_(DT, false, true);               \
-        else GP_LAUNCH_(DT, false, false);                 \
-    } else {                                               \
-        if (sm) GP_LAUNCH_(DT, true, true);                \
-        else GP_LAUNCH_(DT, true, false);                  \
-    }
-    switch (D) {
+static int gp_solve(const GpCall& c, const GpPlan& plan) {
+    if (plan.low_rank) return mpb_gpmp2_lr_launch(c);
+#define GP_LAUNCH_(DT, MULTI, SM)                                                                                                      \
+    hipLaunchKernelGGL((gpmp2_solve_kernel<DT, MULTI, SM>), dim3(c.B), dim3(plan.split ? 128 : 64), 0, c.stream, c.x, c.start, c.goal,   \
+                       (float*)(c.workspace + c.at.jac), c.damping(), (double*)(c.workspace + c.at.solve), c.costs_out, c.B, c.H, c.D, \
+                       c.n_fields, plan.split, c.K)
+#define GP_LAUNCH(DT)                                                 \
+    if (c.n_fields == 1 && plan.sm) GP_LAUNCH_(DT, false, true);      \
+    else if (c.n_fields == 1) GP_LAUNCH_(DT, false, false);           \
+    else if (plan.sm) GP_LAUNCH_(DT, true, true);                     \
+    else GP_LAUNCH_(DT, true, false)
+    switch (c.D) {
         case 2: GP_LAUNCH(2); break;
         case 3: GP_LAUNCH(3); break;
         case 7: GP_LAUNCH(7); break;
@@ -881,24 +834,43 @@ extern "C" int mpb_gpmp2_solve(float* x, const float* start, const float* goal, 
     return mpb_check_launch("mpb_gpmp2_solve");
 }
 
-extern "C" int mpb_gpmp2_step(float* x, const float* start, const float* goal, const float* geom, int geom_flags, void* workspace,
-                              float* costs_out, int B, int H, int D, float dt, float sigma_start, float sigma_gp,
-                              float sigma_goal, float sigma_coll, float delta, int trust_region, float step_size,
-                              int n_iters, int n_interp, int n_fields, void* stream) {
-    if (!x || !start || !goal || !geom || !workspace) return mpb_fail(MPB_E_INVALID, "mpb_gpmp2_step: null pointer");
-    if (!gp_shape_ok(B, H, D) || n_iters < 0 || n_fields < 1 || n_fields > MPB_MAX_FIELDS)
-        return mpb_fail(MPB_E_INVALID, "mpb_gpmp2_step: bad shape");
+extern "C" int mpb_gpmp2_linearize(const float* x, const float* geom, int geom_flags, void* workspace, int B, int H, int D, int n_interp,
+                                   void* stream) {
+    GpCall c = {(char*)workspace, B, H, D, 0, n_interp, geom_flags, (hipStream_t)stream, {}, const_cast<float*>(x), nullptr, geom};
+    const int rc = gp_check(c, "mpb_gpmp2_linearize", GP_X | GP_GEOM | GP_ALIGNED | GP_INTERP);
+    return rc || B == 0 ? rc : gp_linearize(c);
+}
+extern "C" int mpb_gpmp2_diag(void* workspace, double* diag_sum_out, int B, int H, int D, int n_fields, float dt, float sigma_start, float sigma_gp,
+                              float sigma_goal, float sigma_coll, void* stream) {
+    GpCall c = {(char*)workspace, B, H, D, n_fields, 0, 0, (hipStream_t)stream, gp_const(dt, sigma_start, sigma_gp, sigma_goal, sigma_coll)};
+    const int rc = gp_check(c, "mpb_gpmp2_diag", GP_FIELDS);
+    return rc ? rc : gp_diag(c, diag_sum_out);
+}
+extern "C" int mpb_gpmp2_solve(float* x, const float* start, const float* goal, const double* diag_mean, void* workspace, float* costs_out, int B,
+                               int H, int D, int n_fields, float dt, float sigma_start, float sigma_gp, float sigma_goal, float sigma_coll,
+                               float delta, int trust_region, float step_size, void* stream) {
+    GpCall c = {(char*)workspace, B, H, D, n_fields, 0, 0, (hipStream_t)stream, gp_const(dt, sigma_start, sigma_gp, sigma_goal, sigma_coll,
+                delta, trust_region, step_size), x, costs_out, nullptr, start, goal, diag_mean};
+    if (int rc = gp_check(c, "mpb_gpmp2_solve", GP_X | GP_ENDS | GP_ALIGNED | GP_FIELDS)) return rc;
     if (B == 0) return MPB_OK;
-    for (int it = 0; it < n_iters; ++it) {
-        int rc = mpb_gpmp2_linearize(x, geom, geom_flags, workspace, B, H, D, n_interp, stream);
-        if (rc) return rc;
-        if (trust_region) {
-            rc = mpb_gpmp2_diag(workspace, nullptr, B, H, D, n_fields, dt, sigma_start, sigma_gp, sigma_goal, sigma_coll, stream);
-            if (rc) return rc;
-        }
-        rc = mpb_gpmp2_solve(x, start, goal, nullptr, workspace, costs_out, B, H, D, n_fields, dt, sigma_start, sigma_gp, sigma_goal,
-                             sigma_coll, delta, trust_region, step_size, stream);
-        if (rc) return rc;
+    const GpPlan plan = gp_plan(c, (double)sigma_gp / (double)sigma_coll);
+    return plan.rc ? plan.rc : gp_solve(c, plan);
+}
+extern "C" int mpb_gpmp2_step(float* x, const float* start, const float* goal, const float* geom, int geom_flags, void* workspace, float* costs_out,
+                              int B, int H, int D, float dt, float sigma_start, float sigma_gp, float sigma_goal, float sigma_coll, float delta,
+                              int trust_region, float step_size, int n_iters, int n_interp, int n_fields, void* stream) {
+    GpCall c = {(char*)workspace, B, H, D, n_fields, n_interp, geom_flags, (hipStream_t)stream,
+                gp_const(dt, sigma_start, sigma_gp, sigma_goal, sigma_coll, delta, trust_region, step_size), x, costs_out, geom, start, goal};
+    if (int rc = gp_check(c, "mpb_gpmp2_step", GP_X | GP_ENDS | GP_GEOM | GP_FIELDS, n_iters)) return rc;
+    if (B == 0 || n_iters == 0) return MPB_OK;
+    // only once an iteration runs: the alignment and n_interp tests of its first stage, reported under that stage's name as they always were
+    if (int rc = gp_check(c, "mpb_gpmp2_linearize", GP_X | GP_GEOM | GP_ALIGNED | GP_INTERP)) return rc;
+    const GpPlan plan = gp_plan(c, (double)sigma_gp / (double)sigma_coll);
+    if (plan.rc) return plan.rc;             // (the solve's refusals: before anything is enqueued)
+    for (int it = 0; it < n_iters; ++it) {   // (a stage whose launch failed ends the call before the next is enqueued)
+        int rc = gp_linearize(c);
+        if (!rc && trust_region) rc = gp_diag(c, nullptr);
+        if (rc || (rc = gp_solve(c, plan))) return rc;
     }
-    return mpb_check_launch("mpb_gpmp2_step");
+    return MPB_OK;
 }

@@ -957,54 +957,53 @@ __global__ __launch_bounds__(CAP_THREADS, CAP_WPE) void gpmp2_lr_cap(const float
 }
 
 // ------------------------------------------------------------------------------------------------
-// launcher (called by mpb_gpmp2_solve, mpb_gpmp2.hip)
+// launcher (called by gp_solve, mpb_gpmp2.hip)
 // ------------------------------------------------------------------------------------------------
 bool mpb_gpmp2_lr_ok(int H, int D, int n_fields) { return H >= 2 && D >= 1 && D <= MPB_MAX_DOF && n_fields >= 1 && n_fields * (H - 1) <= LR_NMAX; }
 
-// doubles of workspace: shared tables (cyclic-reduction coefficients, G) + per-batch arrays (the steps, w, the GP cost, g_rest / u0, the order)
-size_t mpb_gpmp2_lr_ws_doubles(int B, int H, int D) {
-    const size_t NL = (size_t)B * D;
-    return 2 * (size_t)D * pcr_coef_entries(H) + (size_t)D * H * H + (size_t)H * NL + (size_t)MPB_MAX_FIELDS * B * H + (size_t)B + 64 +
-           (size_t)B * H * 2 * D +         // ... and g_rest
-           (size_t)B + 1;                  // ... and the size class of every particle + the launch order of the capacitance systems (2 B ints)
+// The low-rank area (GpLayout::solve), offsets in doubles: shared tables (cyclic-reduction coefficients, G), then per-batch arrays
+struct LrLayout { size_t coef, G, dth, wdense, gpcost, grest, ord, total; };
+static LrLayout lr_layout(int B, int H, int D) {
+    LrLayout l = {};                                             // coef, at 0: D tables of pcr_coef_entries(H) 16-byte entries
+    l.G = l.coef + 2 * (size_t)D * pcr_coef_entries(H);
+    l.dth = l.G + (size_t)D * H * H;                             // the steps of the particles with collision rows: (D, B, H) float pairs
+    l.wdense = l.dth + (size_t)H * B * D;                        // w
+    l.gpcost = l.wdense + (size_t)MPB_MAX_FIELDS * B * H;        // the GP cost of every particle
+    l.grest = l.gpcost + (size_t)B                               // g_rest / u0
+              + 64;                                              // ... behind 64 doubles no kernel indexes: what follows stays where it was
+    l.ord = l.grest + (size_t)B * H * 2 * D;                     // [0, B): size class of particle b; [B, 2 B): the particles, largest class first
+    l.total = l.ord + (size_t)B + 1;                             // ... 2 B ints, in B + 1 doubles
+    return l;
 }
+size_t mpb_gpmp2_lr_ws_doubles(int B, int H, int D) { return lr_layout(B, H, D).total; }
 
-int mpb_gpmp2_lr_launch(float* x, const float* start, const float* goal, const float* jac, const double* diag_mean, double* ws,
-                        float* costs_out, int B, int H, int D, int n_fields, const GpConst& K, hipStream_t stream) {
-    const size_t NL = (size_t)B * D;
-    const int L = pcr_levels(H);
+int mpb_gpmp2_lr_launch(const GpCall& c) {
+    const int B = c.B, H = c.H, D = c.D, n_fields = c.n_fields, L = pcr_levels(H), n_cu = mpb_device_cu_count();
     const size_t n_coef = pcr_coef_entries(H);
-    double* coef = ws;                                                   // D tables of n_coef 16-byte entries
-    double* G = coef + 2 * (size_t)D * n_coef;
-    double* dth = G + (size_t)D * H * H;                                 // the steps of the particles with collision rows: (D, B, H) float pairs
-    double* wdense = dth + (size_t)H * NL;
-    double* gpcost = wdense + (size_t)MPB_MAX_FIELDS * B * H;
-    double* grest = gpcost + B + 64;
-    int* ord = reinterpret_cast<int*>(grest + (size_t)B * H * 2 * D);        // [0, B): size class of particle b; [B, 2 B): the particles, largest class first
-    static const int n_cu = [] {
-        int dev = 0, n = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-        return n;
-    }();
+    const LrLayout at = lr_layout(B, H, D);
+    double *const ws = (double*)(c.workspace + c.at.solve), *coef = ws + at.coef, *G = ws + at.G, *dth = ws + at.dth, *wdense = ws + at.wdense;
+    double *gpcost = ws + at.gpcost, *grest = ws + at.grest;
+    int* ord = reinterpret_cast<int*>(ws + at.ord);
+    const float* jac = (const float*)(c.workspace + c.at.jac);
     const size_t lds_rows = (size_t)PCR_WAVES * PCR_NP * H * sizeof(lr_d2);
     const size_t lds_setup = n_coef * sizeof(lr_d2) + 12 * (size_t)H * sizeof(double) + lds_rows;
     const size_t lds_solve = n_coef * sizeof(lr_d2) + lds_rows;
     const int NY = (H + 15) / 16;                                                // sixteen columns per block (one pass of eight of its waves: 12 us where a full pass of 32 columns took 15)
-    hipLaunchKernelGGL(gpmp2_pcr_setup, dim3(D, NY), dim3(PCR_THREADS), lds_setup, stream, diag_mean, coef, G, H, D, L, K);
-    hipLaunchKernelGGL(gpmp2_lr_gradient, dim3(B), dim3(256), 0, stream, x, start, goal, jac, grest, gpcost, ord, B, H, D, n_fields, K);
+    hipLaunchKernelGGL(gpmp2_pcr_setup, dim3(D, NY), dim3(PCR_THREADS), lds_setup, c.stream, c.damping(), coef, G, H, D, L, c.K);
+    hipLaunchKernelGGL(gpmp2_lr_gradient, dim3(B), dim3(256), 0, c.stream, c.x, c.start, c.goal, jac, grest, gpcost, ord, B, H, D, n_fields, c.K);
     // particle groups: one block per CU over the D joints, at least one pass of the waves per group
     int NG = n_cu / D;
     if (NG < 1) NG = 1;
     if (NG > (B + PCR_WAVES * PCR_NP - 1) / (PCR_WAVES * PCR_NP)) NG = (B + PCR_WAVES * PCR_NP - 1) / (PCR_WAVES * PCR_NP);
-    hipLaunchKernelGGL(gpmp2_pcr_solve<false>, dim3(D, NG + 1), dim3(PCR_THREADS), lds_solve, stream, grest, jac, wdense, coef, dth, ord, B, H, D,
-                       n_fields, L, NG, K);
+    hipLaunchKernelGGL(gpmp2_pcr_solve<false>, dim3(D, NG + 1), dim3(PCR_THREADS), lds_solve, c.stream, grest, jac, wdense, coef, dth, ord, B, H, D,
+                       n_fields, L, NG, c.K);
     const int n_max = n_fields * (H - 1);
     const int trm = (n_max + 16) >> 4, ntm = (trm * (trm + 1)) >> 1;             // tiles of the largest system the shape allows
     const size_t lds = ((size_t)ntm * LR_TILE + 256) * sizeof(double) + (size_t)LR_NMAX * (D <= 8 ? 8 : MPB_MAX_DOF) * sizeof(float) + (256 + 16) * sizeof(int);
-    if (D <= 8) hipLaunchKernelGGL(gpmp2_lr_cap<8>, dim3(B), dim3(CAP_THREADS), lds, stream, jac, grest, G, gpcost, wdense, costs_out, ord, x, B, H, D, n_fields, ntm, K);
-    else hipLaunchKernelGGL(gpmp2_lr_cap<MPB_MAX_DOF>, dim3(B), dim3(CAP_THREADS), lds, stream, jac, grest, G, gpcost, wdense, costs_out, ord, x, B, H, D, n_fields, ntm, K);
-    hipLaunchKernelGGL(gpmp2_pcr_solve<true>, dim3(D, NG), dim3(PCR_THREADS), lds_solve, stream, grest, jac, wdense, coef, dth, ord, B, H, D,
-                       n_fields, L, NG, K);
-    hipLaunchKernelGGL(gpmp2_lr_apply, dim3(B), dim3(256), 0, stream, x, reinterpret_cast<const float2*>(dth), grest, ord, B, H, D, K.step);
-    return MPB_OK;
+    if (D <= 8) hipLaunchKernelGGL(gpmp2_lr_cap<8>, dim3(B), dim3(CAP_THREADS), lds, c.stream, jac, grest, G, gpcost, wdense, c.costs_out, ord, c.x, B, H, D, n_fields, ntm, c.K);
+    else hipLaunchKernelGGL(gpmp2_lr_cap<MPB_MAX_DOF>, dim3(B), dim3(CAP_THREADS), lds, c.stream, jac, grest, G, gpcost, wdense, c.costs_out, ord, c.x, B, H, D, n_fields, ntm, c.K);
+    hipLaunchKernelGGL(gpmp2_pcr_solve<true>, dim3(D, NG), dim3(PCR_THREADS), lds_solve, c.stream, grest, jac, wdense, coef, dth, ord, B, H, D,
+                       n_fields, L, NG, c.K);
+    hipLaunchKernelGGL(gpmp2_lr_apply, dim3(B), dim3(256), 0, c.stream, c.x, reinterpret_cast<const float2*>(dth), grest, ord, B, H, D, c.K.step);
+    return mpb_check_launch("mpb_gpmp2_solve (low-rank form)");
 }

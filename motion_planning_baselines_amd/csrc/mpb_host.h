@@ -34,6 +34,15 @@ static inline bool mpb_misaligned16(const void* a, const void* b = nullptr, cons
                                     const void* e = nullptr, const void* f = nullptr) {
     return ((((uintptr_t)a) | ((uintptr_t)b) | ((uintptr_t)c) | ((uintptr_t)d) | ((uintptr_t)e) | ((uintptr_t)f)) & 15u) != 0;
 }
+static inline bool mpb_misaligned256(const void* a) { return (((uintptr_t)a) & 255u) != 0; }   // (a workspace carved at 256-byte steps)
+// compute units of the current device, 256 where it cannot be asked (every GPU of a node is the same part: asked once per translation unit)
+static inline int mpb_device_cu_count() {
+    static const int n_cu = [] {
+        int dev = 0, n = 0;
+        return hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0 ? n : 256;
+    }();
+    return n_cu;
+}
 // what the geom_flags of mpb_geom_flags (MPB_GEOM_FLAG_* of include/mpb_geom_layout.h; include/mpb.h says what each promises) tell a
 // launcher: the compile-time robot model every chained field is tagged with (0: none) ...
 static inline int mpb_flags_model(int geom_flags) { return geom_flags & MPB_GEOM_FLAG_MODEL_MASK; }

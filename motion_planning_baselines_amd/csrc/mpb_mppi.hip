@@ -563,11 +563,7 @@ extern "C" int mpb_mppi_step(float* mean, const float* eps, const float* scale_t
     // one wave per sample, at most 16 waves per problem.  With at least two problems per CU, workgroups of 8 waves (two
     // resident per CU: one problem's barriers and serial sections run under the other's rollouts) are 16 % faster than
     // 16 (NP = 1 024, S = 32, T = 64: 68.7 against 81.5 us per iteration); a single problem is fastest on 16
-    static const int n_cu = [] {
-        int dev = 0, n = 256;
-        if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
-        return n > 0 ? n : 256;
-    }();
+    const int n_cu = mpb_device_cu_count();
     int nw = S < 16 ? S : 16;
     if (NP >= 2 * n_cu && S >= 16) nw = 8;
     if (force_nw > 0 && force_nw <= 16 && force_nw <= S) nw = force_nw;

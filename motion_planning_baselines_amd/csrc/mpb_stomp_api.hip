@@ -160,15 +160,6 @@ extern "C" int mpb_stomp_step_profile(float* means, float* samples, float* costs
 // ------------------------------------------------------------------------------------------------
 // the persistent loop: which form serves a call, its workspace, the call itself
 // ------------------------------------------------------------------------------------------------
-static int device_cu_count() {       // (every GPU of a node is the same part: asked once)
-    static const int n_cu = [] {
-        int dev = 0, n = 256;
-        if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
-        return n > 0 ? n : 256;
-    }();
-    return n_cu;
-}
-
 // which form of the loop serves a call, and the workspace it needs
 struct FusedPlan {
     int path;            // MPB_STOMP_PATH_*: 0 two-kernel loop, 1 persistent with exchange, 2 persistent one workgroup per particle
@@ -180,7 +171,7 @@ struct FusedPlan {
 static FusedPlan fused_plan(int geom_flags, int P, int S, int H, int d) {
     FusedPlan f = {MPB_STOMP_PATH_TWO_KERNEL, 1, false, 1, 0};
     if (P < 1 || S < 1) return f;
-    const int n_cu = device_cu_count();
+    const int n_cu = mpb_device_cu_count();
     // MPB_STOMP_HX = 1 sends every shape to the generalised kernel (a test aid: it is compared with the H = 64 kernel)
     const char* hx_env = getenv("MPB_STOMP_HX");
     const int force_hx = hx_env ? atoi(hx_env) : 0;

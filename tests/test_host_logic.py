@@ -363,6 +363,149 @@ def test_stomp_workspace_size():
     assert path(GRIDS, 1 << 30, 2, 128, 32, 7) == 1 and path(GRIDS, 1 << 30, 128, 32, 64, 5) == 1  # S = 128; d = 5
 
 
+def test_gpmp2_workspace_size():
+    """mpb_gpmp2_workspace_bytes (GpLayout, csrc/mpb_gpmp2.h) against byte counts recorded from the library as it was before the layout
+    had one definition: jac for MPB_MAX_FIELDS fields and the two diagonal vectors, each rounded up to 256 bytes, and the larger of the block
+    form's elimination records and the low-rank area -- which is counted for every H, also beyond that form's tile."""
+    from motion_planning_baselines_amd import _lib
+    f = _lib.lib().mpb_gpmp2_workspace_bytes
+    assert f(0, 64, 7) == 430600 and f(1, 2, 1) == 2944 and f(2, 8, 2) == 20736 and f(3, 64, 7) == 493624
+    assert f(2, 128, 12) == 2495016 and f(2, 256, 7) == 4870696 and f(2048, 128, 7) == 352350208
+    assert f(2, 1, 7) == 0 and f(2, 257, 7) == 0 and f(2, 8, 0) == 0 and f(2, 8, 13) == 0 and f(-1, 8, 2) == 0
+
+
+def _gpmp2_refusal_calls():
+    """(label, environment, entry point, arguments) of every refused GPMP2 call of the table below, and of the B == 0 / n_iters == 0
+    calls that return before a launch.  Pointers are host memory: none of these calls may reach a kernel."""
+    import ctypes
+    buf = (ctypes.c_char * 1024)()
+    ok = (ctypes.addressof(buf) + 255) & ~255                 # 256-byte aligned; + 16: 16-byte but not 256-byte aligned; + 4: neither
+    _gpmp2_refusal_calls.keep = buf
+    base = dict(x=ok, start=ok, goal=ok, geom=ok, ws=ok, B=2, H=8, D=2, n_interp=0, n_fields=1, n_iters=1)
+    sig = (0.04, 1e-3, 1.0, 1e-3, 1e-2)                       # dt, sigma_start, sigma_gp, sigma_goal, sigma_coll
+    pack = {
+        'linearize': lambda a: (a['x'], a['geom'], 0, a['ws'], a['B'], a['H'], a['D'], a['n_interp'], None),
+        'diag': lambda a: (a['ws'], None, a['B'], a['H'], a['D'], a['n_fields'], *sig, None),
+        'solve': lambda a: (a['x'], a['start'], a['goal'], None, a['ws'], None, a['B'], a['H'], a['D'], a['n_fields'], *sig, 1e-2, 1, 1.0, None),
+        'step': lambda a: (a['x'], a['start'], a['goal'], a['geom'], 0, a['ws'], None, a['B'], a['H'], a['D'], *sig, 1e-2, 1, 1.0,
+                           a['n_iters'], a['n_interp'], a['n_fields'], None),
+    }
+    takes = {'linearize': ('x', 'geom', 'ws', 'n_interp'), 'diag': ('ws', 'n_fields'), 'solve': ('x', 'start', 'goal', 'ws', 'n_fields'),
+             'step': ('x', 'start', 'goal', 'geom', 'ws', 'n_interp', 'n_fields', 'n_iters')}
+    aligned = {'linearize': ('x', 'geom', 'ws'), 'diag': (), 'solve': ('x', 'ws'), 'step': ('x', 'geom', 'ws')}   # (solve never reads geom)
+    shapes = [('H=1', dict(H=1)), ('H=257', dict(H=257)), ('D=0', dict(D=0)), ('D=13', dict(D=13)), ('B=-1', dict(B=-1)),
+              ('n_interp=-1', dict(n_interp=-1)), ('n_interp=65', dict(n_interp=65)), ('n_fields=0', dict(n_fields=0)),
+              ('n_fields=5', dict(n_fields=5)), ('n_iters=-1', dict(n_iters=-1))]
+
+    def call(entry, label, env=None, **change):
+        return ('%s %s' % (entry, label), env or {}, 'mpb_gpmp2_' + entry, pack[entry](dict(base, **change)))
+    for entry in ('linearize', 'diag', 'solve', 'step'):
+        for p in takes[entry]:
+            if not p.startswith('n_'):
+                yield call(entry, p + ' null', **{p: None})
+        for p in aligned[entry]:
+            yield call(entry, p + ' misaligned', **{p: ok + (16 if p == 'ws' else 4)})
+        for label, change in shapes:
+            if all(k in takes[entry] or k in 'BHD' for k in change):
+                yield call(entry, label, **change)
+        if entry != 'diag':                                    # (mpb_gpmp2_diag has no B == 0 return: it launches)
+            yield call(entry, 'B=0', B=0)
+    yield call('step', 'n_iters=0', n_iters=0)
+    yield call('step', 'x misaligned, n_iters=0', x=ok + 4, n_iters=0)
+    yield call('step', 'x misaligned, B=0', x=ok + 4, B=0)
+    # the form refusals, of mpb_gpmp2_solve only (mpb_gpmp2_step may have enqueued the linearisation before it meets them)
+    yield call('solve', 'D=9 H=129', D=9, H=129)
+    yield call('solve', 'FORM=lr H=129', env=dict(MPB_GPMP2_FORM='lr'), H=129)
+    yield call('solve', 'FORM=block D=9', env=dict(MPB_GPMP2_FORM='block'), D=9)
+
+
+# what the library answered each of those calls before the entry points shared one argument check (code, mpb_last_error), with one
+# exception: without a GPU the trailing hipGetLastError of the old mpb_gpmp2_step turned the two n_iters == 0 calls, which enqueue
+# nothing, into MPB_E_HIP "no ROCm-capable device is detected"; on a GPU they answered MPB_OK, which is what is held here
+GPMP2_REFUSALS = {
+    'linearize x null': (1, 'mpb_gpmp2_linearize: null pointer'),
+    'linearize geom null': (1, 'mpb_gpmp2_linearize: null pointer'),
+    'linearize ws null': (1, 'mpb_gpmp2_linearize: null pointer'),
+    'linearize x misaligned': (1, 'mpb_gpmp2_linearize: x / geom must be 16-byte aligned and the workspace 256-byte aligned'),
+    'linearize geom misaligned': (1, 'mpb_gpmp2_linearize: x / geom must be 16-byte aligned and the workspace 256-byte aligned'),
+    'linearize ws misaligned': (1, 'mpb_gpmp2_linearize: x / geom must be 16-byte aligned and the workspace 256-byte aligned'),
+    'linearize H=1': (1, 'mpb_gpmp2_linearize: bad shape'),
+    'linearize H=257': (1, 'mpb_gpmp2_linearize: bad shape'),
+    'linearize D=0': (1, 'mpb_gpmp2_linearize: bad shape'),
+    'linearize D=13': (1, 'mpb_gpmp2_linearize: bad shape'),
+    'linearize B=-1': (1, 'mpb_gpmp2_linearize: bad shape'),
+    'linearize n_interp=-1': (1, 'mpb_gpmp2_linearize: bad shape'),
+    'linearize n_interp=65': (1, 'mpb_gpmp2_linearize: bad shape'),
+    'linearize B=0': (0, None),
+    'diag ws null': (1, 'mpb_gpmp2_diag: null pointer'),
+    'diag H=1': (1, 'mpb_gpmp2_diag: bad shape'),
+    'diag H=257': (1, 'mpb_gpmp2_diag: bad shape'),
+    'diag D=0': (1, 'mpb_gpmp2_diag: bad shape'),
+    'diag D=13': (1, 'mpb_gpmp2_diag: bad shape'),
+    'diag B=-1': (1, 'mpb_gpmp2_diag: bad shape'),
+    'diag n_fields=0': (1, 'mpb_gpmp2_diag: bad shape'),
+    'diag n_fields=5': (1, 'mpb_gpmp2_diag: bad shape'),
+    'solve x null': (1, 'mpb_gpmp2_solve: null pointer'),
+    'solve start null': (1, 'mpb_gpmp2_solve: null pointer'),
+    'solve goal null': (1, 'mpb_gpmp2_solve: null pointer'),
+    'solve ws null': (1, 'mpb_gpmp2_solve: null pointer'),
+    'solve x misaligned': (1, 'mpb_gpmp2_solve: x must be 16-byte aligned and the workspace 256-byte aligned'),
+    'solve ws misaligned': (1, 'mpb_gpmp2_solve: x must be 16-byte aligned and the workspace 256-byte aligned'),
+    'solve H=1': (1, 'mpb_gpmp2_solve: bad shape'),
+    'solve H=257': (1, 'mpb_gpmp2_solve: bad shape'),
+    'solve D=0': (1, 'mpb_gpmp2_solve: bad shape'),
+    'solve D=13': (1, 'mpb_gpmp2_solve: bad shape'),
+    'solve B=-1': (1, 'mpb_gpmp2_solve: bad shape'),
+    'solve n_fields=0': (1, 'mpb_gpmp2_solve: bad shape'),
+    'solve n_fields=5': (1, 'mpb_gpmp2_solve: bad shape'),
+    'solve B=0': (0, None),
+    'step x null': (1, 'mpb_gpmp2_step: null pointer'),
+    'step start null': (1, 'mpb_gpmp2_step: null pointer'),
+    'step goal null': (1, 'mpb_gpmp2_step: null pointer'),
+    'step geom null': (1, 'mpb_gpmp2_step: null pointer'),
+    'step ws null': (1, 'mpb_gpmp2_step: null pointer'),
+    'step x misaligned': (1, 'mpb_gpmp2_linearize: x / geom must be 16-byte aligned and the workspace 256-byte aligned'),
+    'step geom misaligned': (1, 'mpb_gpmp2_linearize: x / geom must be 16-byte aligned and the workspace 256-byte aligned'),
+    'step ws misaligned': (1, 'mpb_gpmp2_linearize: x / geom must be 16-byte aligned and the workspace 256-byte aligned'),
+    'step H=1': (1, 'mpb_gpmp2_step: bad shape'),
+    'step H=257': (1, 'mpb_gpmp2_step: bad shape'),
+    'step D=0': (1, 'mpb_gpmp2_step: bad shape'),
+    'step D=13': (1, 'mpb_gpmp2_step: bad shape'),
+    'step B=-1': (1, 'mpb_gpmp2_step: bad shape'),
+    'step n_interp=-1': (1, 'mpb_gpmp2_linearize: bad shape'),
+    'step n_interp=65': (1, 'mpb_gpmp2_linearize: bad shape'),
+    'step n_fields=0': (1, 'mpb_gpmp2_step: bad shape'),
+    'step n_fields=5': (1, 'mpb_gpmp2_step: bad shape'),
+    'step n_iters=-1': (1, 'mpb_gpmp2_step: bad shape'),
+    'step B=0': (0, None),
+    'step n_iters=0': (0, None),
+    'step x misaligned, n_iters=0': (0, None),
+    'step x misaligned, B=0': (0, None),
+    'solve D=9 H=129': (2, 'mpb_gpmp2_solve: more than 8 degrees of freedom need the low-rank form (n_fields * (H - 1) <= 127, H <= 128)'),
+    'solve FORM=lr H=129': (2, 'mpb_gpmp2_solve: MPB_GPMP2_FORM=lr, but n_fields * (H - 1) > 127'),
+    'solve FORM=block D=9': (2, 'mpb_gpmp2_solve: more than 8 degrees of freedom need the low-rank form (n_fields * (H - 1) <= 127, H <= 128)'),
+}
+
+
+def test_gpmp2_refusals_keep_code_and_message(monkeypatch):
+    """Every refusal of the four GPMP2 entry points keeps its code, its text and the entry point it names -- mpb_gpmp2_step reports the
+    linearisation's alignment and n_interp tests under that stage's name, and only once an iteration runs.  Skipped where there is a GPU:
+    a refusal that regressed would launch a kernel on the host pointers used here."""
+    if torch.cuda.is_available():
+        pytest.skip('host pointers: a refusal that regressed would reach a kernel')
+    from motion_planning_baselines_amd import _lib
+    h = _lib.lib()
+    seen = {}
+    for label, env, name, args in _gpmp2_refusal_calls():
+        for var in ('MPB_GPMP2_FORM', 'MPB_GPMP2_SM', 'MPB_GPMP2_SPLIT'):
+            monkeypatch.delenv(var, raising=False)
+        for var, value in env.items():
+            monkeypatch.setenv(var, value)
+        code = getattr(h, name)(*args)
+        seen[label] = (code, h.mpb_last_error().decode() if code else None)
+    assert seen == GPMP2_REFUSALS, {k: (seen.get(k), GPMP2_REFUSALS.get(k)) for k in set(seen) | set(GPMP2_REFUSALS) if seen.get(k) != GPMP2_REFUSALS.get(k)}
+
+
 @pytest.mark.parametrize('scene', ['spheres_3d', 'dense_2d', 'grid_circles_2d', 'large_3d'])
 def test_broad_phase_grid_is_conservative_and_fits(scene):
     """geometry.build_grid: the grid fits the LDS image of the kernels (MPB_GRID_MAX_CELLS words), is refined below the
