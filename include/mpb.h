@@ -60,7 +60,8 @@ extern "C" {
  *                        MPB_MAX_DOF 8 -> 12; mpb_gpmp2_solve takes the low-rank form wherever n_fields (H - 1) <= 127 (same
  *                        results to the solver's fp64 rounding);
  *           7            batched RRT-Connect (mpb_rrt_connect_*) and mpb_collision_check added; nothing else changed.  ABI 7 now
- *                        also carries batched RRT* / informed RRT* (mpb_rrt_star_*): additive, no existing signature moved. */
+ *                        also carries batched RRT* / informed RRT* (mpb_rrt_star_*): additive, no existing signature moved.
+ *                        mpb_mppi_plan (how mpb_mppi_step would launch a shape) added the same way: additive. */
 #define MPB_ABI_VERSION 7
 #define MPB_VERSION_TUNING_BUILD 0x40000000
 int mpb_version(void);
@@ -448,6 +449,20 @@ int mpb_mppi_step(float *mean, const float *eps, const float *scale_tril, const 
                   int NP, int S, int T, int c, int control_type, float dt,
                   float k_sigma, float weight, float temp, float step_size,
                   int n_iters, uint64_t seed, uint32_t iter0, void *stream);
+/* How mpb_mppi_step would launch a shape, without launching anything (the same function decides both; the MPB_MPPI_WAVES /
+ * MPB_MPPI_NOISE / MPB_MPPI_NO_GRID tuning variables, read once per process, are part of it).  geom_flags, NP, S, T, c as for
+ * mpb_mppi_step; has_geom / has_eps: whether its geom / eps would be non-NULL (eps picks the kernel instantiation only: the plan
+ * does not depend on it); n_cu: the compute units to plan for, <= 0 asks the current device.  plan[0..3] receive
+ *   [0] the noise product: MPB_MPPI_NOISE_GLOBAL (per lane, factor in global memory), _LDS (per lane, transposed factor in LDS),
+ *       _MATRIX (all samples on the matrix pipe, T <= 64);
+ *   [1] waves per problem;  [2] cells of the broad-phase grid staged in LDS (0: the exhaustive collision walk);
+ *   [3] dynamic LDS of the launch in bytes.
+ * Returns what mpb_mppi_step would return for the shape (MPB_E_INVALID: bad shape, MPB_E_UNSUPPORTED: the controls slab does not
+ * fit LDS; plan[] is zero then). */
+#define MPB_MPPI_NOISE_GLOBAL 0
+#define MPB_MPPI_NOISE_LDS 1
+#define MPB_MPPI_NOISE_MATRIX 2
+int mpb_mppi_plan(int geom_flags, int has_geom, int NP, int S, int T, int c, int has_eps, int n_cu, int *plan);
 /* The point-particle system as stand-alone entry points, for code written against the reference's system object
  * (dynamics/point.py); mpb_mppi_step fuses the same arithmetic.
  * mpb_point_dynamics -- PointParticleDynamics.dynamics (point.py:102-140): x_next = x + (clamp(u, ctrl_min, ctrl_max) +

@@ -63,6 +63,7 @@ SIGNATURES = {
     'mpb_point_dynamics': [_p, _p, _p, _p, _p, _p, _p, ctypes.c_size_t, _i, _f, _p],
     'mpb_point_traj_cost': [_p, _p, _p, _p, _f, _f, _f, _f, _f, _p, _i, _i, _i, _i, _p],
     'mpb_mppi_step': [_p] * 11 + [_i] + [_p] * 6 + [_i, _i, _i, _i, _i, _f, _f, _f, _f, _f, _i, _u64, _u32, _p],
+    'mpb_mppi_plan': [_i, _i, _i, _i, _i, _i, _i, _i, _p],
     'mpb_mt19937_normals': [_p, _i, _i, _p, _i, _i, _p, _p, _p, _i, _p, _i, _p, _p],
     'mpb_collision_check': [_p, _p, _i, _p, _p, _i, _i, _p],
     'mpb_rrt_connect_workspace_bytes': [_i, _i, _i, _i],

@@ -78,9 +78,9 @@ struct MppiLds {
 //                      instructions per wave and iteration at S = 32, T = 64, c = 2, and was LDS-bound;
 //   MPPI_NOISE_LDS     the per-lane product against the transposed factor in LDS;
 //   MPPI_NOISE_GLOBAL  the same against the factor in global memory (it does not fit).
-#define MPPI_NOISE_GLOBAL 0
-#define MPPI_NOISE_LDS 1
-#define MPPI_NOISE_MATRIX 2
+#define MPPI_NOISE_GLOBAL MPB_MPPI_NOISE_GLOBAL      // (include/mpb.h: mpb_mppi_plan reports them)
+#define MPPI_NOISE_LDS MPB_MPPI_NOISE_LDS
+#define MPPI_NOISE_MATRIX MPB_MPPI_NOISE_MATRIX
 
 // CC: the control dimension as a compile-time constant (2: the reference example's point mass; 0: run-time c <= MPPI_MAX_C);
 // GRID: collision through the broad-phase grid (ONE grid-backed field) -- the exhaustive evaluator, with its blocks of obstacles
@@ -541,29 +541,22 @@ __global__ __launch_bounds__(1024) void mppi_kernel(
     for (int e = threadIdx.x; e < T * c; e += blockDim.x) mean_g[e] = m[e];
 }
 
-extern "C" int mpb_mppi_step(float* mean, const float* eps, const float* scale_tril, const float* cov_inv,
-                             const float* state0, const float* goal, const float* ctrl_min, const float* ctrl_max,
-                             const float* discount, const float* c_weights, const float* geom, int geom_flags, float* controls,
-                             float* states, float* costs, float* weights, float* best_cost, float* best_states,
-                             int NP, int S, int T, int c, int control_type,
-                             float dt, float k_sigma, float weight, float temp, float step_size, int n_iters,
-                             uint64_t seed, uint32_t iter0, void* stream) {
-    if (!mean || !scale_tril || !cov_inv || !state0 || !goal || !ctrl_min || !ctrl_max || !discount || !c_weights ||
-        !controls || !states || !costs || !weights)
-        return mpb_fail(MPB_E_INVALID, "mpb_mppi_step: null pointer");
-    if (NP < 0 || S < 1 || S > 1024 || T < 2 || T > MPB_MAX_H || c < 1 || c > MPPI_MAX_C || n_iters < 0)
+// How mpb_mppi_step launches a shape: the ONE place that decides it (mpb_mppi_plan exports it; the tests assert the path they
+// claim to cover through it).  Returns the launcher's own code for the shape: MPB_OK, or the refusal with its message.
+struct MppiPlan {
+    int noise_mode;      // MPPI_NOISE_*
+    int nw;              // waves per workgroup (= per problem)
+    int grid_words;      // cells of the broad-phase grid staged in LDS; 0: the exhaustive collision walk
+    size_t lds_words;    // dynamic LDS of the launch, in words
+};
+static int mppi_plan(int geom_flags, bool has_geom, int NP, int S, int T, int c, int n_cu, MppiPlan* out) {
+    if (NP < 0 || S < 1 || S > 1024 || T < 2 || T > MPB_MAX_H || c < 1 || c > MPPI_MAX_C)
         return mpb_fail(MPB_E_INVALID, "mpb_mppi_step: bad shape");
-    if (!(temp > 0.f)) return mpb_fail(MPB_E_INVALID, "mpb_mppi_step: temp must be > 0");
-    if ((best_cost == nullptr) != (best_states == nullptr))
-        return mpb_fail(MPB_E_INVALID, "mpb_mppi_step: best_cost and best_states must be given together");
-    if (control_type != 0)
-        return mpb_fail(MPB_E_UNSUPPORTED, "mpb_mppi_step: only velocity control (the reference's acceleration mode cannot run)");
-    if (NP == 0 || n_iters == 0) return MPB_OK;
     static const int force_nw = getenv("MPB_MPPI_WAVES") ? atoi(getenv("MPB_MPPI_WAVES")) : 0;       // tuning aid
     // one wave per sample, at most 16 waves per problem.  With at least two problems per CU, workgroups of 8 waves (two
     // resident per CU: one problem's barriers and serial sections run under the other's rollouts) are 16 % faster than
     // 16 (NP = 1 024, S = 32, T = 64: 68.7 against 81.5 us per iteration); a single problem is fastest on 16
-    const int n_cu = mpb_device_cu_count();
+    if (n_cu <= 0) n_cu = mpb_device_cu_count();
     int nw = S < 16 ? S : 16;
     if (NP >= 2 * n_cu && S >= 16) nw = 8;
     if (force_nw > 0 && force_nw <= 16 && force_nw <= S) nw = force_nw;
@@ -582,7 +575,7 @@ extern "C" int mpb_mppi_step(float* mean, const float* eps, const float* scale_t
     // they fit next to the rest (and, with two workgroups per CU, leave room for the second one)
     int grid_words = 0;
     static const int no_grid = getenv("MPB_MPPI_NO_GRID") ? atoi(getenv("MPB_MPPI_NO_GRID")) : 0;           // tuning / tests
-    if (geom && mpb_flags_point_on_one_grid(geom_flags) && !no_grid) {     // ONE grid-backed field, point robot
+    if (has_geom && mpb_flags_point_on_one_grid(geom_flags) && !no_grid) {     // ONE grid-backed field, point robot
         const int cells = mpb_flags_cells(geom_flags);
         const size_t extra = 4 + (size_t)((cells + 3) & ~3) + 4 * (MPB_GRID_MAX_SPH + 1);
         const size_t cap = (nw <= 8 ? 78 : 150) * 1024 / sizeof(float);
@@ -591,7 +584,44 @@ extern "C" int mpb_mppi_step(float* mean, const float* eps, const float* scale_t
             lds_words += extra;
         }
     }
-    const size_t lds = lds_words * sizeof(float);
+    *out = {noise_mode, nw, grid_words, lds_words};
+    return MPB_OK;
+}
+
+extern "C" int mpb_mppi_plan(int geom_flags, int has_geom, int NP, int S, int T, int c, int has_eps, int n_cu, int* plan) {
+    (void)has_eps;       // (injected or drawn normals pick the kernel instantiation, never the layout: part of the call for the record)
+    if (!plan) return mpb_fail(MPB_E_INVALID, "mpb_mppi_plan: null pointer");
+    MppiPlan p = {0, 0, 0, 0};
+    const int rc = mppi_plan(geom_flags, has_geom != 0, NP, S, T, c, n_cu, &p);
+    plan[0] = p.noise_mode;
+    plan[1] = p.nw;
+    plan[2] = p.grid_words;
+    plan[3] = (int)(p.lds_words * sizeof(float));
+    return rc;
+}
+
+extern "C" int mpb_mppi_step(float* mean, const float* eps, const float* scale_tril, const float* cov_inv,
+                             const float* state0, const float* goal, const float* ctrl_min, const float* ctrl_max,
+                             const float* discount, const float* c_weights, const float* geom, int geom_flags, float* controls,
+                             float* states, float* costs, float* weights, float* best_cost, float* best_states,
+                             int NP, int S, int T, int c, int control_type,
+                             float dt, float k_sigma, float weight, float temp, float step_size, int n_iters,
+                             uint64_t seed, uint32_t iter0, void* stream) {
+    if (!mean || !scale_tril || !cov_inv || !state0 || !goal || !ctrl_min || !ctrl_max || !discount || !c_weights ||
+        !controls || !states || !costs || !weights)
+        return mpb_fail(MPB_E_INVALID, "mpb_mppi_step: null pointer");
+    if (NP < 0 || S < 1 || S > 1024 || T < 2 || T > MPB_MAX_H || c < 1 || c > MPPI_MAX_C || n_iters < 0)
+        return mpb_fail(MPB_E_INVALID, "mpb_mppi_step: bad shape");
+    if (!(temp > 0.f)) return mpb_fail(MPB_E_INVALID, "mpb_mppi_step: temp must be > 0");
+    if ((best_cost == nullptr) != (best_states == nullptr))
+        return mpb_fail(MPB_E_INVALID, "mpb_mppi_step: best_cost and best_states must be given together");
+    if (control_type != 0)
+        return mpb_fail(MPB_E_UNSUPPORTED, "mpb_mppi_step: only velocity control (the reference's acceleration mode cannot run)");
+    if (NP == 0 || n_iters == 0) return MPB_OK;
+    MppiPlan plan;
+    if (const int rc = mppi_plan(geom_flags, geom != nullptr, NP, S, T, c, 0, &plan)) return rc;
+    const int nw = plan.nw, noise_mode = plan.noise_mode, grid_words = plan.grid_words;
+    const size_t lds = plan.lds_words * sizeof(float);
 #define MPPI_LAUNCH(CC, GRID)                                          \
     do {                                                               \
         if (noise_mode == MPPI_NOISE_MATRIX && eps) MPPI_LAUNCH_(CC, GRID, true, true);    \

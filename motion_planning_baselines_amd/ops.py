@@ -3,6 +3,7 @@ current HIP stream.  PyTorch is plumbing here (device memory, streams); all arit
 csrc/*.hip.  Every wrapper validates device / dtype / contiguity / shape on the host before
 launching (a kernel that faults can reset the whole GPU host).
 """
+import collections
 import ctypes
 import functools
 import math
@@ -718,6 +719,27 @@ def mppi_step(mean, eps, scale_tril, cov_inv, state0, goal, ctrl_min, ctrl_max, 
         _ptr(costs), _ptr(weights), _ptr(best_cost), _ptr(best_states), NP, S, T, c, 0, float(dt), float(k_sigma),
         float(weight), float(temp),
         float(step_size), int(n_iters), _seed64(seed), int(iter0), _stream()), 'mpb_mppi_step')
+
+
+MPPI_NOISE_GLOBAL, MPPI_NOISE_LDS, MPPI_NOISE_MATRIX = 0, 1, 2
+MppiPlan = collections.namedtuple('MppiPlan', 'noise_mode waves grid_words lds_bytes')
+
+
+def mppi_plan(geom, NP, S, T, c, has_eps=False, n_cu=0):
+    """How mppi_step would launch this shape (mpb_mppi_plan: the launcher's own decision, nothing is launched): MppiPlan(noise_mode
+    MPPI_NOISE_*, waves per problem, grid_words staged in LDS -- 0: exhaustive collision walk --, dynamic LDS bytes).  geom: a
+    DeviceGeometry, None, or the mpb_geom_flags (int) of a packed scene; n_cu: compute units to plan for, 0 asks the device.
+    Raises MPBError where mppi_step would."""
+    out = (ctypes.c_int * 4)()
+    flags = 0 if geom is None else int(geom.flags if isinstance(geom, DeviceGeometry) else geom)
+    args = (flags, int(geom is not None), int(NP), int(S), int(T), int(c), int(bool(has_eps)), int(n_cu), ctypes.cast(out, ctypes.c_void_p))
+    if isinstance(geom, DeviceGeometry):         # (n_cu = 0 asks the CURRENT device: the geometry's)
+        with torch.cuda.device(geom.buf.device):
+            rc = _lib.lib().mpb_mppi_plan(*args)
+    else:
+        rc = _lib.lib().mpb_mppi_plan(*args)
+    _lib.check(rc, 'mpb_mppi_plan')
+    return MppiPlan(*[int(v) for v in out])
 
 
 @_on_tensor_device

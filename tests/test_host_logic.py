@@ -1047,3 +1047,34 @@ def test_list_grid_cell_words_round_trip_by_name():
     bad.view(np.uint32)[off_grid + n_cells // 2] |= reserved_bit
     with pytest.raises(_lib.MPBError, match='list-grid cell out of range'):
         _lib.geom_check(bad)
+
+
+def test_mppi_plan_of_every_tested_shape():
+    """mpb_mppi_plan (the function mpb_mppi_step launches by) at n_cu = 256, for every shape of tests/mppi_path_cases.py and every
+    MPPI shape the suite ran before it: noise path, waves, grid words and LDS bytes are pinned.  The tests that claim to cover a
+    path assert it again on the device; this one says, without a GPU, which of them a retuned launcher has moved."""
+    import mppi_path_cases as M
+    from motion_planning_baselines_amd import ops
+    from motion_planning_baselines_amd._lib import MPBError
+    seen = set()
+    shapes = [(k, cs[:5], M.Plan(*cs[5:9])) for k, cs in M.CASES.items()] + [('earlier', sh, pl) for sh, pl in M.EARLIER]
+    for tag, (NP, S, T, c, scene), want in shapes:
+        flags, has_geom = M.scene_flags(scene)
+        for has_eps in (False, True):          # (injected or drawn: another instantiation, the same layout)
+            got = ops.mppi_plan(flags if has_geom else None, NP, S, T, c, has_eps=has_eps, n_cu=256)
+            assert tuple(got) == tuple(want), (tag, (NP, S, T, c, scene), 'plan moved: %s -> %s' % (tuple(want), tuple(got)))
+        assert got.lds_bytes <= 160 * 1024
+        seen.add((got.noise_mode, got.grid_words > 0))
+    # between them: every noise path with the grid and without it
+    assert seen == {(m, g) for m in (ops.MPPI_NOISE_GLOBAL, ops.MPPI_NOISE_LDS, ops.MPPI_NOISE_MATRIX) for g in (False, True)}
+    # what a caller meets beyond the matrix path's reach: the per-lane LDS product while the transposed factor fits, then global memory
+    assert ops.mppi_plan(None, 2, 16, 128, 1, n_cu=256).noise_mode == ops.MPPI_NOISE_LDS
+    assert ops.mppi_plan(None, 2, 16, 128, 2, n_cu=256).noise_mode == ops.MPPI_NOISE_GLOBAL
+    assert ops.mppi_plan(None, 2, 120, 64, 2, n_cu=256).noise_mode == ops.MPPI_NOISE_LDS
+    # the code is the launcher's: a bad shape and a controls slab beyond LDS are refused as mpb_mppi_step refuses them
+    with pytest.raises(MPBError, match='bad shape'):
+        ops.mppi_plan(None, 2, 0, 64, 2, n_cu=256)
+    with pytest.raises(MPBError, match='too large'):
+        ops.mppi_plan(None, 2, 1024, 256, 4, n_cu=256)
+    # two problems per CU: eight waves, and a grid that leaves room for the second workgroup
+    assert ops.mppi_plan(None, 511, 32, 64, 2, n_cu=256).waves == 16 and ops.mppi_plan(None, 512, 32, 64, 2, n_cu=256).waves == 8
