@@ -61,7 +61,8 @@ extern "C" {
  *                        results to the solver's fp64 rounding);
  *           7            batched RRT-Connect (mpb_rrt_connect_*) and mpb_collision_check added; nothing else changed.  ABI 7 now
  *                        also carries batched RRT* / informed RRT* (mpb_rrt_star_*): additive, no existing signature moved.
- *                        mpb_mppi_plan (how mpb_mppi_step would launch a shape) added the same way: additive. */
+ *                        mpb_mppi_plan (how mpb_mppi_step would launch a shape) added the same way: additive; so was
+ *                        mpb_traj_collision_stats (validation of a trajectory batch). */
 #define MPB_ABI_VERSION 7
 #define MPB_VERSION_TUNING_BUILD 0x40000000
 int mpb_version(void);
@@ -560,6 +561,27 @@ int mpb_mt19937_normals(float *out, int n, int n_calls, const uint32_t *state_in
  * ------------------------------------------------------------------------------------------- */
 int mpb_collision_check(const float *q, const float *geom, int geom_flags, unsigned char *in_collision, float *gap,
                         int N, int D, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Validation of a batch of trajectories (build-defined; the reference's examples ask torch_robotics'
+ * task.get_trajs_collision_and_free / compute_fraction_free_trajs / compute_collision_intensity_trajs /
+ * compute_success_free_trajs, panda_spheres_CHOMP.py:126, :146-148): one launch, one workgroup per trajectory, no dense
+ * point is ever stored.
+ * trajs: N trajectories of H rows, read in place; row h of trajectory n starts at trajs + (n*H + h)*row_stride and its first
+ *   D floats are the joint positions (row_stride >= D; the columns D .. row_stride-1 -- the velocity half of a state
+ *   trajectory, or anything else -- are never read).
+ * Dense points: P = (H-1)(n_interp+1) + 1 per trajectory, the points of mpb_traj_interpolate above: point
+ *   p = seg*(n_interp+1) + k is x0 + ((float)k / (float)(n_interp+1)) * (x1 - x0), the waypoint's own bits for k = 0 and for
+ *   the last point.  A dense point is in collision iff mpb_collision_check says so of it (gap > 0, margin included).
+ * n_in_collision (N): dense points in collision; first_in_collision (N): the smallest such p, -1 when there is none;
+ * max_gap (N): the largest hinge sum (mpb_collision_check's gap) over the dense points, 0 when the trajectory is free;
+ * point_in_collision (N, P) bytes, 0 / 1: optional (may be NULL).  No atomics: the same bits on every run.
+ * Refusals, in this order: D > MPB_MAX_DOF: MPB_E_UNSUPPORTED; N < 0, H < 2, D < 1, n_interp < 0, row_stride < D or P beyond
+ * an int: MPB_E_INVALID; (N == 0: MPB_OK, nothing launched;) a null required pointer, geom not 16-byte aligned: MPB_E_INVALID.
+ * ------------------------------------------------------------------------------------------- */
+int mpb_traj_collision_stats(const float *trajs, size_t row_stride, const float *geom, int geom_flags, int n_interp,
+                             int *n_in_collision, int *first_in_collision, float *max_gap, unsigned char *point_in_collision,
+                             int N, int H, int D, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Batched RRT-Connect -- replaces RRTConnect._run_optimization (rrt_connect.py:93-192) with RRTBase.get_pre_sample /

@@ -66,6 +66,7 @@ SIGNATURES = {
     'mpb_mppi_plan': [_i, _i, _i, _i, _i, _i, _i, _i, _p],
     'mpb_mt19937_normals': [_p, _i, _i, _p, _i, _i, _p, _p, _p, _i, _p, _i, _p, _p],
     'mpb_collision_check': [_p, _p, _i, _p, _p, _i, _i, _p],
+    'mpb_traj_collision_stats': [_p, ctypes.c_size_t, _p, _i, _i, _p, _p, _p, _p, _i, _i, _i, _p],
     'mpb_rrt_connect_workspace_bytes': [_i, _i, _i, _i],
     'mpb_rrt_connect_init': [_p, ctypes.c_size_t, _p, _p, _p, _i, _i, _i, _i, _i, _p],
     'mpb_rrt_connect_run': [_p, ctypes.c_size_t, _p, _i, _p, ctypes.c_size_t, _p, _p, _p, _p] + [_i] * 8 + [_f, _f, _u64, _u32, _p],

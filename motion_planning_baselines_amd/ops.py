@@ -1044,6 +1044,32 @@ def collision_check(q, geom, with_gap=False):
     return (flag, gap) if with_gap else flag
 
 
+@_on_tensor_device
+def traj_collision_stats(trajs, geom, n_interp=5, with_flags=False):
+    """(N, H, W) trajectories, W >= the geometry's degrees of freedom, read in place (the first D columns of a row are the
+    joint positions, the others are never touched) -> per trajectory, over its P = (H-1)(n_interp+1)+1 dense points (the
+    points of traj_interpolate, never stored): n_in_collision int32 (N,), first_in_collision int32 (N,) (-1: none),
+    max_gap fp32 (N,) (the largest hinge sum, 0 when free); with_flags adds the per-point answers, bool (N, P)
+    (mpb_traj_collision_stats)."""
+    if not (isinstance(trajs, torch.Tensor) and trajs.is_cuda):
+        raise _lib.MPBError('traj_collision_stats: trajs must be a GPU tensor; there is no CPU fallback')
+    if trajs.dim() != 3:
+        raise ValueError(f'trajs has shape {tuple(trajs.shape)}, expected (N, H, W)')
+    N, H, W = trajs.shape
+    _chk(trajs, (N, H, W), 'trajs')
+    D, n = geom.n_dof, int(n_interp)
+    if W < D:
+        raise ValueError(f'trajs has {W} columns, the geometry {D} degrees of freedom')
+    P = (H - 1) * (n + 1) + 1
+    count = torch.empty(N, device=trajs.device, dtype=torch.int32)
+    first = torch.empty(N, device=trajs.device, dtype=torch.int32)
+    gap = torch.empty(N, device=trajs.device, dtype=torch.float32)
+    flags = torch.empty(N, max(P, 0), device=trajs.device, dtype=torch.bool) if with_flags else None
+    _lib.check(_lib.lib().mpb_traj_collision_stats(_ptr(trajs), W, _ptr(geom.buf), int(geom.flags), n, _ptr(count), _ptr(first),
+                                                   _ptr(gap), _ptr(flags), N, H, D, _stream()), 'mpb_traj_collision_stats')
+    return (count, first, gap, flags) if with_flags else (count, first, gap)
+
+
 class RRTWorkspace:
     """The caller-allocated state of a batch of RRT-Connect problems: trees, pool lists, status words (layout: rrt_layout.py)."""
     kind = 'connect'

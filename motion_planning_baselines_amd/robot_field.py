@@ -90,7 +90,9 @@ def device_robot_field(robot, field, device):
 
 class PlanningTask:
     """The slice of torch_robotics' planning task that the reference's sample-based planners call (rrt_base.py:56-57,
-    :100-110): compute_collision, random_coll_free_q, random_q, distance_q -- on the GPU.
+    :100-110): compute_collision, random_coll_free_q, random_q, distance_q -- on the GPU -- and what its examples ask after
+    a planner has run (panda_spheres_CHOMP.py:126, :146-148): get_trajs_collision_and_free, compute_fraction_free_trajs,
+    compute_collision_intensity_trajs, compute_success_free_trajs (one launch of mpb_traj_collision_stats each).
 
     The collision predicate is build-defined (torch_robotics is absent): a configuration is in collision iff the
     package's per-waypoint collision cost  sum_f s_f sum_l relu(margin + r_l - min_o sdf_o(x_l))  is positive
@@ -136,3 +138,44 @@ class PlanningTask:
 
     def distance_q(self, q1, q2):
         return torch.linalg.norm(q1 - q2, dim=-1)
+
+    # ---- validation of a trajectory batch (build-defined like the predicate: DESIGN.md 10) -----------------------------------
+    def _trajs_stats(self, trajs, num_interpolation, with_flags=False):
+        """trajs (..., H, W), W >= q_dim, leading dimensions flattened -> (trajs (N, H, W), the outputs of
+        ops.traj_collision_stats).  A contiguous fp32 GPU tensor is read in place, velocity columns and all."""
+        t = torch.as_tensor(trajs, dtype=torch.float32, device=self.device)
+        if t.dim() < 2 or t.shape[-1] < self.q_dim:
+            raise ValueError(f'trajs has shape {tuple(t.shape)}, expected (..., H, W) with W >= {self.q_dim}')
+        t = t.reshape(-1, t.shape[-2], t.shape[-1]).contiguous()
+        return t, ops.traj_collision_stats(t, self.geom, n_interp=int(num_interpolation), with_flags=with_flags)
+
+    def get_trajs_collision_and_free(self, trajs, return_indices=False, num_interpolation=5, **kwargs):
+        """(trajs_coll, trajs_free): the trajectories with a dense point in collision and those without, each (n, H, W) in
+        input order, None for a set without members (the examples test `is not None`).  The dense points are the waypoints
+        and num_interpolation evenly spaced joint-space points per segment; the predicate is compute_collision's (margin
+        included).  return_indices: (trajs_coll, coll_idxs, trajs_free, free_idxs, waypoints_in_collision (N, P) bool)."""
+        t, out = self._trajs_stats(trajs, num_interpolation, with_flags=return_indices)
+        in_coll = out[0] > 0
+        coll_idxs = torch.nonzero(in_coll).flatten()
+        free_idxs = torch.nonzero(~in_coll).flatten()
+        trajs_coll = t[coll_idxs] if coll_idxs.numel() else None
+        trajs_free = t[free_idxs] if free_idxs.numel() else None
+        if return_indices:
+            return trajs_coll, coll_idxs, trajs_free, free_idxs, out[3]
+        return trajs_coll, trajs_free
+
+    def compute_fraction_free_trajs(self, trajs, **kwargs):
+        """Share of the trajectories without a dense point in collision (Python float)."""
+        _, (count, _, _) = self._trajs_stats(trajs, kwargs.get('num_interpolation', 5))
+        return int((count == 0).sum()) / max(count.numel(), 1)
+
+    def compute_collision_intensity_trajs(self, trajs, **kwargs):
+        """Share of all N * P dense points that are in collision (Python float)."""
+        n = int(kwargs.get('num_interpolation', 5))
+        t, (count, _, _) = self._trajs_stats(trajs, n)
+        return int(count.sum(dtype=torch.int64)) / max(count.numel() * ((t.shape[1] - 1) * (n + 1) + 1), 1)
+
+    def compute_success_free_trajs(self, trajs, **kwargs):
+        """1 if any trajectory is free of collisions, else 0."""
+        _, (count, _, _) = self._trajs_stats(trajs, kwargs.get('num_interpolation', 5))
+        return 1 if bool((count == 0).any()) else 0
