@@ -32,6 +32,8 @@
  * kinds, MPB_MAX_DOF / MPB_MAX_FIELDS and the grid limits, the cell-word fields, MPB_GEOM_FLAG_* */
 #include "mpb_geom_layout.h"
 #include "mpb_rrt_layout.h"
+/* the packed self-collision buffer in numbers (generated from self_layout.py): header word indices MPB_SW_*, MPB_SELF_* */
+#include "mpb_self_layout.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -62,7 +64,8 @@ extern "C" {
  *           7            batched RRT-Connect (mpb_rrt_connect_*) and mpb_collision_check added; nothing else changed.  ABI 7 now
  *                        also carries batched RRT* / informed RRT* (mpb_rrt_star_*): additive, no existing signature moved.
  *                        mpb_mppi_plan (how mpb_mppi_step would launch a shape) added the same way: additive; so was
- *                        mpb_traj_collision_stats (validation of a trajectory batch). */
+ *                        mpb_traj_collision_stats (validation of a trajectory batch), and the self-collision field
+ *                        (mpb_self_check, mpb_self_invalidate, mpb_self_collision_eval / _grad / _check). */
 #define MPB_ABI_VERSION 7
 #define MPB_VERSION_TUNING_BUILD 0x40000000
 int mpb_version(void);
@@ -582,6 +585,57 @@ int mpb_collision_check(const float *q, const float *geom, int geom_flags, unsig
 int mpb_traj_collision_stats(const float *trajs, size_t row_stride, const float *geom, int geom_flags, int n_interp,
                              int *n_in_collision, int *first_in_collision, float *max_gap, unsigned char *point_in_collision,
                              int N, int H, int D, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Self-collision field: the robot's collision spheres against each other (build-defined; the reference's Panda
+ * examples get this field from torch_robotics with use_self_collision_storm=True).  Serial chains only.
+ *   c(q) = sum over pairs (a, b) of relu(T_ab - |x_a(q) - x_b(q)|),   T_ab = margin + r_a + r_b,
+ * x_l the collision-sphere centres mpb_fk_collision_points gives; a configuration collides with itself iff c(q) > 0 (the rule of
+ * mpb_collision_check).  Gradient of an active pair (T_ab - n > 0, n = |x_a - x_b|): d c / d x_a = -(x_a - x_b) / n,
+ * d c / d x_b = +(x_a - x_b) / n, d c / d q = J^T of that; a pair with n == 0 contributes zero.
+ *
+ * The self buffer is ONE self-contained array of 32-bit words with a magic and version of its own (mpb_self_layout.h, generated
+ * from self_layout.py -- the one definition): a header of MPB_SELF_HEADER_WORDS words (MPB_SW_MAGIC, _VERSION, _N_DOF, _N_TF =
+ * n_dof + 1, _N_LINKS, _N_PAIRS, _MARGIN, the section offsets _OFF_TF, _OFF_LINKS, _OFF_PAIRS, _TOTAL; the rest zero), then the
+ * joint transforms (n_tf x 12) and the link table (n_links x 8) in the row formats of the geometry buffer -- EVERY link, the pair
+ * indices are positions in this table --, then the pair table, MPB_SELF_PAIR_WORDS words per pair: a | b << MPB_SELF_PAIR_B_SHIFT
+ * with a < b < n_links, and T_ab as fp32.  Limits: MPB_SELF_MAX_LINKS spheres, MPB_SELF_MAX_PAIRS pairs.
+ *
+ * mpb_self_check validates such a buffer held in HOST memory (n_words must equal its total): header, offsets, limits, link
+ * frames sorted in [1, n_dof + 1], every pair a < b < n_links with a positive finite threshold.
+ *
+ * The three device entry points take the buffer in DEVICE memory, 16-byte aligned.  The caller validates it with
+ * mpb_self_check before uploading it: the entry points have no host copy.  They read its 16 header words back ONCE per buffer
+ * address and device (a synchronous 64-byte copy on the first call with that pointer: make that call outside stream capture),
+ * check the header alone and size the launch's LDS from n_links: 768 bytes per sphere, twice that with gradients.  The kernels
+ * compare the header (magic, n_dof, n_links, n_pairs) with the numbers they were launched with and answer NaN (in_collision = 1) when it has changed since.
+ * mpb_self_invalidate(self) forgets what was read at that address: call it whenever ANOTHER self buffer is written to device memory
+ * at an address an earlier call may have seen (an allocator hands a freed block out again).  Host only, never fails.
+ *
+ * mpb_self_collision_eval:  out[b] (+)= weight * k_sigma * sum_{h >= h_begin} c(trajs[b, h, :n_dof]);  trajs (B, H, d), d >= n_dof;
+ *   per_waypoint (B, H) optional (may be NULL): c un-scaled, 0 for h < h_begin.
+ * mpb_self_collision_grad:  the same out, and grad (B, H, d) (+)= d out[b] / d trajs[b]; when not accumulating the velocity
+ *   channels n_dof .. d-1 are written 0, when accumulating they are left alone.
+ *   accumulate != 0 adds onto out AND grad (CHOMP adds the self gradient onto the obstacle gradient): the old value plus the
+ *   fresh one in ONE fp32 rounding, so accumulating equals the buffer plus a fresh evaluation bit for bit.
+ * mpb_self_collision_check: q (N, D) with D == n_dof; in_collision (N) bytes 0 / 1 = c > 0; gap (N) optional: c.  or_into != 0 ORs
+ *   into the existing flags and adds c onto the existing gap (after mpb_collision_check: collides with the world OR with itself).
+ * One wave per trajectory, one lane per waypoint (check: one lane per configuration).  Sums in fixed order (pairs in table order
+ * in fp32, then a fixed wave reduction): the same bits on every run.
+ * Refusals, in this order: rows wider than positions + velocities of MPB_MAX_DOF joints (d > 2 MPB_MAX_DOF; check: D >
+ * MPB_MAX_DOF): MPB_E_UNSUPPORTED; B < 0, H < 1, d < 1, h_begin < 0 (check: N < 0, D < 1): MPB_E_INVALID; (B == 0 / N == 0:
+ * MPB_OK, nothing launched;) a null required pointer, a self buffer not 16-byte aligned: MPB_E_INVALID; the header: bad magic /
+ * version / offsets: MPB_E_INVALID, n_dof > MPB_MAX_DOF, n_links > MPB_SELF_MAX_LINKS, n_pairs > MPB_SELF_MAX_PAIRS:
+ * MPB_E_UNSUPPORTED, d < n_dof (check: D != n_dof): MPB_E_INVALID.
+ * ------------------------------------------------------------------------------------------- */
+int mpb_self_check(const float *self_host, int n_words);
+int mpb_self_invalidate(const float *self);
+int mpb_self_collision_eval(const float *trajs, const float *self, float *out, float *per_waypoint,
+                            int B, int H, int d, int h_begin, float k_sigma, float weight, int accumulate, void *stream);
+int mpb_self_collision_grad(const float *trajs, const float *self, float *out, float *grad,
+                            int B, int H, int d, int h_begin, float k_sigma, float weight, int accumulate, void *stream);
+int mpb_self_collision_check(const float *q, const float *self, unsigned char *in_collision, float *gap,
+                             int N, int D, int or_into, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Batched RRT-Connect -- replaces RRTConnect._run_optimization (rrt_connect.py:93-192) with RRTBase.get_pre_sample /

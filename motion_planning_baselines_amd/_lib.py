@@ -67,6 +67,11 @@ SIGNATURES = {
     'mpb_mt19937_normals': [_p, _i, _i, _p, _i, _i, _p, _p, _p, _i, _p, _i, _p, _p],
     'mpb_collision_check': [_p, _p, _i, _p, _p, _i, _i, _p],
     'mpb_traj_collision_stats': [_p, ctypes.c_size_t, _p, _i, _i, _p, _p, _p, _p, _i, _i, _i, _p],
+    'mpb_self_check': [_p, _i],
+    'mpb_self_invalidate': [_p],
+    'mpb_self_collision_eval': [_p, _p, _p, _p, _i, _i, _i, _i, _f, _f, _i, _p],
+    'mpb_self_collision_grad': [_p, _p, _p, _p, _i, _i, _i, _i, _f, _f, _i, _p],
+    'mpb_self_collision_check': [_p, _p, _p, _p, _i, _i, _i, _p],
     'mpb_rrt_connect_workspace_bytes': [_i, _i, _i, _i],
     'mpb_rrt_connect_init': [_p, ctypes.c_size_t, _p, _p, _p, _i, _i, _i, _i, _i, _p],
     'mpb_rrt_connect_run': [_p, ctypes.c_size_t, _p, _i, _p, ctypes.c_size_t, _p, _p, _p, _p] + [_i] * 8 + [_f, _f, _u64, _u32, _p],
@@ -164,6 +169,12 @@ def geom_check(buf):
     """Validate a packed geometry buffer (numpy fp32) on the host side of the C-ABI."""
     buf = np.ascontiguousarray(buf, dtype=np.float32)
     check(lib().mpb_geom_check(buf.ctypes.data_as(ctypes.c_void_p), int(buf.size)), 'mpb_geom_check')
+
+
+def self_check(buf):
+    """Validate a packed self-collision buffer (numpy fp32) on the host side of the C-ABI."""
+    buf = np.ascontiguousarray(buf, dtype=np.float32)
+    check(lib().mpb_self_check(buf.ctypes.data_as(ctypes.c_void_p), int(buf.size)), 'mpb_self_check')
 
 
 def geom_flags(buf):

@@ -19,6 +19,8 @@ Definitions (all fp32):
   * obstacle sphere: sdf(x) = |x - c| - r.
   * axis-aligned box: q = |x - c| - h; sdf = |max(q,0)| + min(max(qx,qy,qz), 0).
   * per-waypoint collision cost: sum_l relu(margin + r_l - min_o sdf_o(x_l)).
+  * per-waypoint SELF-collision cost (serial chains, SelfCollisionField): sum over pairs (a, b) of
+    relu(margin + r_a + r_b - |x_a - x_b|).
 """
 import math
 import os
@@ -351,6 +353,120 @@ class CollisionField:
 
     def zero_grad(self):  # reference calls field.zero_grad() (field_factor.py:56); nothing to clear here
         pass
+
+
+def fk_spheres_f64(rs, q):
+    """Collision-sphere centres of a serial chain in fp64 on the host: robot spec, q (N, D) -> (N, L, 3), by the module docstring's
+    definition (what the pair builder of SelfCollisionField judges "always in collision" with)."""
+    q = np.asarray(q, dtype=np.float64).reshape(-1, int(rs['n_dof']))
+    tf = np.asarray(rs['joint_tf'], dtype=np.float64)
+    N, D = q.shape
+    R = np.broadcast_to(np.eye(3), (N, 3, 3)).copy()
+    t = np.zeros((N, 3))
+    frames = []
+    for j in range(tf.shape[0]):
+        t = t + R @ tf[j, :, 3]
+        R = R @ tf[j, :, :3]
+        if j < D:
+            c, s = np.cos(q[:, j]), np.sin(q[:, j])
+            Rz = np.zeros((N, 3, 3))
+            Rz[:, 0, 0], Rz[:, 0, 1], Rz[:, 1, 0], Rz[:, 1, 1], Rz[:, 2, 2] = c, -s, s, c, 1.0
+            R = R @ Rz
+        frames.append((R, t))
+    off = np.asarray(rs['link_offset'], dtype=np.float64)
+    return np.stack([frames[int(f) - 1][0] @ off[l] + frames[int(f) - 1][1] for l, f in enumerate(rs['link_frame'])], 1)
+
+
+class SelfCollisionField:
+    """The robot against itself (build-defined; the reference's examples get this field from torch_robotics with
+    use_self_collision_storm=True).  Serial chains only.
+
+    Per-waypoint cost  c(q) = sum over pairs (a, b) of relu(T_ab - |x_a(q) - x_b(q)|),  T_ab = margin + r_a + r_b,  x_l the collision-
+    sphere centres of fk_map_collision; a configuration collides with itself iff c(q) > 0.
+
+    pairs=None builds the default list: all a < b with link_frame[b] - link_frame[a] >= min_frame_gap whose hinge is NOT positive at
+    every one of ALWAYS_SAMPLES configurations drawn uniformly in the joint limits with np.random.RandomState(0), evaluated in fp64
+    (MoveIt's "always in collision" rule: spheres of nearby links that overlap by construction), sorted by (a, b).  An explicit
+    `pairs` is validated: a < b < n_links, no duplicates."""
+
+    ALWAYS_SAMPLES = 1024
+
+    def __init__(self, robot, margin=0.02, min_frame_gap=3, pairs=None):
+        if getattr(robot, 'kind', None) != KIND_CHAIN:
+            raise ValueError('SelfCollisionField serves serial chains only (a point robot has one collision sphere)')
+        from .self_layout import SELF_MAX_LINKS, SELF_MAX_PAIRS
+        self.robot = robot
+        self.margin = float(margin)
+        self.min_frame_gap = int(min_frame_gap)
+        rs = robot.spec()
+        n_links = len(rs['link_radius'])
+        if n_links > SELF_MAX_LINKS:
+            raise ValueError(f'{n_links} collision spheres exceed SELF_MAX_LINKS = {SELF_MAX_LINKS}')
+        if pairs is None:
+            pairs = self.default_pairs(robot, self.margin, self.min_frame_gap)
+        else:
+            pairs = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
+            if len(pairs) and not (np.all(pairs[:, 0] >= 0) and np.all(pairs[:, 0] < pairs[:, 1]) and np.all(pairs[:, 1] < n_links)):
+                raise ValueError(f'every pair needs 0 <= a < b < n_links = {n_links}')
+            if len(np.unique(pairs, axis=0)) != len(pairs):
+                raise ValueError('duplicate pairs')
+        if len(pairs) > SELF_MAX_PAIRS:
+            raise ValueError(f'{len(pairs)} pairs exceed SELF_MAX_PAIRS = {SELF_MAX_PAIRS}')
+        self.pairs = np.ascontiguousarray(pairs, dtype=np.int64).reshape(-1, 2)
+
+    @classmethod
+    def default_pairs(cls, robot, margin, min_frame_gap):
+        rs = robot.spec()
+        lf = np.asarray(rs['link_frame'], dtype=np.int64)
+        a, b = np.triu_indices(len(lf), k=1)                   # a < b, sorted by (a, b)
+        far = lf[b] - lf[a] >= min_frame_gap
+        a, b = a[far], b[far]
+        rng = np.random.RandomState(0)
+        q = rng.uniform(robot.q_min_np.astype(np.float64), robot.q_max_np.astype(np.float64), (cls.ALWAYS_SAMPLES, robot.q_dim))
+        x = fk_spheres_f64(rs, q)
+        T = margin + np.asarray(rs['link_radius'], np.float64)[a] + np.asarray(rs['link_radius'], np.float64)[b]
+        always = np.all(T[None, :] - np.linalg.norm(x[:, a] - x[:, b], axis=-1) > 0.0, axis=0)
+        return np.stack([a[~always], b[~always]], -1)
+
+    def thresholds(self):
+        """T_ab of every pair, fp64: margin + r_a + r_b from the robot's fp32 radii."""
+        r = np.asarray(self.robot.spec()['link_radius'], dtype=np.float64)
+        return self.margin + r[self.pairs[:, 0]] + r[self.pairs[:, 1]]
+
+    def zero_grad(self):
+        pass
+
+
+def pack_self_collision(robot, field):
+    """Pack a chain + its SelfCollisionField into ONE self-contained fp32 word buffer (self_layout.py: header, joint_tf rows, links
+    rows -- both in the row formats of pack_geometry, every link kept --, the pair table with T_ab rounded once from fp64)."""
+    from . import self_layout as S
+    if field.robot is not robot:
+        rs0, rs1 = field.robot.spec(), robot.spec()
+        if not all(np.array_equal(np.asarray(rs0[k]), np.asarray(rs1[k])) for k in ('joint_tf', 'link_frame', 'link_offset', 'link_radius')):
+            raise ValueError('the SelfCollisionField was built for another robot')
+    rs = robot.spec()
+    n_tf, n_links, n_pairs = rs['joint_tf'].shape[0], len(rs['link_radius']), len(field.pairs)
+    off_tf = S.SELF_HEADER_WORDS
+    off_links = off_tf + 12 * n_tf
+    off_pairs = off_links + 8 * n_links
+    total = off_pairs + S.SELF_PAIR_WORDS * n_pairs
+    buf = np.zeros((total,), dtype=np.float32)
+    hdr = S.header(buf)
+    for name, value in dict(magic=S.SELF_MAGIC, version=S.SELF_VERSION, n_dof=rs['n_dof'], n_tf=n_tf, n_links=n_links, n_pairs=n_pairs,
+                            margin=field.margin, off_tf=off_tf, off_links=off_links, off_pairs=off_pairs, total=total).items():
+        hdr[name] = value
+    buf[off_tf:off_links] = rs['joint_tf'].astype(np.float32).reshape(-1)
+    links = np.zeros((n_links, 8), np.float32)
+    links.view(np.int32)[:, 0] = rs['link_frame']
+    links[:, 1:4] = rs['link_offset']
+    links[:, 4] = rs['link_radius']
+    buf[off_links:off_pairs] = links.reshape(-1)
+    pw = np.zeros((n_pairs, S.SELF_PAIR_WORDS), np.float32)
+    pw.view(np.uint32)[:, 0] = (field.pairs[:, 0] | (field.pairs[:, 1] << S.SELF_PAIR_B_SHIFT)).astype(np.uint32)
+    pw[:, 1] = field.thresholds().astype(np.float32)
+    buf[off_pairs:total] = pw.reshape(-1)
+    return buf
 
 
 def _fit_axis(a, b, edge):

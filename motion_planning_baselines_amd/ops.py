@@ -12,7 +12,7 @@ import numpy as np
 import torch
 
 from . import _lib, rrt_layout
-from .geometry import MAX_FIELDS, count_fields, pack_geometry
+from .geometry import MAX_FIELDS, count_fields, pack_geometry, pack_self_collision
 from .geometry import header as geometry_header
 
 
@@ -41,7 +41,7 @@ def _on_tensor_device(fn):
     def run(*args, **kw):
         dev = None
         for a in list(args) + list(kw.values()):
-            t = a.buf if isinstance(a, DeviceGeometry) else a
+            t = a.buf if isinstance(a, (DeviceGeometry, DeviceSelfCollision)) else a
             if isinstance(t, torch.Tensor) and t.is_cuda:
                 if dev is None:
                     dev = t.device
@@ -107,6 +107,91 @@ class DeviceGeometry:
         self.n_dof, self.n_links = int(hdr['n_dof']), int(hdr['n_links'])
         self.n_fields = count_fields(host)
         self.buf = torch.from_numpy(host.copy()).to(device)
+
+
+class DeviceSelfCollision:
+    """A chain + its SelfCollisionField as the packed self buffer (geometry.pack_self_collision) resident in HBM: packed, validated
+    (mpb_self_check) and uploaded once."""
+
+    def __init__(self, robot, field, device):
+        from .self_layout import header as self_header
+        self.robot, self.field = robot, field
+        self.host = pack_self_collision(robot, field)
+        _lib.self_check(self.host)
+        hdr = self_header(self.host)
+        self.n_dof, self.n_links, self.n_pairs = int(hdr['n_dof']), int(hdr['n_links']), int(hdr['n_pairs'])
+        self.buf = torch.from_numpy(self.host.copy()).to(device)
+        # (the library reads a self buffer's header once per address: this address may have held another one before)
+        _lib.check(_lib.lib().mpb_self_invalidate(_ptr(self.buf)), 'mpb_self_invalidate')
+
+
+def _self_out(trajs, out, accumulate):
+    B = trajs.shape[0]
+    if out is None:
+        if accumulate:
+            raise ValueError('accumulate needs an existing out buffer')
+        return torch.empty(B, device=trajs.device, dtype=torch.float32)
+    if out.numel() != B:
+        raise ValueError(f'out has {out.numel()} elements, expected {B}')
+    _chk(out, out.shape, 'out')
+    return out
+
+
+@_on_tensor_device
+def self_collision_eval(trajs, sc, k_sigma, weight=1.0, h_begin=1, per_waypoint=False, out=None, accumulate=False):
+    """trajs (B, H, d) -> out (B,) (+)= weight * k_sigma * sum_{h >= h_begin} c(q_h) of a DeviceSelfCollision
+    (mpb_self_collision_eval); per_waypoint also returns c (B, H), un-scaled, 0 below h_begin."""
+    B, H, d = trajs.shape
+    _chk(trajs, (B, H, d), 'trajs')
+    if d < sc.n_dof:
+        raise ValueError(f'trajs has {d} columns, the chain {sc.n_dof} degrees of freedom')
+    out = _self_out(trajs, out, accumulate)
+    pw = torch.empty(B, H, device=trajs.device, dtype=torch.float32) if per_waypoint else None
+    _lib.check(_lib.lib().mpb_self_collision_eval(_ptr(trajs), _ptr(sc.buf), _ptr(out), _ptr(pw), B, H, d, int(h_begin), float(k_sigma),
+                                                 float(weight), int(bool(accumulate)), _stream()), 'mpb_self_collision_eval')
+    return (out, pw) if per_waypoint else out
+
+
+@_on_tensor_device
+def self_collision_grad(trajs, sc, k_sigma, weight=1.0, h_begin=1, out=None, grad=None, accumulate=False):
+    """(out (B,), grad (B, H, d)) (+)= the self-collision cost and d out / d trajs (mpb_self_collision_grad); accumulate adds onto the
+    given `out` AND `grad` (velocity channels left alone), otherwise both are written (velocity channels 0)."""
+    B, H, d = trajs.shape
+    _chk(trajs, (B, H, d), 'trajs')
+    if d < sc.n_dof:
+        raise ValueError(f'trajs has {d} columns, the chain {sc.n_dof} degrees of freedom')
+    if accumulate and grad is None:
+        raise ValueError('accumulate needs existing out and grad buffers')
+    out = _self_out(trajs, out, accumulate)
+    if grad is None:
+        grad = torch.empty_like(trajs)
+    else:
+        _chk(grad, (B, H, d), 'grad')
+    _lib.check(_lib.lib().mpb_self_collision_grad(_ptr(trajs), _ptr(sc.buf), _ptr(out), _ptr(grad), B, H, d, int(h_begin), float(k_sigma),
+                                                 float(weight), int(bool(accumulate)), _stream()), 'mpb_self_collision_grad')
+    return out, grad
+
+
+@_on_tensor_device
+def self_collision_check(q, sc, with_gap=False, flag=None, gap=None):
+    """(N, D) configurations -> bool (N,): the robot collides with itself (mpb_self_collision_check); with_gap also returns the hinge
+    sum.  Given `flag` (and `gap`) -- the outputs of collision_check --, the answer is ORed into the flags and added onto the gap."""
+    N, D = q.shape
+    _chk(q, (N, D), 'q')
+    if D != sc.n_dof:
+        raise ValueError(f'q has {D} columns, the chain {sc.n_dof} degrees of freedom')
+    or_into = flag is not None
+    if or_into:
+        _chk(flag, (N,), 'flag', dtype=torch.bool)
+        _chk(gap, (N,), 'gap', allow_none=True)
+        if with_gap and gap is None:
+            raise ValueError('with_gap next to flag= needs the gap= to add onto (the gap of collision_check(..., with_gap=True))')
+    else:
+        flag = torch.empty(N, device=q.device, dtype=torch.bool)
+        gap = torch.empty(N, device=q.device, dtype=torch.float32) if with_gap else None
+    _lib.check(_lib.lib().mpb_self_collision_check(_ptr(q), _ptr(sc.buf), _ptr(flag), _ptr(gap), N, D, int(or_into), _stream()),
+               'mpb_self_collision_check')
+    return (flag, gap) if (with_gap or gap is not None) else flag
 
 
 @_on_tensor_device

@@ -14,6 +14,7 @@ import numpy as np
 import torch
 
 from ... import ops
+from ...geometry import SelfCollisionField
 
 
 class Cost(ABC):
@@ -67,6 +68,10 @@ class CostCollision(Cost):
     """Hinge collision cost over one collision field (cost_functions.py:147-231).
 
     eval: ``1/sigma_coll^2 * sum_{h>=1} field_cost(q_h)`` (traj_range [1, None], field_factor.py:31-39).
+
+    `field` may be a geometry.SelfCollisionField (the robot against itself; the reference's examples get that field from
+    task.get_collision_fields() with use_self_collision_storm=True): eval / eval_with_grad / get_linear_system then go to the
+    self-collision kernels (mpb_self_collision_*).  Such a member is never fused into a planner kernel.
     """
 
     def __init__(self, robot, n_support_points, field=None, sigma_coll=None, **kwargs):
@@ -74,12 +79,26 @@ class CostCollision(Cost):
         self.field = field
         self.sigma_coll = sigma_coll
         self._geom = None
+        self._self = None
 
     @property
     def k_sigma(self):
         return 1.0 / (self.sigma_coll ** 2)          # FieldFactor.K (field_factor.py:15)
 
+    @property
+    def is_self(self):
+        return isinstance(self.field, SelfCollisionField)
+
+    def device_self(self, device):
+        """The packed self-collision buffer of a SelfCollisionField member on `device` (packed, checked and uploaded once)."""
+        assert self.is_self
+        if self._self is None or self._self.buf.device != torch.device(device):
+            self._self = ops.DeviceSelfCollision(self.robot, self.field, device)
+        return self._self
+
     def device_geometry(self, device):
+        if self.is_self:
+            raise TypeError('a SelfCollisionField has no obstacle geometry: use device_self()')
         if self._geom is None or self._geom.buf.device != torch.device(device):
             self._geom = ops.DeviceGeometry(self.robot, self.field, device)
         return self._geom
@@ -88,11 +107,15 @@ class CostCollision(Cost):
         if self.field is None:
             return 0
         trajs = self._as_3d(trajs)
+        if self.is_self:
+            return ops.self_collision_eval(trajs, self.device_self(trajs.device), self.k_sigma)
         return ops.cost_collision_eval(trajs, self.device_geometry(trajs.device), self.k_sigma)
 
     def eval_with_grad(self, trajs, weight=1.0):
         """(cost (B,), d cost / d trajs (B,H,d)): what the reference gets from autograd (chomp.py:139)."""
         trajs = self._as_3d(trajs)
+        if self.is_self:
+            return ops.self_collision_grad(trajs, self.device_self(trajs.device), self.k_sigma, weight=weight)
         return ops.cost_collision_grad(trajs, self.device_geometry(trajs.device), self.k_sigma, weight=weight)
 
     def get_linear_system(self, trajs, n_interpolated_points=None, **observation):
@@ -105,12 +128,31 @@ class CostCollision(Cost):
         trajs = self._as_3d(trajs)
         B, H, d = trajs.shape
         assert d == self.dim, 'get_linear_system works on (B, H, 2*n_dof) trajectories'
+        if self.is_self:
+            return self._self_linear_system(trajs)
         rows = ops.gpmp2_collision_rows(trajs, self.device_geometry(trajs.device), n_interp=n_interpolated_points or 0)[0]
         N, D = self.dim * H, self.n_dof
         A = torch.zeros(B, H - 1, N, device=trajs.device, dtype=trajs.dtype)
         for i in range(H - 1):
             A[:, i, (i + 1) * self.dim:(i + 1) * self.dim + D] = rows[:, i + 1, :D]
         b = rows[:, 1:, D].unsqueeze(-1).clone()
+        K = self.k_sigma * torch.eye(H - 1, device=trajs.device, dtype=trajs.dtype).repeat(B, 1, 1)
+        return A, b, K
+
+    def _self_linear_system(self, trajs):
+        """(A, b, K) of a self-collision member in the obstacle member's convention: row i holds -d c / d q of waypoint i + 1 at
+        that waypoint's position columns, b the waypoint costs, K = I / sigma^2.  ONE gradient launch gives every row of A (c_h
+        depends on q_h alone: the gradient of sum_h c_h IS the per-waypoint Jacobian); b takes a cost launch of its own, since
+        mpb_self_collision_grad has no per-waypoint output.  The support points only: a self member has no interpolated
+        Jacobian."""
+        B, H, d = trajs.shape
+        sc, D = self.device_self(trajs.device), self.n_dof
+        _, grad = ops.self_collision_grad(trajs, sc, 1.0, weight=1.0, h_begin=1)
+        _, pw = ops.self_collision_eval(trajs, sc, 1.0, h_begin=1, per_waypoint=True)
+        A = torch.zeros(B, H - 1, self.dim * H, device=trajs.device, dtype=trajs.dtype)
+        for i in range(H - 1):
+            A[:, i, (i + 1) * self.dim:(i + 1) * self.dim + D] = -grad[:, i + 1, :D]
+        b = pw[:, 1:].unsqueeze(-1).clone()
         K = self.k_sigma * torch.eye(H - 1, device=trajs.device, dtype=trajs.dtype).repeat(B, 1, 1)
         return A, b, K
 
@@ -351,7 +393,14 @@ class CostComposite(Cost):
             if isinstance(cost, CostCollision):
                 if cost.field is None:
                     continue
-                c = ops.cost_collision_eval(trajs_coll, cost.device_geometry(trajs.device), cost.k_sigma, weight=w)
+                if cost.is_self:
+                    sc = cost.device_self(trajs.device)
+                    if torch.is_tensor(total) and total.ndim == 1 and total.is_contiguous() and total.dtype == torch.float32:
+                        ops.self_collision_eval(trajs_coll, sc, cost.k_sigma, weight=w, out=total, accumulate=True)
+                        continue
+                    c = ops.self_collision_eval(trajs_coll, sc, cost.k_sigma, weight=w)
+                else:
+                    c = ops.cost_collision_eval(trajs_coll, cost.device_geometry(trajs.device), cost.k_sigma, weight=w)
             elif isinstance(cost, _TrajectoryTermCost):
                 term_members.append((cost.term_spec(trajs.device), float(w)))
                 continue
@@ -368,11 +417,12 @@ class CostComposite(Cost):
 
     def device_plan(self, device):
         """How a planner kernel pipeline can serve this composite without leaving the device:
-        (collision members [(CostCollision, weight)], merged term specs, other members [(cost, weight)])."""
+        (collision members [(CostCollision, weight)], merged term specs, other members [(cost, weight)]).  Self-collision
+        members are in none of the three: self_terms() lists them."""
         coll, terms, other = [], [], []
         for cost, w in zip(self.cost_l, self.weight_cost_l):
             if isinstance(cost, CostCollision):
-                if cost.field is not None:
+                if cost.field is not None and not cost.is_self:
                     coll.append((cost, float(w)))
             elif isinstance(cost, _TrajectoryTermCost):
                 terms.append((cost.term_spec(device), float(w)))
@@ -404,9 +454,13 @@ class CostComposite(Cost):
         return A, b, K
 
     def collision_terms(self):
-        """[(CostCollision, weight)] of the members that carry a field."""
+        """[(CostCollision, weight)] of the members that carry an OBSTACLE field."""
         return [(c, float(w)) for c, w in zip(self.cost_l, self.weight_cost_l)
-                if isinstance(c, CostCollision) and c.field is not None]
+                if isinstance(c, CostCollision) and c.field is not None and not c.is_self]
+
+    def self_terms(self):
+        """[(CostCollision, weight)] of the members whose field is a SelfCollisionField."""
+        return [(c, float(w)) for c, w in zip(self.cost_l, self.weight_cost_l) if isinstance(c, CostCollision) and c.is_self]
 
     def single_collision_term(self):
         """(collision evaluator, weight) if this composite consists of collision fields only (1..4 of them) -- the
@@ -425,6 +479,7 @@ class MergedCollision:
     def __init__(self, terms):
         (c0, w0) = terms[0]
         assert all(c.robot is c0.robot for c, _ in terms), 'collision members must share the robot'
+        assert not any(c.is_self for c, _ in terms), 'a self-collision member has no obstacle field to chain'
         self.robot = c0.robot
         self.fields = [c.field for c, _ in terms]
         self.k_sigma = c0.k_sigma
@@ -451,7 +506,7 @@ def merge_collision_terms(terms):
 def fusable_collision(cost):
     """Return (collision evaluator, weight) when `cost` is a collision cost the kernels can fuse, else None."""
     if isinstance(cost, CostCollision) and cost.field is not None:
-        return cost, 1.0
+        return None if cost.is_self else (cost, 1.0)       # (a self member has its own kernels: never fused)
     if isinstance(cost, CostComposite):
         key = tuple((id(c), float(w)) for c, w in zip(cost.cost_l, cost.weight_cost_l))
         cached = cost.__dict__.get('_fused_cache')
@@ -461,25 +516,39 @@ def fusable_collision(cost):
     return None
 
 
+class DevicePlan(tuple):
+    """(collision evaluator or None, its weight, merged trajectory-term specs) -- unpacks as those three -- plus `.selfs`, the
+    self-collision members [(CostCollision, weight)] a planner serves with mpb_self_collision_eval / _grad accumulating onto the
+    obstacle member's outputs."""
+
+    def __new__(cls, cc, weight, groups, selfs=()):
+        self = super().__new__(cls, (cc, weight, groups))
+        self.selfs = list(selfs)
+        return self
+
+
 def device_plan(cost, device):
-    """(collision evaluator or None, its weight, merged trajectory-term specs) when every member of `cost` is
-    served by the HIP library (collision fields -- up to four, chained -- and trajectory-only terms): the case a
-    planner can run as sample kernel -> term kernel -> update kernel with no host round trip; None otherwise."""
+    """DevicePlan (collision evaluator or None, its weight, merged trajectory-term specs; .selfs) when every member of `cost`
+    is served by the HIP library (collision fields -- up to four, chained --, self-collision fields and trajectory-only terms):
+    the case a planner can run as sample kernel -> self / term kernels -> update kernel with no host round trip; None otherwise."""
     if isinstance(cost, CostComposite):
         key = ('plan', str(device)) + tuple((id(c), float(w)) for c, w in zip(cost.cost_l, cost.weight_cost_l))
         cached = cost.__dict__.get('_plan_cache')
         if cached is not None and cached[0] == key:
             return cached[1]
         coll, groups, other = cost.device_plan(device)
+        selfs = cost.self_terms()
         plan = None
-        if not other and (coll or groups):
+        if not other and (coll or groups or selfs):
             merged = merge_collision_terms(coll) if coll else (None, 0.0)
             if merged is not None:
-                plan = (merged[0], merged[1], groups)
+                plan = DevicePlan(merged[0], merged[1], groups, selfs)
         cost.__dict__['_plan_cache'] = (key, plan)
         return plan
     if isinstance(cost, CostCollision):
-        return (cost, 1.0, []) if cost.field is not None else None
+        if cost.field is None:
+            return None
+        return DevicePlan(None, 0.0, [], [(cost, 1.0)]) if cost.is_self else DevicePlan(cost, 1.0, [])
     if isinstance(cost, _TrajectoryTermCost):
-        return None, 0.0, _merge_term_specs([(cost.term_spec(device), 1.0)])
+        return DevicePlan(None, 0.0, _merge_term_specs([(cost.term_spec(device), 1.0)]))
     return None

@@ -9,7 +9,7 @@ evaluated factor-wise (csrc/mpb_stoch_gpmp.hip).
 import torch
 
 from .. import ops
-from ..geometry import MAX_DOF
+from ..geometry import MAX_DOF, SelfCollisionField
 from .base import OptimizationPlanner, gp_prior_factor, gp_prior_scale_tril
 
 
@@ -35,6 +35,8 @@ class StochGPMP(OptimizationPlanner):
                          multi_goal_states=multi_goal_states, sigma_start_init=sigma_start_init,
                          sigma_goal_init=sigma_goal_init, sigma_gp_init=sigma_gp_init, pos_only=False,
                          tensor_args=tensor_args)
+        if any(isinstance(f, SelfCollisionField) for f in (collision_fields or [])):
+            raise NotImplementedError('StochGPMP: a SelfCollisionField in collision_fields is not wired into the fused StochGPMP cost')
         if not collision_fields or len(collision_fields) > 4:
             raise NotImplementedError('StochGPMP on the GPU takes one to four CollisionFields')
         assert multi_goal_states is not None, 'StochGPMP kernels need goal states'

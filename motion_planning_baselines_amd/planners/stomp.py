@@ -294,8 +294,10 @@ class STOMP(OptimizationPlanner):
         elif not observation and device_plan(self.cost, self.device) is not None:
             # composite of HIP-served members: sample(+collision) kernel -> trajectory-terms kernel(s) -> update
             # kernel, all queued on the stream without a host round trip
-            cc, weight, groups = device_plan(self.cost, self.device)
+            plan = device_plan(self.cost, self.device)
+            cc, weight, groups = plan
             flat = self.state_particles.view(-1, self.n_support_points, self.d_state_opt)
+            flat_costs = self.costs.view(-1)
             for _ in range(opt_iters):
                 eps = self._draw_eps(1)
                 ops.stomp_sample(self._particle_means, None if eps is None else eps[0], self.state_particles,
@@ -305,8 +307,13 @@ class STOMP(OptimizationPlanner):
                                  costs=None if cc is None else self.costs,
                                  k_sigma=0.0 if cc is None else cc.k_sigma, weight=weight)
                 self._iter += 1
-                for gi, spec in enumerate(groups):
-                    ops.cost_terms_eval(flat, self.n_dof, out=self.costs, accumulate=(cc is not None or gi > 0), **spec)
+                have = cc is not None
+                for sm, w in plan.selfs:      # SelfCollisionField members: onto the costs the sample kernel wrote
+                    ops.self_collision_eval(flat, sm.device_self(self.device), sm.k_sigma, weight=w, out=flat_costs, accumulate=have)
+                    have = True
+                for spec in groups:
+                    ops.cost_terms_eval(flat, self.n_dof, out=self.costs, accumulate=have, **spec)
+                    have = True
                 ops.stomp_update(self._particle_means, self.state_particles, self.costs, self._weights_buf,
                                  self.Sigma, self.lr, self.temperature)
         else:

@@ -96,14 +96,21 @@ class PlanningTask:
 
     The collision predicate is build-defined (torch_robotics is absent): a configuration is in collision iff the
     package's per-waypoint collision cost  sum_f s_f sum_l relu(margin + r_l - min_o sdf_o(x_l))  is positive
-    (mpb_collision_check; the same evaluators as every cost kernel).  `field` may be a list of up to four fields."""
+    (mpb_collision_check; the same evaluators as every cost kernel).  `field` may be a list of up to four fields.
 
-    def __init__(self, robot, field, tensor_args=None, seed=0):
+    self_field: a geometry.SelfCollisionField (the reference's use_self_collision_storm=True).  compute_collision and
+    random_coll_free_q then OR the self predicate in (a second launch, mpb_self_collision_check with or_into); the trajectory
+    validation below and the RRT planners built on the task read `geom` alone and raise NotImplementedError rather than ignore
+    it."""
+
+    def __init__(self, robot, field, self_field=None, tensor_args=None, seed=0):
         from .planners.base import require_cuda
         self.tensor_args = tensor_args
         self.device = require_cuda(tensor_args)
         self.robot, self.field = robot, field
         self.geom = ops.DeviceGeometry(robot, field, self.device)
+        self.self_field = self_field
+        self.self_geom = None if self_field is None else ops.DeviceSelfCollision(robot, self_field, self.device)
         self.q_dim = robot.q_dim
         self.q_min = robot.q_min.to(self.device)
         self.q_max = robot.q_max.to(self.device)
@@ -113,7 +120,19 @@ class PlanningTask:
     def compute_collision(self, qs, **kwargs):
         """(..., D) configurations -> bool (...): in collision."""
         q2 = torch.as_tensor(qs, dtype=torch.float32, device=self.device).reshape(-1, self.q_dim).contiguous()
-        return ops.collision_check(q2, self.geom).reshape(qs.shape[:-1])
+        return self._in_collision(q2).reshape(qs.shape[:-1])
+
+    def _in_collision(self, q2):
+        """(N, D) contiguous fp32 on the device -> bool (N,): collides with the world or (self_field) with itself."""
+        flag = ops.collision_check(q2, self.geom)
+        if self.self_geom is not None:
+            ops.self_collision_check(q2, self.self_geom, flag=flag)
+        return flag
+
+    def require_no_self_field(self, what):
+        if self.self_field is not None:
+            raise NotImplementedError(f'{what} reads the obstacle geometry alone: it does not serve a task with a self_field '
+                                      f'(SelfCollisionField) yet')
 
     def random_q(self, n_samples=1):
         """n_samples configurations uniform within the joint limits, (n_samples, D)."""
@@ -129,7 +148,7 @@ class PlanningTask:
         found, have = [], 0
         for _ in range(int(max_tries)):
             q = self.random_q(max(int(max_samples), n_samples)).contiguous()
-            free = q[~ops.collision_check(q, self.geom)]
+            free = q[~self._in_collision(q)]
             found.append(free)
             have += free.shape[0]
             if have >= n_samples:
@@ -143,6 +162,7 @@ class PlanningTask:
     def _trajs_stats(self, trajs, num_interpolation, with_flags=False):
         """trajs (..., H, W), W >= q_dim, leading dimensions flattened -> (trajs (N, H, W), the outputs of
         ops.traj_collision_stats).  A contiguous fp32 GPU tensor is read in place, velocity columns and all."""
+        self.require_no_self_field('trajectory validation (mpb_traj_collision_stats)')
         t = torch.as_tensor(trajs, dtype=torch.float32, device=self.device)
         if t.dim() < 2 or t.shape[-1] < self.q_dim:
             raise ValueError(f'trajs has shape {tuple(t.shape)}, expected (..., H, W) with W >= {self.q_dim}')
