@@ -34,6 +34,8 @@
 #include "mpb_rrt_layout.h"
 /* the packed self-collision buffer in numbers (generated from self_layout.py): header word indices MPB_SW_*, MPB_SELF_* */
 #include "mpb_self_layout.h"
+/* the packed SDF-grid buffer in numbers (generated from sdf_layout.py): header word indices MPB_DW_*, MPB_SDF_* */
+#include "mpb_sdf_layout.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -65,7 +67,8 @@ extern "C" {
  *                        also carries batched RRT* / informed RRT* (mpb_rrt_star_*): additive, no existing signature moved.
  *                        mpb_mppi_plan (how mpb_mppi_step would launch a shape) added the same way: additive; so was
  *                        mpb_traj_collision_stats (validation of a trajectory batch), and the self-collision field
- *                        (mpb_self_check, mpb_self_invalidate, mpb_self_collision_eval / _grad / _check). */
+ *                        (mpb_self_check, mpb_self_invalidate, mpb_self_collision_eval / _grad / _check).  So was the SDF-grid
+ *                        field (mpb_sdf_grid_check, _invalidate, _build, _sample, _eval, _grad, _collision_check). */
 #define MPB_ABI_VERSION 7
 #define MPB_VERSION_TUNING_BUILD 0x40000000
 int mpb_version(void);
@@ -636,6 +639,70 @@ int mpb_self_collision_grad(const float *trajs, const float *self, float *out, f
                             int B, int H, int d, int h_begin, float k_sigma, float weight, int accumulate, void *stream);
 int mpb_self_collision_check(const float *q, const float *self, unsigned char *in_collision, float *gap,
                              int N, int D, int or_into, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * SDF-grid field: a precomputed lattice of signed distances, interpolated at the robot's collision spheres (build-defined, DESIGN.md
+ * 10; the reference's examples build their environments with precompute_sdf_obj_fixed=True, sdf_cell_size=...).  Serves arbitrary
+ * geometry (the caller supplies the node values) at a cost that does not depend on what the scene holds.
+ *   grid:  (nx, ny, nz) fp32 nodes, node (i, j, k) at lo + (i, j, k) * cell (one cell for all axes), word (k * ny + j) * nx + i of
+ *          the node section; nz == 1: planar, z ignored, bilinear.  Limits: every dimension in 2..MPB_SDF_MAX_DIM (nz: or 1),
+ *          at most MPB_SDF_MAX_NODES nodes; 32-bit index arithmetic throughout.
+ *   s(x):  per axis u = (x - lo) * inv_cell (inv_cell = fl32(1 / cell), a header word), clamped to [0, n - 1]; i0 = min(floor(u),
+ *          n - 2); f = u - i0; lerp form fmaf(f, v1 - v0, v0) along x, then y, then z -- a point with f == 0 on every axis returns
+ *          that node's bits.  A point outside the box takes the value of the nearest boundary point and gradient 0 along every axis
+ *          it lies outside on: the grid is expected to cover the workspace.
+ *   c(q) = sum_l relu(margin + r_l - s(x_l(q)))  over the robot's collision spheres (x_l: mpb_fk_collision_points; a point robot has
+ *          its one sphere at q, z = 0 with two coordinates); in collision iff c(q) > 0 (the rule of mpb_collision_check).
+ *   gradient: an active sphere (margin + r_l - s > 0) contributes -grad s(x_l) through J^T, grad s the exact derivative of the
+ *          interpolant (piecewise constant along its own axis), from the same eight (planar: four) node loads as the value.
+ *
+ * The SDF buffer is ONE self-contained array of 32-bit words with a magic and version of its own (mpb_sdf_layout.h, generated from
+ * sdf_layout.py -- the one definition): a header of MPB_SDF_HEADER_WORDS words (MPB_DW_MAGIC, _VERSION, _KIND = MPB_KIND_POINT /
+ * _CHAIN, _N_DOF, _N_TF = n_dof + 1 or 0 for a point robot, _N_LINKS, _MARGIN, _DIMS (3), _LO (3), _CELL, _INV_CELL, the section
+ * offsets _OFF_TF, _OFF_LINKS, _OFF_NODES (a multiple of MPB_SDF_NODE_ALIGN words), _TOTAL; the rest zero), then the joint transforms
+ * (n_tf x 12) and the link table (n_links x 8) in the row formats of the geometry buffer, EVERY link, then the nodes.
+ *
+ * mpb_sdf_grid_check validates such a buffer held in HOST memory (n_words must equal its total): magic / version, kind, limits
+ * (n_dof, n_links, dimensions, node count), the transforms a kind needs, a planar grid only with a point robot, offsets and total,
+ * cell positive and finite with inv_cell its fp32 reciprocal, margin and lo finite, link frames sorted in [1, n_dof + 1].  It reads
+ * the words before the node section alone: the node values are the caller's to check (geometry.GridSDFField refuses non-finite
+ * ones), and a caller whose nodes are built on the device may pass those leading words with the whole buffer's n_words.
+ *
+ * The device entry points take the buffer in DEVICE memory, 16-byte aligned, validated by the caller before the upload.  They read
+ * its 32 header words back ONCE per buffer address and device (a synchronous 128-byte copy on the first call with that pointer:
+ * make that call outside stream capture) and check the header alone.  The kernels form every node index from the dimensions they
+ * were launched with, clamped into the grid whatever the input, compare the header (magic, n_dof, n_links, dims) with those numbers
+ * and answer NaN (in_collision = 1; the builder: nothing written) when it has changed since.  mpb_sdf_grid_invalidate(sdf) forgets
+ * what was read at that address: call it whenever ANOTHER SDF buffer is written at an address an earlier call may have seen.
+ *
+ * mpb_sdf_grid_build: fills the node section of `sdf` with min_o sd_o(node position) over the spheres and boxes of ONE packed
+ *   CollisionField `geom` (a geometry buffer in device memory, any robot; a chain of fields is refused), node position
+ *   fmaf(i, cell, lo) per axis, the signed distances every cost kernel takes.  One thread per node.  Reads both headers back
+ *   synchronously.  Refusals in this order: null pointer, alignment, the SDF header, the geometry header (magic / version: INVALID;
+ *   chained: UNSUPPORTED; no obstacle: INVALID).
+ * mpb_sdf_grid_sample: points (N, 3) -> s (N) and, when grad is not NULL, grad (N, 3) = d s / d x.  No robot.  Refusals: N < 0:
+ *   INVALID; (N == 0: MPB_OK, nothing launched;) null pointer; alignment; the header.
+ * mpb_sdf_grid_eval / _grad: the signature and meaning of mpb_self_collision_eval / _grad, c as above: out[b] (+)= weight * k_sigma *
+ *   sum_{h >= h_begin} c(trajs[b, h, :n_dof]); per_waypoint (B, H) optional: c un-scaled, 0 for h < h_begin; grad (B, H, d) (+)=
+ *   d out[b] / d trajs[b], the velocity channels n_dof .. d-1 written 0 when not accumulating and left alone when accumulating;
+ *   accumulate != 0 adds the fresh value in ONE fp32 rounding.  One wave per trajectory, one lane per waypoint, trips of 64; sums in
+ *   fixed order: the same bits on every run.
+ * mpb_sdf_grid_collision_check: q (N, D) with D == n_dof; in_collision (N) bytes 0 / 1 = c > 0; gap (N) optional: c; or_into != 0
+ *   ORs into the existing flags and adds c onto the existing gap -- the signature and meaning of mpb_self_collision_check.
+ * Refusals of the last three, in this order: d > 2 MPB_MAX_DOF (check: D > MPB_MAX_DOF): MPB_E_UNSUPPORTED; B < 0, H < 1, d < 1,
+ * h_begin < 0 (check: N < 0, D < 1): MPB_E_INVALID; (B == 0 / N == 0: MPB_OK, nothing launched;) a null required pointer, an SDF
+ * buffer not 16-byte aligned: MPB_E_INVALID; the header: as mpb_sdf_grid_check says; d < n_dof (check: D != n_dof): MPB_E_INVALID.
+ * ------------------------------------------------------------------------------------------- */
+int mpb_sdf_grid_check(const float *sdf_host, int n_words);
+int mpb_sdf_grid_invalidate(const float *sdf);
+int mpb_sdf_grid_build(const float *geom, float *sdf, void *stream);
+int mpb_sdf_grid_sample(const float *points, const float *sdf, float *s, float *grad, int N, void *stream);
+int mpb_sdf_grid_eval(const float *trajs, const float *sdf, float *out, float *per_waypoint,
+                      int B, int H, int d, int h_begin, float k_sigma, float weight, int accumulate, void *stream);
+int mpb_sdf_grid_grad(const float *trajs, const float *sdf, float *out, float *grad,
+                      int B, int H, int d, int h_begin, float k_sigma, float weight, int accumulate, void *stream);
+int mpb_sdf_grid_collision_check(const float *q, const float *sdf, unsigned char *in_collision, float *gap,
+                                 int N, int D, int or_into, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Batched RRT-Connect -- replaces RRTConnect._run_optimization (rrt_connect.py:93-192) with RRTBase.get_pre_sample /

@@ -72,6 +72,13 @@ SIGNATURES = {
     'mpb_self_collision_eval': [_p, _p, _p, _p, _i, _i, _i, _i, _f, _f, _i, _p],
     'mpb_self_collision_grad': [_p, _p, _p, _p, _i, _i, _i, _i, _f, _f, _i, _p],
     'mpb_self_collision_check': [_p, _p, _p, _p, _i, _i, _i, _p],
+    'mpb_sdf_grid_check': [_p, _i],
+    'mpb_sdf_grid_invalidate': [_p],
+    'mpb_sdf_grid_build': [_p, _p, _p],
+    'mpb_sdf_grid_sample': [_p, _p, _p, _p, _i, _p],
+    'mpb_sdf_grid_eval': [_p, _p, _p, _p, _i, _i, _i, _i, _f, _f, _i, _p],
+    'mpb_sdf_grid_grad': [_p, _p, _p, _p, _i, _i, _i, _i, _f, _f, _i, _p],
+    'mpb_sdf_grid_collision_check': [_p, _p, _p, _p, _i, _i, _i, _p],
     'mpb_rrt_connect_workspace_bytes': [_i, _i, _i, _i],
     'mpb_rrt_connect_init': [_p, ctypes.c_size_t, _p, _p, _p, _i, _i, _i, _i, _i, _p],
     'mpb_rrt_connect_run': [_p, ctypes.c_size_t, _p, _i, _p, ctypes.c_size_t, _p, _p, _p, _p] + [_i] * 8 + [_f, _f, _u64, _u32, _p],
@@ -175,6 +182,13 @@ def self_check(buf):
     """Validate a packed self-collision buffer (numpy fp32) on the host side of the C-ABI."""
     buf = np.ascontiguousarray(buf, dtype=np.float32)
     check(lib().mpb_self_check(buf.ctypes.data_as(ctypes.c_void_p), int(buf.size)), 'mpb_self_check')
+
+
+def sdf_grid_check(buf, n_words=None):
+    """Validate a packed SDF-grid buffer (numpy fp32) on the host side of the C-ABI.  n_words: the words of the WHOLE buffer when `buf`
+    holds only those before the node section (the validator reads the header and the robot tables alone)."""
+    buf = np.ascontiguousarray(buf, dtype=np.float32)
+    check(lib().mpb_sdf_grid_check(buf.ctypes.data_as(ctypes.c_void_p), int(buf.size if n_words is None else n_words)), 'mpb_sdf_grid_check')
 
 
 def geom_flags(buf):

@@ -1,0 +1,476 @@
+// mpb_sdf_grid.hip -- a precomputed grid of signed distances as a collision field: build, sample, cost, gradient and predicate of a
+// GridSDFField (geometry.py; build-defined; the reference's precompute_sdf_obj_fixed=True).  The grid is a lattice of
+// (nx, ny, nz) fp32 nodes, node (i, j, k) at lo + (i, j, k) * cell, word (k * ny + j) * nx + i of the node section of the packed SDF
+// buffer (include/mpb_sdf_layout.h); nz == 1 is a planar grid (z ignored).
+//
+// Sampling s(x), per axis:  u = (x - lo) * inv_cell, clamped to [0, n - 1];  i0 = min(floor(u), n - 2);  f = u - i0;  lerp form
+// fmaf(f, v1 - v0, v0) along x, then y, then z.  The gradient is the exact derivative of that interpolant (piecewise constant along its own
+// axis), 0 along an axis the point lies outside the box on, from the same eight (planar: four) node loads as the value.
+// Per waypoint  c(q) = sum_l relu(margin + r_l - s(x_l(q)))  over the robot's collision spheres (FKState / fk_advance of mpb_geom.h through
+// a GeomView filled from the SDF buffer; a point robot has its one sphere at q).
+//
+// Mapping: one wave per trajectory (a workgroup IS one wave: no barrier, no LDS), one lane per waypoint, trips of 64 for H > 64; the
+// predicate and the sampler give one lane per configuration / point; the builder one thread per node.  The node gathers are what
+// the kernels wait for (a lane's eight nodes are four pairs of adjacent words anywhere in a grid of tens of MB), so the spheres go in groups of
+// MPB_SDF_GROUP: the chain walk places the group, every load of the group is issued, then the hinges are taken.  With gradients the force
+// -grad s of an active sphere is pulled through J^T at once from the joint axes / origins the same walk has kept (FKState<true>,
+// joint_term), skipped wave-wide when a ballot finds the sphere active in no lane.
+// Order of the sums: spheres in table order in fp32 per waypoint, a lane's waypoints in ascending order, then the fixed-order wave
+// reduction of mpb_common.h: every run gives the same bits.  Every node index is clamped into the grid whatever the input (NaN included).
+#include <mutex>
+
+#include "mpb_common.h"
+#include "mpb_host.h"
+#include "mpb_geom.h"
+#include "../../include/mpb_sdf_layout.h"
+
+#define MPB_SDF_GROUP 4
+
+// the robot of an SDF buffer as the GeomView fk_advance reads (tf, n_dof) and the walk below reads (links, n_links); no obstacles
+__device__ __forceinline__ GeomView sdf_robot_view(const float* __restrict__ s) {
+    const int* si = reinterpret_cast<const int*>(s);
+    GeomView v = {};
+    v.kind = si[MPB_DW_KIND];
+    v.n_dof = si[MPB_DW_N_DOF];
+    v.n_tf = si[MPB_DW_N_TF];
+    v.n_links = si[MPB_DW_N_LINKS];
+    v.margin = s[MPB_DW_MARGIN];
+    v.tf = s + si[MPB_DW_OFF_TF];
+    v.links = s + si[MPB_DW_OFF_LINKS];
+    return v;
+}
+
+// the lattice: dims as the LAUNCHER read them (every node index is formed from these), the rest from the header
+struct SdfLattice {
+    int nx, ny, nz;
+    float lx, ly, lz, inv;
+    const float* nodes;
+};
+
+__device__ __forceinline__ SdfLattice sdf_lattice(const float* __restrict__ s, int nx, int ny, int nz) {
+    const int* si = reinterpret_cast<const int*>(s);
+    SdfLattice S;
+    S.nx = nx; S.ny = ny; S.nz = nz;
+    S.lx = s[MPB_DW_LO]; S.ly = s[MPB_DW_LO + 1]; S.lz = s[MPB_DW_LO + 2];
+    S.inv = s[MPB_DW_INV_CELL];
+    S.nodes = s + si[MPB_DW_OFF_NODES];
+    return S;
+}
+
+// a + b in one rounding whatever produced b (mpb_self_collision.hip says why)
+__device__ __forceinline__ float sdf_add_rounded(float a, float b) {
+#pragma clang fp contract(off)
+    return a + b;
+}
+
+// one axis: cell index i0 in [0, n - 2], fraction f in [0, 1], inside = the point is not beyond the box on this axis (a NaN coordinate
+// lands on node 0 and counts as outside)
+__device__ __forceinline__ void sdf_axis(float x, float lo, float inv, int n, int& i0, float& f, bool& inside) {
+    const float u = (x - lo) * inv;
+    const float top = (float)(n - 1);
+    inside = (u >= 0.f) && (u <= top);
+    const float uc = fminf(fmaxf(u, 0.f), top);
+    i0 = min((int)floorf(uc), n - 2);
+    f = uc - (float)i0;
+}
+
+// the nodes around one point and where it sits among them: the loads are issued here, their first use is in sdf_value / sdf_gradient
+struct SdfTaps {
+    float v000, v100, v010, v110, v001, v101, v011, v111;
+    float fx, fy, fz;
+    bool inx, iny, inz;
+};
+
+// (Loading the two x-neighbours as ONE 8-byte word pair was measured and changed nothing -- 3.007 against 3.011 ms at N = 131 072, DESIGN.md
+// 10: the kernels wait for the four cache lines a sphere's gather touches, not for the address cycles -- so the plain form stays.)
+__device__ __forceinline__ void sdf_load(const SdfLattice& S, float x, float y, float z, SdfTaps& T) {
+    int i0, j0, k0 = 0;
+    sdf_axis(x, S.lx, S.inv, S.nx, i0, T.fx, T.inx);
+    sdf_axis(y, S.ly, S.inv, S.ny, j0, T.fy, T.iny);
+    const float* p = S.nodes + (j0 * S.nx + i0);                 // (the two x-neighbours are adjacent words)
+    if (S.nz > 1) {                                             // (wave-uniform)
+        sdf_axis(z, S.lz, S.inv, S.nz, k0, T.fz, T.inz);
+        p += k0 * S.ny * S.nx;                                  // (< 2^27: the validator's node limit)
+        const float* pz = p + S.ny * S.nx;
+        T.v001 = pz[0]; T.v101 = pz[1]; T.v011 = pz[S.nx]; T.v111 = pz[S.nx + 1];
+    }
+    T.v000 = p[0]; T.v100 = p[1]; T.v010 = p[S.nx]; T.v110 = p[S.nx + 1];
+    if (S.nz <= 1) {
+        T.fz = 0.f; T.inz = false;
+        T.v001 = T.v000; T.v101 = T.v100; T.v011 = T.v010; T.v111 = T.v110;
+    }
+}
+
+__device__ __forceinline__ float sdf_lerp(float f, float v0, float v1) { return fmaf(f, v1 - v0, v0); }
+
+__device__ __forceinline__ float sdf_value(const SdfTaps& T) {
+    const float c00 = sdf_lerp(T.fx, T.v000, T.v100), c10 = sdf_lerp(T.fx, T.v010, T.v110);
+    const float c01 = sdf_lerp(T.fx, T.v001, T.v101), c11 = sdf_lerp(T.fx, T.v011, T.v111);
+    return sdf_lerp(T.fz, sdf_lerp(T.fy, c00, c10), sdf_lerp(T.fy, c01, c11));
+}
+
+// value and d s / d x of the interpolant: along x the y-z interpolation of the four x-differences, along y the z interpolation of the two
+// y-differences of the x-interpolated edges, along z the difference of the two faces; times inv_cell (d u / d x), 0 on a clamped axis
+__device__ __forceinline__ float sdf_gradient(const SdfTaps& T, float inv, float& gx, float& gy, float& gz) {
+    const float c00 = sdf_lerp(T.fx, T.v000, T.v100), c10 = sdf_lerp(T.fx, T.v010, T.v110);
+    const float c01 = sdf_lerp(T.fx, T.v001, T.v101), c11 = sdf_lerp(T.fx, T.v011, T.v111);
+    const float c0 = sdf_lerp(T.fy, c00, c10), c1 = sdf_lerp(T.fy, c01, c11);
+    const float dx0 = sdf_lerp(T.fy, T.v100 - T.v000, T.v110 - T.v010), dx1 = sdf_lerp(T.fy, T.v101 - T.v001, T.v111 - T.v011);
+    const float dx = sdf_lerp(T.fz, dx0, dx1);
+    const float dy = sdf_lerp(T.fz, c10 - c00, c11 - c01);
+    const float dz = c1 - c0;
+    gx = T.inx ? dx * inv : 0.f;
+    gy = T.iny ? dy * inv : 0.f;
+    gz = T.inz ? dz * inv : 0.f;
+    return sdf_lerp(T.fz, c0, c1);
+}
+
+// c(q) of one waypoint; GRAD: dq[i] = d c / d q_i (i < n_dof).  q / dq are register arrays indexed only with compile-time indices.
+template <bool GRAD>
+__device__ __forceinline__ float sdf_waypoint_cost(const GeomView& G, const SdfLattice& S, int L, const float (&q)[MPB_MAX_DOF],
+                                                   float (&dq)[MPB_MAX_DOF]) {
+    constexpr int N = MPB_SDF_GROUP;
+    if (G.kind == MPB_KIND_POINT) {
+        SdfTaps T;
+        sdf_load(S, q[0], q[1], (G.n_dof > 2) ? q[2] : 0.f, T);
+        float gx = 0.f, gy = 0.f, gz = 0.f;
+        const float s = GRAD ? sdf_gradient(T, S.inv, gx, gy, gz) : sdf_value(T);
+        const float h = fmaxf(G.margin + G.links[4] - s, 0.f);
+        if (GRAD) {
+            const bool on = h > 0.f;
+            dq[0] = on ? -gx : 0.f;
+            dq[1] = on ? -gy : 0.f;
+            if (G.n_dof > 2) dq[2] = on ? -gz : 0.f;
+        }
+        return h;
+    }
+    FKState<GRAD> F;
+    fk_identity(F);
+    F.frame = 0;
+    if (GRAD) {
+#pragma unroll
+        for (int i = 0; i < MPB_MAX_DOF; ++i) { F.zx[i] = F.zy[i] = F.zz[i] = F.px[i] = F.py[i] = F.pz[i] = 0.f; }
+    }
+    float cost = 0.f;
+    for (int l0 = 0; l0 < L; l0 += N) {
+        float x[N], y[N], z[N], thr[N];
+        int fr[N];
+        SdfTaps T[N];
+#pragma unroll
+        for (int i = 0; i < N; ++i) {
+            if (l0 + i < L) {                                                          // (wave-uniform)
+                const float4 lk = *reinterpret_cast<const float4*>(G.links + 8 * (l0 + i));   // frame, ox, oy, oz
+                const int f = min(__float_as_int(lk.x), G.n_tf);                         // (a checked buffer never clamps: keeps the walk inside tf)
+                while (F.frame < f) fk_advance<GRAD>(G, F, q);
+                x[i] = mad3(F.r00, lk.y, F.r01, lk.z, F.r02, lk.w, F.tx);
+                y[i] = mad3(F.r10, lk.y, F.r11, lk.z, F.r12, lk.w, F.ty);
+                z[i] = mad3(F.r20, lk.y, F.r21, lk.z, F.r22, lk.w, F.tz);
+                thr[i] = G.margin + G.links[8 * (l0 + i) + 4];
+                fr[i] = f;
+            } else {                                                                   // parked slot: hinge 0 whatever the grid holds
+                x[i] = y[i] = z[i] = 0.f;
+                thr[i] = -3.0e38f;
+                fr[i] = 0;
+            }
+            sdf_load(S, x[i], y[i], z[i], T[i]);
+        }
+#pragma unroll
+        for (int i = 0; i < N; ++i) {
+            if constexpr (GRAD) {
+                float gx, gy, gz;
+                const float s = sdf_gradient(T[i], S.inv, gx, gy, gz);
+                const float h = fmaxf(thr[i] - s, 0.f);
+                cost += h;
+                if (__ballot(h > 0.f) != 0ull) {
+                    const bool on = h > 0.f;
+                    const float fx = on ? -gx : 0.f, fy = on ? -gy : 0.f, fz = on ? -gz : 0.f;
+#pragma unroll
+                    for (int ii = 0; ii < MPB_MAX_DOF; ++ii)
+                        if (ii < fr[i] && ii < G.n_dof)
+                            dq[ii] += joint_term(F.zx[ii], F.zy[ii], F.zz[ii], F.px[ii], F.py[ii], F.pz[ii], x[i], y[i], z[i], fx, fy, fz);
+                }
+            } else {
+                cost += fmaxf(thr[i] - sdf_value(T[i]), 0.f);
+            }
+        }
+    }
+    return cost;
+}
+
+// the launcher read kind / n_dof / n_links / dims from the header; the kernels use ITS numbers for every row and node index and refuse
+// (NaN outputs) a buffer whose header has changed since
+__device__ __forceinline__ bool sdf_header_matches(const float* __restrict__ s, int n_dof, int L, int nx, int ny, int nz) {
+    const int* si = reinterpret_cast<const int*>(s);
+    return si[MPB_DW_MAGIC] == MPB_SDF_MAGIC && si[MPB_DW_N_DOF] == n_dof && si[MPB_DW_N_LINKS] == L && si[MPB_DW_DIMS] == nx &&
+           si[MPB_DW_DIMS + 1] == ny && si[MPB_DW_DIMS + 2] == nz;
+}
+
+template <bool GRAD>
+__global__ __launch_bounds__(64) void sdf_cost_kernel(const float* __restrict__ trajs, const float* __restrict__ sdfb, float* __restrict__ out,
+                                                      float* __restrict__ per_wp, float* __restrict__ grad, int H, int d, int h_begin,
+                                                      float k_sigma, float weight, int accumulate, int D, int L, int nx, int ny, int nz) {
+    const int lane = threadIdx.x, b = blockIdx.x;
+    const GeomView G = sdf_robot_view(sdfb);
+    const SdfLattice S = sdf_lattice(sdfb, nx, ny, nz);
+    const bool ok = sdf_header_matches(sdfb, D, L, nx, ny, nz);        // (D: the launcher's n_dof, which it held d against)
+    const float sc = weight * k_sigma;
+    float csum = 0.f;
+    for (int h0 = 0; h0 < H; h0 += 64) {
+        const int h = h0 + lane;
+        const bool live = ok && h < H && h >= h_begin;
+        float q[MPB_MAX_DOF], dq[MPB_MAX_DOF];
+#pragma unroll
+        for (int i = 0; i < MPB_MAX_DOF; ++i) { q[i] = 0.f; dq[i] = 0.f; }
+        float c = 0.f;
+        if (__ballot(live) != 0ull) {
+            // (a lane that is not live walks along at q = 0 -- its loads stay inside the grid -- and its result is dropped: the ballots of
+            // the walk then see whole waves)
+            if (live) {
+                const float* row = trajs + ((size_t)b * H + h) * d;
+#pragma unroll
+                for (int i = 0; i < MPB_MAX_DOF; ++i) q[i] = (i < D) ? row[i] : 0.f;
+            }
+            c = sdf_waypoint_cost<GRAD>(G, S, L, q, dq);
+            if (!live) c = 0.f;
+        }
+        if (!ok) c = __uint_as_float(0x7FC00000u);
+        if (h < H) {
+            if (per_wp) per_wp[(size_t)b * H + h] = c;
+            if (GRAD) {
+                float* grow = grad + ((size_t)b * H + h) * d;
+#pragma unroll
+                for (int i = 0; i < MPB_MAX_DOF; ++i) {
+                    if (i < D) {
+                        const float g = ok ? (live ? sc * dq[i] : 0.f) : c;
+                        grow[i] = accumulate ? sdf_add_rounded(grow[i], g) : g;
+                    }
+                }
+                if (!accumulate)
+                    for (int i = D; i < d; ++i) grow[i] = 0.f;   // the velocity channels
+            }
+        }
+        csum += c;
+    }
+    csum = wave_sum_f32(csum);
+    if (lane == 0) {
+        const float v = weight * (k_sigma * csum);
+        out[b] = accumulate ? sdf_add_rounded(out[b], v) : v;
+    }
+}
+
+__global__ __launch_bounds__(64) void sdf_check_kernel(const float* __restrict__ q_in, const float* __restrict__ sdfb,
+                                                       unsigned char* __restrict__ in_collision, float* __restrict__ gap, int N, int D,
+                                                       int or_into, int L, int nx, int ny, int nz) {
+    const size_t i = (size_t)blockIdx.x * 64 + threadIdx.x;
+    const bool have = i < (size_t)N;
+    const GeomView G = sdf_robot_view(sdfb);
+    const SdfLattice S = sdf_lattice(sdfb, nx, ny, nz);
+    float q[MPB_MAX_DOF], dq[MPB_MAX_DOF];
+#pragma unroll
+    for (int k = 0; k < MPB_MAX_DOF; ++k) q[k] = (have && k < D) ? q_in[i * D + k] : 0.f;
+    float c = __uint_as_float(0x7FC00000u);
+    if (sdf_header_matches(sdfb, D, L, nx, ny, nz)) c = sdf_waypoint_cost<false>(G, S, L, q, dq);
+    if (!have) return;
+    const bool hit = !(c <= 0.f);                              // (a refused buffer reads as in collision)
+    in_collision[i] = (hit || (or_into && in_collision[i] != 0)) ? 1 : 0;
+    if (gap) gap[i] = or_into ? sdf_add_rounded(gap[i], c) : c;
+}
+
+// the interpolant alone: one lane per point
+__global__ __launch_bounds__(256) void sdf_sample_kernel(const float* __restrict__ pts, const float* __restrict__ sdfb, float* __restrict__ s_out,
+                                                         float* __restrict__ g_out, int N, int nx, int ny, int nz) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (size_t)N) return;
+    const int* si = reinterpret_cast<const int*>(sdfb);
+    const bool ok = si[MPB_DW_MAGIC] == MPB_SDF_MAGIC && si[MPB_DW_DIMS] == nx && si[MPB_DW_DIMS + 1] == ny && si[MPB_DW_DIMS + 2] == nz;
+    const SdfLattice S = sdf_lattice(sdfb, nx, ny, nz);
+    const float nan = __uint_as_float(0x7FC00000u);
+    float s = nan, gx = nan, gy = nan, gz = nan;
+    if (ok) {
+        SdfTaps T;
+        sdf_load(S, pts[3 * i], pts[3 * i + 1], pts[3 * i + 2], T);
+        s = sdf_gradient(T, S.inv, gx, gy, gz);
+    }
+    s_out[i] = s;
+    if (g_out) { g_out[3 * i] = gx; g_out[3 * i + 1] = gy; g_out[3 * i + 2] = gz; }
+}
+
+// the builder: one thread per node, min over the spheres and boxes of ONE packed CollisionField (sphere_sd / box_sd of mpb_geom.h: the
+// distances every cost kernel takes), the obstacle index wave-uniform
+__global__ __launch_bounds__(256) void sdf_build_kernel(const float* __restrict__ geom, float* __restrict__ sdfb, int nx, int ny, int nz,
+                                                        int n_sph, int n_box) {
+    const unsigned n = blockIdx.x * 256u + threadIdx.x;
+    const unsigned n_nodes = (unsigned)nx * (unsigned)ny * (unsigned)nz;
+    if (n >= n_nodes) return;
+    const int* si = reinterpret_cast<const int*>(sdfb);
+    const int* gi = reinterpret_cast<const int*>(geom);
+    float* nodes = sdfb + si[MPB_DW_OFF_NODES];
+    const bool ok = si[MPB_DW_MAGIC] == MPB_SDF_MAGIC && si[MPB_DW_DIMS] == nx && si[MPB_DW_DIMS + 1] == ny && si[MPB_DW_DIMS + 2] == nz &&
+                    gi[MPB_GW_MAGIC] == MPB_GEOM_MAGIC && gi[MPB_GW_N_SPH] == n_sph && gi[MPB_GW_N_BOX] == n_box;
+    if (!ok) return;                                           // (nothing is written through offsets the launcher has not read)
+    const unsigned i = n % (unsigned)nx, jk = n / (unsigned)nx, j = jk % (unsigned)ny, k = jk / (unsigned)ny;
+    const float cell = sdfb[MPB_DW_CELL];
+    const float x = fmaf((float)i, cell, sdfb[MPB_DW_LO]), y = fmaf((float)j, cell, sdfb[MPB_DW_LO + 1]), z = fmaf((float)k, cell, sdfb[MPB_DW_LO + 2]);
+    const float4* sp = reinterpret_cast<const float4*>(geom + gi[MPB_GW_OFF_SPH]);
+    const float4* bp = reinterpret_cast<const float4*>(geom + gi[MPB_GW_OFF_BOX]);
+    float best = 3.0e38f;
+    for (int o = 0; o < n_sph; ++o) best = fminf(best, sphere_sd(x, y, z, sp[o]));
+    for (int o = 0; o < n_box; ++o) best = fminf(best, box_sd(x, y, z, bp[2 * o], bp[2 * o + 1]));
+    nodes[n] = best;
+}
+
+// ---- host side ------------------------------------------------------------------------------------------------------
+// header, offsets and limits (n_words < 0: the total is not compared with a word count)
+static int sdf_header_check(const int32_t* si, long long n_words, const char* who) {
+    if (si[MPB_DW_MAGIC] != MPB_SDF_MAGIC || si[MPB_DW_VERSION] != MPB_SDF_VERSION) return mpb_failf(MPB_E_INVALID, "%s: bad magic/version of the SDF-grid buffer", who);
+    const int kind = si[MPB_DW_KIND], n_dof = si[MPB_DW_N_DOF], n_tf = si[MPB_DW_N_TF], n_links = si[MPB_DW_N_LINKS];
+    const int nx = si[MPB_DW_DIMS], ny = si[MPB_DW_DIMS + 1], nz = si[MPB_DW_DIMS + 2];
+    if (kind != MPB_KIND_POINT && kind != MPB_KIND_CHAIN) return mpb_failf(MPB_E_INVALID, "%s: unknown robot kind %d", who, kind);
+    if (n_dof < 1 || n_dof > MPB_MAX_DOF) return mpb_failf(MPB_E_UNSUPPORTED, "%s: n_dof = %d outside 1..MPB_MAX_DOF = %d", who, n_dof, MPB_MAX_DOF);
+    if (n_links < 1 || n_links > MPB_SDF_MAX_LINKS) return mpb_failf(MPB_E_UNSUPPORTED, "%s: %d collision spheres outside 1..MPB_SDF_MAX_LINKS = %d", who, n_links, MPB_SDF_MAX_LINKS);
+    if (nx < 2 || ny < 2 || nz < 1 || nx > MPB_SDF_MAX_DIM || ny > MPB_SDF_MAX_DIM || nz > MPB_SDF_MAX_DIM)
+        return mpb_failf(MPB_E_UNSUPPORTED, "%s: grid of %d x %d x %d nodes: a dimension outside 2..MPB_SDF_MAX_DIM = %d (nz: 1 = planar)", who, nx, ny, nz, MPB_SDF_MAX_DIM);
+    const long long n_nodes = (long long)nx * ny * nz;
+    if (n_nodes > MPB_SDF_MAX_NODES) return mpb_failf(MPB_E_UNSUPPORTED, "%s: %lld nodes exceed MPB_SDF_MAX_NODES = %d", who, n_nodes, MPB_SDF_MAX_NODES);
+    if (kind == MPB_KIND_CHAIN ? (n_tf != n_dof + 1) : (n_tf != 0 || n_links != 1 || n_dof > 3 || n_dof < 2))
+        return mpb_failf(MPB_E_INVALID, "%s: a chain needs n_dof + 1 transforms, a point robot none, one sphere and 2 or 3 coordinates", who);
+    if (kind == MPB_KIND_CHAIN && nz == 1) return mpb_failf(MPB_E_INVALID, "%s: a planar grid (nz = 1) serves point robots only", who);
+    const int off_tf = si[MPB_DW_OFF_TF], off_links = si[MPB_DW_OFF_LINKS], off_nodes = si[MPB_DW_OFF_NODES], total = si[MPB_DW_TOTAL];
+    const int want_nodes = (off_links + 8 * n_links + MPB_SDF_NODE_ALIGN - 1) / MPB_SDF_NODE_ALIGN * MPB_SDF_NODE_ALIGN;
+    if (off_tf != MPB_SDF_HEADER_WORDS || off_links != off_tf + 12 * n_tf || off_nodes != want_nodes || (long long)total != off_nodes + n_nodes ||
+        (n_words >= 0 && total != n_words))
+        return mpb_failf(MPB_E_INVALID, "%s: inconsistent section offsets / total of the SDF-grid buffer", who);
+    const float* sf = reinterpret_cast<const float*>(si);
+    const float cell = sf[MPB_DW_CELL], inv = sf[MPB_DW_INV_CELL], margin = sf[MPB_DW_MARGIN];
+    if (!(cell > 0.f && cell < 3.0e38f) || inv != 1.0f / cell) return mpb_failf(MPB_E_INVALID, "%s: cell must be positive and finite, inv_cell its fp32 reciprocal", who);
+    if (!(fabsf(margin) < 3.0e38f) || !(fabsf(sf[MPB_DW_LO]) < 3.0e38f) || !(fabsf(sf[MPB_DW_LO + 1]) < 3.0e38f) || !(fabsf(sf[MPB_DW_LO + 2]) < 3.0e38f))
+        return mpb_failf(MPB_E_INVALID, "%s: margin and lo must be finite", who);
+    return MPB_OK;
+}
+
+extern "C" int mpb_sdf_grid_check(const float* s, int n_words) {
+    if (!s || n_words < MPB_SDF_HEADER_WORDS) return mpb_failf(MPB_E_INVALID, "%s: SDF-grid buffer too small", __func__);
+    const int32_t* si = reinterpret_cast<const int32_t*>(s);
+    const int rc = sdf_header_check(si, n_words, __func__);
+    if (rc) return rc;
+    if (si[MPB_DW_KIND] == MPB_KIND_CHAIN) {
+        int prev = 1;
+        for (int l = 0; l < si[MPB_DW_N_LINKS]; ++l) {
+            const int f = si[si[MPB_DW_OFF_LINKS] + 8 * l];
+            if (f < prev || f > si[MPB_DW_N_DOF] + 1) return mpb_failf(MPB_E_INVALID, "%s: link frames must be sorted in [1, n_dof+1]", __func__);
+            prev = f;
+        }
+    }
+    return MPB_OK;
+}
+
+// What a launch needs of a DEVICE buffer's header: read once per buffer address and device -- a 128-byte synchronous copy on the first
+// call with that pointer -- and kept in a small table, as mpb_self_collision.hip does.  The kernels compare the header with the numbers
+// they were launched with, so an entry that outlived its buffer yields NaN outputs, never a node index outside the grid it was sized
+// for.  mpb_sdf_grid_invalidate drops the entry of an address that gets another buffer.
+struct SdfShape { const void* ptr; int dev, kind, n_dof, n_links, nx, ny, nz; };
+static std::mutex g_sdf_mu;
+static SdfShape g_sdf_table[16];
+static int g_sdf_n = 0, g_sdf_next = 0;
+
+extern "C" int mpb_sdf_grid_invalidate(const float* sdfb) {
+    std::lock_guard<std::mutex> lock(g_sdf_mu);
+    for (int i = 0; i < g_sdf_n; ++i)
+        if (g_sdf_table[i].ptr == sdfb) g_sdf_table[i].ptr = nullptr;     // (on every device: the caller names an address)
+    return MPB_OK;
+}
+
+static int sdf_shape(const float* sdfb, SdfShape& out, const char* who) {
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return mpb_failf(MPB_E_HIP, "%s: hipGetDevice failed", who);
+    std::lock_guard<std::mutex> lock(g_sdf_mu);
+    for (int i = 0; i < g_sdf_n; ++i)
+        if (g_sdf_table[i].ptr == sdfb && g_sdf_table[i].dev == dev) { out = g_sdf_table[i]; return MPB_OK; }
+    int32_t hdr[MPB_SDF_HEADER_WORDS];
+    const hipError_t e = hipMemcpy(hdr, sdfb, sizeof(hdr), hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return mpb_failf(MPB_E_HIP, "%s: reading the SDF-grid header failed: %s", who, hipGetErrorString(e));
+    const int rc = sdf_header_check(hdr, -1, who);
+    if (rc) return rc;
+    out = {sdfb, dev, hdr[MPB_DW_KIND], hdr[MPB_DW_N_DOF], hdr[MPB_DW_N_LINKS], hdr[MPB_DW_DIMS], hdr[MPB_DW_DIMS + 1], hdr[MPB_DW_DIMS + 2]};
+    g_sdf_table[g_sdf_next] = out;
+    g_sdf_next = (g_sdf_next + 1) % 16;
+    g_sdf_n = g_sdf_n < 16 ? g_sdf_n + 1 : 16;
+    return MPB_OK;
+}
+
+extern "C" int mpb_sdf_grid_build(const float* geom, float* sdfb, void* stream) {
+    if (!geom || !sdfb) return mpb_failf(MPB_E_INVALID, "%s: null pointer", __func__);
+    if (mpb_misaligned16(geom, sdfb)) return mpb_failf(MPB_E_INVALID, "%s: the geometry and the SDF-grid buffer must be 16-byte aligned", __func__);
+    SdfShape S;
+    int rc = sdf_shape(sdfb, S, __func__);
+    if (rc) return rc;
+    int32_t gh[MPB_GEOM_HEADER_WORDS];
+    const hipError_t e = hipMemcpy(gh, geom, sizeof(gh), hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return mpb_failf(MPB_E_HIP, "%s: reading the geometry header failed: %s", __func__, hipGetErrorString(e));
+    if (gh[MPB_GW_MAGIC] != MPB_GEOM_MAGIC || (gh[MPB_GW_VERSION] != MPB_GEOM_VERSION && gh[MPB_GW_VERSION] != MPB_GEOM_VERSION_LIST))
+        return mpb_failf(MPB_E_INVALID, "%s: bad magic/version of the geometry buffer", __func__);
+    if (gh[MPB_GW_NEXT] != 0) return mpb_failf(MPB_E_UNSUPPORTED, "%s: the grid is built from ONE CollisionField, this geometry buffer chains several", __func__);
+    const int n_sph = gh[MPB_GW_N_SPH], n_box = gh[MPB_GW_N_BOX];
+    if (n_sph < 0 || n_box < 0 || n_sph + n_box < 1) return mpb_failf(MPB_E_INVALID, "%s: the geometry buffer holds no obstacle", __func__);
+    const unsigned n_nodes = (unsigned)S.nx * (unsigned)S.ny * (unsigned)S.nz;
+    hipLaunchKernelGGL(sdf_build_kernel, dim3((n_nodes + 255u) / 256u), dim3(256), 0, (hipStream_t)stream, geom, sdfb, S.nx, S.ny, S.nz, n_sph, n_box);
+    return mpb_check_launch(__func__);
+}
+
+extern "C" int mpb_sdf_grid_sample(const float* points, const float* sdfb, float* s, float* grad, int N, void* stream) {
+    if (N < 0) return mpb_failf(MPB_E_INVALID, "%s: bad shape", __func__);
+    if (N == 0) return MPB_OK;
+    if (!points || !sdfb || !s) return mpb_failf(MPB_E_INVALID, "%s: null pointer", __func__);
+    if (mpb_misaligned16(sdfb)) return mpb_failf(MPB_E_INVALID, "%s: the SDF-grid buffer must be 16-byte aligned", __func__);
+    SdfShape S;
+    const int rc = sdf_shape(sdfb, S, __func__);
+    if (rc) return rc;
+    hipLaunchKernelGGL(sdf_sample_kernel, dim3((N + 255) / 256), dim3(256), 0, (hipStream_t)stream, points, sdfb, s, grad, N, S.nx, S.ny, S.nz);
+    return mpb_check_launch(__func__);
+}
+
+static int sdf_cost_launch(bool want_grad, const char* who, const float* trajs, const float* sdfb, float* out, float* per_wp, float* grad,
+                           int B, int H, int d, int h_begin, float k_sigma, float weight, int accumulate, void* stream) {
+    if (d > 2 * MPB_MAX_DOF) return mpb_failf(MPB_E_UNSUPPORTED, "%s: rows of d = %d exceed positions + velocities of MPB_MAX_DOF = %d joints", who, d, MPB_MAX_DOF);
+    if (B < 0 || H < 1 || d < 1 || h_begin < 0) return mpb_failf(MPB_E_INVALID, "%s: bad shape", who);
+    if (B == 0) return MPB_OK;
+    if (!trajs || !sdfb || !out || (want_grad && !grad)) return mpb_failf(MPB_E_INVALID, "%s: null pointer", who);
+    if (mpb_misaligned16(sdfb)) return mpb_failf(MPB_E_INVALID, "%s: the SDF-grid buffer must be 16-byte aligned", who);
+    SdfShape S;
+    const int rc = sdf_shape(sdfb, S, who);
+    if (rc) return rc;
+    if (d < S.n_dof) return mpb_failf(MPB_E_INVALID, "%s: rows of d = %d are narrower than the robot's %d coordinates", who, d, S.n_dof);
+    if (want_grad)
+        hipLaunchKernelGGL(sdf_cost_kernel<true>, dim3(B), dim3(64), 0, (hipStream_t)stream, trajs, sdfb, out, per_wp, grad, H, d, h_begin, k_sigma,
+                           weight, accumulate, S.n_dof, S.n_links, S.nx, S.ny, S.nz);
+    else
+        hipLaunchKernelGGL(sdf_cost_kernel<false>, dim3(B), dim3(64), 0, (hipStream_t)stream, trajs, sdfb, out, per_wp, (float*)nullptr, H, d, h_begin,
+                           k_sigma, weight, accumulate, S.n_dof, S.n_links, S.nx, S.ny, S.nz);
+    return mpb_check_launch(who);
+}
+
+extern "C" int mpb_sdf_grid_eval(const float* trajs, const float* sdfb, float* out, float* per_waypoint, int B, int H, int d, int h_begin,
+                                 float k_sigma, float weight, int accumulate, void* stream) {
+    return sdf_cost_launch(false, __func__, trajs, sdfb, out, per_waypoint, nullptr, B, H, d, h_begin, k_sigma, weight, accumulate, stream);
+}
+
+extern "C" int mpb_sdf_grid_grad(const float* trajs, const float* sdfb, float* out, float* grad, int B, int H, int d, int h_begin, float k_sigma,
+                                 float weight, int accumulate, void* stream) {
+    return sdf_cost_launch(true, __func__, trajs, sdfb, out, nullptr, grad, B, H, d, h_begin, k_sigma, weight, accumulate, stream);
+}
+
+extern "C" int mpb_sdf_grid_collision_check(const float* q, const float* sdfb, unsigned char* in_collision, float* gap, int N, int D, int or_into,
+                                            void* stream) {
+    if (D > MPB_MAX_DOF) return mpb_failf(MPB_E_UNSUPPORTED, "%s: D = %d exceeds MPB_MAX_DOF = %d", __func__, D, MPB_MAX_DOF);
+    if (N < 0 || D < 1) return mpb_failf(MPB_E_INVALID, "%s: bad shape", __func__);
+    if (N == 0) return MPB_OK;
+    if (!q || !sdfb || !in_collision) return mpb_failf(MPB_E_INVALID, "%s: null pointer", __func__);
+    if (mpb_misaligned16(sdfb)) return mpb_failf(MPB_E_INVALID, "%s: the SDF-grid buffer must be 16-byte aligned", __func__);
+    SdfShape S;
+    const int rc = sdf_shape(sdfb, S, __func__);
+    if (rc) return rc;
+    if (D != S.n_dof) return mpb_failf(MPB_E_INVALID, "%s: D = %d, the robot has %d coordinates", __func__, D, S.n_dof);
+    hipLaunchKernelGGL(sdf_check_kernel, dim3((N + 63) / 64), dim3(64), 0, (hipStream_t)stream, q, sdfb, in_collision, gap, N, D, or_into, S.n_links,
+                       S.nx, S.ny, S.nz);
+    return mpb_check_launch(__func__);
+}

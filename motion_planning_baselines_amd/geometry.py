@@ -21,6 +21,8 @@ Definitions (all fp32):
   * per-waypoint collision cost: sum_l relu(margin + r_l - min_o sdf_o(x_l)).
   * per-waypoint SELF-collision cost (serial chains, SelfCollisionField): sum over pairs (a, b) of
     relu(margin + r_a + r_b - |x_a - x_b|).
+  * per-waypoint GRID cost (GridSDFField): sum_l relu(margin + r_l - s(x_l)), s the tri- / bilinear interpolant of a lattice of
+    signed distances (its class says how).
 """
 import math
 import os
@@ -336,6 +338,9 @@ class CollisionField:
             a = np.zeros((0, w), np.float32) if x is None else np.asarray(x, dtype=np.float32)
             return a.reshape(-1, w)
         sp = np.asarray(spheres, np.float32) if spheres is not None and len(spheres) else None
+        bx_ = np.asarray(boxes, np.float32) if boxes is not None and len(boxes) else None
+        # every primitive given in its 2-D form (circles, rectangles): what GridSDFField.from_field makes a planar grid of
+        self.is_2d = all(a is None or a.shape[-1] == w for a, w in ((sp, 3), (bx_, 4)))
         if sp is not None and sp.shape[-1] == 3:  # 2-D circles (cx, cy, r)
             sp = np.concatenate([sp[:, :2], np.zeros((len(sp), 1), np.float32), sp[:, 2:3]], 1)
         bx = np.asarray(boxes, np.float32) if boxes is not None and len(boxes) else None
@@ -466,6 +471,127 @@ def pack_self_collision(robot, field):
     pw.view(np.uint32)[:, 0] = (field.pairs[:, 0] | (field.pairs[:, 1] << S.SELF_PAIR_B_SHIFT)).astype(np.uint32)
     pw[:, 1] = field.thresholds().astype(np.float32)
     buf[off_pairs:total] = pw.reshape(-1)
+    return buf
+
+
+class GridSDFField:
+    """A precomputed grid of signed distances as a collision field (build-defined; the reference's examples build
+    their environments with precompute_sdf_obj_fixed=True, sdf_cell_size=...).  Serves arbitrary geometry -- meshes, rounded boxes,
+    scans: whatever the caller can tabulate -- at eight node loads per collision sphere whatever the scene holds.
+
+    Grid: (nx, ny, nz) fp32 nodes, node (i, j, k) at lo + (i, j, k) * cell with ONE cell for all axes, stored at (k * ny + j) * nx + i:
+    `values` is an array of shape (nz, ny, nx), or (ny, nx) for a planar grid (nz == 1: z is ignored, interpolation is bilinear -- the
+    2-D point-mass examples).  Limits: every dimension in 2..SDF_MAX_DIM = 1024 (nz: or 1), at most SDF_MAX_NODES = 2^27 nodes.
+
+    Sampling s(x), per axis: u = (x - lo) * inv_cell with inv_cell = fl32(1 / cell); u clamped to [0, n - 1]; i0 = min(floor(u), n - 2);
+    f = u - i0; lerp form fmaf(f, v1 - v0, v0) along x, then y, then z: a point with f == 0 on every axis returns that node's bits.
+    OUTSIDE the box the point is clamped: the value is that of the nearest boundary point and the gradient is zero along each clamped
+    axis -- the grid is expected to COVER THE WORKSPACE (every position a collision sphere can take); nothing warns when it does not.
+
+    Cost per waypoint c(q) = sum_l relu(margin + r_l - s(x_l(q))) over the robot's collision spheres; in collision iff c(q) > 0; an
+    active sphere's gradient is -grad s(x_l) through J^T, grad s the exact derivative of the interpolant.
+
+    GridSDFField(values, lo, cell, margin): the caller's node values (checked finite here).
+    GridSDFField.from_field(collision_field, lo, hi, cell): min_o sdf_o of a CollisionField at every node, evaluated ON THE GPU when
+    the field is put on a device (ops.DeviceSDFGrid, mpb_sdf_grid_build); `values` stays None on the host."""
+
+    def __init__(self, values, lo, cell, margin=0.05):
+        v = np.asarray(values, dtype=np.float32)
+        if v.ndim == 2:
+            v = v[None]
+        if v.ndim != 3:
+            raise ValueError(f'GridSDFField: values of shape {np.shape(values)}, expected (nz, ny, nx) or (ny, nx)')
+        self.dims = self._check_dims(v.shape[2], v.shape[1], v.shape[0])
+        if not np.all(np.isfinite(v)):
+            raise ValueError('GridSDFField: non-finite node values')
+        self.values = np.ascontiguousarray(v)
+        self.source = None
+        self._set_frame(lo, cell, margin)
+
+    @staticmethod
+    def _check_dims(nx, ny, nz):
+        from .sdf_layout import SDF_MAX_DIM, SDF_MAX_NODES
+        nx, ny, nz = int(nx), int(ny), int(nz)
+        if nx < 2 or ny < 2 or nz < 1 or max(nx, ny, nz) > SDF_MAX_DIM:
+            raise ValueError(f'GridSDFField: grid of {nx} x {ny} x {nz} nodes: every dimension must lie in 2..SDF_MAX_DIM = {SDF_MAX_DIM} '
+                             f'(nz: or 1 for a planar grid)')
+        if nx * ny * nz > SDF_MAX_NODES:
+            raise ValueError(f'GridSDFField: {nx * ny * nz} nodes exceed SDF_MAX_NODES = {SDF_MAX_NODES}')
+        return nx, ny, nz
+
+    def _set_frame(self, lo, cell, margin):
+        lo = np.asarray(lo, dtype=np.float64).reshape(-1)
+        if lo.size == 2:
+            lo = np.concatenate([lo, [0.0]])
+        if lo.size != 3 or not np.all(np.isfinite(lo)):
+            raise ValueError('GridSDFField: lo must be 2 or 3 finite coordinates')
+        self.lo = lo.astype(np.float32)
+        self.cell = np.float32(cell)
+        if not (np.isfinite(self.cell) and self.cell > 0):
+            raise ValueError('GridSDFField: cell must be positive and finite')
+        self.inv_cell = np.float32(1.0) / self.cell
+        self.margin = float(margin)
+
+    @property
+    def planar(self):
+        return self.dims[2] == 1
+
+    @classmethod
+    def from_field(cls, collision_field, lo, hi, cell, margin=None, planar=None):
+        """The grid of min_o sdf_o of `collision_field` over the box [lo, hi]: ceil((hi - lo) / cell) + 1 nodes per axis, cell as the fp32 number
+        the header stores (the last node at or beyond hi).  planar (default: the field came from 2-D primitives) keeps ONE layer of nodes, at z = lo[2] (0 when lo has
+        two coordinates).  margin defaults to the field's.  The nodes are evaluated on the GPU, when the field goes to a device."""
+        if not isinstance(collision_field, CollisionField):
+            raise TypeError('GridSDFField.from_field takes ONE CollisionField')
+        self = cls.__new__(cls)
+        planar = bool(collision_field.is_2d) if planar is None else bool(planar)
+        lo = np.asarray(lo, dtype=np.float64).reshape(-1)
+        hi = np.asarray(hi, dtype=np.float64).reshape(-1)
+        if lo.size != hi.size or lo.size not in (2, 3) or (lo.size == 2 and not planar):
+            raise ValueError('GridSDFField.from_field: lo and hi must both have 3 coordinates (2 for a planar grid)')
+        n = [int(math.ceil((hi[a] - lo[a]) / float(np.float32(cell)))) + 1 for a in range(2 if planar else 3)]    # (the cell the header stores)
+        self.dims = cls._check_dims(n[0], n[1], 1 if planar else n[2])
+        self.values = None
+        self.source = collision_field
+        self._set_frame(lo, cell, collision_field.margin if margin is None else margin)
+        return self
+
+    def zero_grad(self):
+        pass
+
+
+def pack_sdf_grid(robot, field, with_nodes=True):
+    """Pack a robot + a GridSDFField into ONE self-contained fp32 word buffer (sdf_layout.py: header, joint_tf rows, links rows -- both
+    in the row formats of pack_geometry, every link kept --, then the node section, 16-byte aligned).  The node section holds the
+    field's values; for a field made by from_field it is left zero for mpb_sdf_grid_build to fill on the device.  with_nodes=False
+    returns the words BEFORE the node section only (the header's total still counts the nodes): what an upload needs when the nodes
+    are built on the device."""
+    from . import sdf_layout as S
+    rs = robot.spec()
+    if rs['kind'] == KIND_CHAIN and field.planar:
+        raise ValueError('a planar GridSDFField (nz = 1) serves point robots only: a chain moves in three dimensions')
+    n_tf, n_links = rs['joint_tf'].shape[0], len(rs['link_radius'])
+    if n_links > S.SDF_MAX_LINKS:
+        raise ValueError(f'{n_links} collision spheres exceed SDF_MAX_LINKS = {S.SDF_MAX_LINKS}')
+    nx, ny, nz = field.dims
+    off_tf = S.SDF_HEADER_WORDS
+    off_links = off_tf + 12 * n_tf
+    off_nodes = (off_links + 8 * n_links + S.SDF_NODE_ALIGN - 1) // S.SDF_NODE_ALIGN * S.SDF_NODE_ALIGN
+    total = off_nodes + nx * ny * nz
+    buf = np.zeros((total if with_nodes else off_nodes,), dtype=np.float32)
+    hdr = S.header(buf)
+    for name, value in dict(magic=S.SDF_MAGIC, version=S.SDF_VERSION, kind=rs['kind'], n_dof=rs['n_dof'], n_tf=n_tf, n_links=n_links,
+                            margin=field.margin, dims=(nx, ny, nz), lo=field.lo, cell=field.cell, inv_cell=field.inv_cell, off_tf=off_tf,
+                            off_links=off_links, off_nodes=off_nodes, total=total).items():
+        hdr[name] = value
+    buf[off_tf:off_links] = rs['joint_tf'].astype(np.float32).reshape(-1)
+    links = np.zeros((n_links, 8), np.float32)
+    links.view(np.int32)[:, 0] = rs['link_frame'] if rs['kind'] == KIND_CHAIN else 1
+    links[:, 1:4] = rs['link_offset']
+    links[:, 4] = rs['link_radius']
+    buf[off_links:off_links + 8 * n_links] = links.reshape(-1)
+    if with_nodes and field.values is not None:
+        buf[off_nodes:total] = field.values.reshape(-1)
     return buf
 
 

@@ -12,7 +12,7 @@ import numpy as np
 import torch
 
 from . import _lib, rrt_layout
-from .geometry import MAX_FIELDS, count_fields, pack_geometry, pack_self_collision
+from .geometry import MAX_FIELDS, count_fields, pack_geometry, pack_sdf_grid, pack_self_collision
 from .geometry import header as geometry_header
 
 
@@ -41,7 +41,7 @@ def _on_tensor_device(fn):
     def run(*args, **kw):
         dev = None
         for a in list(args) + list(kw.values()):
-            t = a.buf if isinstance(a, (DeviceGeometry, DeviceSelfCollision)) else a
+            t = a.buf if isinstance(a, (DeviceGeometry, DeviceSelfCollision, DeviceSDFGrid)) else a
             if isinstance(t, torch.Tensor) and t.is_cuda:
                 if dev is None:
                     dev = t.device
@@ -191,6 +191,117 @@ def self_collision_check(q, sc, with_gap=False, flag=None, gap=None):
         gap = torch.empty(N, device=q.device, dtype=torch.float32) if with_gap else None
     _lib.check(_lib.lib().mpb_self_collision_check(_ptr(q), _ptr(sc.buf), _ptr(flag), _ptr(gap), N, D, int(or_into), _stream()),
                'mpb_self_collision_check')
+    return (flag, gap) if (with_gap or gap is not None) else flag
+
+
+class DeviceSDFGrid:
+    """A robot + a GridSDFField as the packed SDF buffer (geometry.pack_sdf_grid) resident in HBM: packed, validated (mpb_sdf_grid_check)
+    and uploaded once -- or, for a field made by GridSDFField.from_field, the header and the robot tables uploaded and the nodes built
+    ON the device (mpb_sdf_grid_build) from the CollisionField.  `.nodes` is the node section as a (nz, ny, nx) view of the buffer."""
+
+    def __init__(self, robot, field, device):
+        from .sdf_layout import header as sdf_header
+        self.robot, self.field = robot, field
+        built = field.values is None
+        self.host = pack_sdf_grid(robot, field, with_nodes=not built)      # (built: the words before the node section only)
+        hdr = sdf_header(self.host)
+        total, off_nodes = int(hdr['total']), int(hdr['off_nodes'])
+        _lib.sdf_grid_check(self.host, n_words=total)
+        self.kind, self.n_dof, self.n_links = int(hdr['kind']), int(hdr['n_dof']), int(hdr['n_links'])
+        self.dims = tuple(int(v) for v in hdr['dims'])
+        if built:
+            self.buf = torch.empty(total, device=device, dtype=torch.float32)
+            self.buf[:off_nodes].copy_(torch.from_numpy(self.host))
+        else:
+            self.buf = torch.from_numpy(self.host).to(device)
+        # (the library reads an SDF buffer's header once per address: this address may have held another one before)
+        _lib.check(_lib.lib().mpb_sdf_grid_invalidate(_ptr(self.buf)), 'mpb_sdf_grid_invalidate')
+        nx, ny, nz = self.dims
+        self.nodes = self.buf[off_nodes:].view(nz, ny, nx)
+        if built:
+            from .geometry import RobotPointMass
+            geom = DeviceGeometry(RobotPointMass(3), field.source, device, use_model=False)
+            sdf_grid_build(geom, self)
+
+
+@_on_tensor_device
+def sdf_grid_build(geom, sdf):
+    """Fill the node section of a DeviceSDFGrid with min_o sdf_o(node position) of the ONE CollisionField of a DeviceGeometry
+    (mpb_sdf_grid_build; any robot: only the obstacle tables are read)."""
+    if geom.n_fields != 1:
+        raise ValueError(f'sdf_grid_build takes the geometry of ONE CollisionField, this one chains {geom.n_fields}')
+    _chk(geom.buf, geom.buf.shape, 'geom.buf')
+    _chk(sdf.buf, sdf.buf.shape, 'sdf.buf')
+    _lib.check(_lib.lib().mpb_sdf_grid_build(_ptr(geom.buf), _ptr(sdf.buf), _stream()), 'mpb_sdf_grid_build')
+    return sdf.nodes
+
+
+@_on_tensor_device
+def sdf_grid_sample(points, sdf, with_grad=False):
+    """points (N, 3) -> s (N,) of the grid's interpolant, with_grad also d s / d x (N, 3) (mpb_sdf_grid_sample).  No robot."""
+    N = points.shape[0]
+    _chk(points, (N, 3), 'points')
+    s = torch.empty(N, device=points.device, dtype=torch.float32)
+    g = torch.empty(N, 3, device=points.device, dtype=torch.float32) if with_grad else None
+    _lib.check(_lib.lib().mpb_sdf_grid_sample(_ptr(points), _ptr(sdf.buf), _ptr(s), _ptr(g), N, _stream()), 'mpb_sdf_grid_sample')
+    return (s, g) if with_grad else s
+
+
+@_on_tensor_device
+def sdf_grid_eval(trajs, sdf, k_sigma, weight=1.0, h_begin=1, per_waypoint=False, out=None, accumulate=False):
+    """trajs (B, H, d) -> out (B,) (+)= weight * k_sigma * sum_{h >= h_begin} c(q_h) of a DeviceSDFGrid (mpb_sdf_grid_eval);
+    per_waypoint also returns c (B, H), un-scaled, 0 below h_begin."""
+    B, H, d = trajs.shape
+    _chk(trajs, (B, H, d), 'trajs')
+    if d < sdf.n_dof:
+        raise ValueError(f'trajs has {d} columns, the robot {sdf.n_dof} degrees of freedom')
+    out = _self_out(trajs, out, accumulate)
+    pw = torch.empty(B, H, device=trajs.device, dtype=torch.float32) if per_waypoint else None
+    _lib.check(_lib.lib().mpb_sdf_grid_eval(_ptr(trajs), _ptr(sdf.buf), _ptr(out), _ptr(pw), B, H, d, int(h_begin), float(k_sigma),
+                                           float(weight), int(bool(accumulate)), _stream()), 'mpb_sdf_grid_eval')
+    return (out, pw) if per_waypoint else out
+
+
+@_on_tensor_device
+def sdf_grid_grad(trajs, sdf, k_sigma, weight=1.0, h_begin=1, out=None, grad=None, accumulate=False):
+    """(out (B,), grad (B, H, d)) (+)= the grid cost and d out / d trajs (mpb_sdf_grid_grad); accumulate adds onto the given `out` AND
+    `grad` (velocity channels left alone), otherwise both are written (velocity channels 0)."""
+    B, H, d = trajs.shape
+    _chk(trajs, (B, H, d), 'trajs')
+    if d < sdf.n_dof:
+        raise ValueError(f'trajs has {d} columns, the robot {sdf.n_dof} degrees of freedom')
+    if accumulate and grad is None:
+        raise ValueError('accumulate needs existing out and grad buffers')
+    out = _self_out(trajs, out, accumulate)
+    if grad is None:
+        grad = torch.empty_like(trajs)
+    else:
+        _chk(grad, (B, H, d), 'grad')
+    _lib.check(_lib.lib().mpb_sdf_grid_grad(_ptr(trajs), _ptr(sdf.buf), _ptr(out), _ptr(grad), B, H, d, int(h_begin), float(k_sigma),
+                                           float(weight), int(bool(accumulate)), _stream()), 'mpb_sdf_grid_grad')
+    return out, grad
+
+
+@_on_tensor_device
+def sdf_grid_check(q, sdf, with_gap=False, flag=None, gap=None):
+    """(N, D) configurations -> bool (N,): the grid cost of the configuration is positive (mpb_sdf_grid_collision_check); with_gap also
+    returns the hinge sum.  Given `flag` (and `gap`) -- the outputs of collision_check --, the answer is ORed into the flags and added
+    onto the gap."""
+    N, D = q.shape
+    _chk(q, (N, D), 'q')
+    if D != sdf.n_dof:
+        raise ValueError(f'q has {D} columns, the robot {sdf.n_dof} degrees of freedom')
+    or_into = flag is not None
+    if or_into:
+        _chk(flag, (N,), 'flag', dtype=torch.bool)
+        _chk(gap, (N,), 'gap', allow_none=True)
+        if with_gap and gap is None:
+            raise ValueError('with_gap next to flag= needs the gap= to add onto (the gap of collision_check(..., with_gap=True))')
+    else:
+        flag = torch.empty(N, device=q.device, dtype=torch.bool)
+        gap = torch.empty(N, device=q.device, dtype=torch.float32) if with_gap else None
+    _lib.check(_lib.lib().mpb_sdf_grid_collision_check(_ptr(q), _ptr(sdf.buf), _ptr(flag), _ptr(gap), N, D, int(or_into), _stream()),
+               'mpb_sdf_grid_collision_check')
     return (flag, gap) if (with_gap or gap is not None) else flag
 
 

@@ -100,24 +100,23 @@ class CHOMP(OptimizationPlanner):
             return
         # any composite of HIP-served members (collision fields + GP / smoothness / joint-limit / start / goal terms): the
         # reference differentiates it by autograd (chomp.py:135-139); here per iteration the collision gradient kernel
-        # (J^T grad sdf), the self-collision gradient kernel of each SelfCollisionField member accumulating into the same
-        # buffer, then ONE pass that adds the closed-form gradients of the trajectory terms and of the
+        # (J^T grad sdf), the gradient kernel of each member that has kernels of its own (SelfCollisionField, GridSDFField)
+        # accumulating into the same buffer, then ONE pass that adds the closed-form gradients of the trajectory terms and of the
         # smoothness prior, clamps, masks the end rows and steps (chomp.py:141-147)
         plan = device_plan(self.cost, self.device) if self.cost is not None else None
         if plan is None:
             return self._run_optimization_autograd(opt_iters, B_global, **observation)
         cc, weight, groups = plan
         x = self._particle_means
-        grad = torch.empty_like(x) if (cc is not None or plan.selfs or len(groups) > 1) else None
+        grad = torch.empty_like(x) if (cc is not None or plan.own or len(groups) > 1) else None
         prior_bw = float(B_global) * float(self.weight_prior_cost)
         for _ in range(opt_iters):
             have = False
             if cc is not None:
                 self.costs, _ = ops.cost_collision_grad(x, cc.device_geometry(self.device), cc.k_sigma, weight=weight, grad=grad)
                 have = True
-            for sm, w in plan.selfs:     # the robot against itself: accumulates onto the obstacle cost and gradient
-                self.costs, _ = ops.self_collision_grad(x, sm.device_self(self.device), sm.k_sigma, weight=w, out=self.costs if have else None,
-                                                        grad=grad, accumulate=have)
+            for om, w in plan.own:       # the robot against itself, an SDF grid: accumulate onto the obstacle cost and gradient
+                self.costs, _ = om.own_grad(x, weight=w, out=self.costs if have else None, grad=grad, accumulate=have)
                 have = True
             for spec in groups[:-1]:     # term groups that could not be merged into one launch: accumulate
                 ops.cost_terms_grad(x, self.n_dof, grad_in=grad if have else None, grad_out=grad, jl_scale=float(B_global), **spec)

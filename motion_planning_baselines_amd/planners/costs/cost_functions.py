@@ -14,7 +14,7 @@ import numpy as np
 import torch
 
 from ... import ops
-from ...geometry import SelfCollisionField
+from ...geometry import GridSDFField, SelfCollisionField
 
 
 class Cost(ABC):
@@ -72,6 +72,10 @@ class CostCollision(Cost):
     `field` may be a geometry.SelfCollisionField (the robot against itself; the reference's examples get that field from
     task.get_collision_fields() with use_self_collision_storm=True): eval / eval_with_grad / get_linear_system then go to the
     self-collision kernels (mpb_self_collision_*).  Such a member is never fused into a planner kernel.
+
+    `field` may also be a geometry.GridSDFField (a precomputed grid of signed distances, the reference's precompute_sdf_obj_fixed=True):
+    the same three go to the SDF-grid kernels (mpb_sdf_grid_*).  Both kinds are "members with kernels of their own" (own_kernels): never
+    an obstacle member, never fused, served by own_eval / own_grad -- which is all a planner's device path needs to know of them.
     """
 
     def __init__(self, robot, n_support_points, field=None, sigma_coll=None, **kwargs):
@@ -80,6 +84,7 @@ class CostCollision(Cost):
         self.sigma_coll = sigma_coll
         self._geom = None
         self._self = None
+        self._sdf = None
 
     @property
     def k_sigma(self):
@@ -88,6 +93,39 @@ class CostCollision(Cost):
     @property
     def is_self(self):
         return isinstance(self.field, SelfCollisionField)
+
+    @property
+    def is_grid(self):
+        return isinstance(self.field, GridSDFField)
+
+    @property
+    def own_kernels(self):
+        """The member's field is no obstacle list: it has eval / gradient kernels of its own (own_eval, own_grad)."""
+        return self.is_self or self.is_grid
+
+    def device_sdf(self, device):
+        """The packed SDF buffer of a GridSDFField member on `device` (packed, checked and uploaded -- or built there -- once)."""
+        assert self.is_grid
+        if self._sdf is None or self._sdf.buf.device != torch.device(device):
+            self._sdf = ops.DeviceSDFGrid(self.robot, self.field, device)
+        return self._sdf
+
+    def own_eval(self, trajs, weight=1.0, k_sigma=None, **kw):
+        """ops.self_collision_eval / ops.sdf_grid_eval of this member on (B, H, d) trajectories: h_begin, per_waypoint, out, accumulate
+        as those take them; k_sigma defaults to the member's."""
+        k = self.k_sigma if k_sigma is None else k_sigma
+        if self.is_self:
+            return ops.self_collision_eval(trajs, self.device_self(trajs.device), k, weight=weight, **kw)
+        assert self.is_grid
+        return ops.sdf_grid_eval(trajs, self.device_sdf(trajs.device), k, weight=weight, **kw)
+
+    def own_grad(self, trajs, weight=1.0, k_sigma=None, **kw):
+        """ops.self_collision_grad / ops.sdf_grid_grad of this member: h_begin, out, grad, accumulate as those take them."""
+        k = self.k_sigma if k_sigma is None else k_sigma
+        if self.is_self:
+            return ops.self_collision_grad(trajs, self.device_self(trajs.device), k, weight=weight, **kw)
+        assert self.is_grid
+        return ops.sdf_grid_grad(trajs, self.device_sdf(trajs.device), k, weight=weight, **kw)
 
     def device_self(self, device):
         """The packed self-collision buffer of a SelfCollisionField member on `device` (packed, checked and uploaded once)."""
@@ -99,6 +137,8 @@ class CostCollision(Cost):
     def device_geometry(self, device):
         if self.is_self:
             raise TypeError('a SelfCollisionField has no obstacle geometry: use device_self()')
+        if self.is_grid:
+            raise TypeError('a GridSDFField has no obstacle geometry: use device_sdf()')
         if self._geom is None or self._geom.buf.device != torch.device(device):
             self._geom = ops.DeviceGeometry(self.robot, self.field, device)
         return self._geom
@@ -107,15 +147,15 @@ class CostCollision(Cost):
         if self.field is None:
             return 0
         trajs = self._as_3d(trajs)
-        if self.is_self:
-            return ops.self_collision_eval(trajs, self.device_self(trajs.device), self.k_sigma)
+        if self.own_kernels:
+            return self.own_eval(trajs)
         return ops.cost_collision_eval(trajs, self.device_geometry(trajs.device), self.k_sigma)
 
     def eval_with_grad(self, trajs, weight=1.0):
         """(cost (B,), d cost / d trajs (B,H,d)): what the reference gets from autograd (chomp.py:139)."""
         trajs = self._as_3d(trajs)
-        if self.is_self:
-            return ops.self_collision_grad(trajs, self.device_self(trajs.device), self.k_sigma, weight=weight)
+        if self.own_kernels:
+            return self.own_grad(trajs, weight=weight)
         return ops.cost_collision_grad(trajs, self.device_geometry(trajs.device), self.k_sigma, weight=weight)
 
     def get_linear_system(self, trajs, n_interpolated_points=None, **observation):
@@ -128,7 +168,7 @@ class CostCollision(Cost):
         trajs = self._as_3d(trajs)
         B, H, d = trajs.shape
         assert d == self.dim, 'get_linear_system works on (B, H, 2*n_dof) trajectories'
-        if self.is_self:
+        if self.own_kernels:
             return self._self_linear_system(trajs)
         rows = ops.gpmp2_collision_rows(trajs, self.device_geometry(trajs.device), n_interp=n_interpolated_points or 0)[0]
         N, D = self.dim * H, self.n_dof
@@ -140,15 +180,15 @@ class CostCollision(Cost):
         return A, b, K
 
     def _self_linear_system(self, trajs):
-        """(A, b, K) of a self-collision member in the obstacle member's convention: row i holds -d c / d q of waypoint i + 1 at
+        """(A, b, K) of a self-collision or SDF-grid member in the obstacle member's convention: row i holds -d c / d q of waypoint i + 1 at
         that waypoint's position columns, b the waypoint costs, K = I / sigma^2.  ONE gradient launch gives every row of A (c_h
         depends on q_h alone: the gradient of sum_h c_h IS the per-waypoint Jacobian); b takes a cost launch of its own, since
         mpb_self_collision_grad has no per-waypoint output.  The support points only: a self member has no interpolated
         Jacobian."""
         B, H, d = trajs.shape
-        sc, D = self.device_self(trajs.device), self.n_dof
-        _, grad = ops.self_collision_grad(trajs, sc, 1.0, weight=1.0, h_begin=1)
-        _, pw = ops.self_collision_eval(trajs, sc, 1.0, h_begin=1, per_waypoint=True)
+        D = self.n_dof
+        _, grad = self.own_grad(trajs, k_sigma=1.0, h_begin=1)
+        _, pw = self.own_eval(trajs, k_sigma=1.0, h_begin=1, per_waypoint=True)
         A = torch.zeros(B, H - 1, self.dim * H, device=trajs.device, dtype=trajs.dtype)
         for i in range(H - 1):
             A[:, i, (i + 1) * self.dim:(i + 1) * self.dim + D] = -grad[:, i + 1, :D]
@@ -393,12 +433,11 @@ class CostComposite(Cost):
             if isinstance(cost, CostCollision):
                 if cost.field is None:
                     continue
-                if cost.is_self:
-                    sc = cost.device_self(trajs.device)
+                if cost.own_kernels:
                     if torch.is_tensor(total) and total.ndim == 1 and total.is_contiguous() and total.dtype == torch.float32:
-                        ops.self_collision_eval(trajs_coll, sc, cost.k_sigma, weight=w, out=total, accumulate=True)
+                        cost.own_eval(trajs_coll, weight=w, out=total, accumulate=True)
                         continue
-                    c = ops.self_collision_eval(trajs_coll, sc, cost.k_sigma, weight=w)
+                    c = cost.own_eval(trajs_coll, weight=w)
                 else:
                     c = ops.cost_collision_eval(trajs_coll, cost.device_geometry(trajs.device), cost.k_sigma, weight=w)
             elif isinstance(cost, _TrajectoryTermCost):
@@ -417,12 +456,12 @@ class CostComposite(Cost):
 
     def device_plan(self, device):
         """How a planner kernel pipeline can serve this composite without leaving the device:
-        (collision members [(CostCollision, weight)], merged term specs, other members [(cost, weight)]).  Self-collision
-        members are in none of the three: self_terms() lists them."""
+        (collision members [(CostCollision, weight)], merged term specs, other members [(cost, weight)]).  Members with kernels
+        of their own (self-collision, SDF grid) are in none of the three: own_terms() lists them."""
         coll, terms, other = [], [], []
         for cost, w in zip(self.cost_l, self.weight_cost_l):
             if isinstance(cost, CostCollision):
-                if cost.field is not None and not cost.is_self:
+                if cost.field is not None and not cost.own_kernels:
                     coll.append((cost, float(w)))
             elif isinstance(cost, _TrajectoryTermCost):
                 terms.append((cost.term_spec(device), float(w)))
@@ -456,7 +495,12 @@ class CostComposite(Cost):
     def collision_terms(self):
         """[(CostCollision, weight)] of the members that carry an OBSTACLE field."""
         return [(c, float(w)) for c, w in zip(self.cost_l, self.weight_cost_l)
-                if isinstance(c, CostCollision) and c.field is not None and not c.is_self]
+                if isinstance(c, CostCollision) and c.field is not None and not c.own_kernels]
+
+    def own_terms(self):
+        """[(CostCollision, weight)] of the members with kernels of their own (a SelfCollisionField or a GridSDFField), in composite
+        order."""
+        return [(c, float(w)) for c, w in zip(self.cost_l, self.weight_cost_l) if isinstance(c, CostCollision) and c.own_kernels]
 
     def self_terms(self):
         """[(CostCollision, weight)] of the members whose field is a SelfCollisionField."""
@@ -479,7 +523,7 @@ class MergedCollision:
     def __init__(self, terms):
         (c0, w0) = terms[0]
         assert all(c.robot is c0.robot for c, _ in terms), 'collision members must share the robot'
-        assert not any(c.is_self for c, _ in terms), 'a self-collision member has no obstacle field to chain'
+        assert not any(c.own_kernels for c, _ in terms), 'a self-collision or SDF-grid member has no obstacle field to chain'
         self.robot = c0.robot
         self.fields = [c.field for c, _ in terms]
         self.k_sigma = c0.k_sigma
@@ -506,7 +550,7 @@ def merge_collision_terms(terms):
 def fusable_collision(cost):
     """Return (collision evaluator, weight) when `cost` is a collision cost the kernels can fuse, else None."""
     if isinstance(cost, CostCollision) and cost.field is not None:
-        return None if cost.is_self else (cost, 1.0)       # (a self member has its own kernels: never fused)
+        return None if cost.own_kernels else (cost, 1.0)   # (a self / SDF-grid member has its own kernels: never fused)
     if isinstance(cost, CostComposite):
         key = tuple((id(c), float(w)) for c, w in zip(cost.cost_l, cost.weight_cost_l))
         cached = cost.__dict__.get('_fused_cache')
@@ -517,38 +561,39 @@ def fusable_collision(cost):
 
 
 class DevicePlan(tuple):
-    """(collision evaluator or None, its weight, merged trajectory-term specs) -- unpacks as those three -- plus `.selfs`, the
-    self-collision members [(CostCollision, weight)] a planner serves with mpb_self_collision_eval / _grad accumulating onto the
-    obstacle member's outputs."""
+    """(collision evaluator or None, its weight, merged trajectory-term specs) -- unpacks as those three -- plus `.own`, the
+    members with kernels of their own [(CostCollision, weight)] (self-collision and SDF-grid fields) that a planner serves with
+    member.own_eval / member.own_grad accumulating onto the obstacle member's outputs; `.selfs` is the self-collision part of it."""
 
-    def __new__(cls, cc, weight, groups, selfs=()):
+    def __new__(cls, cc, weight, groups, own=()):
         self = super().__new__(cls, (cc, weight, groups))
-        self.selfs = list(selfs)
+        self.own = list(own)
+        self.selfs = [(c, w) for c, w in self.own if c.is_self]
         return self
 
 
 def device_plan(cost, device):
     """DevicePlan (collision evaluator or None, its weight, merged trajectory-term specs; .selfs) when every member of `cost`
-    is served by the HIP library (collision fields -- up to four, chained --, self-collision fields and trajectory-only terms):
-    the case a planner can run as sample kernel -> self / term kernels -> update kernel with no host round trip; None otherwise."""
+    is served by the HIP library (collision fields -- up to four, chained --, self-collision and SDF-grid fields and trajectory-only
+    terms): the case a planner can run as sample kernel -> own / term kernels -> update kernel with no host round trip; None otherwise."""
     if isinstance(cost, CostComposite):
         key = ('plan', str(device)) + tuple((id(c), float(w)) for c, w in zip(cost.cost_l, cost.weight_cost_l))
         cached = cost.__dict__.get('_plan_cache')
         if cached is not None and cached[0] == key:
             return cached[1]
         coll, groups, other = cost.device_plan(device)
-        selfs = cost.self_terms()
+        own = cost.own_terms()
         plan = None
-        if not other and (coll or groups or selfs):
+        if not other and (coll or groups or own):
             merged = merge_collision_terms(coll) if coll else (None, 0.0)
             if merged is not None:
-                plan = DevicePlan(merged[0], merged[1], groups, selfs)
+                plan = DevicePlan(merged[0], merged[1], groups, own)
         cost.__dict__['_plan_cache'] = (key, plan)
         return plan
     if isinstance(cost, CostCollision):
         if cost.field is None:
             return None
-        return DevicePlan(None, 0.0, [], [(cost, 1.0)]) if cost.is_self else DevicePlan(cost, 1.0, [])
+        return DevicePlan(None, 0.0, [], [(cost, 1.0)]) if cost.own_kernels else DevicePlan(cost, 1.0, [])
     if isinstance(cost, _TrajectoryTermCost):
         return DevicePlan(None, 0.0, _merge_term_specs([(cost.term_spec(device), 1.0)]))
     return None

@@ -11,7 +11,7 @@ import torch
 import torch.distributed as dist
 
 from .. import ops
-from ..geometry import SelfCollisionField
+from ..geometry import GridSDFField, SelfCollisionField
 from .base import OptimizationPlanner
 from .costs.cost_functions import Cost, CostCollision, CostComposite, CostGP, CostGoalPrior, _TrajectoryTermCost
 
@@ -84,6 +84,9 @@ class GPMP2(OptimizationPlanner):
         if any(isinstance(f, SelfCollisionField) for f in collision_fields):
             raise NotImplementedError('GPMP2: a SelfCollisionField in collision_fields is not wired into the low-rank solve; pass it as '
                                       'extra_costs=[CostCollision(robot, H, field=SelfCollisionField(...), sigma_coll=...)] (the dense step)')
+        if any(isinstance(f, GridSDFField) for f in collision_fields):
+            raise NotImplementedError('GPMP2: a GridSDFField in collision_fields is not wired into the low-rank solve; pass it as '
+                                      'extra_costs=[CostCollision(robot, H, field=GridSDFField(...), sigma_coll=...)] (the dense step)')
         scales = [1.0] * len(collision_fields)
         n_fields_own = len(collision_fields)
         # the sigmas the block solve runs on: an extra CostGP / CostGoalPrior on the planner's OWN start / goal states is one
@@ -102,9 +105,9 @@ class GPMP2(OptimizationPlanner):
                 raise ValueError('GPMP2 extra_costs: the %s is built for n_support_points=%s, n_dof=%s; this planner has %s, %s'
                                  % (what, c.n_support_points, c.n_dof, n_support_points, n_dof))
         for c in extra_costs:
-            if isinstance(c, CostCollision) and c.is_self:
-                # the robot against itself: its rows come from the self-collision kernels (CostCollision.get_linear_system), stacked by
-                # the dense step below
+            if isinstance(c, CostCollision) and c.own_kernels:
+                # the robot against itself, an SDF grid: the rows come from the member's own kernels (CostCollision.get_linear_system),
+                # stacked by the dense step below
                 _same_problem(c, 'CostCollision')
                 dense_extras.append(c)
             elif isinstance(c, CostCollision) and c.field is not None:

@@ -38,6 +38,8 @@ class RRTBase(MPPlanner):
         self.task = task
         if getattr(task, 'self_field', None) is not None:       # (the kernels' in-kernel predicate knows obstacles only)
             task.require_no_self_field(f'{self.NAME} (the batched RRT kernels)')
+        if getattr(task, 'sdf_field', None) is not None:
+            task.require_no_sdf_field(f'{self.NAME} (the batched RRT kernels)')
         self.n_iters = int(n_iters)
         self.step_size, self.n_radius, self.max_time = float(step_size), float(n_radius), float(max_time)
         self.start_state_pos, self.goal_state_pos = start_state_pos, goal_state_pos

@@ -308,8 +308,8 @@ class STOMP(OptimizationPlanner):
                                  k_sigma=0.0 if cc is None else cc.k_sigma, weight=weight)
                 self._iter += 1
                 have = cc is not None
-                for sm, w in plan.selfs:      # SelfCollisionField members: onto the costs the sample kernel wrote
-                    ops.self_collision_eval(flat, sm.device_self(self.device), sm.k_sigma, weight=w, out=flat_costs, accumulate=have)
+                for om, w in plan.own:        # SelfCollisionField / GridSDFField members: onto the costs the sample kernel wrote
+                    om.own_eval(flat, weight=w, out=flat_costs, accumulate=have)
                     have = True
                 for spec in groups:
                     ops.cost_terms_eval(flat, self.n_dof, out=self.costs, accumulate=have, **spec)

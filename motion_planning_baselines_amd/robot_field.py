@@ -82,6 +82,42 @@ class DeviceField:
         pass
 
 
+class _SDFSample(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pts, sdf):
+        p2 = pts.reshape(-1, 3).to(torch.float32).contiguous()
+        s, g = ops.sdf_grid_sample(p2, sdf, with_grad=True)          # (value and gradient come from the same node loads)
+        ctx.save_for_backward(g)
+        ctx.p_shape = pts.shape
+        return s.reshape(pts.shape[:-1])
+
+    @staticmethod
+    def backward(ctx, grad_s):
+        (g,) = ctx.saved_tensors
+        return (grad_s.reshape(-1, 1).to(torch.float32) * g).reshape(ctx.p_shape), None
+
+
+def sdf_grid_sample(points, sdf):
+    """points (..., 3) -> s (...) of the interpolant of an ops.DeviceSDFGrid (mpb_sdf_grid_sample), differentiable w.r.t. the points:
+    torch.autograd multiplies by the kernel's own d s / d x."""
+    return _SDFSample.apply(points, sdf)
+
+
+class DeviceGridField:
+    """`field` of the reference's cost layer over a geometry.GridSDFField: compute_cost(q_pos, link_pos) = sum_l relu(margin + r_l -
+    s(x_l)) with s from sdf_grid_sample above (differentiable w.r.t. link_pos)."""
+
+    def __init__(self, sdf):
+        self._sdf = sdf
+        self._thr = torch.as_tensor(sdf.robot.spec()['link_radius'], dtype=torch.float32, device=sdf.buf.device) + float(sdf.field.margin)
+
+    def compute_cost(self, q_pos, link_pos, **kwargs):
+        return torch.relu(self._thr - sdf_grid_sample(link_pos, self._sdf)).sum(-1)
+
+    def zero_grad(self):
+        pass
+
+
 def device_robot_field(robot, field, device):
     """(DeviceRobot, DeviceField) for one robot / collision field pair (geometry.Robot*, geometry.CollisionField)."""
     geom = ops.DeviceGeometry(robot, field, device, keep_all_links=True)
@@ -101,9 +137,12 @@ class PlanningTask:
     self_field: a geometry.SelfCollisionField (the reference's use_self_collision_storm=True).  compute_collision and
     random_coll_free_q then OR the self predicate in (a second launch, mpb_self_collision_check with or_into); the trajectory
     validation below and the RRT planners built on the task read `geom` alone and raise NotImplementedError rather than ignore
-    it."""
+    it.
 
-    def __init__(self, robot, field, self_field=None, tensor_args=None, seed=0):
+    sdf_field: a geometry.GridSDFField (a precomputed grid of signed distances: geometry the obstacle list cannot hold).  Its predicate
+    (mpb_sdf_grid_collision_check with or_into) is ORed in the same way, and the same callers refuse such a task by name."""
+
+    def __init__(self, robot, field, self_field=None, tensor_args=None, seed=0, sdf_field=None):
         from .planners.base import require_cuda
         self.tensor_args = tensor_args
         self.device = require_cuda(tensor_args)
@@ -111,6 +150,8 @@ class PlanningTask:
         self.geom = ops.DeviceGeometry(robot, field, self.device)
         self.self_field = self_field
         self.self_geom = None if self_field is None else ops.DeviceSelfCollision(robot, self_field, self.device)
+        self.sdf_field = sdf_field
+        self.sdf_geom = None if sdf_field is None else ops.DeviceSDFGrid(robot, sdf_field, self.device)
         self.q_dim = robot.q_dim
         self.q_min = robot.q_min.to(self.device)
         self.q_max = robot.q_max.to(self.device)
@@ -123,11 +164,19 @@ class PlanningTask:
         return self._in_collision(q2).reshape(qs.shape[:-1])
 
     def _in_collision(self, q2):
-        """(N, D) contiguous fp32 on the device -> bool (N,): collides with the world or (self_field) with itself."""
+        """(N, D) contiguous fp32 on the device -> bool (N,): collides with the world, (self_field) with itself or (sdf_field) with
+        what the grid holds."""
         flag = ops.collision_check(q2, self.geom)
         if self.self_geom is not None:
             ops.self_collision_check(q2, self.self_geom, flag=flag)
+        if self.sdf_geom is not None:
+            ops.sdf_grid_check(q2, self.sdf_geom, flag=flag)
         return flag
+
+    def require_no_sdf_field(self, what):
+        if self.sdf_field is not None:
+            raise NotImplementedError(f'{what} reads the obstacle geometry alone: it does not serve a task with an sdf_field '
+                                      f'(GridSDFField) yet')
 
     def require_no_self_field(self, what):
         if self.self_field is not None:
@@ -163,6 +212,7 @@ class PlanningTask:
         """trajs (..., H, W), W >= q_dim, leading dimensions flattened -> (trajs (N, H, W), the outputs of
         ops.traj_collision_stats).  A contiguous fp32 GPU tensor is read in place, velocity columns and all."""
         self.require_no_self_field('trajectory validation (mpb_traj_collision_stats)')
+        self.require_no_sdf_field('trajectory validation (mpb_traj_collision_stats)')
         t = torch.as_tensor(trajs, dtype=torch.float32, device=self.device)
         if t.dim() < 2 or t.shape[-1] < self.q_dim:
             raise ValueError(f'trajs has shape {tuple(t.shape)}, expected (..., H, W) with W >= {self.q_dim}')
