@@ -68,7 +68,8 @@ extern "C" {
  *                        mpb_mppi_plan (how mpb_mppi_step would launch a shape) added the same way: additive; so was
  *                        mpb_traj_collision_stats (validation of a trajectory batch), and the self-collision field
  *                        (mpb_self_check, mpb_self_invalidate, mpb_self_collision_eval / _grad / _check).  So was the SDF-grid
- *                        field (mpb_sdf_grid_check, _invalidate, _build, _sample, _eval, _grad, _collision_check). */
+ *                        field (mpb_sdf_grid_check, _invalidate, _build, _sample, _eval, _grad, _collision_check), and its build from
+ *                        occupancy voxels (mpb_sdf_grid_build_occupancy). */
 #define MPB_ABI_VERSION 7
 #define MPB_VERSION_TUNING_BUILD 0x40000000
 int mpb_version(void);
@@ -680,6 +681,18 @@ int mpb_self_collision_check(const float *q, const float *self, unsigned char *i
  *   fmaf(i, cell, lo) per axis, the signed distances every cost kernel takes.  One thread per node.  Reads both headers back
  *   synchronously.  Refusals in this order: null pointer, alignment, the SDF header, the geometry header (magic / version: INVALID;
  *   chained: UNSUPPORTED; no obstacle: INVALID).
+ * mpb_sdf_grid_build_occupancy: fills the node section of `sdf` from an occupancy voxel map (a scan): `occupancy` is nx * ny * nz bytes
+ *   in node order in device memory, read only; a node is the centre of a voxel of edge `cell`, a byte != 0 says that voxel is solid, the
+ *   surface is the set of voxel faces between a solid and a free voxel.  Integer part, exact: D2 of a free node = the smallest squared
+ *   index distance di^2 + dj^2 + dk^2 to an occupied node, D2 of an occupied node = the smallest to a free node, and D2 = D2_none =
+ *   (nx-1)^2 + (ny-1)^2 + (nz-1)^2 + 1 when the other class has no member (D2 < 2^24: exact in fp32).  Float part, bit-defined: node
+ *   value v = cell * (sqrt(D2) - 0.5) for a free node, -v for an occupied one, in fp32 as three separately rounded operations (a
+ *   correctly rounded root, a subtract, a multiply; no fma), `cell` the header's fp32 word.  Against an exact field whose obstacles lie
+ *   inside the grid and are unions of balls of radius >= (sqrt(3)/2) cell: free nodes -(sqrt(3) - 1/2) cell <= sdf - v < cell / 2,
+ *   occupied nodes sdf - v > -cell / 2.  A separable transform, one pass per axis (x, y, then z; a planar grid has no z pass), in
+ *   place: the partial squared distances live in the node section as int32 until the last pass writes fp32; no workspace, no atomics,
+ *   the same bits on every run.  Dimensions from the cached header read, as for the other device entry points.  Refusals in this
+ *   order: null pointer, alignment of `sdf`, the SDF header.
  * mpb_sdf_grid_sample: points (N, 3) -> s (N) and, when grad is not NULL, grad (N, 3) = d s / d x.  No robot.  Refusals: N < 0:
  *   INVALID; (N == 0: MPB_OK, nothing launched;) null pointer; alignment; the header.
  * mpb_sdf_grid_eval / _grad: the signature and meaning of mpb_self_collision_eval / _grad, c as above: out[b] (+)= weight * k_sigma *
@@ -696,6 +709,7 @@ int mpb_self_collision_check(const float *q, const float *self, unsigned char *i
 int mpb_sdf_grid_check(const float *sdf_host, int n_words);
 int mpb_sdf_grid_invalidate(const float *sdf);
 int mpb_sdf_grid_build(const float *geom, float *sdf, void *stream);
+int mpb_sdf_grid_build_occupancy(const unsigned char *occupancy, float *sdf, void *stream);
 int mpb_sdf_grid_sample(const float *points, const float *sdf, float *s, float *grad, int N, void *stream);
 int mpb_sdf_grid_eval(const float *trajs, const float *sdf, float *out, float *per_waypoint,
                       int B, int H, int d, int h_begin, float k_sigma, float weight, int accumulate, void *stream);

@@ -75,6 +75,7 @@ SIGNATURES = {
     'mpb_sdf_grid_check': [_p, _i],
     'mpb_sdf_grid_invalidate': [_p],
     'mpb_sdf_grid_build': [_p, _p, _p],
+    'mpb_sdf_grid_build_occupancy': [_p, _p, _p],
     'mpb_sdf_grid_sample': [_p, _p, _p, _p, _i, _p],
     'mpb_sdf_grid_eval': [_p, _p, _p, _p, _i, _i, _i, _i, _f, _f, _i, _p],
     'mpb_sdf_grid_grad': [_p, _p, _p, _p, _i, _i, _i, _i, _f, _f, _i, _p],

@@ -10,13 +10,15 @@
 // a GeomView filled from the SDF buffer; a point robot has its one sphere at q).
 //
 // Mapping: one wave per trajectory (a workgroup IS one wave: no barrier, no LDS), one lane per waypoint, trips of 64 for H > 64; the
-// predicate and the sampler give one lane per configuration / point; the builder one thread per node.  The node gathers are what
+// predicate and the sampler give one lane per configuration / point; the builder one thread per node (the builder from occupancy voxels
+// is a distance transform with LDS tiles of its own, described where it stands).  The node gathers are what
 // the kernels wait for (a lane's eight nodes are four pairs of adjacent words anywhere in a grid of tens of MB), so the spheres go in groups of
 // MPB_SDF_GROUP: the chain walk places the group, every load of the group is issued, then the hinges are taken.  With gradients the force
 // -grad s of an active sphere is pulled through J^T at once from the joint axes / origins the same walk has kept (FKState<true>,
 // joint_term), skipped wave-wide when a ballot finds the sphere active in no lane.
 // Order of the sums: spheres in table order in fp32 per waypoint, a lane's waypoints in ascending order, then the fixed-order wave
 // reduction of mpb_common.h: every run gives the same bits.  Every node index is clamped into the grid whatever the input (NaN included).
+#include <algorithm>
 #include <mutex>
 
 #include "mpb_common.h"
@@ -319,6 +321,92 @@ __global__ __launch_bounds__(256) void sdf_build_kernel(const float* __restrict_
     nodes[n] = best;
 }
 
+// ---- the grid from occupancy voxels: exact squared Euclidean distance transform, one pass per axis (include/mpb.h has the definition) --
+// The partial squared index distances live IN the node section as one signed int32 per node until the last pass writes fp32 over them:
+// a free node holds +(partial distance to the occupied class), an occupied node -(partial distance to the free class).  A node is at
+// distance 0 from its own class in every partial transform, so a word w reads as max(w, 0) towards the occupied class and max(-w, 0)
+// towards the free class; 0 is never stored and the sign is the class.  "None in this line" is MPB_EDT_NONE: two more passes add at
+// most 2 * 1023^2 to it, which stays below 2^31; the last pass clamps whatever is >= MPB_EDT_NONE to D2_none.
+// A pass loads a tile of WHOLE lines into LDS, then writes the tile back: in place is safe, no other workgroup touches those lines.
+// The minimum  min_j f(j) + (i - j)^2  is taken by scanning outward from i in both directions until delta^2 >= the best so far (what
+// remains cannot win: exact); integer minima do not depend on order, no atomics: the same bits on every run.
+#define MPB_EDT_NONE (1 << 30)
+#define MPB_EDT_X_TILE 1024                          // nodes of an x tile: whole lines, max(1, 1024 / nx) of them
+#define MPB_EDT_T 32                                 // x positions of a y / z tile: rows of 128 bytes, a wave's lanes in consecutive banks
+
+__device__ __forceinline__ bool edt_header_matches(const float* __restrict__ s, int nx, int ny, int nz) {
+    const int* si = reinterpret_cast<const int*>(s);
+    return si[MPB_DW_MAGIC] == MPB_SDF_MAGIC && si[MPB_DW_DIMS] == nx && si[MPB_DW_DIMS + 1] == ny && si[MPB_DW_DIMS + 2] == nz;
+}
+
+// along x, from the occupancy bytes (read only): the squared distance to the nearest node of the OTHER class in the node's own line
+__global__ __launch_bounds__(256) void occ_edt_x_kernel(const unsigned char* __restrict__ occ, float* __restrict__ sdfb, int nx, int ny, int nz) {
+    __shared__ unsigned char line[MPB_EDT_X_TILE];
+    if (!edt_header_matches(sdfb, nx, ny, nz)) return;           // (block-uniform: nothing is written through offsets the launcher has not read)
+    int* nodes = reinterpret_cast<int*>(sdfb) + reinterpret_cast<const int*>(sdfb)[MPB_DW_OFF_NODES];
+    const unsigned n_nodes = (unsigned)nx * (unsigned)ny * (unsigned)nz;
+    const unsigned tile = (unsigned)max(1, MPB_EDT_X_TILE / nx) * (unsigned)nx;      // <= 1024 nodes, whole lines
+    const unsigned base = blockIdx.x * tile;
+    const unsigned cnt = min(tile, n_nodes - base);
+    for (unsigned l = threadIdx.x; l < cnt; l += 256u) line[l] = occ[base + l] != 0 ? 1 : 0;
+    __syncthreads();
+    for (unsigned l = threadIdx.x; l < cnt; l += 256u) {
+        const int i = (int)(l % (unsigned)nx);
+        const unsigned char* row = line + (l - (unsigned)i);
+        const unsigned char c = row[i];
+        int g = MPB_EDT_NONE;
+        for (int d = 1; i - d >= 0 || i + d < nx; ++d) {
+            const bool lo = i - d >= 0 && row[i - d] != c, hi = i + d < nx && row[i + d] != c;
+            if (lo || hi) { g = d * d; break; }
+        }
+        nodes[base + l] = c ? -g : g;
+    }
+}
+
+// cell * (sqrt(D2) - 0.5) in three separately rounded fp32 operations.  D2 < 2^24 is exact in fp32 and in fp64; the fp64 root is
+// correctly rounded and rounding it to fp32 is the correctly rounded fp32 root (53 >= 2 * 24 + 2 bits: double rounding is innocuous)
+__device__ __forceinline__ float edt_value(int d2, float cell) {
+#pragma clang fp contract(off)
+    const float root = (float)sqrt((double)d2);
+    return __fmul_rn(cell, __fsub_rn(root, 0.5f));
+}
+
+// along y (axis 1) or z (axis 2): a tile is MPB_EDT_T consecutive x positions by the whole line, laid out [position along the axis][T];
+// blockIdx.y is the other of the two axes.  LAST: the pass that turns D2 into the node value.
+template <bool LAST>
+__global__ __launch_bounds__(1024) void occ_edt_axis_kernel(float* __restrict__ sdfb, int nx, int ny, int nz, int axis) {
+    extern __shared__ int edt_tile[];
+    if (!edt_header_matches(sdfb, nx, ny, nz)) return;           // (block-uniform)
+    int* nodes = reinterpret_cast<int*>(sdfb) + reinterpret_cast<const int*>(sdfb)[MPB_DW_OFF_NODES];
+    const int n = axis == 1 ? ny : nz;
+    const unsigned stride = axis == 1 ? (unsigned)nx : (unsigned)nx * (unsigned)ny;
+    const int col = threadIdx.x & (MPB_EDT_T - 1), row0 = threadIdx.x / MPB_EDT_T, rows = blockDim.x / MPB_EDT_T;
+    const int x = blockIdx.x * MPB_EDT_T + col;
+    const bool live = x < nx;
+    const unsigned base = (axis == 1 ? blockIdx.y * (unsigned)nx * (unsigned)ny : blockIdx.y * (unsigned)nx) + (unsigned)x;
+    if (live)
+        for (int r = row0; r < n; r += rows) edt_tile[r * MPB_EDT_T + col] = nodes[base + (unsigned)r * stride];
+    __syncthreads();
+    if (!live) return;
+    const float cell = sdfb[MPB_DW_CELL];
+    const int d2_none = (nx - 1) * (nx - 1) + (ny - 1) * (ny - 1) + (nz - 1) * (nz - 1) + 1;
+    for (int r = row0; r < n; r += rows) {
+        const int w = edt_tile[r * MPB_EDT_T + col];
+        const int sgn = w < 0 ? -1 : 1;                          // the node's class; f(j) = max(sgn * word(j), 0): towards the other class
+        int best = sgn * w;
+        for (int d = 1; d * d < best && (r - d >= 0 || r + d < n); ++d) {
+            if (r - d >= 0) best = min(best, max(sgn * edt_tile[(r - d) * MPB_EDT_T + col], 0) + d * d);
+            if (r + d < n) best = min(best, max(sgn * edt_tile[(r + d) * MPB_EDT_T + col], 0) + d * d);
+        }
+        if (LAST) {
+            const float v = edt_value(best >= MPB_EDT_NONE ? d2_none : best, cell);
+            reinterpret_cast<float*>(nodes)[base + (unsigned)r * stride] = sgn < 0 ? -v : v;
+        } else {
+            nodes[base + (unsigned)r * stride] = sgn * best;
+        }
+    }
+}
+
 // ---- host side ------------------------------------------------------------------------------------------------------
 // header, offsets and limits (n_words < 0: the total is not compared with a word count)
 static int sdf_header_check(const int32_t* si, long long n_words, const char* who) {
@@ -415,6 +503,45 @@ extern "C" int mpb_sdf_grid_build(const float* geom, float* sdfb, void* stream) 
     const unsigned n_nodes = (unsigned)S.nx * (unsigned)S.ny * (unsigned)S.nz;
     hipLaunchKernelGGL(sdf_build_kernel, dim3((n_nodes + 255u) / 256u), dim3(256), 0, (hipStream_t)stream, geom, sdfb, S.nx, S.ny, S.nz, n_sph, n_box);
     return mpb_check_launch(__func__);
+}
+
+// LDS of a y / z pass: n rows of MPB_EDT_T words, 128 KB at n = 1 024; beyond the default limit of 48 KB the kernel's limit is raised to
+// the largest tile there is -- once per kernel and device, as the self-collision launcher does
+template <bool LAST>
+static int edt_axis_launch(float* sdfb, const SdfShape& S, int axis, void* stream, const char* who) {
+    static bool raised[64] = {};
+    const int n = axis == 1 ? S.ny : S.nz, other = axis == 1 ? S.nz : S.ny;
+    const size_t bytes = (size_t)n * MPB_EDT_T * sizeof(int);
+    if (bytes > 48 * 1024) {
+        std::lock_guard<std::mutex> lock(g_sdf_mu);
+        if (!(S.dev >= 0 && S.dev < 64 && raised[S.dev])) {
+            const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(occ_edt_axis_kernel<LAST>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                     MPB_SDF_MAX_DIM * MPB_EDT_T * (int)sizeof(int));
+            if (e != hipSuccess) return mpb_failf(MPB_E_HIP, "%s: raising the LDS limit to %zu bytes failed: %s", who, bytes, hipGetErrorString(e));
+            if (S.dev >= 0 && S.dev < 64) raised[S.dev] = true;
+        }
+    }
+    const int threads = std::min(1024, (n * MPB_EDT_T + 63) / 64 * 64);          // one thread per node of the tile up to 1 024, whole waves
+    hipLaunchKernelGGL(occ_edt_axis_kernel<LAST>, dim3((S.nx + MPB_EDT_T - 1) / MPB_EDT_T, other), dim3(threads), bytes, (hipStream_t)stream, sdfb,
+                       S.nx, S.ny, S.nz, axis);
+    return mpb_check_launch(who);
+}
+
+extern "C" int mpb_sdf_grid_build_occupancy(const unsigned char* occupancy, float* sdfb, void* stream) {
+    if (!occupancy || !sdfb) return mpb_fail(MPB_E_INVALID, "mpb_sdf_grid_build_occupancy: null pointer");
+    if (mpb_misaligned16(sdfb)) return mpb_failf(MPB_E_INVALID, "%s: the SDF-grid buffer must be 16-byte aligned", __func__);
+    SdfShape S;
+    int rc = sdf_shape(sdfb, S, __func__);
+    if (rc) return rc;
+    const unsigned n_nodes = (unsigned)S.nx * (unsigned)S.ny * (unsigned)S.nz;
+    const unsigned tile = (unsigned)(MPB_EDT_X_TILE / S.nx > 1 ? MPB_EDT_X_TILE / S.nx : 1) * (unsigned)S.nx;
+    hipLaunchKernelGGL(occ_edt_x_kernel, dim3((n_nodes + tile - 1) / tile), dim3(256), 0, (hipStream_t)stream, occupancy, sdfb, S.nx, S.ny, S.nz);
+    rc = mpb_check_launch(__func__);
+    if (rc) return rc;
+    if (S.nz == 1) return edt_axis_launch<true>(sdfb, S, 1, stream, __func__);
+    rc = edt_axis_launch<false>(sdfb, S, 1, stream, __func__);
+    if (rc) return rc;
+    return edt_axis_launch<true>(sdfb, S, 2, stream, __func__);
 }
 
 extern "C" int mpb_sdf_grid_sample(const float* points, const float* sdfb, float* s, float* grad, int N, void* stream) {

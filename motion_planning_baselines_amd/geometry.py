@@ -493,7 +493,9 @@ class GridSDFField:
 
     GridSDFField(values, lo, cell, margin): the caller's node values (checked finite here).
     GridSDFField.from_field(collision_field, lo, hi, cell): min_o sdf_o of a CollisionField at every node, evaluated ON THE GPU when
-    the field is put on a device (ops.DeviceSDFGrid, mpb_sdf_grid_build); `values` stays None on the host."""
+    the field is put on a device (ops.DeviceSDFGrid, mpb_sdf_grid_build); `values` stays None on the host.
+    GridSDFField.from_occupancy(occupancy, lo, cell): from an occupancy voxel map (a scan), by an exact Euclidean distance transform ON
+    THE GPU (mpb_sdf_grid_build_occupancy, include/mpb.h has the definition); `values` stays None, the occupancy is the field's source."""
 
     def __init__(self, values, lo, cell, margin=0.05):
         v = np.asarray(values, dtype=np.float32)
@@ -556,14 +558,51 @@ class GridSDFField:
         self._set_frame(lo, cell, collision_field.margin if margin is None else margin)
         return self
 
+    @classmethod
+    def from_occupancy(cls, occupancy, lo, cell, margin=0.05):
+        """The grid of an occupancy voxel map: `occupancy` of shape (nz, ny, nx), or (ny, nx) for a planar grid, a numpy array or a torch
+        tensor (on the CPU or already on the GPU) of any dtype, element != 0 meaning that the voxel of edge `cell` centred on the node is
+        solid.  Node value: cell * (sqrt(D2) - 0.5) at a free node, minus that at an occupied one, D2 the smallest squared index distance
+        to a node of the other class (include/mpb.h, mpb_sdf_grid_build_occupancy) -- evaluated on the GPU when the field goes to a
+        device; ops.DeviceSDFGrid.update_occupancy rebuilds it there for the next scan.  The occupancy is kept as `source`: uint8 / bool
+        arrays as they are, any other dtype as `!= 0` (never as fp32)."""
+        occ = occupancy_bytes(occupancy, 'GridSDFField.from_occupancy')
+        self = cls.__new__(cls)
+        self.dims = cls._check_dims(occ.shape[2], occ.shape[1], occ.shape[0])
+        self.values = None
+        self.source = occ
+        self._set_frame(lo, cell, margin)
+        return self
+
     def zero_grad(self):
         pass
+
+
+def occupancy_bytes(occupancy, who):
+    """An occupancy map as a contiguous (nz, ny, nx) array of one byte per node, of the kind it came as (numpy array, or torch tensor on
+    its device): uint8 / bool as they are, any other dtype as `!= 0`; (ny, nx) becomes (1, ny, nx)."""
+    if isinstance(occupancy, torch.Tensor):
+        occ = occupancy if occupancy.dtype in (torch.uint8, torch.bool) else occupancy != 0
+        occ = occ[None] if occ.dim() == 2 else occ
+        if occ.dim() == 3:
+            occ = occ.contiguous()
+    else:
+        occ = np.asarray(occupancy)
+        if occ.dtype == object:
+            raise ValueError(f'{who}: occupancy must be a numeric or bool array')
+        occ = occ if occ.dtype in (np.uint8, np.bool_) else occ != 0
+        occ = occ[None] if occ.ndim == 2 else occ
+        if occ.ndim == 3:
+            occ = np.ascontiguousarray(occ)
+    if len(occ.shape) != 3:
+        raise ValueError(f'{who}: occupancy of shape {tuple(np.shape(occupancy))}, expected (nz, ny, nx) or (ny, nx)')
+    return occ
 
 
 def pack_sdf_grid(robot, field, with_nodes=True):
     """Pack a robot + a GridSDFField into ONE self-contained fp32 word buffer (sdf_layout.py: header, joint_tf rows, links rows -- both
     in the row formats of pack_geometry, every link kept --, then the node section, 16-byte aligned).  The node section holds the
-    field's values; for a field made by from_field it is left zero for mpb_sdf_grid_build to fill on the device.  with_nodes=False
+    field's values; for a field made by from_field / from_occupancy it is left zero for the build kernels to fill on the device.  with_nodes=False
     returns the words BEFORE the node section only (the header's total still counts the nodes): what an upload needs when the nodes
     are built on the device."""
     from . import sdf_layout as S

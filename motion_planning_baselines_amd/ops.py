@@ -7,12 +7,13 @@ import collections
 import ctypes
 import functools
 import math
+import warnings
 
 import numpy as np
 import torch
 
 from . import _lib, rrt_layout
-from .geometry import MAX_FIELDS, count_fields, pack_geometry, pack_sdf_grid, pack_self_collision
+from .geometry import MAX_FIELDS, CollisionField, count_fields, occupancy_bytes, pack_geometry, pack_sdf_grid, pack_self_collision
 from .geometry import header as geometry_header
 
 
@@ -196,8 +197,10 @@ def self_collision_check(q, sc, with_gap=False, flag=None, gap=None):
 
 class DeviceSDFGrid:
     """A robot + a GridSDFField as the packed SDF buffer (geometry.pack_sdf_grid) resident in HBM: packed, validated (mpb_sdf_grid_check)
-    and uploaded once -- or, for a field made by GridSDFField.from_field, the header and the robot tables uploaded and the nodes built
-    ON the device (mpb_sdf_grid_build) from the CollisionField.  `.nodes` is the node section as a (nz, ny, nx) view of the buffer."""
+    and uploaded once -- or, for a field without host values, the header and the robot tables uploaded and the nodes built ON the
+    device from the field's source: a CollisionField (GridSDFField.from_field, mpb_sdf_grid_build) or an occupancy voxel map
+    (GridSDFField.from_occupancy, mpb_sdf_grid_build_occupancy: the bytes uploaded once, a GPU tensor used in place).  `.nodes` is the
+    node section as a (nz, ny, nx) view of the buffer."""
 
     def __init__(self, robot, field, device):
         from .sdf_layout import header as sdf_header
@@ -218,10 +221,31 @@ class DeviceSDFGrid:
         _lib.check(_lib.lib().mpb_sdf_grid_invalidate(_ptr(self.buf)), 'mpb_sdf_grid_invalidate')
         nx, ny, nz = self.dims
         self.nodes = self.buf[off_nodes:].view(nz, ny, nx)
-        if built:
+        if built and isinstance(field.source, CollisionField):
             from .geometry import RobotPointMass
             geom = DeviceGeometry(RobotPointMass(3), field.source, device, use_model=False)
             sdf_grid_build(geom, self)
+        elif built:
+            self.update_occupancy(field.source)
+
+    def update_occupancy(self, occupancy):
+        """Rebuild the node section in place from the next scan: an occupancy map of the same dimensions, as GridSDFField.from_occupancy
+        takes it (a GPU tensor of uint8 / bool on the buffer's device is used in place, anything else becomes bytes and is uploaded;
+        the bytes are only read, a read-only numpy array -- a memory-mapped scan -- is fine).  The header does not change.  A field made
+        by from_occupancy then holds the new scan as its `source`, so a DeviceSDFGrid made from it later (another device, a
+        PlanningTask built afterwards) builds THIS scan; under a field with host `values` or one made by from_field only this device
+        buffer changes, the field keeps what it held.  Returns `.nodes`."""
+        occ = occupancy_bytes(occupancy, 'DeviceSDFGrid.update_occupancy')
+        nx, ny, nz = self.dims
+        if tuple(occ.shape) != (nz, ny, nx):
+            raise ValueError(f'update_occupancy: occupancy of shape {tuple(occ.shape)}, the grid has (nz, ny, nx) = {(nz, ny, nx)}')
+        if self.field.values is None and not isinstance(self.field.source, CollisionField):
+            self.field.source = occ
+        if not isinstance(occ, torch.Tensor):
+            with warnings.catch_warnings():        # (torch warns that a read-only array could be written through the tensor: it is only uploaded)
+                warnings.filterwarnings('ignore', message='The given NumPy array is not writable', category=UserWarning)
+                occ = torch.from_numpy(occ)
+        return sdf_grid_build_occupancy(occ.to(self.buf.device), self)
 
 
 @_on_tensor_device
@@ -233,6 +257,20 @@ def sdf_grid_build(geom, sdf):
     _chk(geom.buf, geom.buf.shape, 'geom.buf')
     _chk(sdf.buf, sdf.buf.shape, 'sdf.buf')
     _lib.check(_lib.lib().mpb_sdf_grid_build(_ptr(geom.buf), _ptr(sdf.buf), _stream()), 'mpb_sdf_grid_build')
+    return sdf.nodes
+
+
+@_on_tensor_device
+def sdf_grid_build_occupancy(occupancy, sdf):
+    """Fill the node section of a DeviceSDFGrid from an occupancy voxel map: a contiguous uint8 or bool GPU tensor of shape (nz, ny, nx) on
+    the buffer's device, element != 0 = solid, read only (mpb_sdf_grid_build_occupancy: the exact Euclidean distance transform, in
+    place in the node section; include/mpb.h has the definition).  Returns sdf.nodes."""
+    if not isinstance(occupancy, torch.Tensor) or occupancy.dtype not in (torch.uint8, torch.bool):
+        raise ValueError(f'occupancy must be a uint8 or bool tensor (got {getattr(occupancy, "dtype", type(occupancy))})')
+    nx, ny, nz = sdf.dims
+    _chk(occupancy, (nz, ny, nx), 'occupancy', dtype=occupancy.dtype)
+    _chk(sdf.buf, sdf.buf.shape, 'sdf.buf')
+    _lib.check(_lib.lib().mpb_sdf_grid_build_occupancy(_ptr(occupancy), _ptr(sdf.buf), _stream()), 'mpb_sdf_grid_build_occupancy')
     return sdf.nodes
 
 
