@@ -69,7 +69,8 @@ extern "C" {
  *                        mpb_traj_collision_stats (validation of a trajectory batch), and the self-collision field
  *                        (mpb_self_check, mpb_self_invalidate, mpb_self_collision_eval / _grad / _check).  So was the SDF-grid
  *                        field (mpb_sdf_grid_check, _invalidate, _build, _sample, _eval, _grad, _collision_check), and its build from
- *                        occupancy voxels (mpb_sdf_grid_build_occupancy). */
+ *                        occupancy voxels (mpb_sdf_grid_build_occupancy).  So were the end-effector pose and batched inverse
+ *                        kinematics (mpb_fk_ee_pose, mpb_ik_solve): additive. */
 #define MPB_ABI_VERSION 7
 #define MPB_VERSION_TUNING_BUILD 0x40000000
 int mpb_version(void);
@@ -717,6 +718,49 @@ int mpb_sdf_grid_grad(const float *trajs, const float *sdf, float *out, float *g
                       int B, int H, int d, int h_begin, float k_sigma, float weight, int accumulate, void *stream);
 int mpb_sdf_grid_collision_check(const float *q, const float *sdf, unsigned char *in_collision, float *gap,
                                  int N, int D, int or_into, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * End effector: pose, geometric Jacobian, batched inverse kinematics (build-defined; the reference's Panda examples ask
+ * torch_robotics' robot.get_EE_position, panda_spheres_GPMP.py:63-64).  Serial chains only (MPB_KIND_CHAIN): a point robot has no end
+ * effector.
+ *   pose:   the last frame of the chain walk, frame_{n_dof + 1} = [R | t], row-major 3 x 4 (the walk of mpb_fk_collision_points).
+ *   J (6 x D), column j:  rows 0-2  z_j x (t - p_j),  rows 3-5  z_j   (z_j, p_j: axis and origin of joint j in the world).
+ *   IK of a target (R*, t*) from a seed q0: damped least squares with a fixed budget.  At the start of each of n_iters iterations, and
+ *   once more after the last step, the error is evaluated:
+ *     e_p = t* - t;  E = R* R^T,  w = vee(E - E^T) / 2,  c = (tr E - 1) / 2,  theta = atan2(|w|, c),
+ *     e_w = (theta / |w|) w, plain w when |w| < 1e-6 (exactly half a turn away the rotation part of the step is therefore zero).
+ *   The problem is converged when |e_p| <= pos_tol and (theta <= rot_tol or position_only); a converged problem is frozen, its q is not
+ *   touched again.  Otherwise one step:  dq = J^T (J J^T + damping^2 I)^{-1} e,  e = (e_p, e_w) -- with position_only e = e_p and the
+ *   upper half of J --, then q <- clamp(q + dq, q_min, q_max), no clamp when the limits are not given.  No step-length cap, no line
+ *   search, no null-space term.
+ *   Bounds: 0 <= n_iters <= MPB_IK_MAX_ITERS, so a launch is bounded whatever the input, NaN included (a NaN problem never converges);
+ *   damping >= MPB_IK_MIN_DAMPING: J J^T + damping^2 I is then SPD with condition number at most about 3e5 for chains of up to 12
+ *   joints and reach up to about 1.2 m, which is what the unpivoted fp32 Cholesky of the kernel tolerates.
+ *
+ * geom: a packed geometry buffer in DEVICE memory, 16-byte aligned.  Only the first field's header (kind, n_dof, n_tf) and its joint_tf
+ * section are read: no obstacle is touched and no geom_flags are needed.  The launchers read the header back ONCE per buffer address and
+ * device (a synchronous 128-byte copy on the first call with that pointer -- make that call outside stream capture -- and again whenever
+ * what was read does not fit the call's D); the kernels compare the header with the D they were launched with and answer NaN
+ * (converged = 0) when it has changed since.
+ *
+ * mpb_fk_ee_pose: q (N, D) -> pose (N, 12); jac (N, 6, D) optional (may be NULL).  One lane per configuration.
+ * mpb_ik_solve: target (N, 12), q_seed (N, S, D): S seeds per target; q_min, q_max (D each): both or neither (NULL).  Outputs per
+ *   problem, all at the returned q: q_out (N, S, D), pos_err = |e_p| and rot_err = theta (N, S), converged (N, S) bytes 0 / 1,
+ *   iters_used (N, S) = steps taken.  n_iters == 0 evaluates and steps nowhere: q_out is q_seed's bits.  One lane per (target, seed);
+ *   no LDS, no atomics, no cross-lane arithmetic: a problem's bits depend on its own inputs only, and the pose the solver sees is the
+ *   pose mpb_fk_ee_pose returns, bit for bit.  A wave leaves the iteration loop when all of its problems have converged.
+ * Refusals, in this order: (1) D > MPB_MAX_DOF: MPB_E_UNSUPPORTED; (2) N < 0, D < 1 (solve: S < 0, N * S beyond an int, n_iters
+ * outside 0..MPB_IK_MAX_ITERS, damping below MPB_IK_MIN_DAMPING or NaN, a negative or NaN tolerance): MPB_E_INVALID; (3) (N == 0 or S ==
+ * 0: MPB_OK, nothing launched;) (4) a null required pointer, one of q_min / q_max without the other, geom not 16-byte aligned:
+ * MPB_E_INVALID; then what only the header tells: bad magic / version: MPB_E_INVALID; (5) a point robot: MPB_E_UNSUPPORTED; (6) D !=
+ * n_dof: MPB_E_INVALID.
+ * ------------------------------------------------------------------------------------------- */
+#define MPB_IK_MAX_ITERS 1024
+#define MPB_IK_MIN_DAMPING 1e-2f
+int mpb_fk_ee_pose(const float *q, const float *geom, float *pose, float *jac, int N, int D, void *stream);
+int mpb_ik_solve(const float *target, const float *q_seed, const float *geom, const float *q_min, const float *q_max,
+                 float *q_out, float *pos_err, float *rot_err, unsigned char *converged, int *iters_used,
+                 int N, int S, int D, int n_iters, float damping, float pos_tol, float rot_tol, int position_only, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Batched RRT-Connect -- replaces RRTConnect._run_optimization (rrt_connect.py:93-192) with RRTBase.get_pre_sample /

@@ -1,0 +1,320 @@
+// mpb_ik.hip -- the end effector: its pose and geometric Jacobian (mpb_fk_ee_pose) and batched inverse kinematics by damped least
+// squares with a fixed budget (mpb_ik_solve).  What the reference's Panda examples ask of the robot (robot.get_EE_position,
+// panda_spheres_GPMP.py:63-64; provider: torch_robotics, absent -- the semantics are build-defined) and the front end
+// that turns "put the hand there" into the goal configurations the planners take.
+//
+// One LANE per problem: a configuration for the pose op, a (target, seed) pair for the solver.  No LDS, no barrier, no atomics, no
+// cross-lane arithmetic -- a problem's bits depend on its own inputs only, whatever wave it rides in.  The one cross-lane operation is
+// the ballot that lets a wave leave the iteration loop when all of its problems have converged; it changes which waves keep working,
+// never a value.
+//   - The walk is fk_identity / fk_advance<true> of mpb_geom.h through a GeomView filled from the buffer's first header (kind, n_dof,
+//     n_tf, joint_tf: nothing else is read, no obstacle is touched): the chain's transforms are wave-uniform scalar loads, and the pose
+//     the solver sees is, bit for bit, the pose mpb_fk_ee_pose returns.
+//   - J (6 x D) is never stored.  Column j is (z_j x (t - p_j), z_j) from the z / p arrays FKState<true> keeps; the 21 (position only: 6)
+//     distinct entries of J J^T are accumulated joint by joint in a loop fully unrolled over MPB_MAX_DOF, joints at or beyond n_dof
+//     contributing zero through selects; the system is solved by a fully unrolled unpivoted Cholesky in registers (damping >= 1e-2
+//     bounds its condition number, include/mpb.h), and dq_j = J_j^T y is formed from the same arrays.
+//   - No register array is indexed by a run-time value: every loop over joints or matrix entries has compile-time bounds.
+//   - The square roots and reciprocals of the Cholesky are the IEEE ones (six of each per iteration, next to a chain walk and a
+//     joint loop of several hundred instructions each): a step is up to several radians long and multiplies their error.
+#include <limits.h>
+
+#include <mutex>
+
+#include "mpb_common.h"
+#include "mpb_geom.h"
+#include "mpb_host.h"
+
+// the chain of a geometry buffer's first field as the GeomView fk_advance reads (tf, n_dof); no links, no obstacles
+__device__ __forceinline__ GeomView ik_chain_view(const float* __restrict__ g) {
+    const int* gi = reinterpret_cast<const int*>(g);
+    GeomView v = {};
+    v.kind = gi[MPB_GW_KIND];
+    v.n_dof = gi[MPB_GW_N_DOF];
+    v.n_tf = gi[MPB_GW_N_TF];
+    v.tf = g + gi[MPB_GW_OFF_TF];
+    return v;
+}
+
+// the launcher read kind / n_dof from the header once per buffer address; the kernels walk by the BUFFER's numbers and refuse (NaN
+// outputs, nothing converged) when those are not the launcher's -- an address that got another robot since
+__device__ __forceinline__ bool ik_header_matches(const float* __restrict__ g, int D) {
+    const int* gi = reinterpret_cast<const int*>(g);
+    return gi[MPB_GW_MAGIC] == MPB_GEOM_MAGIC && gi[MPB_GW_KIND] == MPB_KIND_CHAIN && gi[MPB_GW_N_DOF] == D && gi[MPB_GW_N_TF] == D + 1;
+}
+
+// frame_{n_dof + 1} of configuration q: the end effector's R, t in F, the joints' axes z_j and origins p_j in its arrays
+__device__ __forceinline__ void ee_walk(const GeomView& G, const float (&q)[MPB_MAX_DOF], FKState<true>& F) {
+    fk_identity(F);
+    F.frame = 0;
+#pragma unroll
+    for (int i = 0; i < MPB_MAX_DOF; ++i) { F.zx[i] = F.zy[i] = F.zz[i] = F.px[i] = F.py[i] = F.pz[i] = 0.f; }
+    for (int j = 0; j <= G.n_dof; ++j) fk_advance<true>(G, F, q);
+}
+
+// column j of the Jacobian's upper half, z_j x (t - p_j), in the fma form of joint_term (mpb_geom.h); zero for a joint the chain has not
+template <int J>
+__device__ __forceinline__ void ee_jv(const FKState<true>& F, int D, float& cx, float& cy, float& cz) {
+    const float ex = F.tx - F.px[J], ey = F.ty - F.py[J], ez = F.tz - F.pz[J];
+    const bool on = J < D;
+    cx = on ? fmaf(F.zy[J], ez, -(F.zz[J] * ey)) : 0.f;
+    cy = on ? fmaf(F.zz[J], ex, -(F.zx[J] * ez)) : 0.f;
+    cz = on ? fmaf(F.zx[J], ey, -(F.zy[J] * ex)) : 0.f;
+}
+
+__global__ __launch_bounds__(64) void fk_ee_pose_kernel(const float* __restrict__ q_in, const float* __restrict__ geom, float* __restrict__ pose,
+                                                        float* __restrict__ jac, int N, int D) {
+    const int n = blockIdx.x * 64 + threadIdx.x;
+    if (n >= N) return;
+    float* po = pose + (size_t)n * 12;
+    float* jo = jac ? jac + (size_t)n * 6 * D : nullptr;
+    if (!ik_header_matches(geom, D)) {
+        const float nan = __int_as_float(0x7FC00000);
+        for (int i = 0; i < 12; ++i) po[i] = nan;
+        if (jo) for (int i = 0; i < 6 * D; ++i) jo[i] = nan;
+        return;
+    }
+    const GeomView G = ik_chain_view(geom);
+    float q[MPB_MAX_DOF];
+#pragma unroll
+    for (int i = 0; i < MPB_MAX_DOF; ++i) q[i] = (i < D) ? q_in[(size_t)n * D + i] : 0.f;
+    FKState<true> F;
+    ee_walk(G, q, F);
+    po[0] = F.r00; po[1] = F.r01; po[2] = F.r02; po[3] = F.tx;
+    po[4] = F.r10; po[5] = F.r11; po[6] = F.r12; po[7] = F.ty;
+    po[8] = F.r20; po[9] = F.r21; po[10] = F.r22; po[11] = F.tz;
+    if (jo) {
+        static_for<0, MPB_MAX_DOF>([&](auto jc) {
+            constexpr int J = decltype(jc)::value;
+            if (J < D) {
+                float cx, cy, cz;
+                ee_jv<J>(F, D, cx, cy, cz);
+                jo[0 * D + J] = cx; jo[1 * D + J] = cy; jo[2 * D + J] = cz;
+                jo[3 * D + J] = F.zx[J]; jo[4 * D + J] = F.zy[J]; jo[5 * D + J] = F.zz[J];
+            }
+        });
+    }
+}
+
+// x = A^{-1} e for the SPD A given by its lower triangle (A[i][j], j <= i): unpivoted Cholesky A = L L^T with reciprocal pivots, the
+// two substitutions.  Fully unrolled, every index a compile-time constant.
+template <int NR>
+__device__ __forceinline__ void spd_solve(float (&A)[NR][NR], const float (&e)[NR], float (&x)[NR]) {
+    float inv[NR];
+#pragma unroll
+    for (int i = 0; i < NR; ++i) {
+#pragma unroll
+        for (int j = 0; j <= i; ++j) {
+            float s = A[i][j];
+#pragma unroll
+            for (int k = 0; k < j; ++k) s = fmaf(-A[i][k], A[j][k], s);
+            if (i == j) {
+                const float l = sqrtf(s);
+                inv[i] = 1.0f / l;
+                A[i][i] = l;
+            } else {
+                A[i][j] = s * inv[j];
+            }
+        }
+    }
+    float y[NR];
+#pragma unroll
+    for (int i = 0; i < NR; ++i) {
+        float s = e[i];
+#pragma unroll
+        for (int k = 0; k < i; ++k) s = fmaf(-A[i][k], y[k], s);
+        y[i] = s * inv[i];
+    }
+#pragma unroll
+    for (int i = NR - 1; i >= 0; --i) {
+        float s = y[i];
+#pragma unroll
+        for (int k = i + 1; k < NR; ++k) s = fmaf(-A[k][i], x[k], s);
+        x[i] = s * inv[i];
+    }
+}
+
+// PO: position only -- the error is e_p, the system the 3 x 3 of the Jacobian's upper half
+template <bool PO>
+__global__ __launch_bounds__(64) void ik_solve_kernel(const float* __restrict__ target, const float* __restrict__ q_seed,
+                                                      const float* __restrict__ geom, const float* __restrict__ q_min,
+                                                      const float* __restrict__ q_max, float* __restrict__ q_out, float* __restrict__ pos_err,
+                                                      float* __restrict__ rot_err, unsigned char* __restrict__ converged,
+                                                      int* __restrict__ iters_used, int total, int S, int D, int n_iters, float damping,
+                                                      float pos_tol, float rot_tol) {
+    constexpr int NR = PO ? 3 : 6;
+    const int p = blockIdx.x * 64 + threadIdx.x;
+    const bool valid = p < total;
+    const int pc = valid ? p : total - 1;                    // (a lane past the end works on the last problem and stores nothing)
+    const float nan = __int_as_float(0x7FC00000);
+    if (!ik_header_matches(geom, D)) {
+        if (valid) {
+            for (int i = 0; i < D; ++i) q_out[(size_t)p * D + i] = nan;
+            pos_err[p] = nan; rot_err[p] = nan; converged[p] = 0; iters_used[p] = 0;
+        }
+        return;
+    }
+    const GeomView G = ik_chain_view(geom);
+    const float* T = target + (size_t)(pc / S) * 12;
+    const float s00 = T[0], s01 = T[1], s02 = T[2], gx = T[3], s10 = T[4], s11 = T[5], s12 = T[6], gy = T[7], s20 = T[8], s21 = T[9],
+                s22 = T[10], gz = T[11];
+    float q[MPB_MAX_DOF];
+#pragma unroll
+    for (int i = 0; i < MPB_MAX_DOF; ++i) q[i] = (i < D) ? q_seed[(size_t)pc * D + i] : 0.f;
+    const float lam2 = damping * damping;
+    const bool limits = q_min != nullptr;
+    int used = 0;
+    float pe = nan, th = nan;
+    bool conv = false;
+    for (int it = 0;; ++it) {
+        FKState<true> F;
+        ee_walk(G, q, F);
+        float e[NR];
+        e[0] = gx - F.tx; e[1] = gy - F.ty; e[2] = gz - F.tz;
+        pe = sqrtf(fmaf(e[2], e[2], fmaf(e[1], e[1], e[0] * e[0])));
+        // E = R* R^T, w = vee(E - E^T) / 2, c = (tr E - 1) / 2
+        const float e00 = dot3(s00, F.r00, s01, F.r01, s02, F.r02), e01 = dot3(s00, F.r10, s01, F.r11, s02, F.r12),
+                    e02 = dot3(s00, F.r20, s01, F.r21, s02, F.r22);
+        const float e10 = dot3(s10, F.r00, s11, F.r01, s12, F.r02), e11 = dot3(s10, F.r10, s11, F.r11, s12, F.r12),
+                    e12 = dot3(s10, F.r20, s11, F.r21, s12, F.r22);
+        const float e20 = dot3(s20, F.r00, s21, F.r01, s22, F.r02), e21 = dot3(s20, F.r10, s21, F.r11, s22, F.r12),
+                    e22 = dot3(s20, F.r20, s21, F.r21, s22, F.r22);
+        const float wx = 0.5f * (e21 - e12), wy = 0.5f * (e02 - e20), wz = 0.5f * (e10 - e01);
+        const float c = 0.5f * (((e00 + e11) + e22) - 1.0f);
+        const float nw = sqrtf(fmaf(wz, wz, fmaf(wy, wy, wx * wx)));
+        th = atan2f(nw, c);
+        conv = pe <= pos_tol && (PO || th <= rot_tol);
+        if (it >= n_iters) break;
+        if (__ballot(!conv) == 0ull) break;                  // wave-uniform: every problem of the wave is frozen
+        if constexpr (!PO) {
+            const float sc = (nw < 1e-6f) ? 1.0f : th / nw;  // (exactly half a turn away: w = 0, no rotation step)
+            e[3] = sc * wx; e[4] = sc * wy; e[5] = sc * wz;
+        }
+        // A = J J^T + damping^2 I, lower triangle, joint by joint
+        float A[NR][NR];
+#pragma unroll
+        for (int a = 0; a < NR; ++a)
+#pragma unroll
+            for (int b = 0; b < NR; ++b) A[a][b] = 0.f;
+        static_for<0, MPB_MAX_DOF>([&](auto jc) {
+            constexpr int J = decltype(jc)::value;
+            float col[6];
+            ee_jv<J>(F, D, col[0], col[1], col[2]);
+            const bool on = J < D;
+            col[3] = on ? F.zx[J] : 0.f; col[4] = on ? F.zy[J] : 0.f; col[5] = on ? F.zz[J] : 0.f;
+#pragma unroll
+            for (int a = 0; a < NR; ++a)
+#pragma unroll
+                for (int b = 0; b <= a; ++b) A[a][b] = fmaf(col[a], col[b], A[a][b]);
+        });
+#pragma unroll
+        for (int a = 0; a < NR; ++a) A[a][a] += lam2;
+        float y[NR];
+        spd_solve<NR>(A, e, y);
+        // q <- clamp(q + J^T y); a converged problem is frozen
+        static_for<0, MPB_MAX_DOF>([&](auto jc) {
+            constexpr int J = decltype(jc)::value;
+            if (J < D) {
+                float cx, cy, cz;
+                ee_jv<J>(F, D, cx, cy, cz);
+                float dq = fmaf(cz, y[2], fmaf(cy, y[1], cx * y[0]));
+                if constexpr (!PO) dq = fmaf(F.zz[J], y[5], fmaf(F.zy[J], y[4], fmaf(F.zx[J], y[3], dq)));
+                float qn = q[J] + dq;
+                if (limits) qn = fminf(fmaxf(qn, q_min[J]), q_max[J]);
+                q[J] = conv ? q[J] : qn;
+            }
+        });
+        used += conv ? 0 : 1;
+    }
+    if (valid) {
+        static_for<0, MPB_MAX_DOF>([&](auto jc) {
+            constexpr int J = decltype(jc)::value;
+            if (J < D) q_out[(size_t)p * D + J] = q[J];
+        });
+        pos_err[p] = pe;
+        rot_err[p] = th;
+        converged[p] = conv ? 1 : 0;
+        iters_used[p] = used;
+    }
+}
+
+// ---- host side ------------------------------------------------------------------------------------------------------
+// kind / n_dof of a DEVICE geometry buffer's first header: read once per buffer address and device -- a 128-byte synchronous copy -- and
+// kept in a small table, as mpb_sdf_grid.hip does.  An entry that does not agree with the caller's D is read again before the call is
+// refused (the address may hold another robot by now); one that agrees although the buffer changed is caught by the kernels, which compare
+// the header with the D they were launched with and answer NaN.
+struct IkShape { const void* ptr; int dev, kind, n_dof; };
+static std::mutex g_ik_mu;
+static IkShape g_ik_table[16];
+static int g_ik_n = 0, g_ik_next = 0;
+
+static int ik_shape(const float* geom, int D, IkShape& out, const char* who) {
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return mpb_failf(MPB_E_HIP, "%s: hipGetDevice failed", who);
+    std::lock_guard<std::mutex> lock(g_ik_mu);
+    int slot = -1;
+    for (int i = 0; i < g_ik_n; ++i)
+        if (g_ik_table[i].ptr == geom && g_ik_table[i].dev == dev) slot = i;
+    if (slot >= 0 && g_ik_table[slot].kind == MPB_KIND_CHAIN && g_ik_table[slot].n_dof == D) { out = g_ik_table[slot]; return MPB_OK; }
+    int32_t hdr[MPB_GEOM_HEADER_WORDS];
+    const hipError_t e = hipMemcpy(hdr, geom, sizeof(hdr), hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return mpb_failf(MPB_E_HIP, "%s: reading the geometry header failed: %s", who, hipGetErrorString(e));
+    if (hdr[MPB_GW_MAGIC] != MPB_GEOM_MAGIC || (hdr[MPB_GW_VERSION] != MPB_GEOM_VERSION && hdr[MPB_GW_VERSION] != MPB_GEOM_VERSION_LIST))
+        return mpb_failf(MPB_E_INVALID, "%s: bad magic/version of the geometry buffer", who);
+    out = {geom, dev, hdr[MPB_GW_KIND], hdr[MPB_GW_N_DOF]};
+    if (slot < 0) {
+        slot = g_ik_next;
+        g_ik_next = (g_ik_next + 1) % 16;
+        g_ik_n = g_ik_n < 16 ? g_ik_n + 1 : 16;
+    }
+    g_ik_table[slot] = out;
+    return MPB_OK;
+}
+
+// refusals 5 and 6 of include/mpb.h: what only the buffer's header tells
+static int ik_chain_check(const float* geom, int D, const char* who) {
+    IkShape S;
+    const int rc = ik_shape(geom, D, S, who);
+    if (rc) return rc;
+    if (S.kind != MPB_KIND_CHAIN) return mpb_failf(MPB_E_UNSUPPORTED, "%s: a point robot has no end effector", who);
+    if (D != S.n_dof) return mpb_failf(MPB_E_INVALID, "%s: D = %d, the chain has %d joints", who, D, S.n_dof);
+    return MPB_OK;
+}
+
+extern "C" int mpb_fk_ee_pose(const float* q, const float* geom, float* pose, float* jac, int N, int D, void* stream) {
+    if (D > MPB_MAX_DOF) return mpb_failf(MPB_E_UNSUPPORTED, "%s: D = %d exceeds MPB_MAX_DOF = %d", __func__, D, MPB_MAX_DOF);
+    if (N < 0 || D < 1) return mpb_failf(MPB_E_INVALID, "%s: bad shape", __func__);
+    if (N == 0) return MPB_OK;
+    if (!q || !geom || !pose) return mpb_failf(MPB_E_INVALID, "%s: null pointer", __func__);
+    if (mpb_misaligned16(geom)) return mpb_failf(MPB_E_INVALID, "%s: geom must be 16-byte aligned", __func__);
+    const int rc = ik_chain_check(geom, D, __func__);
+    if (rc) return rc;
+    hipLaunchKernelGGL(fk_ee_pose_kernel, dim3((N + 63) / 64), dim3(64), 0, (hipStream_t)stream, q, geom, pose, jac, N, D);
+    return mpb_check_launch(__func__);
+}
+
+extern "C" int mpb_ik_solve(const float* target, const float* q_seed, const float* geom, const float* q_min, const float* q_max, float* q_out,
+                            float* pos_err, float* rot_err, unsigned char* converged, int* iters_used, int N, int S, int D, int n_iters,
+                            float damping, float pos_tol, float rot_tol, int position_only, void* stream) {
+    if (D > MPB_MAX_DOF) return mpb_failf(MPB_E_UNSUPPORTED, "%s: D = %d exceeds MPB_MAX_DOF = %d", __func__, D, MPB_MAX_DOF);
+    if (N < 0 || S < 0 || D < 1 || (long long)N * (long long)S > INT_MAX - 64) return mpb_failf(MPB_E_INVALID, "%s: bad shape", __func__);
+    if (n_iters < 0 || n_iters > MPB_IK_MAX_ITERS)
+        return mpb_failf(MPB_E_INVALID, "%s: n_iters = %d outside 0..%d", __func__, n_iters, MPB_IK_MAX_ITERS);
+    // (written so that a NaN is refused)
+    if (!(damping >= MPB_IK_MIN_DAMPING)) return mpb_failf(MPB_E_INVALID, "%s: damping = %g below %g", __func__, (double)damping, (double)MPB_IK_MIN_DAMPING);
+    if (!(pos_tol >= 0.f) || !(rot_tol >= 0.f)) return mpb_failf(MPB_E_INVALID, "%s: negative tolerance", __func__);
+    if (N == 0 || S == 0) return MPB_OK;
+    if (!target || !q_seed || !geom || !q_out || !pos_err || !rot_err || !converged || !iters_used || (q_min == nullptr) != (q_max == nullptr))
+        return mpb_failf(MPB_E_INVALID, "%s: null pointer (q_min and q_max: both or neither)", __func__);
+    if (mpb_misaligned16(geom)) return mpb_failf(MPB_E_INVALID, "%s: geom must be 16-byte aligned", __func__);
+    const int rc = ik_chain_check(geom, D, __func__);
+    if (rc) return rc;
+    const int total = N * S;
+    if (position_only)
+        hipLaunchKernelGGL(ik_solve_kernel<true>, dim3((total + 63) / 64), dim3(64), 0, (hipStream_t)stream, target, q_seed, geom, q_min, q_max, q_out,
+                           pos_err, rot_err, converged, iters_used, total, S, D, n_iters, damping, pos_tol, rot_tol);
+    else
+        hipLaunchKernelGGL(ik_solve_kernel<false>, dim3((total + 63) / 64), dim3(64), 0, (hipStream_t)stream, target, q_seed, geom, q_min, q_max, q_out,
+                           pos_err, rot_err, converged, iters_used, total, S, D, n_iters, damping, pos_tol, rot_tol);
+    return mpb_check_launch(__func__);
+}

@@ -13,7 +13,7 @@ import numpy as np
 import torch
 
 from . import _lib, rrt_layout
-from .geometry import MAX_FIELDS, CollisionField, count_fields, occupancy_bytes, pack_geometry, pack_sdf_grid, pack_self_collision
+from .geometry import KIND_CHAIN, MAX_FIELDS, CollisionField, count_fields, occupancy_bytes, pack_geometry, pack_sdf_grid, pack_self_collision
 from .geometry import header as geometry_header
 
 
@@ -105,7 +105,7 @@ class DeviceGeometry:
         self.flags = _lib.geom_flags(host)
         self.host = host
         hdr = geometry_header(host)
-        self.n_dof, self.n_links = int(hdr['n_dof']), int(hdr['n_links'])
+        self.n_dof, self.n_links, self.kind = int(hdr['n_dof']), int(hdr['n_links']), int(hdr['kind'])
         self.n_fields = count_fields(host)
         self.buf = torch.from_numpy(host.copy()).to(device)
 
@@ -1276,6 +1276,68 @@ def collision_check(q, geom, with_gap=False):
     _lib.check(_lib.lib().mpb_collision_check(_ptr(q), _ptr(geom.buf), int(geom.flags), _ptr(flag), _ptr(gap), N, D, _stream()),
                'mpb_collision_check')
     return (flag, gap) if with_gap else flag
+
+
+# ---- end effector: pose, Jacobian, batched inverse kinematics (csrc/mpb_ik.hip) ----------------------------------------------------
+IK_MAX_ITERS, IK_MIN_DAMPING = 1024, 1e-2          # include/mpb.h MPB_IK_MAX_ITERS, MPB_IK_MIN_DAMPING
+
+
+def _need_chain(geom, what):
+    if geom.kind != KIND_CHAIN:
+        raise ValueError(f'{what}: a point robot has no end effector (serial chains only)')
+
+
+@_on_tensor_device
+def fk_ee_pose(q, geom, with_jacobian=False):
+    """(N, D) configurations -> the end-effector pose (N, 3, 4) = [R | t], the last frame of the chain walk; with_jacobian also
+    returns the geometric Jacobian (N, 6, D): rows 0-2 z_j x (t - p_j), rows 3-5 z_j (mpb_fk_ee_pose)."""
+    if q.dim() != 2:
+        raise ValueError(f'q has shape {tuple(q.shape)}, expected (N, D)')
+    N, D = q.shape
+    _chk(q, (N, D), 'q')
+    _need_chain(geom, 'fk_ee_pose')
+    if D != geom.n_dof:
+        raise ValueError(f'q has {D} columns, the geometry {geom.n_dof} degrees of freedom')
+    pose = torch.empty(N, 3, 4, device=q.device, dtype=torch.float32)
+    jac = torch.empty(N, 6, D, device=q.device, dtype=torch.float32) if with_jacobian else None
+    _lib.check(_lib.lib().mpb_fk_ee_pose(_ptr(q), _ptr(geom.buf), _ptr(pose), _ptr(jac), N, D, _stream()), 'mpb_fk_ee_pose')
+    return (pose, jac) if with_jacobian else pose
+
+
+@_on_tensor_device
+def ik_solve(target, q_seed, geom, q_min=None, q_max=None, n_iters=64, damping=0.1, pos_tol=1e-3, rot_tol=1e-2, position_only=False):
+    """Damped-least-squares inverse kinematics of N targets from S seeds each (mpb_ik_solve): target (N, 3, 4) = [R* | t*], q_seed
+    (N, S, D), q_min / q_max (D,) both or neither -> q (N, S, D), pos_err (N, S), rot_err (N, S), converged bool (N, S), iters int32
+    (N, S), all at the returned q.  A fixed budget of n_iters steps per problem; a converged problem is frozen."""
+    if q_seed.dim() != 3:
+        raise ValueError(f'q_seed has shape {tuple(q_seed.shape)}, expected (N, S, D)')
+    N, S, D = q_seed.shape
+    _chk(q_seed, (N, S, D), 'q_seed')
+    _chk(target, (N, 3, 4), 'target')
+    _need_chain(geom, 'ik_solve')
+    if D != geom.n_dof:
+        raise ValueError(f'q_seed has {D} columns, the geometry {geom.n_dof} degrees of freedom')
+    if (q_min is None) != (q_max is None):
+        raise ValueError('q_min and q_max: both or neither')
+    _chk(q_min, (D,), 'q_min', allow_none=True)
+    _chk(q_max, (D,), 'q_max', allow_none=True)
+    n_iters, damping, pos_tol, rot_tol = int(n_iters), float(damping), float(pos_tol), float(rot_tol)
+    if not 0 <= n_iters <= IK_MAX_ITERS:
+        raise ValueError(f'n_iters = {n_iters} outside 0..{IK_MAX_ITERS}')
+    if not damping >= IK_MIN_DAMPING:
+        raise ValueError(f'damping = {damping} below {IK_MIN_DAMPING}: the unpivoted fp32 Cholesky needs the floor')
+    if not (pos_tol >= 0.0 and rot_tol >= 0.0):
+        raise ValueError('pos_tol and rot_tol must not be negative')
+    dev = q_seed.device
+    q = torch.empty(N, S, D, device=dev, dtype=torch.float32)
+    pos_err = torch.empty(N, S, device=dev, dtype=torch.float32)
+    rot_err = torch.empty(N, S, device=dev, dtype=torch.float32)
+    conv = torch.empty(N, S, device=dev, dtype=torch.bool)
+    iters = torch.empty(N, S, device=dev, dtype=torch.int32)
+    _lib.check(_lib.lib().mpb_ik_solve(_ptr(target), _ptr(q_seed), _ptr(geom.buf), _ptr(q_min), _ptr(q_max), _ptr(q), _ptr(pos_err),
+                                       _ptr(rot_err), _ptr(conv), _ptr(iters), N, S, D, n_iters, damping, pos_tol, rot_tol,
+                                       1 if position_only else 0, _stream()), 'mpb_ik_solve')
+    return q, pos_err, rot_err, conv, iters
 
 
 @_on_tensor_device

@@ -46,6 +46,32 @@ class _FieldCost(torch.autograd.Function):
         return ops.field_cost_points_vjp(p4, ctx.geom, g).reshape(ctx.p_shape), None
 
 
+class _EEPose(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, q, geom):
+        q2 = q.reshape(-1, q.shape[-1]).to(torch.float32).contiguous()
+        pose, jac = ops.fk_ee_pose(q2, geom, with_jacobian=True)
+        ctx.save_for_backward(pose, jac)
+        ctx.q_shape = q.shape
+        return pose.reshape(*q.shape[:-1], 3, 4)
+
+    @staticmethod
+    def backward(ctx, grad_pose):
+        pose, jac = ctx.saved_tensors
+        g = grad_pose.reshape(-1, 3, 4).to(torch.float32)
+        # d t / d q_j = Jv_j; d R[:, c] / d q_j = z_j x R[:, c], so  grad_q_j = Jv_j . G_t + z_j . sum_c (R[:, c] x G_R[:, c])
+        m = torch.linalg.cross(pose[:, :, :3], g[:, :, :3], dim=1).sum(-1)                    # (N, 3)
+        gq = torch.einsum('nkj,nk->nj', jac[:, :3], g[:, :, 3]) + torch.einsum('nkj,nk->nj', jac[:, 3:], m)
+        return gq.reshape(ctx.q_shape), None
+
+
+def ee_pose(q, geom):
+    """(..., D) configurations -> the end-effector pose (..., 3, 4) = [R | t] of an ops.DeviceGeometry's chain (mpb_fk_ee_pose),
+    differentiable w.r.t. q: the backward is formed in torch from the kernel's own Jacobian.  An end-effector cost can thus be a
+    caller-supplied cost of CHOMP or a member of an MPPI cost."""
+    return _EEPose.apply(q, geom)
+
+
 class DeviceRobot:
     """robot API of the reference's cost layer, evaluated on the GPU."""
 
@@ -65,6 +91,15 @@ class DeviceRobot:
     def fk_map_collision(self, q_pos, **kwargs):
         """(..., H, >=q_dim) joint positions -> (..., H, L, 3) collision-sphere positions (differentiable)."""
         return _FKPoints.apply(q_pos, self._geom)
+
+    def get_EE_pose(self, q):
+        """(..., >=q_dim) joint positions -> (..., 3, 4) end-effector pose [R | t] (differentiable); leading dimensions are kept."""
+        return ee_pose(q[..., :self.q_dim], self._geom)
+
+    def get_EE_position(self, q):
+        """(..., >=q_dim) joint positions -> (..., 3) end-effector position (differentiable): the reference's robot.get_EE_position
+        (panda_spheres_GPMP.py:63-64)."""
+        return self.get_EE_pose(q)[..., :, 3]
 
 
 class DeviceField:
@@ -140,7 +175,11 @@ class PlanningTask:
     it.
 
     sdf_field: a geometry.GridSDFField (a precomputed grid of signed distances: geometry the obstacle list cannot hold).  Its predicate
-    (mpb_sdf_grid_collision_check with or_into) is ORed in the same way, and the same callers refuse such a task by name."""
+    (mpb_sdf_grid_collision_check with or_into) is ORed in the same way, and the same callers refuse such a task by name.
+
+    End-effector goals (serial chains): get_EE_pose / get_EE_position (the reference's robot.get_EE_position,
+    panda_spheres_GPMP.py:63-64) and inverse_kinematics -- a pose in, many goal configurations out, filtered by the predicates above
+    (mpb_fk_ee_pose, mpb_ik_solve)."""
 
     def __init__(self, robot, field, self_field=None, tensor_args=None, seed=0, sdf_field=None):
         from .planners.base import require_cuda
@@ -207,6 +246,54 @@ class PlanningTask:
     def distance_q(self, q1, q2):
         return torch.linalg.norm(q1 - q2, dim=-1)
 
+    # ---- end-effector goals (build-defined: DESIGN.md 10) ---------------------------------------------------------------------
+    def get_EE_pose(self, q):
+        """(..., D) configurations -> (..., 3, 4) end-effector pose [R | t] (differentiable, robot_field.ee_pose)."""
+        return ee_pose(torch.as_tensor(q, dtype=torch.float32, device=self.device), self.geom)
+
+    def get_EE_position(self, q):
+        """(..., D) configurations -> (..., 3) end-effector position."""
+        return self.get_EE_pose(q)[..., :, 3]
+
+    def inverse_kinematics(self, ee_pose, n_seeds=32, n_iters=64, damping=0.1, pos_tol=1e-3, rot_tol=1e-2, position_only=False,
+                           q_seed=None, q_ref=None, collision_free=True):
+        """Goal configurations for end-effector targets: damped-least-squares IK from many seeds per target (mpb_ik_solve, within
+        the joint limits), then the task's own collision predicate on every solution.
+        ee_pose: (N, 3, 4) = [R* | t*], or (N, 3) positions with position_only.  Seeds: q_seed (N, S, D) when given, else n_seeds per
+        target from random_q (the task's generator: reproducible per `seed`); with q_ref (D,) or (N, D), seed 0 of every target is
+        q_ref.  collision_free=False skips the predicate (free = converged).  Returns an IKResult."""
+        t = torch.as_tensor(ee_pose, dtype=torch.float32, device=self.device)
+        if position_only and t.dim() == 2 and t.shape[-1] == 3:
+            eye = torch.eye(3, device=self.device, dtype=torch.float32).expand(t.shape[0], 3, 3)
+            t = torch.cat([eye, t[:, :, None]], -1)
+        if t.dim() != 3 or tuple(t.shape[1:]) != (3, 4):
+            raise ValueError(f'ee_pose has shape {tuple(t.shape)}, expected (N, 3, 4)' + (' or (N, 3)' if position_only else ''))
+        N, D = t.shape[0], self.q_dim
+        if q_seed is None:
+            S = int(n_seeds)
+            if S < 1:
+                raise ValueError(f'n_seeds = {n_seeds}: at least one seed per target')
+            seeds = self.random_q(N * S).reshape(N, S, D)
+        else:
+            seeds = torch.as_tensor(q_seed, dtype=torch.float32, device=self.device).clone()
+            if seeds.dim() != 3 or seeds.shape[0] != N or seeds.shape[2] != D:
+                raise ValueError(f'q_seed has shape {tuple(seeds.shape)}, expected ({N}, S, {D})')
+        if q_ref is not None:
+            q_ref = torch.as_tensor(q_ref, dtype=torch.float32, device=self.device)
+            if tuple(q_ref.shape) not in ((D,), (N, D)):
+                raise ValueError(f'q_ref has shape {tuple(q_ref.shape)}, expected ({D},) or ({N}, {D})')
+            q_ref = q_ref.expand(N, D).contiguous()
+            if seeds.shape[1] > 0:
+                seeds[:, 0] = q_ref
+        q, pos_err, rot_err, conv, iters = ops.ik_solve(t.contiguous(), seeds.contiguous(), self.geom, q_min=self.q_min.contiguous(),
+                                                        q_max=self.q_max.contiguous(), n_iters=n_iters, damping=damping, pos_tol=pos_tol,
+                                                        rot_tol=rot_tol, position_only=position_only)
+        free = conv.clone()
+        if collision_free and q.numel():
+            free &= ~self._in_collision(q.reshape(-1, D)).reshape(conv.shape)
+        return IKResult(q, conv, free, pos_err, rot_err, iters, q_ref)
+
+
     # ---- validation of a trajectory batch (build-defined like the predicate: DESIGN.md 10) -----------------------------------
     def _trajs_stats(self, trajs, num_interpolation, with_flags=False):
         """trajs (..., H, W), W >= q_dim, leading dimensions flattened -> (trajs (N, H, W), the outputs of
@@ -249,3 +336,26 @@ class PlanningTask:
         """1 if any trajectory is free of collisions, else 0."""
         _, (count, _, _) = self._trajs_stats(trajs, kwargs.get('num_interpolation', 5))
         return 1 if bool((count == 0).any()) else 0
+
+
+class IKResult:
+    """What PlanningTask.inverse_kinematics returns: q (N, S, D), converged / free bool (N, S) (free = converged and not in collision
+    by the task's predicates), pos_err / rot_err (N, S) at q, iters int32 (N, S) steps taken."""
+
+    def __init__(self, q, converged, free, pos_err, rot_err, iters, q_ref=None):
+        self.q, self.converged, self.free, self.pos_err, self.rot_err, self.iters, self.q_ref = q, converged, free, pos_err, rot_err, iters, q_ref
+
+    def select(self, k=1):
+        """(q (N, k, D), valid bool (N, k)): per target its first k free solutions -- ordered by distance to q_ref when one was given
+        (stable: ties by seed index), otherwise by seed index; rows beyond a target's free solutions are invalid (and hold the
+        solutions that follow in that order)."""
+        N, S, D = self.q.shape
+        k = int(k)
+        if not 1 <= k <= S:
+            raise ValueError(f'k = {k} outside 1..{S}')
+        order = torch.arange(S, device=self.q.device).expand(N, S)
+        if self.q_ref is not None:
+            order = torch.argsort(torch.linalg.norm(self.q - self.q_ref[:, None, :], dim=-1), dim=1, stable=True)
+        free = torch.gather(self.free, 1, order)
+        pick = torch.gather(order, 1, torch.argsort((~free).to(torch.uint8), dim=1, stable=True)[:, :k])      # free ones first, order kept
+        return torch.gather(self.q, 1, pick[:, :, None].expand(N, k, D)), torch.gather(self.free, 1, pick)
