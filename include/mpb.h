@@ -70,7 +70,8 @@ extern "C" {
  *                        (mpb_self_check, mpb_self_invalidate, mpb_self_collision_eval / _grad / _check).  So was the SDF-grid
  *                        field (mpb_sdf_grid_check, _invalidate, _build, _sample, _eval, _grad, _collision_check), and its build from
  *                        occupancy voxels (mpb_sdf_grid_build_occupancy).  So were the end-effector pose and batched inverse
- *                        kinematics (mpb_fk_ee_pose, mpb_ik_solve): additive. */
+ *                        kinematics (mpb_fk_ee_pose, mpb_ik_solve): additive.  So was the
+ *                        end-effector pose cost (mpb_ee_cost_eval, mpb_ee_cost_grad). */
 #define MPB_ABI_VERSION 7
 #define MPB_VERSION_TUNING_BUILD 0x40000000
 int mpb_version(void);
@@ -761,6 +762,44 @@ int mpb_fk_ee_pose(const float *q, const float *geom, float *pose, float *jac, i
 int mpb_ik_solve(const float *target, const float *q_seed, const float *geom, const float *q_min, const float *q_max,
                  float *q_out, float *pos_err, float *rot_err, unsigned char *converged, int *iters_used,
                  int N, int S, int D, int n_iters, float damping, float pos_tol, float rot_tol, int position_only, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * End-effector pose cost of a trajectory batch and its gradient (build-defined): the task-space term of the planners --
+ * arrive at a pose, follow a Cartesian path, keep a tool axis (the cup upright) along the way.  Serial chains only; geom as for
+ * mpb_fk_ee_pose (the first field's header and joint_tf alone, the header read back once per address, the kernels answer NaN when it has
+ * changed since).  Per waypoint h of the range [h_begin, h_end), (R, t) the pose mpb_fk_ee_pose returns for trajs[b, h, :D] -- the
+ * kernels walk the chain with the same routine and see those bits -- and [R* | t*] the waypoint's target:
+ *   position term (k_pos > 0):            e_p = t* - t,  c_p = |e_p|^2
+ *   rotation term, full (k_rot > 0, use_axis == 0):  e_w the rotation error of mpb_ik_solve above (E = R* R^T, w, c, theta = atan2(|w|,
+ *            c), e_w = (theta / |w|) w, plain w below |w| = 1e-6),  c_r = |e_w|^2
+ *   rotation term about one free tool axis (k_rot > 0, use_axis != 0): a = (ax, ay, az) a unit vector of the TOOL frame, u = R a,
+ *            u* = R* a,  c_a = |u - u*|^2: the rotation about a is free, the cost is smooth everywhere
+ *   c_h = k_pos c_p + k_rot (c_r or c_a);   out[b] (+)= weight * sum_{h_begin <= h < h_end} c_h
+ *   gradient, DEFINED by the closed forms through J = (J_v; J_w) of mpb_fk_ee_pose:  d c_p / dq = -2 J_v^T e_p,
+ *            d c_r / dq = -2 J_w^T e_w,  d c_a / dq = -2 J_w^T (u x u*).  The first and the last are exact derivatives; the second is
+ *            the exact derivative of theta^2 for orthonormal R, R*, and theta = pi is a cut locus of c_r (a kink, like a hinge's edge).
+ * A term with k = 0 is off; k = 1 / sigma^2 is the caller's.
+ * target: ONE base pointer to poses of 12 words (row-major 3 x 4, as mpb_fk_ee_pose writes them); trajectory b at waypoint h reads pose
+ *   (b / group) * stride_g + h * stride_h (strides in poses; either may be 0): one pose for all (0, 0), one per goal (1, 0; group =
+ *   B / G trajectories per goal), one per waypoint (0, 1), both (H, 1).  The caller guarantees the poses those indices reach.
+ * per_waypoint (B, H) optional: c_h, un-scaled by weight, 0 outside the range.  grad (B, H, d) (+)= d out[b] / d trajs[b]: without
+ *   accumulate EVERY element is written (velocity channels D .. d-1 and rows outside the range 0); with accumulate the fresh value is
+ *   added in ONE fp32 rounding onto out and onto the position channels of the range's rows, and nothing else is touched.
+ * Two launch forms, chosen by the shape alone: a range of more than one waypoint runs one wave per trajectory, one lane per waypoint,
+ *   trips of 64 (a lane sums its trips in ascending order, then a fixed-order wave reduction); a range of exactly one waypoint runs one
+ *   lane per trajectory.  No LDS, no atomics: the same bits on every run.
+ * Refusals, in this order, the first nine before any HIP call: D > MPB_MAX_DOF or d > 2 MPB_MAX_DOF: MPB_E_UNSUPPORTED; B < 0, H < 1,
+ * D < 1, 64 H d beyond an int; d < D; a range outside 0 <= h_begin < h_end <= H; group < 1 or not dividing B; a negative stride; k_pos or
+ * k_rot negative, NaN or infinite; both 0; use_axis with k_rot == 0 or with an axis whose length is not 1 within 1e-3: MPB_E_INVALID;
+ * (B == 0: MPB_OK, nothing launched;) a null required pointer, geom not 16-byte aligned: MPB_E_INVALID; then what only the header
+ * tells, as for mpb_fk_ee_pose: bad magic / version: MPB_E_INVALID; a point robot: MPB_E_UNSUPPORTED; D != n_dof: MPB_E_INVALID.
+ * ------------------------------------------------------------------------------------------- */
+int mpb_ee_cost_eval(const float *trajs, const float *geom, const float *target, float *out, float *per_waypoint,
+                     int B, int H, int d, int D, int h_begin, int h_end, int group, int stride_g, int stride_h,
+                     float k_pos, float k_rot, int use_axis, float ax, float ay, float az, float weight, int accumulate, void *stream);
+int mpb_ee_cost_grad(const float *trajs, const float *geom, const float *target, float *out, float *grad,
+                     int B, int H, int d, int D, int h_begin, int h_end, int group, int stride_g, int stride_h,
+                     float k_pos, float k_rot, int use_axis, float ax, float ay, float az, float weight, int accumulate, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Batched RRT-Connect -- replaces RRTConnect._run_optimization (rrt_connect.py:93-192) with RRTBase.get_pre_sample /

@@ -1340,6 +1340,81 @@ def ik_solve(target, q_seed, geom, q_min=None, q_max=None, n_iters=64, damping=0
     return q, pos_err, rot_err, conv, iters
 
 
+def _ee_cost_args(trajs, geom, target, k_pos, k_rot, axis, h_begin, h_end, target_per_waypoint, what):
+    """The checks ee_cost_eval / ee_cost_grad share -> the C arguments after the pointers: (B, H, d, D, h_begin, h_end, group, stride_g,
+    stride_h, k_pos, k_rot, use_axis, ax, ay, az)."""
+    if trajs.dim() != 3:
+        raise ValueError(f'trajs has shape {tuple(trajs.shape)}, expected (B, H, d)')
+    B, H, d = trajs.shape
+    _chk(trajs, (B, H, d), 'trajs')
+    _need_chain(geom, what)
+    D = geom.n_dof
+    if d < D:
+        raise ValueError(f'trajs has {d} columns, the chain {D} degrees of freedom')
+    h_end = H if h_end is None else int(h_end)
+    h_begin = int(h_begin)
+    if not 0 <= h_begin < h_end <= H:
+        raise ValueError(f'bad range [{h_begin}, {h_end}) of H = {H} waypoints')
+    per = (H, 3, 4) if target_per_waypoint else (3, 4)
+    if target is None or target.dim() not in (len(per), len(per) + 1) or tuple(target.shape[-len(per):]) != per:
+        raise ValueError(f'target has shape {None if target is None else tuple(target.shape)}, expected {per} or (G,) + {per}')
+    G = target.shape[0] if target.dim() == len(per) + 1 else 1
+    _chk(target, target.shape, 'target')
+    if G < 1 or B % G != 0:
+        raise ValueError(f'{G} targets do not divide the batch of {B} trajectories')
+    k_pos, k_rot = float(k_pos), float(k_rot)
+    if not (0.0 <= k_pos < math.inf and 0.0 <= k_rot < math.inf):
+        raise ValueError('k_pos and k_rot must be finite and not negative')
+    if k_pos == 0.0 and k_rot == 0.0:
+        raise ValueError('both terms are off (k_pos = k_rot = 0)')
+    a = (0.0, 0.0, 0.0)
+    if axis is not None:
+        a = tuple(float(x) for x in np.asarray(axis, dtype=np.float64).reshape(-1))
+        if len(a) != 3 or not abs(math.sqrt(sum(x * x for x in a)) - 1.0) <= 1e-3:
+            raise ValueError(f'axis {a} is not a unit 3-vector (within 1e-3)')
+        if k_rot == 0.0:
+            raise ValueError('an axis needs the rotation term (k_rot > 0)')
+    stride_h = 1 if target_per_waypoint else 0
+    stride_g = 0 if G == 1 else (H if target_per_waypoint else 1)
+    return (B, H, d, D, h_begin, h_end, max(B // G, 1), stride_g, stride_h, k_pos, k_rot, int(axis is not None)) + a
+
+
+@_on_tensor_device
+def ee_cost_eval(trajs, geom, target, k_pos=0.0, k_rot=0.0, axis=None, weight=1.0, h_begin=1, h_end=None, target_per_waypoint=False,
+                 per_waypoint=False, out=None, accumulate=False):
+    """trajs (B, H, d) -> out (B,) (+)= weight * sum_{h_begin <= h < h_end} c_h, the end-effector pose cost of a DeviceGeometry's chain
+    (mpb_ee_cost_eval; include/mpb.h has the definition): c_h = k_pos |t* - t|^2 + k_rot (|e_w|^2, or |R a - R* a|^2 with `axis` = a, a
+    unit vector of the tool frame).  target (3, 4) or (G, 3, 4) -- trajectory b reads target b // (B / G) --, with target_per_waypoint
+    (H, 3, 4) or (G, H, 3, 4).  per_waypoint also returns c (B, H), un-scaled by weight, 0 outside the range."""
+    args = _ee_cost_args(trajs, geom, target, k_pos, k_rot, axis, h_begin, h_end, target_per_waypoint, 'ee_cost_eval')
+    B, H = args[0], args[1]
+    out = _self_out(trajs, out, accumulate)
+    pw = torch.empty(B, H, device=trajs.device, dtype=torch.float32) if per_waypoint else None
+    _lib.check(_lib.lib().mpb_ee_cost_eval(_ptr(trajs), _ptr(geom.buf), _ptr(target), _ptr(out), _ptr(pw), *args, float(weight),
+                                          int(bool(accumulate)), _stream()), 'mpb_ee_cost_eval')
+    return (out, pw) if per_waypoint else out
+
+
+@_on_tensor_device
+def ee_cost_grad(trajs, geom, target, k_pos=0.0, k_rot=0.0, axis=None, weight=1.0, h_begin=1, h_end=None, target_per_waypoint=False,
+                 out=None, grad=None, accumulate=False):
+    """(out (B,), grad (B, H, d)) (+)= the end-effector pose cost and d out / d trajs by the closed forms through the geometric Jacobian
+    (mpb_ee_cost_grad); accumulate adds onto the given `out` AND onto the position channels of the range's rows of `grad` (nothing else
+    is touched), otherwise every element of both is written (velocity channels and rows outside the range 0)."""
+    args = _ee_cost_args(trajs, geom, target, k_pos, k_rot, axis, h_begin, h_end, target_per_waypoint, 'ee_cost_grad')
+    B, H, d = args[0], args[1], args[2]
+    if accumulate and grad is None:
+        raise ValueError('accumulate needs existing out and grad buffers')
+    out = _self_out(trajs, out, accumulate)
+    if grad is None:
+        grad = torch.empty_like(trajs)
+    else:
+        _chk(grad, (B, H, d), 'grad')
+    _lib.check(_lib.lib().mpb_ee_cost_grad(_ptr(trajs), _ptr(geom.buf), _ptr(target), _ptr(out), _ptr(grad), *args, float(weight),
+                                          int(bool(accumulate)), _stream()), 'mpb_ee_cost_grad')
+    return out, grad
+
+
 @_on_tensor_device
 def traj_collision_stats(trajs, geom, n_interp=5, with_flags=False):
     """(N, H, W) trajectories, W >= the geometry's degrees of freedom, read in place (the first D columns of a row are the

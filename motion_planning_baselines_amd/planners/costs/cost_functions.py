@@ -388,6 +388,186 @@ class CostGoal(Cost):
         return A, b, K
 
 
+class CostEEPose(Cost):
+    """End-effector pose cost (build-defined; kernels of its own: mpb_ee_cost_eval / _grad): over the waypoints h of
+    `traj_range`, with (R, t) the end-effector pose of q_h and [R* | t*] the target,
+
+        c_h = |t* - t|^2 / sigma_pos^2 + (|e_w|^2  or  |R a - R* a|^2) / sigma_rot^2,        cost = sum_h c_h
+
+    - sigma_pos given: the position term.  sigma_rot given: the rotation term -- e_w the rotation error of the inverse kinematics
+      (angle * axis of R* R^T), or, with `axis` = a (a unit vector of the TOOL frame), the distance of the world directions R a and R* a:
+      the rotation about a is free ("keep the cup upright"; `target_for_axis` builds such a target).  At least one sigma.
+    - traj_range: 'goal' (the last waypoint), 'path' (waypoints 1 .. H-1, the collision members' range) or (h_begin, h_end).
+    - target: (3, 4) for all, or (G, 3, 4), one per goal: trajectory b of a flat batch of B reads target b // (B / G) (the reshape of
+      CostGoalPrior.eval; B % G != 0 is a ValueError).  With target_per_waypoint (H, 3, 4) or (G, H, 3, 4): a Cartesian path to track.
+
+    The gradient is the closed form through the geometric Jacobian (include/mpb.h).  theta = pi is a cut locus of the full rotation
+    term; the axis term has none.  A member with kernels of its own (own_kernels), like the self-collision and SDF-grid members: never
+    fused, served by own_eval / own_grad on CHOMP's and STOMP's planned paths, by CostComposite.eval for MPPI, and by
+    get_linear_system as one of GPMP2's extra_costs.  CHOMP zeroes the gradient rows of both endpoints, so a 'goal' member does nothing
+    there: it acts wherever the last waypoint is free to move."""
+
+    own_kernels = True
+    is_self = False
+    is_grid = False
+
+    def __init__(self, robot, n_support_points, target, sigma_pos=None, sigma_rot=None, axis=None, traj_range='goal',
+                 target_per_waypoint=False, tensor_args=None, **kwargs):
+        super().__init__(robot, n_support_points, tensor_args=tensor_args, **kwargs)
+        from ...geometry import KIND_CHAIN
+        if getattr(robot, 'kind', None) != KIND_CHAIN:
+            raise ValueError('CostEEPose: a point robot has no end effector (serial chains only)')
+        if sigma_pos is None and sigma_rot is None:
+            raise ValueError('CostEEPose: give sigma_pos, sigma_rot or both')
+        for name, sg in (('sigma_pos', sigma_pos), ('sigma_rot', sigma_rot)):
+            if sg is not None and not (float(sg) > 0.0 and np.isfinite(float(sg))):
+                raise ValueError(f'CostEEPose: {name} must be positive and finite')
+        if axis is not None:
+            if sigma_rot is None:
+                raise ValueError('CostEEPose: an axis needs sigma_rot')
+            axis = tuple(float(x) for x in np.asarray(axis, dtype=np.float64).reshape(-1))
+            if len(axis) != 3 or not abs(float(np.linalg.norm(axis)) - 1.0) <= 1e-3:
+                raise ValueError(f'CostEEPose: axis {axis} is not a unit 3-vector (within 1e-3)')
+        H = int(n_support_points)
+        if isinstance(traj_range, str):
+            if traj_range not in ('goal', 'path'):
+                raise ValueError("CostEEPose: traj_range is 'goal', 'path' or (h_begin, h_end)")
+        else:
+            h0, h1 = (int(x) for x in traj_range)
+            if not 0 <= h0 < h1 <= H:
+                raise ValueError(f'CostEEPose: bad range [{h0}, {h1}) of {H} support points')
+            traj_range = (h0, h1)
+        target = torch.as_tensor(target)
+        per = (H, 3, 4) if target_per_waypoint else (3, 4)
+        if target.dim() not in (len(per), len(per) + 1) or tuple(target.shape[-len(per):]) != per:
+            raise ValueError(f'CostEEPose: target has shape {tuple(target.shape)}, expected {per} or (G,) + {per}')
+        self.target = target.detach().to(torch.float32)
+        self.num_goals = int(target.shape[0]) if target.dim() == len(per) + 1 else 1
+        self.sigma_pos, self.sigma_rot, self.axis = sigma_pos, sigma_rot, axis
+        self.traj_range, self.target_per_waypoint = traj_range, bool(target_per_waypoint)
+        self._geom = None
+        self._target_dev = None
+
+    @property
+    def k_pos(self):
+        return 0.0 if self.sigma_pos is None else 1.0 / float(self.sigma_pos) ** 2
+
+    @property
+    def k_rot(self):
+        return 0.0 if self.sigma_rot is None else 1.0 / float(self.sigma_rot) ** 2
+
+    @staticmethod
+    def target_for_axis(axis, direction, position=(0.0, 0.0, 0.0)):
+        """A target (3, 4) = [R* | position] whose R* takes the tool axis `axis` to the world direction `direction` (R* a = d, the
+        smallest such rotation): the target of an `axis` member that keeps the tool axis pointing along d."""
+        a = np.asarray(axis, dtype=np.float64).reshape(3)
+        d = np.asarray(direction, dtype=np.float64).reshape(3)
+        a, d = a / np.linalg.norm(a), d / np.linalg.norm(d)
+        v, c = np.cross(a, d), float(a @ d)
+        if c < -1.0 + 1e-12:                                    # opposite: half a turn about any axis perpendicular to a
+            p = np.cross(a, np.eye(3)[int(np.argmin(np.abs(a)))])
+            p /= np.linalg.norm(p)
+            R = 2.0 * np.outer(p, p) - np.eye(3)
+        else:
+            V = np.array([[0.0, -v[2], v[1]], [v[2], 0.0, -v[0]], [-v[1], v[0], 0.0]])
+            R = np.eye(3) + V + V @ V / (1.0 + c)
+        return torch.as_tensor(np.concatenate([R, np.asarray(position, dtype=np.float64).reshape(3, 1)], 1), dtype=torch.float32)
+
+    def device_geometry(self, device):
+        """The chain on `device` (the end-effector kernels read the header and the joint transforms alone: the field is unused)."""
+        if self._geom is None or self._geom.buf.device != torch.device(device):
+            from ...geometry import CollisionField
+            far = CollisionField(spheres=np.array([[1.0e6, 1.0e6, 1.0e6, 1.0]], np.float32))
+            self._geom = ops.DeviceGeometry(self.robot, far, device)
+        return self._geom
+
+    def device_target(self, device):
+        if self._target_dev is None or self._target_dev.device != torch.device(device):
+            self._target_dev = self.target.to(device).contiguous()
+        return self._target_dev
+
+    def range_of(self, H):
+        """[h_begin, h_end) on trajectories of H waypoints."""
+        if self.traj_range == 'goal':
+            return H - 1, H
+        if self.traj_range == 'path':
+            return 1, H
+        return self.traj_range
+
+    def _kernel_kw(self, trajs, k_sigma, kw):
+        h0, h1 = self.range_of(trajs.shape[1])
+        kw = dict(kw)
+        kw.setdefault('h_begin', h0)
+        kw.setdefault('h_end', h1)
+        on = lambda k: k if (k_sigma is None or k == 0.0) else float(k_sigma)
+        return dict(k_pos=on(self.k_pos), k_rot=on(self.k_rot), axis=self.axis, target_per_waypoint=self.target_per_waypoint, **kw)
+
+    def own_eval(self, trajs, weight=1.0, k_sigma=None, **kw):
+        """ops.ee_cost_eval of this member on (B, H, d) trajectories, in the collision members' contract: h_begin, per_waypoint, out,
+        accumulate as that takes them (the range defaults to the member's); k_sigma replaces 1 / sigma^2 of every term that is on."""
+        return ops.ee_cost_eval(trajs, self.device_geometry(trajs.device), self.device_target(trajs.device), weight=weight,
+                                **self._kernel_kw(trajs, k_sigma, kw))
+
+    def own_grad(self, trajs, weight=1.0, k_sigma=None, **kw):
+        """ops.ee_cost_grad of this member: h_begin, out, grad, accumulate as that takes them."""
+        return ops.ee_cost_grad(trajs, self.device_geometry(trajs.device), self.device_target(trajs.device), weight=weight,
+                                **self._kernel_kw(trajs, k_sigma, kw))
+
+    def eval(self, trajs, **observation):
+        return self.own_eval(self._as_3d(trajs))
+
+    def eval_with_grad(self, trajs, weight=1.0):
+        """(cost (B,), d cost / d trajs (B, H, d))."""
+        return self.own_grad(self._as_3d(trajs), weight=weight)
+
+    def get_linear_system(self, trajs, **observation):
+        """Dense (A, b, K) in the reference's convention: per waypoint of the range one block of rows at that waypoint's position
+        columns -- three rows of the position term (A = J_v, b = e_p, K = I / sigma_pos^2), then three of the rotation term (full:
+        A = J_w, b = e_w; axis: A = -[u]x J_w, b = u* - u; K = I / sigma_rot^2) -- so that A = -d b / d q and A^T K b is minus half the
+        gradient.  For the full term the Jacobian of the rotation logarithm is dropped: J_r^{-T} e_w = e_w, the product stays exact.
+        The slow inspection path, like every dense route: mpb_fk_ee_pose with its Jacobian, the error in torch."""
+        trajs = self._as_3d(trajs)
+        B, H, d = trajs.shape
+        D = self.n_dof
+        h0, h1 = self.range_of(H)
+        n = h1 - h0
+        kw = dict(device=trajs.device, dtype=trajs.dtype)
+        q = trajs[:, h0:h1, :D].reshape(-1, D).to(torch.float32).contiguous()
+        pose, J = ops.fk_ee_pose(q, self.device_geometry(trajs.device), with_jacobian=True)
+        tgt = self.device_target(trajs.device)
+        if self.num_goals == 1:
+            tgt = tgt.unsqueeze(0)
+        if B % self.num_goals != 0:
+            raise ValueError(f'{self.num_goals} targets do not divide the batch of {B} trajectories')
+        tgt = tgt.repeat_interleave(B // self.num_goals, 0)                                       # (B, [H,] 3, 4)
+        tgt = (tgt[:, h0:h1] if self.target_per_waypoint else tgt.unsqueeze(1).expand(B, n, 3, 4)).reshape(-1, 3, 4).to(pose.dtype)
+        R, t, Rs, ts = pose[:, :, :3], pose[:, :, 3], tgt[:, :, :3], tgt[:, :, 3]
+        As, bs, ks = [], [], []
+        if self.sigma_pos is not None:
+            As.append(J[:, :3]); bs.append(ts - t); ks.append(self.k_pos)
+        if self.sigma_rot is not None and self.axis is None:
+            E = Rs @ R.transpose(1, 2)
+            w = 0.5 * torch.stack([E[:, 2, 1] - E[:, 1, 2], E[:, 0, 2] - E[:, 2, 0], E[:, 1, 0] - E[:, 0, 1]], -1)
+            c = 0.5 * (E[:, 0, 0] + E[:, 1, 1] + E[:, 2, 2] - 1.0)
+            nw = w.norm(dim=-1)
+            small = nw < 1e-6
+            sc = torch.where(small, torch.ones_like(nw), torch.atan2(nw, c) / torch.where(small, torch.ones_like(nw), nw))
+            As.append(J[:, 3:]); bs.append(sc[:, None] * w); ks.append(self.k_rot)
+        elif self.sigma_rot is not None:
+            a = torch.tensor(self.axis, device=trajs.device, dtype=pose.dtype)
+            u, us = R @ a, Rs @ a
+            As.append(-torch.linalg.cross(u[:, :, None].expand(-1, 3, D), J[:, 3:], dim=1)); bs.append(us - u); ks.append(self.k_rot)
+        m = 3 * len(As)
+        rows = torch.cat(As, 1).reshape(B, n, m, D).to(**kw)
+        A = torch.zeros(B, n * m, self.dim * H if d == self.dim else d * H, **kw)
+        for i in range(n):
+            A[:, i * m:(i + 1) * m, (h0 + i) * d:(h0 + i) * d + D] = rows[:, i]
+        b = torch.cat(bs, 1).reshape(B, n * m, 1).to(**kw)
+        kd = torch.cat([torch.full((3,), k, **kw) for k in ks]).repeat(n)
+        K = torch.diag(kd).repeat(B, 1, 1)
+        return A, b, K
+
+
 def _merge_term_specs(members):
     """Group (spec, weight) pairs into as few mpb_cost_terms_eval launches as possible: a member joins a
     group when none of its terms is already in it and the shared scalar dt agrees."""
@@ -430,7 +610,12 @@ class CostComposite(Cost):
         total = None
         term_members = []
         for cost, w in zip(self.cost_l, self.weight_cost_l):
-            if isinstance(cost, CostCollision):
+            if isinstance(cost, CostEEPose):              # (its range and per-waypoint targets are those of the support points)
+                if torch.is_tensor(total) and total.ndim == 1 and total.is_contiguous() and total.dtype == torch.float32:
+                    cost.own_eval(trajs, weight=w, out=total, accumulate=True)
+                    continue
+                c = cost.own_eval(trajs, weight=w)
+            elif isinstance(cost, CostCollision):
                 if cost.field is None:
                     continue
                 if cost.own_kernels:
@@ -457,9 +642,11 @@ class CostComposite(Cost):
     def device_plan(self, device):
         """How a planner kernel pipeline can serve this composite without leaving the device:
         (collision members [(CostCollision, weight)], merged term specs, other members [(cost, weight)]).  Members with kernels
-        of their own (self-collision, SDF grid) are in none of the three: own_terms() lists them."""
+        of their own (self-collision, SDF grid, end-effector pose) are in none of the three: own_terms() lists them."""
         coll, terms, other = [], [], []
         for cost, w in zip(self.cost_l, self.weight_cost_l):
+            if isinstance(cost, CostEEPose):
+                continue
             if isinstance(cost, CostCollision):
                 if cost.field is not None and not cost.own_kernels:
                     coll.append((cost, float(w)))
@@ -498,9 +685,9 @@ class CostComposite(Cost):
                 if isinstance(c, CostCollision) and c.field is not None and not c.own_kernels]
 
     def own_terms(self):
-        """[(CostCollision, weight)] of the members with kernels of their own (a SelfCollisionField or a GridSDFField), in composite
-        order."""
-        return [(c, float(w)) for c, w in zip(self.cost_l, self.weight_cost_l) if isinstance(c, CostCollision) and c.own_kernels]
+        """[(member, weight)] of the members with kernels of their own (a CostCollision over a SelfCollisionField or a GridSDFField, a
+        CostEEPose), in composite order."""
+        return [(c, float(w)) for c, w in zip(self.cost_l, self.weight_cost_l) if isinstance(c, (CostCollision, CostEEPose)) and c.own_kernels]
 
     def self_terms(self):
         """[(CostCollision, weight)] of the members whose field is a SelfCollisionField."""
@@ -562,7 +749,7 @@ def fusable_collision(cost):
 
 class DevicePlan(tuple):
     """(collision evaluator or None, its weight, merged trajectory-term specs) -- unpacks as those three -- plus `.own`, the
-    members with kernels of their own [(CostCollision, weight)] (self-collision and SDF-grid fields) that a planner serves with
+    members with kernels of their own [(member, weight)] (self-collision and SDF-grid fields, end-effector pose costs) that a planner serves with
     member.own_eval / member.own_grad accumulating onto the obstacle member's outputs; `.selfs` is the self-collision part of it."""
 
     def __new__(cls, cc, weight, groups, own=()):
@@ -574,8 +761,8 @@ class DevicePlan(tuple):
 
 def device_plan(cost, device):
     """DevicePlan (collision evaluator or None, its weight, merged trajectory-term specs; .selfs) when every member of `cost`
-    is served by the HIP library (collision fields -- up to four, chained --, self-collision and SDF-grid fields and trajectory-only
-    terms): the case a planner can run as sample kernel -> own / term kernels -> update kernel with no host round trip; None otherwise."""
+    is served by the HIP library (collision fields -- up to four, chained --, self-collision and SDF-grid fields, end-effector pose costs
+    and trajectory-only terms): the case a planner can run as sample kernel -> own / term kernels -> update kernel with no host round trip; None otherwise."""
     if isinstance(cost, CostComposite):
         key = ('plan', str(device)) + tuple((id(c), float(w)) for c, w in zip(cost.cost_l, cost.weight_cost_l))
         cached = cost.__dict__.get('_plan_cache')
@@ -594,6 +781,8 @@ def device_plan(cost, device):
         if cost.field is None:
             return None
         return DevicePlan(None, 0.0, [], [(cost, 1.0)]) if cost.own_kernels else DevicePlan(cost, 1.0, [])
+    if isinstance(cost, CostEEPose):
+        return DevicePlan(None, 0.0, [], [(cost, 1.0)])
     if isinstance(cost, _TrajectoryTermCost):
         return DevicePlan(None, 0.0, _merge_term_specs([(cost.term_spec(device), 1.0)]))
     return None
