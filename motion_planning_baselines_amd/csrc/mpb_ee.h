@@ -3,8 +3,6 @@
 // upper half, and the launchers' cached read of a device buffer's header.  Every kernel that walks through ee_walk sees the bits
 // mpb_fk_ee_pose returns.
 #pragma once
-#include <mutex>
-
 #include "mpb_common.h"
 #include "mpb_geom.h"
 #include "mpb_host.h"
@@ -47,42 +45,24 @@ __device__ __forceinline__ void ee_jv(const FKState<true>& F, int D, float& cx, 
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------------
-// kind / n_dof of a DEVICE geometry buffer's first header: read once per buffer address and device -- a 128-byte synchronous copy -- and
-// kept in a small table, as mpb_sdf_grid.hip does -- ONE table for the translation units that include this header (inline variables).  An entry that does not agree with the caller's D is read again before the call is
-// refused (the address may hold another robot by now); one that agrees although the buffer changed is caught by the kernels, which compare
-// the header with the D they were launched with and answer NaN.
+// kind / n_dof of a device geometry buffer's first header, through the cache of mpb_host.h (its contract is stated there) -- ONE table for
+// the translation units that include this header (an inline variable).  A geometry buffer has no invalidate: an entry that does not agree
+// with the caller's D is read again, in place, before the call is refused (the address may hold another robot by now).
 struct IkShape { const void* ptr; int dev, kind, n_dof; };
-inline std::mutex g_ik_mu;
-inline IkShape g_ik_table[16];
-inline int g_ik_n = 0, g_ik_next = 0;
-
-inline int ik_shape(const float* geom, int D, IkShape& out, const char* who) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return mpb_failf(MPB_E_HIP, "%s: hipGetDevice failed", who);
-    std::lock_guard<std::mutex> lock(g_ik_mu);
-    int slot = -1;
-    for (int i = 0; i < g_ik_n; ++i)
-        if (g_ik_table[i].ptr == geom && g_ik_table[i].dev == dev) slot = i;
-    if (slot >= 0 && g_ik_table[slot].kind == MPB_KIND_CHAIN && g_ik_table[slot].n_dof == D) { out = g_ik_table[slot]; return MPB_OK; }
-    int32_t hdr[MPB_GEOM_HEADER_WORDS];
-    const hipError_t e = hipMemcpy(hdr, geom, sizeof(hdr), hipMemcpyDeviceToHost);
-    if (e != hipSuccess) return mpb_failf(MPB_E_HIP, "%s: reading the geometry header failed: %s", who, hipGetErrorString(e));
-    if (hdr[MPB_GW_MAGIC] != MPB_GEOM_MAGIC || (hdr[MPB_GW_VERSION] != MPB_GEOM_VERSION && hdr[MPB_GW_VERSION] != MPB_GEOM_VERSION_LIST))
-        return mpb_failf(MPB_E_INVALID, "%s: bad magic/version of the geometry buffer", who);
-    out = {geom, dev, hdr[MPB_GW_KIND], hdr[MPB_GW_N_DOF]};
-    if (slot < 0) {
-        slot = g_ik_next;
-        g_ik_next = (g_ik_next + 1) % 16;
-        g_ik_n = g_ik_n < 16 ? g_ik_n + 1 : 16;
-    }
-    g_ik_table[slot] = out;
-    return MPB_OK;
-}
+inline MpbHeaderCache<IkShape, MPB_GEOM_HEADER_WORDS> g_ik_cache;
 
 // refusals 5 and 6 of include/mpb.h: what only the buffer's header tells
 inline int ik_chain_check(const float* geom, int D, const char* who) {
     IkShape S;
-    const int rc = ik_shape(geom, D, S, who);
+    const int rc = g_ik_cache.get(
+        geom, S, who, "geometry",
+        [who](const int32_t* hdr, IkShape& s) {
+            if (hdr[MPB_GW_MAGIC] != MPB_GEOM_MAGIC || (hdr[MPB_GW_VERSION] != MPB_GEOM_VERSION && hdr[MPB_GW_VERSION] != MPB_GEOM_VERSION_LIST))
+                return mpb_failf(MPB_E_INVALID, "%s: bad magic/version of the geometry buffer", who);
+            s.kind = hdr[MPB_GW_KIND], s.n_dof = hdr[MPB_GW_N_DOF];
+            return MPB_OK;
+        },
+        [D](const IkShape& s) { return s.kind == MPB_KIND_CHAIN && s.n_dof == D; });
     if (rc) return rc;
     if (S.kind != MPB_KIND_CHAIN) return mpb_failf(MPB_E_UNSUPPORTED, "%s: a point robot has no end effector", who);
     if (D != S.n_dof) return mpb_failf(MPB_E_INVALID, "%s: D = %d, the chain has %d joints", who, D, S.n_dof);

@@ -19,6 +19,7 @@
 #include <string.h>
 
 #include "mpb_ee.h"
+#include "mpb_member_cost.h"   // add_rounded
 
 #define MPB_EE_POS 0        // position term alone
 #define MPB_EE_ROT 1        // position (k_pos may be 0) + full rotation
@@ -35,12 +36,6 @@ struct EeCostArgs {
     float k_pos, k_rot, ax, ay, az, weight;
     int accumulate;
 };
-
-// a + b in one rounding whatever produced b (mpb_self_collision.hip says why)
-__device__ __forceinline__ float ee_add_rounded(float a, float b) {
-#pragma clang fp contract(off)
-    return a + b;
-}
 
 // c_h of one waypoint against the target pose T (12 words); GRAD: dq[j] = d c_h / d q_j (0 for j >= D)
 template <int TERMS, bool GRAD>
@@ -140,7 +135,7 @@ __global__ __launch_bounds__(64) void ee_cost_wave_kernel(const EeCostArgs A) {
                     for (int i = 0; i < MPB_MAX_DOF; ++i) {
                         if (i < Dl) {
                             const float g = ok ? A.weight * dq[i] : nan;
-                            grow[i] = A.accumulate ? ee_add_rounded(grow[i], g) : g;
+                            grow[i] = A.accumulate ? add_rounded(grow[i], g) : g;
                         }
                     }
                     if (!A.accumulate)
@@ -155,7 +150,7 @@ __global__ __launch_bounds__(64) void ee_cost_wave_kernel(const EeCostArgs A) {
     csum = wave_sum_f32(csum);
     if (lane == 0) {
         const float v = A.weight * csum;
-        A.out[b] = A.accumulate ? ee_add_rounded(A.out[b], v) : v;
+        A.out[b] = A.accumulate ? add_rounded(A.out[b], v) : v;
     }
 }
 
@@ -202,12 +197,12 @@ __global__ __launch_bounds__(64) void ee_cost_lane_kernel(const EeCostArgs A) {
         for (int i = 0; i < MPB_MAX_DOF; ++i) {
             if (i < A.D) {
                 const float g = ok ? A.weight * dq[i] : nan;
-                grow[i] = A.accumulate ? ee_add_rounded(grow[i], g) : g;
+                grow[i] = A.accumulate ? add_rounded(grow[i], g) : g;
             }
         }
     }
     const float v = A.weight * c;
-    A.out[b] = A.accumulate ? ee_add_rounded(A.out[b], v) : v;
+    A.out[b] = A.accumulate ? add_rounded(A.out[b], v) : v;
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------------

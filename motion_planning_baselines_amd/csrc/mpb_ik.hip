@@ -19,7 +19,7 @@
 //     joint loop of several hundred instructions each): a step is up to several radians long and multiplies their error.
 #include <limits.h>
 
-#include "mpb_ee.h"   // ik_chain_view, ik_header_matches, ee_walk, ee_jv and the launchers' ik_shape / ik_chain_check: shared with mpb_ee_cost.hip
+#include "mpb_ee.h"   // ik_chain_view, ik_header_matches, ee_walk, ee_jv and the launchers' ik_chain_check: shared with mpb_ee_cost.hip
 
 __global__ __launch_bounds__(64) void fk_ee_pose_kernel(const float* __restrict__ q_in, const float* __restrict__ geom, float* __restrict__ pose,
                                                         float* __restrict__ jac, int N, int D) {

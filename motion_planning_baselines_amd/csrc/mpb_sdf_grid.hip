@@ -19,11 +19,11 @@
 // Order of the sums: spheres in table order in fp32 per waypoint, a lane's waypoints in ascending order, then the fixed-order wave
 // reduction of mpb_common.h: every run gives the same bits.  Every node index is clamped into the grid whatever the input (NaN included).
 #include <algorithm>
-#include <mutex>
 
 #include "mpb_common.h"
 #include "mpb_host.h"
 #include "mpb_geom.h"
+#include "mpb_member_cost.h"
 #include "../../include/mpb_sdf_layout.h"
 
 #define MPB_SDF_GROUP 4
@@ -57,12 +57,6 @@ __device__ __forceinline__ SdfLattice sdf_lattice(const float* __restrict__ s, i
     S.inv = s[MPB_DW_INV_CELL];
     S.nodes = s + si[MPB_DW_OFF_NODES];
     return S;
-}
-
-// a + b in one rounding whatever produced b (mpb_self_collision.hip says why)
-__device__ __forceinline__ float sdf_add_rounded(float a, float b) {
-#pragma clang fp contract(off)
-    return a + b;
 }
 
 // one axis: cell index i0 in [0, n - 2], fraction f in [0, 1], inside = the point is not beyond the box on this axis (a NaN coordinate
@@ -164,9 +158,7 @@ __device__ __forceinline__ float sdf_waypoint_cost(const GeomView& G, const SdfL
                 const float4 lk = *reinterpret_cast<const float4*>(G.links + 8 * (l0 + i));   // frame, ox, oy, oz
                 const int f = min(__float_as_int(lk.x), G.n_tf);                         // (a checked buffer never clamps: keeps the walk inside tf)
                 while (F.frame < f) fk_advance<GRAD>(G, F, q);
-                x[i] = mad3(F.r00, lk.y, F.r01, lk.z, F.r02, lk.w, F.tx);
-                y[i] = mad3(F.r10, lk.y, F.r11, lk.z, F.r12, lk.w, F.ty);
-                z[i] = mad3(F.r20, lk.y, F.r21, lk.z, F.r22, lk.w, F.tz);
+                link_centre(F, lk, x[i], y[i], z[i]);
                 thr[i] = G.margin + G.links[8 * (l0 + i) + 4];
                 fr[i] = f;
             } else {                                                                   // parked slot: hinge 0 whatever the grid holds
@@ -244,7 +236,7 @@ __global__ __launch_bounds__(64) void sdf_cost_kernel(const float* __restrict__ 
                 for (int i = 0; i < MPB_MAX_DOF; ++i) {
                     if (i < D) {
                         const float g = ok ? (live ? sc * dq[i] : 0.f) : c;
-                        grow[i] = accumulate ? sdf_add_rounded(grow[i], g) : g;
+                        grow[i] = accumulate ? add_rounded(grow[i], g) : g;
                     }
                 }
                 if (!accumulate)
@@ -253,11 +245,7 @@ __global__ __launch_bounds__(64) void sdf_cost_kernel(const float* __restrict__ 
         }
         csum += c;
     }
-    csum = wave_sum_f32(csum);
-    if (lane == 0) {
-        const float v = weight * (k_sigma * csum);
-        out[b] = accumulate ? sdf_add_rounded(out[b], v) : v;
-    }
+    member_store_out(out, b, lane, csum, k_sigma, weight, accumulate);
 }
 
 __global__ __launch_bounds__(64) void sdf_check_kernel(const float* __restrict__ q_in, const float* __restrict__ sdfb,
@@ -272,10 +260,7 @@ __global__ __launch_bounds__(64) void sdf_check_kernel(const float* __restrict__
     for (int k = 0; k < MPB_MAX_DOF; ++k) q[k] = (have && k < D) ? q_in[i * D + k] : 0.f;
     float c = __uint_as_float(0x7FC00000u);
     if (sdf_header_matches(sdfb, D, L, nx, ny, nz)) c = sdf_waypoint_cost<false>(G, S, L, q, dq);
-    if (!have) return;
-    const bool hit = !(c <= 0.f);                              // (a refused buffer reads as in collision)
-    in_collision[i] = (hit || (or_into && in_collision[i] != 0)) ? 1 : 0;
-    if (gap) gap[i] = or_into ? sdf_add_rounded(gap[i], c) : c;
+    if (have) member_store_hit(in_collision, gap, i, c, or_into);
 }
 
 // the interpolant alone: one lane per point
@@ -452,38 +437,22 @@ extern "C" int mpb_sdf_grid_check(const float* s, int n_words) {
     return MPB_OK;
 }
 
-// What a launch needs of a DEVICE buffer's header: read once per buffer address and device -- a 128-byte synchronous copy on the first
-// call with that pointer -- and kept in a small table, as mpb_self_collision.hip does.  The kernels compare the header with the numbers
-// they were launched with, so an entry that outlived its buffer yields NaN outputs, never a node index outside the grid it was sized
-// for.  mpb_sdf_grid_invalidate drops the entry of an address that gets another buffer.
+// what a launch needs of a device buffer's header (every node index comes from the dims), through the cache of mpb_host.h (its contract
+// is stated there); mpb_sdf_grid_invalidate drops the entry of an address that gets another buffer
 struct SdfShape { const void* ptr; int dev, kind, n_dof, n_links, nx, ny, nz; };
-static std::mutex g_sdf_mu;
-static SdfShape g_sdf_table[16];
-static int g_sdf_n = 0, g_sdf_next = 0;
+static MpbHeaderCache<SdfShape, MPB_SDF_HEADER_WORDS> g_sdf_cache;
 
 extern "C" int mpb_sdf_grid_invalidate(const float* sdfb) {
-    std::lock_guard<std::mutex> lock(g_sdf_mu);
-    for (int i = 0; i < g_sdf_n; ++i)
-        if (g_sdf_table[i].ptr == sdfb) g_sdf_table[i].ptr = nullptr;     // (on every device: the caller names an address)
+    g_sdf_cache.drop(sdfb);
     return MPB_OK;
 }
 
 static int sdf_shape(const float* sdfb, SdfShape& out, const char* who) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return mpb_failf(MPB_E_HIP, "%s: hipGetDevice failed", who);
-    std::lock_guard<std::mutex> lock(g_sdf_mu);
-    for (int i = 0; i < g_sdf_n; ++i)
-        if (g_sdf_table[i].ptr == sdfb && g_sdf_table[i].dev == dev) { out = g_sdf_table[i]; return MPB_OK; }
-    int32_t hdr[MPB_SDF_HEADER_WORDS];
-    const hipError_t e = hipMemcpy(hdr, sdfb, sizeof(hdr), hipMemcpyDeviceToHost);
-    if (e != hipSuccess) return mpb_failf(MPB_E_HIP, "%s: reading the SDF-grid header failed: %s", who, hipGetErrorString(e));
-    const int rc = sdf_header_check(hdr, -1, who);
-    if (rc) return rc;
-    out = {sdfb, dev, hdr[MPB_DW_KIND], hdr[MPB_DW_N_DOF], hdr[MPB_DW_N_LINKS], hdr[MPB_DW_DIMS], hdr[MPB_DW_DIMS + 1], hdr[MPB_DW_DIMS + 2]};
-    g_sdf_table[g_sdf_next] = out;
-    g_sdf_next = (g_sdf_next + 1) % 16;
-    g_sdf_n = g_sdf_n < 16 ? g_sdf_n + 1 : 16;
-    return MPB_OK;
+    return g_sdf_cache.get(sdfb, out, who, "SDF-grid", [who](const int32_t* hdr, SdfShape& S) {
+        S.kind = hdr[MPB_DW_KIND], S.n_dof = hdr[MPB_DW_N_DOF], S.n_links = hdr[MPB_DW_N_LINKS];
+        S.nx = hdr[MPB_DW_DIMS], S.ny = hdr[MPB_DW_DIMS + 1], S.nz = hdr[MPB_DW_DIMS + 2];
+        return sdf_header_check(hdr, -1, who);
+    });
 }
 
 extern "C" int mpb_sdf_grid_build(const float* geom, float* sdfb, void* stream) {
@@ -505,22 +474,13 @@ extern "C" int mpb_sdf_grid_build(const float* geom, float* sdfb, void* stream) 
     return mpb_check_launch(__func__);
 }
 
-// LDS of a y / z pass: n rows of MPB_EDT_T words, 128 KB at n = 1 024; beyond the default limit of 48 KB the kernel's limit is raised to
-// the largest tile there is -- once per kernel and device, as the self-collision launcher does
+// LDS of a y / z pass: n rows of MPB_EDT_T words, 128 KB at n = MPB_SDF_MAX_DIM = 1 024; the kernel's limit is raised where that takes it
 template <bool LAST>
 static int edt_axis_launch(float* sdfb, const SdfShape& S, int axis, void* stream, const char* who) {
-    static bool raised[64] = {};
     const int n = axis == 1 ? S.ny : S.nz, other = axis == 1 ? S.nz : S.ny;
     const size_t bytes = (size_t)n * MPB_EDT_T * sizeof(int);
-    if (bytes > 48 * 1024) {
-        std::lock_guard<std::mutex> lock(g_sdf_mu);
-        if (!(S.dev >= 0 && S.dev < 64 && raised[S.dev])) {
-            const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(occ_edt_axis_kernel<LAST>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                     MPB_SDF_MAX_DIM * MPB_EDT_T * (int)sizeof(int));
-            if (e != hipSuccess) return mpb_failf(MPB_E_HIP, "%s: raising the LDS limit to %zu bytes failed: %s", who, bytes, hipGetErrorString(e));
-            if (S.dev >= 0 && S.dev < 64) raised[S.dev] = true;
-        }
-    }
+    const int rc = mpb_raise_lds_limit(reinterpret_cast<const void*>(occ_edt_axis_kernel<LAST>), S.dev, bytes, who);
+    if (rc) return rc;
     const int threads = std::min(1024, (n * MPB_EDT_T + 63) / 64 * 64);          // one thread per node of the tile up to 1 024, whole waves
     hipLaunchKernelGGL(occ_edt_axis_kernel<LAST>, dim3((S.nx + MPB_EDT_T - 1) / MPB_EDT_T, other), dim3(threads), bytes, (hipStream_t)stream, sdfb,
                        S.nx, S.ny, S.nz, axis);
@@ -558,21 +518,13 @@ extern "C" int mpb_sdf_grid_sample(const float* points, const float* sdfb, float
 
 static int sdf_cost_launch(bool want_grad, const char* who, const float* trajs, const float* sdfb, float* out, float* per_wp, float* grad,
                            int B, int H, int d, int h_begin, float k_sigma, float weight, int accumulate, void* stream) {
-    if (d > 2 * MPB_MAX_DOF) return mpb_failf(MPB_E_UNSUPPORTED, "%s: rows of d = %d exceed positions + velocities of MPB_MAX_DOF = %d joints", who, d, MPB_MAX_DOF);
-    if (B < 0 || H < 1 || d < 1 || h_begin < 0) return mpb_failf(MPB_E_INVALID, "%s: bad shape", who);
-    if (B == 0) return MPB_OK;
-    if (!trajs || !sdfb || !out || (want_grad && !grad)) return mpb_failf(MPB_E_INVALID, "%s: null pointer", who);
-    if (mpb_misaligned16(sdfb)) return mpb_failf(MPB_E_INVALID, "%s: the SDF-grid buffer must be 16-byte aligned", who);
+    int rc = mpb_check_rows(who, "SDF-grid", trajs, sdfb, out, want_grad, grad, B, H, d, h_begin);
+    if (rc || B == 0) return rc;
     SdfShape S;
-    const int rc = sdf_shape(sdfb, S, who);
-    if (rc) return rc;
+    if ((rc = sdf_shape(sdfb, S, who))) return rc;
     if (d < S.n_dof) return mpb_failf(MPB_E_INVALID, "%s: rows of d = %d are narrower than the robot's %d coordinates", who, d, S.n_dof);
-    if (want_grad)
-        hipLaunchKernelGGL(sdf_cost_kernel<true>, dim3(B), dim3(64), 0, (hipStream_t)stream, trajs, sdfb, out, per_wp, grad, H, d, h_begin, k_sigma,
-                           weight, accumulate, S.n_dof, S.n_links, S.nx, S.ny, S.nz);
-    else
-        hipLaunchKernelGGL(sdf_cost_kernel<false>, dim3(B), dim3(64), 0, (hipStream_t)stream, trajs, sdfb, out, per_wp, (float*)nullptr, H, d, h_begin,
-                           k_sigma, weight, accumulate, S.n_dof, S.n_links, S.nx, S.ny, S.nz);
+    hipLaunchKernelGGL(want_grad ? sdf_cost_kernel<true> : sdf_cost_kernel<false>, dim3(B), dim3(64), 0, (hipStream_t)stream, trajs, sdfb, out,
+                       per_wp, grad, H, d, h_begin, k_sigma, weight, accumulate, S.n_dof, S.n_links, S.nx, S.ny, S.nz);
     return mpb_check_launch(who);
 }
 
@@ -588,14 +540,10 @@ extern "C" int mpb_sdf_grid_grad(const float* trajs, const float* sdfb, float* o
 
 extern "C" int mpb_sdf_grid_collision_check(const float* q, const float* sdfb, unsigned char* in_collision, float* gap, int N, int D, int or_into,
                                             void* stream) {
-    if (D > MPB_MAX_DOF) return mpb_failf(MPB_E_UNSUPPORTED, "%s: D = %d exceeds MPB_MAX_DOF = %d", __func__, D, MPB_MAX_DOF);
-    if (N < 0 || D < 1) return mpb_failf(MPB_E_INVALID, "%s: bad shape", __func__);
-    if (N == 0) return MPB_OK;
-    if (!q || !sdfb || !in_collision) return mpb_failf(MPB_E_INVALID, "%s: null pointer", __func__);
-    if (mpb_misaligned16(sdfb)) return mpb_failf(MPB_E_INVALID, "%s: the SDF-grid buffer must be 16-byte aligned", __func__);
+    int rc = mpb_check_configs(__func__, "SDF-grid", q, sdfb, in_collision, N, D);
+    if (rc || N == 0) return rc;
     SdfShape S;
-    const int rc = sdf_shape(sdfb, S, __func__);
-    if (rc) return rc;
+    if ((rc = sdf_shape(sdfb, S, __func__))) return rc;
     if (D != S.n_dof) return mpb_failf(MPB_E_INVALID, "%s: D = %d, the robot has %d coordinates", __func__, D, S.n_dof);
     hipLaunchKernelGGL(sdf_check_kernel, dim3((N + 63) / 64), dim3(64), 0, (hipStream_t)stream, q, sdfb, in_collision, gap, N, D, or_into, S.n_links,
                        S.nx, S.ny, S.nz);

@@ -16,11 +16,10 @@
 // limit of MPB_SELF_MAX_LINKS = 64 takes 48 KB / 96 KB of the 160 KB a workgroup may have.
 // Order of the sums: pairs in table order in fp32 per waypoint, a lane's waypoints in ascending order, then the fixed-order wave
 // reduction of mpb_common.h: every run gives the same bits.
-#include <mutex>
-
 #include "mpb_common.h"
 #include "mpb_host.h"
 #include "mpb_geom.h"
+#include "mpb_member_cost.h"
 #include "../../include/mpb_self_layout.h"
 
 // the chain of a self buffer as the GeomView fk_advance reads (tf, n_dof) and the walks below read (links, n_links); no obstacles
@@ -35,13 +34,6 @@ __device__ __forceinline__ GeomView self_view(const float* __restrict__ s) {
     v.tf = s + si[MPB_SW_OFF_TF];
     v.links = s + si[MPB_SW_OFF_LINKS];
     return v;
-}
-
-// a + b in one rounding whatever produced b: without this the compiler contracts  old + scale * x  into one fma, and accumulating onto
-// a buffer would not equal the buffer plus a fresh evaluation bit for bit
-__device__ __forceinline__ float add_rounded(float a, float b) {
-#pragma clang fp contract(off)
-    return a + b;
 }
 
 // phase 1: centres of the L collision spheres of configuration q into this lane's column of pos ([link][xyz][lane]); GRAD: zero the
@@ -112,9 +104,8 @@ __device__ __forceinline__ void self_apply_jt(const GeomView& G, int L, const fl
         while (F.frame < f) fk_advance<true>(G, F, q);
         const float* g = frc + l * 192 + lane;
         const float fx = g[0], fy = g[64], fz = g[128];
-        const float x = mad3(F.r00, lk.y, F.r01, lk.z, F.r02, lk.w, F.tx);
-        const float y = mad3(F.r10, lk.y, F.r11, lk.z, F.r12, lk.w, F.ty);
-        const float z = mad3(F.r20, lk.y, F.r21, lk.z, F.r22, lk.w, F.tz);
+        float x, y, z;
+        link_centre(F, lk, x, y, z);
 #pragma unroll
         for (int i = 0; i < MPB_MAX_DOF; ++i)
             if (i < f && i < G.n_dof) dq[i] += joint_term(F.zx[i], F.zy[i], F.zz[i], F.px[i], F.py[i], F.pz[i], x, y, z, fx, fy, fz);
@@ -178,11 +169,7 @@ __global__ __launch_bounds__(64) void self_cost_kernel(const float* __restrict__
         }
         csum += c;
     }
-    csum = wave_sum_f32(csum);
-    if (lane == 0) {
-        const float v = weight * (k_sigma * csum);
-        out[b] = accumulate ? add_rounded(out[b], v) : v;
-    }
+    member_store_out(out, b, lane, csum, k_sigma, weight, accumulate);
 }
 
 __global__ __launch_bounds__(64) void self_check_kernel(const float* __restrict__ q_in, const float* __restrict__ selfb,
@@ -203,9 +190,7 @@ __global__ __launch_bounds__(64) void self_check_kernel(const float* __restrict_
         self_store_centres<false>(G, L, q, self_lds, nullptr, lane);
         c = self_pair_sum<false>(pairs, n_pairs, L, self_lds, nullptr, lane, any);
     }
-    const bool hit = !(c <= 0.f);                              // (a refused buffer reads as in collision)
-    in_collision[i] = (hit || (or_into && in_collision[i] != 0)) ? 1 : 0;
-    if (gap) gap[i] = or_into ? add_rounded(gap[i], c) : c;
+    member_store_hit(in_collision, gap, i, c, or_into);
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------------
@@ -245,80 +230,41 @@ extern "C" int mpb_self_check(const float* s, int n_words) {
     return MPB_OK;
 }
 
-// What a launch needs of a DEVICE buffer's header (LDS bytes come from n_links): read once per buffer -- a 64-byte synchronous copy
-// on the first call with that pointer -- and kept in a small table.  The kernels compare the header with the numbers they were
-// launched with, so an entry that outlived its buffer yields NaN outputs, never an address outside the LDS that was sized for it.
-// Memory that gets ANOTHER buffer at an address an earlier call has seen (an allocator hands a freed block out again) must be announced
-// with mpb_self_invalidate, which drops the entry.
+// what a launch needs of a device buffer's header (LDS bytes come from n_links), through the cache of mpb_host.h (its contract is stated
+// there); memory that gets ANOTHER buffer at an address an earlier call has seen must be announced with mpb_self_invalidate
 struct SelfShape { const void* ptr; int dev, n_dof, n_links, n_pairs; };
-static std::mutex g_self_mu;
-static SelfShape g_self_table[16];
-static int g_self_n = 0, g_self_next = 0;
+static MpbHeaderCache<SelfShape, MPB_SELF_HEADER_WORDS> g_self_cache;
 
 extern "C" int mpb_self_invalidate(const float* selfb) {
-    std::lock_guard<std::mutex> lock(g_self_mu);
-    for (int i = 0; i < g_self_n; ++i)
-        if (g_self_table[i].ptr == selfb) g_self_table[i].ptr = nullptr;     // (on every device: the caller names an address)
+    g_self_cache.drop(selfb);
     return MPB_OK;
 }
 
 static int self_shape(const float* selfb, SelfShape& out, const char* who) {
-    SelfShape* table = g_self_table;
-    int& n = g_self_n;
-    int& next = g_self_next;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return mpb_failf(MPB_E_HIP, "%s: hipGetDevice failed", who);
-    std::lock_guard<std::mutex> lock(g_self_mu);
-    for (int i = 0; i < n; ++i)
-        if (table[i].ptr == selfb && table[i].dev == dev) { out = table[i]; return MPB_OK; }
-    int32_t hdr[MPB_SELF_HEADER_WORDS];
-    const hipError_t e = hipMemcpy(hdr, selfb, sizeof(hdr), hipMemcpyDeviceToHost);
-    if (e != hipSuccess) return mpb_failf(MPB_E_HIP, "%s: reading the self-collision header failed: %s", who, hipGetErrorString(e));
-    const int rc = self_header_check(hdr, -1, who);
-    if (rc) return rc;
-    out = {selfb, dev, hdr[MPB_SW_N_DOF], hdr[MPB_SW_N_LINKS], hdr[MPB_SW_N_PAIRS]};
-    table[next] = out;
-    next = (next + 1) % 16;
-    n = n < 16 ? n + 1 : 16;
-    return MPB_OK;
+    return g_self_cache.get(selfb, out, who, "self-collision", [who](const int32_t* hdr, SelfShape& S) {
+        S.n_dof = hdr[MPB_SW_N_DOF], S.n_links = hdr[MPB_SW_N_LINKS], S.n_pairs = hdr[MPB_SW_N_PAIRS];
+        return self_header_check(hdr, -1, who);
+    });
 }
 
-// LDS of a launch; beyond the default limit of 48 KB the kernel's limit is raised -- once per (kernel, device) and size reached, remembered
-// here so that a planner's per-iteration launches make no runtime call for it.  WHICH: 0 cost, 1 gradient, 2 predicate.
-template <int WHICH, class K>
-static int self_lds_bytes(K kernel, int dev, int n_links, size_t& bytes, const char* who) {
-    static int raised[64] = {};                                  // bytes the limit stands at, per device (0: the default)
-    bytes = (size_t)n_links * 192 * sizeof(float) * (WHICH == 1 ? 2 : 1);
-    if (bytes <= 48 * 1024) return MPB_OK;
-    std::lock_guard<std::mutex> lock(g_self_mu);
-    if (dev >= 0 && dev < 64 && raised[dev] >= (int)bytes) return MPB_OK;
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-    if (e != hipSuccess) return mpb_failf(MPB_E_HIP, "%s: raising the LDS limit to %zu bytes failed: %s", who, bytes, hipGetErrorString(e));
-    if (dev >= 0 && dev < 64) raised[dev] = (int)bytes;
-    return MPB_OK;
+// LDS of a launch ([L][3][64] words, twice with gradients), the kernel's limit raised where that takes it
+static int self_lds_bytes(const void* kernel, const SelfShape& S, bool grad, size_t& bytes, const char* who) {
+    bytes = (size_t)S.n_links * 192 * sizeof(float) * (grad ? 2 : 1);
+    return mpb_raise_lds_limit(kernel, S.dev, bytes, who);
 }
 
 static int self_cost_launch(bool want_grad, const char* who, const float* trajs, const float* selfb, float* out, float* per_wp, float* grad,
                             int B, int H, int d, int h_begin, float k_sigma, float weight, int accumulate, void* stream) {
-    if (d > 2 * MPB_MAX_DOF) return mpb_failf(MPB_E_UNSUPPORTED, "%s: rows of d = %d exceed positions + velocities of MPB_MAX_DOF = %d joints", who, d, MPB_MAX_DOF);
-    if (B < 0 || H < 1 || d < 1 || h_begin < 0) return mpb_failf(MPB_E_INVALID, "%s: bad shape", who);
-    if (B == 0) return MPB_OK;
-    if (!trajs || !selfb || !out || (want_grad && !grad)) return mpb_failf(MPB_E_INVALID, "%s: null pointer", who);
-    if (mpb_misaligned16(selfb)) return mpb_failf(MPB_E_INVALID, "%s: the self-collision buffer must be 16-byte aligned", who);
+    int rc = mpb_check_rows(who, "self-collision", trajs, selfb, out, want_grad, grad, B, H, d, h_begin);
+    if (rc || B == 0) return rc;
     SelfShape S;
-    int rc = self_shape(selfb, S, who);
-    if (rc) return rc;
+    if ((rc = self_shape(selfb, S, who))) return rc;
     if (d < S.n_dof) return mpb_failf(MPB_E_INVALID, "%s: rows of d = %d are narrower than the chain's %d joints", who, d, S.n_dof);
+    const auto kernel = want_grad ? self_cost_kernel<true> : self_cost_kernel<false>;
     size_t lds;
-    if (want_grad) {
-        if ((rc = self_lds_bytes<1>(self_cost_kernel<true>, S.dev, S.n_links, lds, who))) return rc;
-        hipLaunchKernelGGL(self_cost_kernel<true>, dim3(B), dim3(64), lds, (hipStream_t)stream, trajs, selfb, out, per_wp, grad, H, d, h_begin,
-                           k_sigma, weight, accumulate, S.n_dof, S.n_links, S.n_pairs);
-    } else {
-        if ((rc = self_lds_bytes<0>(self_cost_kernel<false>, S.dev, S.n_links, lds, who))) return rc;
-        hipLaunchKernelGGL(self_cost_kernel<false>, dim3(B), dim3(64), lds, (hipStream_t)stream, trajs, selfb, out, per_wp, (float*)nullptr, H, d,
-                           h_begin, k_sigma, weight, accumulate, S.n_dof, S.n_links, S.n_pairs);
-    }
+    if ((rc = self_lds_bytes(reinterpret_cast<const void*>(kernel), S, want_grad, lds, who))) return rc;
+    hipLaunchKernelGGL(kernel, dim3(B), dim3(64), lds, (hipStream_t)stream, trajs, selfb, out, per_wp, grad, H, d, h_begin, k_sigma, weight,
+                       accumulate, S.n_dof, S.n_links, S.n_pairs);
     return mpb_check_launch(who);
 }
 
@@ -334,17 +280,13 @@ extern "C" int mpb_self_collision_grad(const float* trajs, const float* selfb, f
 
 extern "C" int mpb_self_collision_check(const float* q, const float* selfb, unsigned char* in_collision, float* gap, int N, int D,
                                         int or_into, void* stream) {
-    if (D > MPB_MAX_DOF) return mpb_failf(MPB_E_UNSUPPORTED, "%s: D = %d exceeds MPB_MAX_DOF = %d", __func__, D, MPB_MAX_DOF);
-    if (N < 0 || D < 1) return mpb_failf(MPB_E_INVALID, "%s: bad shape", __func__);
-    if (N == 0) return MPB_OK;
-    if (!q || !selfb || !in_collision) return mpb_failf(MPB_E_INVALID, "%s: null pointer", __func__);
-    if (mpb_misaligned16(selfb)) return mpb_failf(MPB_E_INVALID, "%s: the self-collision buffer must be 16-byte aligned", __func__);
+    int rc = mpb_check_configs(__func__, "self-collision", q, selfb, in_collision, N, D);
+    if (rc || N == 0) return rc;
     SelfShape S;
-    int rc = self_shape(selfb, S, __func__);
-    if (rc) return rc;
+    if ((rc = self_shape(selfb, S, __func__))) return rc;
     if (D != S.n_dof) return mpb_failf(MPB_E_INVALID, "%s: D = %d, the chain has %d joints", __func__, D, S.n_dof);
     size_t lds;
-    if ((rc = self_lds_bytes<2>(self_check_kernel, S.dev, S.n_links, lds, __func__))) return rc;
+    if ((rc = self_lds_bytes(reinterpret_cast<const void*>(self_check_kernel), S, false, lds, __func__))) return rc;
     hipLaunchKernelGGL(self_check_kernel, dim3((N + 63) / 64), dim3(64), lds, (hipStream_t)stream, q, selfb, in_collision, gap, N, D, or_into,
                        S.n_links, S.n_pairs);
     return mpb_check_launch(__func__);

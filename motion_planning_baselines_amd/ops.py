@@ -42,7 +42,7 @@ def _on_tensor_device(fn):
     def run(*args, **kw):
         dev = None
         for a in list(args) + list(kw.values()):
-            t = a.buf if isinstance(a, (DeviceGeometry, DeviceSelfCollision, DeviceSDFGrid)) else a
+            t = a.buf if isinstance(a, (DeviceGeometry, _DeviceMemberBuffer)) else a
             if isinstance(t, torch.Tensor) and t.is_cuda:
                 if dev is None:
                     dev = t.device
@@ -110,9 +110,21 @@ class DeviceGeometry:
         self.buf = torch.from_numpy(host.copy()).to(device)
 
 
-class DeviceSelfCollision:
+class _DeviceMemberBuffer:
+    """What the buffers of the cost members with kernels of their own share: the packed robot + field in HBM as `buf`, the robot's `n_dof`,
+    and the library's cached header dropped for the address on upload (INVALIDATE); MEMBER_OPS below says which wrappers serve which."""
+    INVALIDATE = None
+
+    def _adopt(self, buf):
+        self.buf = buf
+        # (the library reads such a buffer's header once per address: this address may have held another one before)
+        _lib.check(getattr(_lib.lib(), self.INVALIDATE)(_ptr(buf)), self.INVALIDATE)
+
+
+class DeviceSelfCollision(_DeviceMemberBuffer):
     """A chain + its SelfCollisionField as the packed self buffer (geometry.pack_self_collision) resident in HBM: packed, validated
     (mpb_self_check) and uploaded once."""
+    INVALIDATE = 'mpb_self_invalidate'
 
     def __init__(self, robot, field, device):
         from .self_layout import header as self_header
@@ -121,12 +133,11 @@ class DeviceSelfCollision:
         _lib.self_check(self.host)
         hdr = self_header(self.host)
         self.n_dof, self.n_links, self.n_pairs = int(hdr['n_dof']), int(hdr['n_links']), int(hdr['n_pairs'])
-        self.buf = torch.from_numpy(self.host.copy()).to(device)
-        # (the library reads a self buffer's header once per address: this address may have held another one before)
-        _lib.check(_lib.lib().mpb_self_invalidate(_ptr(self.buf)), 'mpb_self_invalidate')
+        self._adopt(torch.from_numpy(self.host.copy()).to(device))
 
 
-def _self_out(trajs, out, accumulate):
+def _cost_out(trajs, out, accumulate):
+    """The (B,) sums a cost wrapper writes: the caller's `out`, checked, or a fresh one (which nothing can be accumulated onto)."""
     B = trajs.shape[0]
     if out is None:
         if accumulate:
@@ -138,49 +149,41 @@ def _self_out(trajs, out, accumulate):
     return out
 
 
-@_on_tensor_device
-def self_collision_eval(trajs, sc, k_sigma, weight=1.0, h_begin=1, per_waypoint=False, out=None, accumulate=False):
-    """trajs (B, H, d) -> out (B,) (+)= weight * k_sigma * sum_{h >= h_begin} c(q_h) of a DeviceSelfCollision
-    (mpb_self_collision_eval); per_waypoint also returns c (B, H), un-scaled, 0 below h_begin."""
+# the three wrappers over a packed robot buffer (a _DeviceMemberBuffer `mb`), by C entry point and the robot's noun
+def _row_cost_eval(symbol, noun, trajs, mb, k_sigma, weight, h_begin, per_waypoint, out, accumulate):
     B, H, d = trajs.shape
     _chk(trajs, (B, H, d), 'trajs')
-    if d < sc.n_dof:
-        raise ValueError(f'trajs has {d} columns, the chain {sc.n_dof} degrees of freedom')
-    out = _self_out(trajs, out, accumulate)
+    if d < mb.n_dof:
+        raise ValueError(f'trajs has {d} columns, the {noun} {mb.n_dof} degrees of freedom')
+    out = _cost_out(trajs, out, accumulate)
     pw = torch.empty(B, H, device=trajs.device, dtype=torch.float32) if per_waypoint else None
-    _lib.check(_lib.lib().mpb_self_collision_eval(_ptr(trajs), _ptr(sc.buf), _ptr(out), _ptr(pw), B, H, d, int(h_begin), float(k_sigma),
-                                                 float(weight), int(bool(accumulate)), _stream()), 'mpb_self_collision_eval')
+    _lib.check(getattr(_lib.lib(), symbol)(_ptr(trajs), _ptr(mb.buf), _ptr(out), _ptr(pw), B, H, d, int(h_begin), float(k_sigma), float(weight),
+                                           int(bool(accumulate)), _stream()), symbol)
     return (out, pw) if per_waypoint else out
 
 
-@_on_tensor_device
-def self_collision_grad(trajs, sc, k_sigma, weight=1.0, h_begin=1, out=None, grad=None, accumulate=False):
-    """(out (B,), grad (B, H, d)) (+)= the self-collision cost and d out / d trajs (mpb_self_collision_grad); accumulate adds onto the
-    given `out` AND `grad` (velocity channels left alone), otherwise both are written (velocity channels 0)."""
+def _row_cost_grad(symbol, noun, trajs, mb, k_sigma, weight, h_begin, out, grad, accumulate):
     B, H, d = trajs.shape
     _chk(trajs, (B, H, d), 'trajs')
-    if d < sc.n_dof:
-        raise ValueError(f'trajs has {d} columns, the chain {sc.n_dof} degrees of freedom')
+    if d < mb.n_dof:
+        raise ValueError(f'trajs has {d} columns, the {noun} {mb.n_dof} degrees of freedom')
     if accumulate and grad is None:
         raise ValueError('accumulate needs existing out and grad buffers')
-    out = _self_out(trajs, out, accumulate)
+    out = _cost_out(trajs, out, accumulate)
     if grad is None:
         grad = torch.empty_like(trajs)
     else:
         _chk(grad, (B, H, d), 'grad')
-    _lib.check(_lib.lib().mpb_self_collision_grad(_ptr(trajs), _ptr(sc.buf), _ptr(out), _ptr(grad), B, H, d, int(h_begin), float(k_sigma),
-                                                 float(weight), int(bool(accumulate)), _stream()), 'mpb_self_collision_grad')
+    _lib.check(getattr(_lib.lib(), symbol)(_ptr(trajs), _ptr(mb.buf), _ptr(out), _ptr(grad), B, H, d, int(h_begin), float(k_sigma), float(weight),
+                                           int(bool(accumulate)), _stream()), symbol)
     return out, grad
 
 
-@_on_tensor_device
-def self_collision_check(q, sc, with_gap=False, flag=None, gap=None):
-    """(N, D) configurations -> bool (N,): the robot collides with itself (mpb_self_collision_check); with_gap also returns the hinge
-    sum.  Given `flag` (and `gap`) -- the outputs of collision_check --, the answer is ORed into the flags and added onto the gap."""
+def _config_predicate(symbol, noun, q, mb, with_gap, flag, gap):
     N, D = q.shape
     _chk(q, (N, D), 'q')
-    if D != sc.n_dof:
-        raise ValueError(f'q has {D} columns, the chain {sc.n_dof} degrees of freedom')
+    if D != mb.n_dof:
+        raise ValueError(f'q has {D} columns, the {noun} {mb.n_dof} degrees of freedom')
     or_into = flag is not None
     if or_into:
         _chk(flag, (N,), 'flag', dtype=torch.bool)
@@ -190,17 +193,38 @@ def self_collision_check(q, sc, with_gap=False, flag=None, gap=None):
     else:
         flag = torch.empty(N, device=q.device, dtype=torch.bool)
         gap = torch.empty(N, device=q.device, dtype=torch.float32) if with_gap else None
-    _lib.check(_lib.lib().mpb_self_collision_check(_ptr(q), _ptr(sc.buf), _ptr(flag), _ptr(gap), N, D, int(or_into), _stream()),
-               'mpb_self_collision_check')
+    _lib.check(getattr(_lib.lib(), symbol)(_ptr(q), _ptr(mb.buf), _ptr(flag), _ptr(gap), N, D, int(or_into), _stream()), symbol)
     return (flag, gap) if (with_gap or gap is not None) else flag
 
 
-class DeviceSDFGrid:
+@_on_tensor_device
+def self_collision_eval(trajs, sc, k_sigma, weight=1.0, h_begin=1, per_waypoint=False, out=None, accumulate=False):
+    """trajs (B, H, d) -> out (B,) (+)= weight * k_sigma * sum_{h >= h_begin} c(q_h) of a DeviceSelfCollision
+    (mpb_self_collision_eval); per_waypoint also returns c (B, H), un-scaled, 0 below h_begin."""
+    return _row_cost_eval('mpb_self_collision_eval', 'chain', trajs, sc, k_sigma, weight, h_begin, per_waypoint, out, accumulate)
+
+
+@_on_tensor_device
+def self_collision_grad(trajs, sc, k_sigma, weight=1.0, h_begin=1, out=None, grad=None, accumulate=False):
+    """(out (B,), grad (B, H, d)) (+)= the self-collision cost and d out / d trajs (mpb_self_collision_grad); accumulate adds onto the
+    given `out` AND `grad` (velocity channels left alone), otherwise both are written (velocity channels 0)."""
+    return _row_cost_grad('mpb_self_collision_grad', 'chain', trajs, sc, k_sigma, weight, h_begin, out, grad, accumulate)
+
+
+@_on_tensor_device
+def self_collision_check(q, sc, with_gap=False, flag=None, gap=None):
+    """(N, D) configurations -> bool (N,): the robot collides with itself (mpb_self_collision_check); with_gap also returns the hinge
+    sum.  Given `flag` (and `gap`) -- the outputs of collision_check --, the answer is ORed into the flags and added onto the gap."""
+    return _config_predicate('mpb_self_collision_check', 'chain', q, sc, with_gap, flag, gap)
+
+
+class DeviceSDFGrid(_DeviceMemberBuffer):
     """A robot + a GridSDFField as the packed SDF buffer (geometry.pack_sdf_grid) resident in HBM: packed, validated (mpb_sdf_grid_check)
     and uploaded once -- or, for a field without host values, the header and the robot tables uploaded and the nodes built ON the
     device from the field's source: a CollisionField (GridSDFField.from_field, mpb_sdf_grid_build) or an occupancy voxel map
     (GridSDFField.from_occupancy, mpb_sdf_grid_build_occupancy: the bytes uploaded once, a GPU tensor used in place).  `.nodes` is the
     node section as a (nz, ny, nx) view of the buffer."""
+    INVALIDATE = 'mpb_sdf_grid_invalidate'
 
     def __init__(self, robot, field, device):
         from .sdf_layout import header as sdf_header
@@ -213,12 +237,11 @@ class DeviceSDFGrid:
         self.kind, self.n_dof, self.n_links = int(hdr['kind']), int(hdr['n_dof']), int(hdr['n_links'])
         self.dims = tuple(int(v) for v in hdr['dims'])
         if built:
-            self.buf = torch.empty(total, device=device, dtype=torch.float32)
-            self.buf[:off_nodes].copy_(torch.from_numpy(self.host))
+            buf = torch.empty(total, device=device, dtype=torch.float32)
+            buf[:off_nodes].copy_(torch.from_numpy(self.host))
         else:
-            self.buf = torch.from_numpy(self.host).to(device)
-        # (the library reads an SDF buffer's header once per address: this address may have held another one before)
-        _lib.check(_lib.lib().mpb_sdf_grid_invalidate(_ptr(self.buf)), 'mpb_sdf_grid_invalidate')
+            buf = torch.from_numpy(self.host).to(device)
+        self._adopt(buf)
         nx, ny, nz = self.dims
         self.nodes = self.buf[off_nodes:].view(nz, ny, nx)
         if built and isinstance(field.source, CollisionField):
@@ -289,35 +312,14 @@ def sdf_grid_sample(points, sdf, with_grad=False):
 def sdf_grid_eval(trajs, sdf, k_sigma, weight=1.0, h_begin=1, per_waypoint=False, out=None, accumulate=False):
     """trajs (B, H, d) -> out (B,) (+)= weight * k_sigma * sum_{h >= h_begin} c(q_h) of a DeviceSDFGrid (mpb_sdf_grid_eval);
     per_waypoint also returns c (B, H), un-scaled, 0 below h_begin."""
-    B, H, d = trajs.shape
-    _chk(trajs, (B, H, d), 'trajs')
-    if d < sdf.n_dof:
-        raise ValueError(f'trajs has {d} columns, the robot {sdf.n_dof} degrees of freedom')
-    out = _self_out(trajs, out, accumulate)
-    pw = torch.empty(B, H, device=trajs.device, dtype=torch.float32) if per_waypoint else None
-    _lib.check(_lib.lib().mpb_sdf_grid_eval(_ptr(trajs), _ptr(sdf.buf), _ptr(out), _ptr(pw), B, H, d, int(h_begin), float(k_sigma),
-                                           float(weight), int(bool(accumulate)), _stream()), 'mpb_sdf_grid_eval')
-    return (out, pw) if per_waypoint else out
+    return _row_cost_eval('mpb_sdf_grid_eval', 'robot', trajs, sdf, k_sigma, weight, h_begin, per_waypoint, out, accumulate)
 
 
 @_on_tensor_device
 def sdf_grid_grad(trajs, sdf, k_sigma, weight=1.0, h_begin=1, out=None, grad=None, accumulate=False):
     """(out (B,), grad (B, H, d)) (+)= the grid cost and d out / d trajs (mpb_sdf_grid_grad); accumulate adds onto the given `out` AND
     `grad` (velocity channels left alone), otherwise both are written (velocity channels 0)."""
-    B, H, d = trajs.shape
-    _chk(trajs, (B, H, d), 'trajs')
-    if d < sdf.n_dof:
-        raise ValueError(f'trajs has {d} columns, the robot {sdf.n_dof} degrees of freedom')
-    if accumulate and grad is None:
-        raise ValueError('accumulate needs existing out and grad buffers')
-    out = _self_out(trajs, out, accumulate)
-    if grad is None:
-        grad = torch.empty_like(trajs)
-    else:
-        _chk(grad, (B, H, d), 'grad')
-    _lib.check(_lib.lib().mpb_sdf_grid_grad(_ptr(trajs), _ptr(sdf.buf), _ptr(out), _ptr(grad), B, H, d, int(h_begin), float(k_sigma),
-                                           float(weight), int(bool(accumulate)), _stream()), 'mpb_sdf_grid_grad')
-    return out, grad
+    return _row_cost_grad('mpb_sdf_grid_grad', 'robot', trajs, sdf, k_sigma, weight, h_begin, out, grad, accumulate)
 
 
 @_on_tensor_device
@@ -325,22 +327,14 @@ def sdf_grid_check(q, sdf, with_gap=False, flag=None, gap=None):
     """(N, D) configurations -> bool (N,): the grid cost of the configuration is positive (mpb_sdf_grid_collision_check); with_gap also
     returns the hinge sum.  Given `flag` (and `gap`) -- the outputs of collision_check --, the answer is ORed into the flags and added
     onto the gap."""
-    N, D = q.shape
-    _chk(q, (N, D), 'q')
-    if D != sdf.n_dof:
-        raise ValueError(f'q has {D} columns, the robot {sdf.n_dof} degrees of freedom')
-    or_into = flag is not None
-    if or_into:
-        _chk(flag, (N,), 'flag', dtype=torch.bool)
-        _chk(gap, (N,), 'gap', allow_none=True)
-        if with_gap and gap is None:
-            raise ValueError('with_gap next to flag= needs the gap= to add onto (the gap of collision_check(..., with_gap=True))')
-    else:
-        flag = torch.empty(N, device=q.device, dtype=torch.bool)
-        gap = torch.empty(N, device=q.device, dtype=torch.float32) if with_gap else None
-    _lib.check(_lib.lib().mpb_sdf_grid_collision_check(_ptr(q), _ptr(sdf.buf), _ptr(flag), _ptr(gap), N, D, int(or_into), _stream()),
-               'mpb_sdf_grid_collision_check')
-    return (flag, gap) if (with_gap or gap is not None) else flag
+    return _config_predicate('mpb_sdf_grid_collision_check', 'robot', q, sdf, with_gap, flag, gap)
+
+
+# the wrappers that serve each member buffer, for the callers that hold one without caring which (CostCollision.own_eval / own_grad,
+# PlanningTask's predicate)
+MemberOps = collections.namedtuple('MemberOps', 'eval grad check')
+MEMBER_OPS = {DeviceSelfCollision: MemberOps(self_collision_eval, self_collision_grad, self_collision_check),
+              DeviceSDFGrid: MemberOps(sdf_grid_eval, sdf_grid_grad, sdf_grid_check)}
 
 
 @_on_tensor_device
@@ -1388,7 +1382,7 @@ def ee_cost_eval(trajs, geom, target, k_pos=0.0, k_rot=0.0, axis=None, weight=1.
     (H, 3, 4) or (G, H, 3, 4).  per_waypoint also returns c (B, H), un-scaled by weight, 0 outside the range."""
     args = _ee_cost_args(trajs, geom, target, k_pos, k_rot, axis, h_begin, h_end, target_per_waypoint, 'ee_cost_eval')
     B, H = args[0], args[1]
-    out = _self_out(trajs, out, accumulate)
+    out = _cost_out(trajs, out, accumulate)
     pw = torch.empty(B, H, device=trajs.device, dtype=torch.float32) if per_waypoint else None
     _lib.check(_lib.lib().mpb_ee_cost_eval(_ptr(trajs), _ptr(geom.buf), _ptr(target), _ptr(out), _ptr(pw), *args, float(weight),
                                           int(bool(accumulate)), _stream()), 'mpb_ee_cost_eval')
@@ -1405,7 +1399,7 @@ def ee_cost_grad(trajs, geom, target, k_pos=0.0, k_rot=0.0, axis=None, weight=1.
     B, H, d = args[0], args[1], args[2]
     if accumulate and grad is None:
         raise ValueError('accumulate needs existing out and grad buffers')
-    out = _self_out(trajs, out, accumulate)
+    out = _cost_out(trajs, out, accumulate)
     if grad is None:
         grad = torch.empty_like(trajs)
     else:

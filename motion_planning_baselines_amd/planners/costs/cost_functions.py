@@ -83,8 +83,7 @@ class CostCollision(Cost):
         self.field = field
         self.sigma_coll = sigma_coll
         self._geom = None
-        self._self = None
-        self._sdf = None
+        self._own = None
 
     @property
     def k_sigma(self):
@@ -103,36 +102,34 @@ class CostCollision(Cost):
         """The member's field is no obstacle list: it has eval / gradient kernels of its own (own_eval, own_grad)."""
         return self.is_self or self.is_grid
 
+    def device_own(self, device):
+        """The packed buffer of a member with kernels of its own on `device` -- an ops.DeviceSelfCollision or an ops.DeviceSDFGrid: packed,
+        checked and uploaded (the grid, where it has no host values, built there) once."""
+        assert self.own_kernels
+        if self._own is None or self._own.buf.device != torch.device(device):
+            self._own = (ops.DeviceSelfCollision if self.is_self else ops.DeviceSDFGrid)(self.robot, self.field, device)
+        return self._own
+
+    def device_self(self, device):
+        """device_own of a SelfCollisionField member."""
+        assert self.is_self
+        return self.device_own(device)
+
     def device_sdf(self, device):
-        """The packed SDF buffer of a GridSDFField member on `device` (packed, checked and uploaded -- or built there -- once)."""
+        """device_own of a GridSDFField member."""
         assert self.is_grid
-        if self._sdf is None or self._sdf.buf.device != torch.device(device):
-            self._sdf = ops.DeviceSDFGrid(self.robot, self.field, device)
-        return self._sdf
+        return self.device_own(device)
 
     def own_eval(self, trajs, weight=1.0, k_sigma=None, **kw):
         """ops.self_collision_eval / ops.sdf_grid_eval of this member on (B, H, d) trajectories: h_begin, per_waypoint, out, accumulate
         as those take them; k_sigma defaults to the member's."""
-        k = self.k_sigma if k_sigma is None else k_sigma
-        if self.is_self:
-            return ops.self_collision_eval(trajs, self.device_self(trajs.device), k, weight=weight, **kw)
-        assert self.is_grid
-        return ops.sdf_grid_eval(trajs, self.device_sdf(trajs.device), k, weight=weight, **kw)
+        own = self.device_own(trajs.device)
+        return ops.MEMBER_OPS[type(own)].eval(trajs, own, self.k_sigma if k_sigma is None else k_sigma, weight=weight, **kw)
 
     def own_grad(self, trajs, weight=1.0, k_sigma=None, **kw):
         """ops.self_collision_grad / ops.sdf_grid_grad of this member: h_begin, out, grad, accumulate as those take them."""
-        k = self.k_sigma if k_sigma is None else k_sigma
-        if self.is_self:
-            return ops.self_collision_grad(trajs, self.device_self(trajs.device), k, weight=weight, **kw)
-        assert self.is_grid
-        return ops.sdf_grid_grad(trajs, self.device_sdf(trajs.device), k, weight=weight, **kw)
-
-    def device_self(self, device):
-        """The packed self-collision buffer of a SelfCollisionField member on `device` (packed, checked and uploaded once)."""
-        assert self.is_self
-        if self._self is None or self._self.buf.device != torch.device(device):
-            self._self = ops.DeviceSelfCollision(self.robot, self.field, device)
-        return self._self
+        own = self.device_own(trajs.device)
+        return ops.MEMBER_OPS[type(own)].grad(trajs, own, self.k_sigma if k_sigma is None else k_sigma, weight=weight, **kw)
 
     def device_geometry(self, device):
         if self.is_self:

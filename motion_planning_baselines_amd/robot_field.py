@@ -206,10 +206,9 @@ class PlanningTask:
         """(N, D) contiguous fp32 on the device -> bool (N,): collides with the world, (self_field) with itself or (sdf_field) with
         what the grid holds."""
         flag = ops.collision_check(q2, self.geom)
-        if self.self_geom is not None:
-            ops.self_collision_check(q2, self.self_geom, flag=flag)
-        if self.sdf_geom is not None:
-            ops.sdf_grid_check(q2, self.sdf_geom, flag=flag)
+        for own in (self.self_geom, self.sdf_geom):
+            if own is not None:
+                ops.MEMBER_OPS[type(own)].check(q2, own, flag=flag)
         return flag
 
     def require_no_sdf_field(self, what):

@@ -258,6 +258,23 @@ def test_corrupted_header_reads_as_nan_and_the_validator_raises(gpu_device):
         ops.sdf_grid_eval(x, sdf, 1.0)
 
 
+def test_a_buffer_evicted_from_the_header_table_is_read_again(gpu_device):
+    """The library keeps the headers of 16 buffer addresses, replaced in turn.  Seventeen live buffers of the smallest grid
+    mpb_sdf_grid_check takes (2 x 2 x 1 nodes under a planar point robot), each with node values -- so a cost -- of its own, evaluated
+    once each at B = 1, H = 2: the seventeenth takes the first one's place, and the first, read again, gives the bits of its first
+    evaluation."""
+    from motion_planning_baselines_amd import geometry as G, ops
+    robot = G.RobotPointMass(2)
+    x = torch.tensor([[[0.25, 0.5], [0.75, 0.125]]], device=gpu_device)
+    sdfs = [ops.DeviceSDFGrid(robot, G.GridSDFField(np.array([[0.01, 0.02], [0.03, 0.04]], np.float32) - 0.001 * i, (0.0, 0.0), 1.0, margin=0.05),
+                              gpu_device) for i in range(17)]
+    assert len({sdf.buf.data_ptr() for sdf in sdfs}) == 17 and sdfs[0].dims == (2, 2, 1)
+    first = [ops.sdf_grid_eval(x, sdf, 2.0, h_begin=0, per_waypoint=True) for sdf in sdfs]
+    assert len({float(out) for out, _ in first}) == 17 and all(bool((pw > 0).all()) for _, pw in first)
+    out, pw = ops.sdf_grid_eval(x, sdfs[0], 2.0, h_begin=0, per_waypoint=True)
+    assert torch.equal(out, first[0][0]) and torch.equal(pw, first[0][1])
+
+
 # ------------------------------------------------------------------------------------------------
 # built against supplied
 # ------------------------------------------------------------------------------------------------

@@ -94,7 +94,7 @@ def test_home_poses_cost_nothing(gpu_device):
 
 
 def test_accumulate_is_the_prefill_plus_a_fresh_evaluation_bit_for_bit(gpu_device):
-    """accumulate adds the fresh value onto the old one in ONE fp32 rounding (add_rounded in csrc/mpb_self_collision.hip keeps the
+    """accumulate adds the fresh value onto the old one in ONE fp32 rounding (add_rounded in csrc/mpb_member_cost.h keeps the
     compiler from contracting old + scale * x into an fma): out and grad equal prefill + fresh BIT FOR BIT; the velocity channels of
     an accumulated grad are left alone; two runs give identical bits."""
     from motion_planning_baselines_amd import ops
@@ -314,3 +314,20 @@ def test_a_header_changed_behind_the_library_is_answered_with_nan(gpu_device):
     _lib.lib().mpb_self_invalidate(ctypes.c_void_p(sc.buf.data_ptr()))
     with pytest.raises(_lib.MPBError, match='transforms'):
         ops.self_collision_eval(x, sc, 1.0)
+
+
+def test_a_buffer_evicted_from_the_header_table_is_read_again(gpu_device):
+    """The library keeps the headers of 16 buffer addresses, replaced in turn.  Seventeen live buffers of the smallest chain the validator
+    takes (2 spheres, 1 pair; two joints, so that the pair's distance follows q_1), each with a margin -- so a cost -- of its own,
+    evaluated once each at B = 1, H = 2: the seventeenth takes the first one's place, and the first, read again, gives the bits of its
+    first evaluation."""
+    from motion_planning_baselines_amd import geometry as G, ops
+    tfs = np.stack([G._mdh(0.0, 0.0, 0.1), G._mdh(0.0, 0.3, 0.0)])
+    robot = G.RobotSerialChain(tfs, [1, 2], [(0.0, 0.0, 0.0), (0.2, 0.0, 0.0)], [0.05, 0.05], q_min=[-2.0, -2.0], q_max=[2.0, 2.0])
+    x = torch.tensor([[[0.3, 0.5], [-0.4, 2.0]]], device=gpu_device)                      # centres 0.49 and 0.28 apart
+    scs = [ops.DeviceSelfCollision(robot, G.SelfCollisionField(robot, margin=0.5 + 0.01 * i, pairs=[(0, 1)]), gpu_device) for i in range(17)]
+    assert len({sc.buf.data_ptr() for sc in scs}) == 17 and (scs[0].n_links, scs[0].n_pairs) == (2, 1)
+    first = [ops.self_collision_eval(x, sc, 2.0, h_begin=0, per_waypoint=True) for sc in scs]
+    assert len({float(out) for out, _ in first}) == 17 and all(bool((pw > 0).all()) for _, pw in first)
+    out, pw = ops.self_collision_eval(x, scs[0], 2.0, h_begin=0, per_waypoint=True)
+    assert torch.equal(out, first[0][0]) and torch.equal(pw, first[0][1])
