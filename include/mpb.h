@@ -36,6 +36,9 @@
 #include "mpb_self_layout.h"
 /* the packed SDF-grid buffer in numbers (generated from sdf_layout.py): header word indices MPB_DW_*, MPB_SDF_* */
 #include "mpb_sdf_layout.h"
+/* the packed triangle-mesh buffer in numbers (generated from mesh_layout.py): header word indices MPB_MW_*, record words MPB_TRI_*,
+ * feature codes MPB_FEAT_*, MPB_MESH_* */
+#include "mpb_mesh_layout.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -71,7 +74,8 @@ extern "C" {
  *                        field (mpb_sdf_grid_check, _invalidate, _build, _sample, _eval, _grad, _collision_check), and its build from
  *                        occupancy voxels (mpb_sdf_grid_build_occupancy).  So were the end-effector pose and batched inverse
  *                        kinematics (mpb_fk_ee_pose, mpb_ik_solve): additive.  So was the
- *                        end-effector pose cost (mpb_ee_cost_eval, mpb_ee_cost_grad). */
+ *                        end-effector pose cost (mpb_ee_cost_eval, mpb_ee_cost_grad), and the SDF grid's build from triangle
+ *                        meshes (mpb_mesh_check, mpb_sdf_grid_build_mesh). */
 #define MPB_ABI_VERSION 7
 #define MPB_VERSION_TUNING_BUILD 0x40000000
 int mpb_version(void);
@@ -719,6 +723,61 @@ int mpb_sdf_grid_grad(const float *trajs, const float *sdf, float *out, float *g
                       int B, int H, int d, int h_begin, float k_sigma, float weight, int accumulate, void *stream);
 int mpb_sdf_grid_collision_check(const float *q, const float *sdf, unsigned char *in_collision, float *gap,
                                  int N, int D, int or_into, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * SDF grid from triangle meshes: the exact signed distance to a mesh at every node (build-defined).
+ *   mesh:  triangles (a, b, c), counter-clockwise seen from outside, as ONE self-contained array of 32-bit words with a magic and
+ *          version of its own (mpb_mesh_layout.h, generated from mesh_layout.py -- the one definition): a header of
+ *          MPB_MESH_HEADER_WORDS words (MPB_MW_MAGIC, _VERSION, _N_TRI in 1..MPB_MESH_MAX_TRIS, _N_GROUPS = ceil(n_tri / MPB_MESH_GROUP),
+ *          _SIGNED 0 / 1, _THICKNESS >= 0, _BB_LO (3), _BB_HI (3), _OFF_TRIS = MPB_MESH_HEADER_WORDS, _OFF_BOXES, _TOTAL; the rest zero);
+ *          n_groups * MPB_MESH_GROUP triangle records of MPB_MESH_TRI_WORDS words -- MPB_TRI_A, _B, _C, the unit face normal _N_FACE,
+ *          the pseudonormals of the edges _N_AB, _N_BC, _N_CA (sum of the two faces' unit normals) and of the vertices _N_A, _N_B, _N_C
+ *          (angle-weighted sum of the faces' normals), two zero words; the records beyond n_tri repeat record n_tri - 1 --; then one box
+ *          of MPB_MESH_BOX_WORDS words per group of MPB_MESH_GROUP consecutive records: lo (3), 0, hi (3), 0, containing the group's
+ *          fp32 vertices.  The pseudonormals are computed in fp64 and rounded to fp32 once per edge / vertex: every record that shares
+ *          an edge or a vertex carries the same bits.
+ *   node:  p = fmaf(i, cell, lo) per axis, as mpb_sdf_grid_build forms it.  With a pose [R | t] (mesh frame to grid frame, row-major
+ *          3 x 4) the node is taken into the mesh frame, p' = R^T (p - t):  d = p - t per axis (one rounding each), then per axis m
+ *          p'_m = fmaf(R[2][m], d_z, fmaf(R[1][m], d_y, R[0][m] * d_x)).  A null pose leaves p untouched, bit for bit.
+ *   distance to one triangle, in fp32 with contraction off, every dot product dot(u, v) = fmaf(u_z, v_z, fmaf(u_y, v_y, u_x * v_x)):
+ *          ab = b - a, ac = c - a, bc = c - b, ap = p - a, bp = p - b, cp = p - c; d1 = dot(ab, ap), d2 = dot(ac, ap), d3 = dot(ab, bp),
+ *          d4 = dot(ac, bp), d5 = dot(ab, cp), d6 = dot(ac, cp); vc = d1 * d4 - d3 * d2, vb = d5 * d2 - d1 * d6, va = d3 * d6 - d5 * d4
+ *          (two rounded products, one rounded difference).  The region walk of Ericson, Real-Time Collision Detection 5.1.5, vertex
+ *          regions first, then edge regions, then the face -- the first that holds names the feature:
+ *            A:  d1 <= 0 and d2 <= 0;   B:  d3 >= 0 and d4 <= d3;   C:  d6 >= 0 and d5 <= d6;
+ *            AB: vc <= 0, d1 >= 0, d3 <= 0, u = d1 / (d1 - d3) along ab from a;
+ *            CA: vb <= 0, d2 >= 0, d6 <= 0, u = d2 / (d2 - d6) along ac from a;
+ *            BC: va <= 0, d4 - d3 >= 0, d5 - d6 >= 0, u = (d4 - d3) / ((d4 - d3) + (d5 - d6)) along bc from b;
+ *            face: u = vb / (va + vb + vc) along ab, w = vc / (va + vb + vc) along ac, from a.
+ *          A quotient n / m is n * (1.0f / m), the reciprocal a correctly rounded division; u is clamped to [0, 1], w to [0, 1 - u]: the
+ *          point c = base + u e1 + w e2 lies on the triangle whatever the rounding.  The offset is taken from the base's difference,
+ *          r = fmaf(-w, e2, fmaf(-u, e1, p - base)) per axis, and dist2 = dot(r, r).
+ *   winner: the triangle with the smallest dist2; triangles are visited in ascending record order and a candidate replaces the best
+ *          only when strictly smaller: the winner is unique, a padding record never wins.
+ *   sign:  s = dot(r, n_feature) of the winner (Baerentzen and Aanaes: the angle-weighted pseudonormal); s < 0 is inside.
+ *   value: a signed mesh v = sqrt(dist2) outside, -sqrt(dist2) inside; an unsigned mesh (open surfaces, scans) v = sqrt(dist2) -
+ *          thickness; the root correctly rounded.
+ *
+ * mpb_mesh_check validates a mesh buffer held in HOST memory (n_words must equal its total): magic / version, counts within limits,
+ * signed 0 / 1, thickness finite and >= 0, offsets and total, every float word finite, every record inside its group's box, every
+ * box inside the header's.
+ *
+ * mpb_sdf_grid_build_mesh: fills the node section of `sdf` with v.  `mesh` and `sdf` in device memory, 16-byte aligned; `pose_host`
+ *   12 floats in HOST memory, read during the call, or NULL.  The grid's dimensions, lo and cell come from the cached SDF header read,
+ *   as for the other builders; the mesh header is read back the same way (once per address and device) and compared in the kernel:
+ *   when either has changed, nothing is written.  mpb_sdf_grid_invalidate(mesh) forgets a mesh buffer's address too.
+ *   flags: MPB_MESH_MIN: the node becomes min(what it holds, v) -- several meshes, each with a pose of its own, or a mesh on top of
+ *   an mpb_sdf_grid_build, give the union; MPB_MESH_NO_CULL: every group is visited.  Otherwise groups are culled, exactly: pass 1 gives
+ *   each node the smallest, over groups, squared distance to the box's farthest corner (an upper bound of its dist2); in pass 2 a group
+ *   is skipped for a wave (a block of 4 x 4 x 4 nodes, planar 8 x 8) when no lane's squared distance to the box is at or below
+ *   min(best so far, pass-1 bound) + slack, slack = 2^-14 M^2 with M the largest absolute coordinate among the nodes (in the mesh
+ *   frame) and the mesh's box (DESIGN.md 10 derives it).  The bound only culls: the same triangle wins with and without culling, the
+ *   node bits are identical.  One thread per node, triangle records through uniform loads, no LDS, no atomics, no cross-lane
+ *   arithmetic: the same bits on every run.  Refusals in this order: null pointer, alignment, the SDF header, the mesh header,
+ *   unknown flag bits, a pose that is not finite: MPB_E_INVALID.
+ * ------------------------------------------------------------------------------------------- */
+int mpb_mesh_check(const float *mesh_host, int n_words);
+int mpb_sdf_grid_build_mesh(const float *mesh, const float *pose_host, float *sdf, int flags, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
  * End effector: pose, geometric Jacobian, batched inverse kinematics (build-defined; the reference's Panda examples ask

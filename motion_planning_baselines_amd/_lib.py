@@ -76,6 +76,8 @@ SIGNATURES = {
     'mpb_sdf_grid_invalidate': [_p],
     'mpb_sdf_grid_build': [_p, _p, _p],
     'mpb_sdf_grid_build_occupancy': [_p, _p, _p],
+    'mpb_mesh_check': [_p, _i],
+    'mpb_sdf_grid_build_mesh': [_p, _p, _p, _i, _p],
     'mpb_sdf_grid_sample': [_p, _p, _p, _p, _i, _p],
     'mpb_sdf_grid_eval': [_p, _p, _p, _p, _i, _i, _i, _i, _f, _f, _i, _p],
     'mpb_sdf_grid_grad': [_p, _p, _p, _p, _i, _i, _i, _i, _f, _f, _i, _p],
@@ -194,6 +196,12 @@ def sdf_grid_check(buf, n_words=None):
     holds only those before the node section (the validator reads the header and the robot tables alone)."""
     buf = np.ascontiguousarray(buf, dtype=np.float32)
     check(lib().mpb_sdf_grid_check(buf.ctypes.data_as(ctypes.c_void_p), int(buf.size if n_words is None else n_words)), 'mpb_sdf_grid_check')
+
+
+def mesh_check(buf):
+    """Validate a packed triangle-mesh buffer (numpy fp32, geometry.pack_mesh) on the host side of the C-ABI."""
+    buf = np.ascontiguousarray(buf, dtype=np.float32)
+    check(lib().mpb_mesh_check(buf.ctypes.data_as(ctypes.c_void_p), int(buf.size)), 'mpb_mesh_check')
 
 
 def geom_flags(buf):

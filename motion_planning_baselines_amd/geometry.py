@@ -474,6 +474,150 @@ def pack_self_collision(robot, field):
     return buf
 
 
+class TriangleMesh:
+    """A triangle mesh as the source of a GridSDFField (GridSDFField.from_mesh): `vertices` (nv, 3), `faces` (nt, 3) vertex indices,
+    triangles counter-clockwise seen from outside.  The vertices are kept as the fp32 numbers the packed buffer carries; every check
+    below is taken in fp64 on THOSE.  signed=True: a closed, consistently oriented surface, the grid's node value carries the sign
+    (inside negative).  signed=False: any triangle soup -- open surfaces, scans --, node value distance - thickness.
+
+    Refused, by ValueError: non-finite vertices; indices out of range; more than MESH_MAX_TRIS = 2^20 triangles; a triangle of zero
+    area; for a signed mesh a directed edge that occurs twice (not consistently oriented) or whose reverse does not occur exactly once
+    (not closed), and a negative total signed volume (oriented inside out)."""
+
+    def __init__(self, vertices, faces, signed=True, thickness=0.0):
+        from .mesh_layout import MESH_MAX_TRIS
+        v = np.asarray(vertices, dtype=np.float64)
+        f = np.asarray(faces)
+        if v.ndim != 2 or v.shape[1] != 3 or f.ndim != 2 or f.shape[1] != 3 or f.shape[0] < 1:
+            raise ValueError(f'TriangleMesh: vertices of shape {v.shape} and faces of shape {f.shape}, expected (nv, 3) and (nt >= 1, 3)')
+        if not np.issubdtype(f.dtype, np.integer):
+            raise ValueError('TriangleMesh: faces must be integer vertex indices')
+        if not np.all(np.isfinite(v)) or not np.all(np.isfinite(v.astype(np.float32))):
+            raise ValueError('TriangleMesh: non-finite vertices')
+        f = f.astype(np.int64)
+        if f.min() < 0 or f.max() >= v.shape[0]:
+            raise ValueError(f'TriangleMesh: vertex indices out of range 0..{v.shape[0] - 1}')
+        if f.shape[0] > MESH_MAX_TRIS:
+            raise ValueError(f'TriangleMesh: {f.shape[0]} triangles exceed MESH_MAX_TRIS = {MESH_MAX_TRIS}')
+        self.vertices = np.ascontiguousarray(v.astype(np.float32))
+        self.faces = np.ascontiguousarray(f)
+        self.signed = bool(signed)
+        self.thickness = float(thickness)
+        if not (np.isfinite(self.thickness) and self.thickness >= 0.0) or (self.signed and self.thickness != 0.0):
+            raise ValueError('TriangleMesh: thickness must be finite and >= 0, and 0 for a signed mesh')
+        a, b, c = (self.vertices.astype(np.float64)[f[:, m]] for m in range(3))
+        cross = np.cross(b - a, c - a)
+        area2 = np.linalg.norm(cross, axis=1)
+        if np.any(area2 == 0.0):
+            raise ValueError(f'TriangleMesh: triangle {int(np.argmax(area2 == 0.0))} is degenerate (zero area)')
+        if self.signed:
+            nv = v.shape[0]
+            directed = np.concatenate([f[:, 0] * nv + f[:, 1], f[:, 1] * nv + f[:, 2], f[:, 2] * nv + f[:, 0]])
+            reverse = np.concatenate([f[:, 1] * nv + f[:, 0], f[:, 2] * nv + f[:, 1], f[:, 0] * nv + f[:, 2]])
+            if np.unique(directed).size != directed.size:
+                raise ValueError('TriangleMesh: a directed edge occurs twice: a signed mesh must be consistently oriented')
+            if not np.all(np.isin(reverse, directed)):
+                raise ValueError('TriangleMesh: an edge without its reverse: a signed mesh must be closed')
+            if float(np.einsum('ij,ij->', a, cross)) < 0.0:
+                raise ValueError('TriangleMesh: negative signed volume: the triangles are oriented inside out')
+
+    @property
+    def n_tri(self):
+        return self.faces.shape[0]
+
+    def transformed(self, pose):
+        """The mesh with every vertex taken through [R | t] (fp64, then rounded to fp32)."""
+        P = np.asarray(pose, dtype=np.float64)
+        return TriangleMesh(self.vertices.astype(np.float64) @ P[:3, :3].T + P[:3, 3], self.faces, signed=self.signed, thickness=self.thickness)
+
+
+def mesh_pseudonormals(mesh):
+    """(face (nt, 3), edge (nt, 3, 3), vertex (nt, 3, 3)) fp32 of a TriangleMesh: the unit face normals, per triangle the pseudonormals
+    of its edges ab, bc, ca (sum of the unit normals of the faces on the edge) and of its vertices a, b, c (angle-weighted sum of the
+    normals of the faces at the vertex; Baerentzen and Aanaes).  Computed in fp64 ONCE per edge and per vertex and rounded to fp32:
+    every copy carries identical bits."""
+    v, f = mesh.vertices.astype(np.float64), mesh.faces
+    nv, nt = v.shape[0], f.shape[0]
+    p = v[f]                                                         # (nt, 3, 3)
+    n = np.cross(p[:, 1] - p[:, 0], p[:, 2] - p[:, 0])
+    n /= np.linalg.norm(n, axis=1, keepdims=True)
+    ends = np.stack([f[:, [0, 1]], f[:, [1, 2]], f[:, [2, 0]]], axis=1)           # (nt, 3 edges, 2)
+    key = ends.min(-1) * nv + ends.max(-1)
+    uniq, inv = np.unique(key.reshape(-1), return_inverse=True)
+    edge_sum = np.zeros((uniq.size, 3))
+    np.add.at(edge_sum, inv.reshape(-1), np.repeat(n, 3, axis=0))
+    vert_sum = np.zeros((nv, 3))
+    for m in range(3):
+        e1, e2 = p[:, (m + 1) % 3] - p[:, m], p[:, (m + 2) % 3] - p[:, m]
+        cosang = np.einsum('ij,ij->i', e1, e2) / (np.linalg.norm(e1, axis=1) * np.linalg.norm(e2, axis=1))
+        np.add.at(vert_sum, f[:, m], np.arccos(np.clip(cosang, -1.0, 1.0))[:, None] * n)
+    edge32, vert32 = edge_sum.astype(np.float32), vert_sum.astype(np.float32)
+    return n.astype(np.float32), edge32[inv.reshape(nt, 3)], vert32[f]
+
+
+def _morton30(u):
+    """30-bit Morton codes of points u (n, 3) in [0, 1]^3: 10 bits per axis, x lowest."""
+    q = np.minimum((u * 1024.0).astype(np.int64), 1023)
+    code = np.zeros(q.shape[0], np.int64)
+    for bit in range(10):
+        for axis in range(3):
+            code |= ((q[:, axis] >> bit) & 1) << (3 * bit + axis)
+    return code
+
+
+def pack_mesh(mesh):
+    """Pack a TriangleMesh into ONE self-contained fp32 word buffer (mesh_layout.py: header, triangle records, group boxes).  The
+    triangles are sorted by the Morton code of their centroid in the mesh's box (stable), so that a group of MESH_GROUP consecutive
+    records is spatially compact; the last group is padded by repeating the last record (a repeat is never strictly nearer: it never
+    wins).  A group's box is the minimum and maximum of its records' fp32 vertices -- exact in fp32, so it contains them."""
+    from . import mesh_layout as M
+    v, f = mesh.vertices, mesh.faces
+    nt = f.shape[0]
+    n_face, n_edge, n_vert = mesh_pseudonormals(mesh)
+    v64 = v.astype(np.float64)
+    lo, hi = v64[f].reshape(-1, 3).min(0), v64[f].reshape(-1, 3).max(0)
+    cen = (v64[f].mean(1) - lo) / np.where(hi > lo, hi - lo, 1.0)
+    order = np.argsort(_morton30(cen), kind='stable')
+    rec = np.zeros((nt, M.MESH_TRI_WORDS), np.float32)
+    rec[:, 0:9] = v[f].reshape(nt, 9)
+    rec[:, 9:12] = n_face
+    rec[:, 12:21] = n_edge.reshape(nt, 9)
+    rec[:, 21:30] = n_vert.reshape(nt, 9)
+    rec = rec[order]
+    ng = (nt + M.MESH_GROUP - 1) // M.MESH_GROUP
+    rec = np.concatenate([rec, np.repeat(rec[-1:], ng * M.MESH_GROUP - nt, axis=0)])
+    corners = rec[:, 0:9].reshape(ng, M.MESH_GROUP * 3, 3)
+    boxes = np.zeros((ng, M.MESH_BOX_WORDS), np.float32)
+    boxes[:, 0:3], boxes[:, 4:7] = corners.min(1), corners.max(1)
+    off_tris = M.MESH_HEADER_WORDS
+    off_boxes = off_tris + ng * M.MESH_GROUP * M.MESH_TRI_WORDS
+    total = off_boxes + ng * M.MESH_BOX_WORDS
+    buf = np.zeros((total,), np.float32)
+    hdr = M.header(buf)
+    for name, value in dict(magic=M.MESH_MAGIC, version=M.MESH_VERSION, n_tri=nt, n_groups=ng, signed=int(mesh.signed), thickness=mesh.thickness,
+                            bb_lo=boxes[:, 0:3].min(0), bb_hi=boxes[:, 4:7].max(0), off_tris=off_tris, off_boxes=off_boxes, total=total).items():
+        hdr[name] = value
+    buf[off_tris:off_boxes] = rec.reshape(-1)
+    buf[off_boxes:total] = boxes.reshape(-1)
+    return buf
+
+
+def mesh_pose(pose, who):
+    """A pose [R | t] (3 x 4 or 4 x 4, mesh frame to grid frame) as a contiguous fp32 (3, 4), or None; refused unless R is orthonormal
+    with determinant +1 within 1e-5."""
+    if pose is None:
+        return None
+    P = np.asarray(pose, dtype=np.float64)
+    if P.shape == (4, 4):
+        P = P[:3]
+    if P.shape != (3, 4) or not np.all(np.isfinite(P)):
+        raise ValueError(f'{who}: a pose is a finite 3 x 4 (or 4 x 4) matrix [R | t]')
+    R = P[:, :3]
+    if np.abs(R.T @ R - np.eye(3)).max() > 1e-5 or abs(np.linalg.det(R) - 1.0) > 1e-5:
+        raise ValueError(f'{who}: the rotation of a pose must be orthonormal with determinant +1 within 1e-5')
+    return np.ascontiguousarray(P.astype(np.float32))
+
+
 class GridSDFField:
     """A precomputed grid of signed distances as a collision field (build-defined; the reference's examples build
     their environments with precompute_sdf_obj_fixed=True, sdf_cell_size=...).  Serves arbitrary geometry -- meshes, rounded boxes,
@@ -495,7 +639,9 @@ class GridSDFField:
     GridSDFField.from_field(collision_field, lo, hi, cell): min_o sdf_o of a CollisionField at every node, evaluated ON THE GPU when
     the field is put on a device (ops.DeviceSDFGrid, mpb_sdf_grid_build); `values` stays None on the host.
     GridSDFField.from_occupancy(occupancy, lo, cell): from an occupancy voxel map (a scan), by an exact Euclidean distance transform ON
-    THE GPU (mpb_sdf_grid_build_occupancy, include/mpb.h has the definition); `values` stays None, the occupancy is the field's source."""
+    THE GPU (mpb_sdf_grid_build_occupancy, include/mpb.h has the definition); `values` stays None, the occupancy is the field's source.
+    GridSDFField.from_mesh(mesh, lo, hi, cell): the exact signed distance to triangle meshes (TriangleMesh), each under a pose of its
+    own, ON THE GPU (mpb_sdf_grid_build_mesh, include/mpb.h has the definition); `values` stays None, the source is the mesh list."""
 
     def __init__(self, values, lo, cell, margin=0.05):
         v = np.asarray(values, dtype=np.float32)
@@ -574,6 +720,35 @@ class GridSDFField:
         self._set_frame(lo, cell, margin)
         return self
 
+    @classmethod
+    def from_mesh(cls, mesh, lo, hi, cell, margin=0.05, pose=None, planar=False):
+        """The grid of the exact signed distance to triangle meshes over the box [lo, hi] (dimensions as in from_field): `mesh` is a
+        TriangleMesh, placed by `pose` ([R | t], mesh frame to grid frame; None: as it stands), or a list of (TriangleMesh, pose) whose
+        union is taken (the minimum of their node values).  Node value: include/mpb.h, mpb_sdf_grid_build_mesh -- evaluated on the GPU
+        when the field goes to a device; ops.DeviceSDFGrid.update_mesh rebuilds it there when an object moves.  `values` stays None;
+        the field's `source` is the list of (TriangleMesh, pose as fp32 (3, 4) or None).  planar keeps ONE layer of nodes, at
+        z = lo[2] (0 when lo has two coordinates)."""
+        if isinstance(mesh, TriangleMesh):
+            items = [(mesh, pose)]
+        else:
+            if pose is not None:
+                raise ValueError('GridSDFField.from_mesh: a list of (TriangleMesh, pose) carries its poses, pose= must stay None')
+            items = [tuple(it) for it in mesh]
+        if not items or any(len(it) != 2 or not isinstance(it[0], TriangleMesh) for it in items):
+            raise TypeError('GridSDFField.from_mesh takes a TriangleMesh or a non-empty list of (TriangleMesh, pose)')
+        self = cls.__new__(cls)
+        planar = bool(planar)
+        lo = np.asarray(lo, dtype=np.float64).reshape(-1)
+        hi = np.asarray(hi, dtype=np.float64).reshape(-1)
+        if lo.size != hi.size or lo.size not in (2, 3) or (lo.size == 2 and not planar):
+            raise ValueError('GridSDFField.from_mesh: lo and hi must both have 3 coordinates (2 for a planar grid)')
+        n = [int(math.ceil((hi[a] - lo[a]) / float(np.float32(cell)))) + 1 for a in range(2 if planar else 3)]    # (the cell the header stores)
+        self.dims = cls._check_dims(n[0], n[1], 1 if planar else n[2])
+        self.values = None
+        self.source = [(m, mesh_pose(p, 'GridSDFField.from_mesh')) for m, p in items]
+        self._set_frame(lo, cell, margin)
+        return self
+
     def zero_grad(self):
         pass
 
@@ -602,7 +777,7 @@ def occupancy_bytes(occupancy, who):
 def pack_sdf_grid(robot, field, with_nodes=True):
     """Pack a robot + a GridSDFField into ONE self-contained fp32 word buffer (sdf_layout.py: header, joint_tf rows, links rows -- both
     in the row formats of pack_geometry, every link kept --, then the node section, 16-byte aligned).  The node section holds the
-    field's values; for a field made by from_field / from_occupancy it is left zero for the build kernels to fill on the device.  with_nodes=False
+    field's values; for a field made by from_field / from_occupancy / from_mesh it is left zero for the build kernels to fill on the device.  with_nodes=False
     returns the words BEFORE the node section only (the header's total still counts the nodes): what an upload needs when the nodes
     are built on the device."""
     from . import sdf_layout as S

@@ -13,7 +13,7 @@ import numpy as np
 import torch
 
 from . import _lib, rrt_layout
-from .geometry import KIND_CHAIN, MAX_FIELDS, CollisionField, count_fields, occupancy_bytes, pack_geometry, pack_sdf_grid, pack_self_collision
+from .geometry import KIND_CHAIN, MAX_FIELDS, CollisionField, TriangleMesh, count_fields, mesh_pose, occupancy_bytes, pack_geometry, pack_mesh, pack_sdf_grid, pack_self_collision
 from .geometry import header as geometry_header
 
 
@@ -221,9 +221,10 @@ def self_collision_check(q, sc, with_gap=False, flag=None, gap=None):
 class DeviceSDFGrid(_DeviceMemberBuffer):
     """A robot + a GridSDFField as the packed SDF buffer (geometry.pack_sdf_grid) resident in HBM: packed, validated (mpb_sdf_grid_check)
     and uploaded once -- or, for a field without host values, the header and the robot tables uploaded and the nodes built ON the
-    device from the field's source: a CollisionField (GridSDFField.from_field, mpb_sdf_grid_build) or an occupancy voxel map
-    (GridSDFField.from_occupancy, mpb_sdf_grid_build_occupancy: the bytes uploaded once, a GPU tensor used in place).  `.nodes` is the
-    node section as a (nz, ny, nx) view of the buffer."""
+    device from the field's source: a CollisionField (GridSDFField.from_field, mpb_sdf_grid_build), an occupancy voxel map
+    (GridSDFField.from_occupancy, mpb_sdf_grid_build_occupancy: the bytes uploaded once, a GPU tensor used in place) or triangle meshes
+    (GridSDFField.from_mesh, mpb_sdf_grid_build_mesh: each mesh packed and uploaded once as a DeviceMesh in `.meshes`, update_mesh
+    rebuilds the nodes under new poses).  `.nodes` is the node section as a (nz, ny, nx) view of the buffer."""
     INVALIDATE = 'mpb_sdf_grid_invalidate'
 
     def __init__(self, robot, field, device):
@@ -248,8 +249,33 @@ class DeviceSDFGrid(_DeviceMemberBuffer):
             from .geometry import RobotPointMass
             geom = DeviceGeometry(RobotPointMass(3), field.source, device, use_model=False)
             sdf_grid_build(geom, self)
+        elif built and isinstance(field.source, list):
+            self.meshes = [DeviceMesh(m, device) for m, _ in field.source]
+            self._build_meshes([p for _, p in field.source])
         elif built:
             self.update_occupancy(field.source)
+
+    def _build_meshes(self, poses):
+        for n, (mesh, pose) in enumerate(zip(self.meshes, poses)):
+            sdf_grid_build_mesh(mesh, self, pose=pose, combine=n > 0)
+        return self.nodes
+
+    def update_mesh(self, poses):
+        """Rebuild the node section in place with the objects of a field made by GridSDFField.from_mesh under new poses: `poses` is one
+        pose per object in the field's order ([R | t], mesh frame to grid frame, or None: as the mesh stands), or a single pose (an
+        array) when the field has one object.  Nothing is packed again and nothing is uploaded but the 12 floats per object: the DeviceMesh buffers
+        made at construction are read in place.  The field then holds the new poses in its `source`, so a DeviceSDFGrid made from it
+        later builds THIS placement.  Returns `.nodes`."""
+        if getattr(self, 'meshes', None) is None:
+            raise ValueError('update_mesh: this grid was not built from meshes (GridSDFField.from_mesh)')
+        if poses is None or tuple(getattr(poses, 'shape', ())) in ((3, 4), (4, 4)):      # a single pose (an array, or None)
+            poses = [poses]
+        poses = list(poses)
+        if len(poses) != len(self.meshes):
+            raise ValueError(f'update_mesh: {len(poses)} poses for {len(self.meshes)} objects')
+        poses = [mesh_pose(p, 'DeviceSDFGrid.update_mesh') for p in poses]
+        self.field.source = [(m, p) for (m, _), p in zip(self.field.source, poses)]
+        return self._build_meshes(poses)
 
     def update_occupancy(self, occupancy):
         """Rebuild the node section in place from the next scan: an occupancy map of the same dimensions, as GridSDFField.from_occupancy
@@ -257,12 +283,12 @@ class DeviceSDFGrid(_DeviceMemberBuffer):
         the bytes are only read, a read-only numpy array -- a memory-mapped scan -- is fine).  The header does not change.  A field made
         by from_occupancy then holds the new scan as its `source`, so a DeviceSDFGrid made from it later (another device, a
         PlanningTask built afterwards) builds THIS scan; under a field with host `values` or one made by from_field only this device
-        buffer changes, the field keeps what it held.  Returns `.nodes`."""
+        buffer changes, the field keeps what it held; so does one made by from_mesh.  Returns `.nodes`."""
         occ = occupancy_bytes(occupancy, 'DeviceSDFGrid.update_occupancy')
         nx, ny, nz = self.dims
         if tuple(occ.shape) != (nz, ny, nx):
             raise ValueError(f'update_occupancy: occupancy of shape {tuple(occ.shape)}, the grid has (nz, ny, nx) = {(nz, ny, nx)}')
-        if self.field.values is None and not isinstance(self.field.source, CollisionField):
+        if self.field.values is None and not isinstance(self.field.source, (CollisionField, list)):     # (a list: from_mesh)
             self.field.source = occ
         if not isinstance(occ, torch.Tensor):
             with warnings.catch_warnings():        # (torch warns that a read-only array could be written through the tensor: it is only uploaded)
@@ -294,6 +320,41 @@ def sdf_grid_build_occupancy(occupancy, sdf):
     _chk(occupancy, (nz, ny, nx), 'occupancy', dtype=occupancy.dtype)
     _chk(sdf.buf, sdf.buf.shape, 'sdf.buf')
     _lib.check(_lib.lib().mpb_sdf_grid_build_occupancy(_ptr(occupancy), _ptr(sdf.buf), _stream()), 'mpb_sdf_grid_build_occupancy')
+    return sdf.nodes
+
+
+class DeviceMesh(_DeviceMemberBuffer):
+    """A TriangleMesh as the packed mesh buffer (geometry.pack_mesh) resident in HBM: packed, validated (mpb_mesh_check) and uploaded
+    once; what mpb_sdf_grid_build_mesh reads.  (The library forgets both kinds of buffer an address held through mpb_sdf_grid_invalidate.)"""
+    INVALIDATE = 'mpb_sdf_grid_invalidate'
+
+    def __init__(self, mesh, device):
+        from .mesh_layout import header as mesh_header
+        if not isinstance(mesh, TriangleMesh):
+            raise TypeError('DeviceMesh takes a geometry.TriangleMesh')
+        self.mesh = mesh
+        self.host = pack_mesh(mesh)
+        _lib.mesh_check(self.host)
+        hdr = mesh_header(self.host)
+        self.n_tri, self.n_groups = int(hdr['n_tri']), int(hdr['n_groups'])
+        self._adopt(torch.from_numpy(self.host.copy()).to(device))
+
+
+@_on_tensor_device
+def sdf_grid_build_mesh(mesh, sdf, pose=None, combine=False, cull=True):
+    """Fill the node section of a DeviceSDFGrid with the exact (signed) distance to a DeviceMesh placed by `pose` ([R | t], mesh frame to
+    grid frame, 3 x 4 or 4 x 4; None: as the mesh stands) -- mpb_sdf_grid_build_mesh, include/mpb.h has the definition.  combine: the
+    node becomes min(what it holds, the new value) (MPB_MESH_MIN: the union with what was built before); cull=False visits every
+    group of triangles (MPB_MESH_NO_CULL: the same bits, slower).  Returns sdf.nodes."""
+    from .mesh_layout import MESH_MIN, MESH_NO_CULL
+    if not isinstance(mesh, DeviceMesh) or not isinstance(sdf, DeviceSDFGrid):
+        raise TypeError('sdf_grid_build_mesh takes a DeviceMesh and a DeviceSDFGrid')
+    _chk(mesh.buf, mesh.buf.shape, 'mesh.buf')
+    _chk(sdf.buf, sdf.buf.shape, 'sdf.buf')
+    flags = (0 if cull else MESH_NO_CULL) | (MESH_MIN if combine else 0)
+    P = mesh_pose(pose, 'sdf_grid_build_mesh')
+    _lib.check(_lib.lib().mpb_sdf_grid_build_mesh(_ptr(mesh.buf), None if P is None else P.ctypes.data_as(ctypes.c_void_p), _ptr(sdf.buf),
+                                                  int(flags), _stream()), 'mpb_sdf_grid_build_mesh')
     return sdf.nodes
 
 
