@@ -963,6 +963,52 @@ int mpb_rrt_star_run(void *workspace, size_t workspace_bytes, const float *geom,
                      int n_iters_after_success, int informed, float step_size, float n_radius, float goal_prob,
                      float cost_eps, float eps, uint64_t seed, uint32_t problem_offset, void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Batched path shortcutting -- the pass between the tree and the optimiser (pybullet-planning's smooth_path, OMPL's
+ * PathSimplifier; the reference did not carry it over: build-defined).  One launch, one single-wave
+ * workgroup per path, the path in LDS; no atomics and a fixed order: the same bits on every run, and a path's bits depend
+ * on its own inputs only.
+ * paths_in (N,Lmax,D), lengths_in (N): the batch mpb_rrt_*_run writes and mpb_traj_resample reads.  paths_out, lengths_out:
+ *   the edited batch; paths_out == paths_in is allowed (in place; otherwise the two do not overlap).  Rows at and past a
+ *   path's length are written as zeros.  The first and the last row of a path keep their input bits.  A path of fewer than
+ *   3 nodes passes through; lengths_in[b] outside 0 .. Lmax: lengths_out[b] = 0, NaN in all four stats, a zeroed path.
+ * A path of current length L >= 3 runs n_iters iterations; iteration i:
+ *   draws u1, u2 in [0,1): draws == NULL -> one Philox4x32-10 call (counter = (problem_offset + b, i, tag, 0), key = seed;
+ *     the tag is this entry point's own), u = (top 24 bits of .x, .y) * 2^-24; else (N, n_iters, 2) fp32 recorded draws,
+ *     clamped into [0,1), NaN read as 0.
+ *   position of a draw: s = fl32(u * (float)(L-1)), a = min((int)s, L-2), t = s - (float)a; the two ordered so that
+ *     (a1,t1) <= (a2,t2).  a1 == a2: SKIP.
+ *   point of a position: q_a + t * (q_{a+1} - q_a), rounded after each operation (no fma).  t == 0, or a point allclose
+ *     (torch.allclose's defaults, the point against the node) to node a, IS node a; else a point allclose to node a+1 is
+ *     that node.  With lo the last node at or before point 1 and hi the first node at or after point 2: hi - lo < 2
+ *     (both on one segment) or the two points allclose: SKIP.
+ *   candidate P1 -> P2: checked as mpb_rrt_connect_run checks an extension, without its n_radius clamp: dist the
+ *     sequential fp32 sum in index order, n_pts = (int)(dist / check_step) + 2 points of extend_path's linspace (more than
+ *     2^20: SKIP), a point in collision iff mpb_collision_check says so; the scan stops after the 64 points that hold the
+ *     first hit.  A hit: REJECT with the index of the first point in collision.
+ *   free: nodes lo+1 .. hi-1 are replaced by the points that are no nodes (0, 1 or 2 rows), ACCEPT; unless the new length
+ *     would exceed Lmax (one node replaced by two on a full path): OVERFLOW, nothing changes.
+ * stats (N,4) fp32: candidates checked (REJECT + OVERFLOW + ACCEPT), accepted, the joint-space length before and after
+ *   (the distances above summed in fp32 in path order).  log (N,n_iters) int32, optional (may be NULL):
+ *   MPB_SHORTCUT_* | (first index << MPB_SHORTCUT_LOG_INDEX_SHIFT); IDLE: the path had fewer than 3 nodes.
+ * Refusals, in this order, all before the first HIP call: D > MPB_MAX_DOF: MPB_E_UNSUPPORTED; N < 0 or D < 1; Lmax < 2 or
+ *   4 * Lmax * Dp bytes (Dp = D rounded up to 4) beyond the 160 KB of LDS less the 17 408 bytes of the staged grid -- Lmax
+ *   at most 9152 / 4576 / 3050 for Dp = 4 / 8 / 12; n_iters < 0 or > MPB_SHORTCUT_MAX_ITERS; check_step not finite or <= 0;
+ *   a null required pointer; geom not 16-byte aligned: MPB_E_INVALID.  N == 0: MPB_OK, nothing launched; n_iters == 0:
+ *   MPB_OK, the outputs are a copy (stats: 0, 0, length, length).  Nothing more is refused: geom is device memory.
+ * ------------------------------------------------------------------------------------------- */
+#define MPB_SHORTCUT_IDLE 0
+#define MPB_SHORTCUT_SKIP 1
+#define MPB_SHORTCUT_REJECT 2
+#define MPB_SHORTCUT_OVERFLOW 3
+#define MPB_SHORTCUT_ACCEPT 4
+#define MPB_SHORTCUT_LOG_INDEX_SHIFT 8
+#define MPB_SHORTCUT_MAX_ITERS 1048576
+int mpb_path_shortcut(const float *paths_in, const int *lengths_in, float *paths_out, int *lengths_out,
+                      float *stats, int *log, const float *geom, int geom_flags, const float *draws,
+                      int N, int Lmax, int D, int n_iters, float check_step,
+                      uint64_t seed, uint32_t problem_offset, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1623,3 +1623,43 @@ def rrt_star_tree(ws):
     `rewires`, `informed_rejections`, `best_cost_iters`, `iters_after_first_success`, and the first success: `first_cost`,
     `first_iter`, `first_count` (all (B,))."""
     return _rrt_read('star', ws, hidden=('goal_q', 'cand', 'best_cost_eps'))
+
+
+# ---- path shortcutting between the tree and the optimiser (csrc/mpb_path_shortcut.hip) ---------------------------------------------
+# include/mpb.h MPB_SHORTCUT_*: the codes of the log's low bits, the shift of the first-collision index, the bound of n_iters
+SHORTCUT_CODES = ('IDLE', 'SKIP', 'REJECT', 'OVERFLOW', 'ACCEPT')
+SHORTCUT_IDLE, SHORTCUT_SKIP, SHORTCUT_REJECT, SHORTCUT_OVERFLOW, SHORTCUT_ACCEPT = range(5)
+SHORTCUT_LOG_INDEX_SHIFT, SHORTCUT_MAX_ITERS = 8, 1 << 20
+SHORTCUT_PHILOX_TAG = 0x53484354                # word 2 of the Philox counter (csrc/mpb_path_shortcut.hip SC_TAG)
+
+
+@_on_tensor_device
+def path_shortcut(paths, lengths, geom, n_iters, check_step, draws=None, seed=0, problem_offset=0, with_log=False, out=None):
+    """Shortcut N padded polylines (paths (N, Lmax, D), lengths (N,) int32 -- what optimize_batched of the RRT planners returns) in
+    one launch (mpb_path_shortcut; include/mpb.h has the definition): n_iters times per path two draws pick two points on the
+    polyline, and the nodes between them are replaced by the straight segment when that is collision-free at spacing check_step.
+    draws: None (device Philox; path b draws from stream problem_offset + b of `seed`) or (N, n_iters, 2) fp32 recorded uniforms.
+    out: None (new tensors) or (paths, lengths) to write into; out[0] may be `paths` itself (in place).
+    Returns (paths, lengths, stats (N, 4) fp32: candidates checked, accepted, length before, length after[, log (N, n_iters) int32:
+    SHORTCUT_* | first index in collision << SHORTCUT_LOG_INDEX_SHIFT])."""
+    if not (isinstance(paths, torch.Tensor) and paths.dim() == 3):
+        raise ValueError(f'paths has shape {tuple(getattr(paths, "shape", ()))}, expected (N, Lmax, D)')
+    N, Lmax, D = paths.shape
+    _chk(paths, (N, Lmax, D), 'paths')
+    _chk(lengths, (N,), 'lengths', dtype=torch.int32)
+    if D != geom.n_dof:
+        raise ValueError(f'paths has {D} columns, the geometry {geom.n_dof} degrees of freedom')
+    n_iters = int(n_iters)
+    _chk(draws, (N, n_iters, 2), 'draws', allow_none=True)
+    if out is None:
+        paths_out, lengths_out = torch.empty_like(paths), torch.empty_like(lengths)
+    else:
+        paths_out, lengths_out = out
+        _chk(paths_out, (N, Lmax, D), 'out[0]')
+        _chk(lengths_out, (N,), 'out[1]', dtype=torch.int32)
+    stats = torch.empty(N, 4, device=paths.device, dtype=torch.float32)
+    log = torch.empty(N, max(n_iters, 0), device=paths.device, dtype=torch.int32) if with_log else None
+    _lib.check(_lib.lib().mpb_path_shortcut(_ptr(paths), _ptr(lengths), _ptr(paths_out), _ptr(lengths_out), _ptr(stats), _ptr(log),
+                                            _ptr(geom.buf), int(geom.flags), _ptr(draws), N, Lmax, D, n_iters, float(check_step),
+                                            _seed64(seed), int(problem_offset) & 0xFFFFFFFF, _stream()), 'mpb_path_shortcut')
+    return (paths_out, lengths_out, stats, log) if with_log else (paths_out, lengths_out, stats)

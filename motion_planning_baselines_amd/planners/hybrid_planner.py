@@ -17,6 +17,10 @@ into mpb_traj_resample -- no host round trip, no padding loop; a problem without
 start -> goal, written on the device (hybrid_planner.py:47-51).  Any other sample-based planner stays the caller's
 (duck-typed: ``optimize(refill_samples_buffer=True, ...) -> list of (n_i, D) tensors or None``, ``start_state_pos``,
 ``goal_state_pos``) and takes the list path below.
+
+``shortcut_iters > 0`` puts the shortcut pass every sample-based stack has (pybullet-planning's ``smooth_path``, OMPL's
+``PathSimplifier``; the reference did not carry it over) between the two halves: one launch of mpb_path_shortcut over all paths, so
+that mpb_traj_resample spends its support points on the shortened polylines and not on the tree's zig-zag.
 """
 import torch
 
@@ -26,11 +30,15 @@ from .base import MPPlanner, require_cuda
 
 class HybridPlanner(MPPlanner):
 
-    def __init__(self, sample_based_planner, opt_based_planner, **kwargs):
+    def __init__(self, sample_based_planner, opt_based_planner, shortcut_iters=0, shortcut_step=None, **kwargs):
+        """shortcut_iters > 0: that many shortcut attempts per path (mpb_path_shortcut) between the sample-based planner and the
+        resampling, checked at spacing shortcut_step (None: the sample-based planner's step_size)."""
         super().__init__("HybridSampleAndOptimizationPlanner", **kwargs)
         self.sample_based_planner = sample_based_planner
         self.opt_based_planner = opt_based_planner
         self.device = require_cuda(self.tensor_args)
+        self.shortcut_iters, self.shortcut_step = int(shortcut_iters), shortcut_step
+        self.shortcut_stats = None                                # (N, 4) of the last optimize() that shortcut
 
     def render(self, ax, **kwargs):
         raise NotImplementedError
@@ -47,11 +55,24 @@ class HybridPlanner(MPPlanner):
             paths.append(torch.as_tensor(traj, dtype=torch.float32).reshape(-1, traj.shape[-1]))
         N, D = len(paths), paths[0].shape[-1]
         Lmax = max(p.shape[0] for p in paths)
+        if self.shortcut_iters > 0:
+            Lmax += 1                                             # (room for the one node a corner cut adds)
         padded = torch.zeros(N, Lmax, D, dtype=torch.float32)
         for i, p in enumerate(paths):
             padded[i, :p.shape[0]] = p.to('cpu') if not p.is_cuda else p.cpu()
         lengths = torch.tensor([p.shape[0] for p in paths], dtype=torch.int32)
-        out = ops.traj_resample(padded.to(self.device), lengths.to(self.device), H, dt)
+        padded, lengths = padded.to(self.device), lengths.to(self.device)
+        if self.shortcut_iters > 0:
+            task = getattr(self.opt_based_planner, 'task', None)
+            if task is None or not hasattr(task, 'shortcut_paths'):
+                raise NotImplementedError('HybridPlanner(shortcut_iters > 0): the sample-based planner hands its paths over as a list '
+                                          'and offers no shortcut(), and the optimisation-based planner carries no PlanningTask '
+                                          '(`task`) to check shortcuts against')
+            step = self.shortcut_step if self.shortcut_step is not None else getattr(self.sample_based_planner, 'step_size', None)
+            if step is None:
+                raise ValueError('HybridPlanner(shortcut_iters > 0): the sample-based planner has no step_size, give shortcut_step')
+            padded, lengths, self.shortcut_stats = task.shortcut_paths(padded, lengths, n_iters=self.shortcut_iters, check_step=step)
+        out = ops.traj_resample(padded, lengths, H, dt)
         return out.unsqueeze(0)                                   # 'n h d -> 1 n h d' (:64)
 
     def batched_paths_to_initial_means(self, paths, lengths):
@@ -73,6 +94,12 @@ class HybridPlanner(MPPlanner):
     def optimize(self, debug=False, print_times=False, return_iterations=False, **kwargs):
         if hasattr(self.sample_based_planner, 'optimize_batched'):
             paths, lengths, _ = self.sample_based_planner.optimize_batched(**kwargs)
+            if self.shortcut_iters > 0:
+                if not hasattr(self.sample_based_planner, 'shortcut'):
+                    raise NotImplementedError('HybridPlanner(shortcut_iters > 0): the sample-based planner offers optimize_batched() '
+                                              'but no shortcut(paths, lengths, n_iters, check_step)')
+                paths, lengths, self.shortcut_stats = self.sample_based_planner.shortcut(paths, lengths, self.shortcut_iters,
+                                                                                         check_step=self.shortcut_step)
             means = self.batched_paths_to_initial_means(paths, lengths)
         else:
             traj_l = self.sample_based_planner.optimize(refill_samples_buffer=True, debug=debug, **kwargs)

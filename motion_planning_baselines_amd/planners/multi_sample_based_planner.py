@@ -20,6 +20,10 @@ class MultiSampleBasedPlanner:
         """(paths, lengths, status) of the n_trajectories copies (times the planner's own problems), on the device."""
         return self.planner.optimize_batched(n_copies=self.n_trajectories, **kwargs)
 
+    def shortcut(self, paths, lengths, n_iters, check_step=None, **kwargs):
+        """The planner's shortcut() on the (paths, lengths) of optimize_batched."""
+        return self.planner.shortcut(paths, lengths, n_iters, check_step=check_step, **kwargs)
+
     def optimize(self, **kwargs):
         """List of n_trajectories paths ((n, D) tensors) or None."""
         paths, lengths, _ = self.optimize_batched(**kwargs)

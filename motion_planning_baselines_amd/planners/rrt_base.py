@@ -109,6 +109,14 @@ class RRTBase(MPPlanner):
                            f'PATH_TOO_LONG); construct the planner with a larger max_path_nodes')
         return out
 
+    def shortcut(self, paths, lengths, n_iters, check_step=None, **kwargs):
+        """Shortcut the (paths, lengths) of optimize_batched on the planner's task (PlanningTask.shortcut_paths): ->
+        (paths, lengths, stats).  check_step defaults to step_size, the density the planner's own edges were checked at; path b
+        draws from the stream of `seed` (default: the planner's) its problem index names."""
+        kwargs.setdefault('seed', self.seed)
+        return self.task.shortcut_paths(paths, lengths, n_iters=n_iters, check_step=self.step_size if check_step is None else check_step,
+                                        **kwargs)
+
     def optimize(self, opt_iters=None, **observation):
         """One problem: the (n, D) path or None like the reference; several: a list of those."""
         paths, lengths, status = self.optimize_batched(**observation)

@@ -336,6 +336,16 @@ class PlanningTask:
         _, (count, _, _) = self._trajs_stats(trajs, kwargs.get('num_interpolation', 5))
         return 1 if bool((count == 0).any()) else 0
 
+    # ---- shortcutting of a path batch (build-defined: DESIGN.md 10) ------------------------------------------------------------
+    def shortcut_paths(self, paths, lengths, n_iters=64, check_step=0.05, **kwargs):
+        """(paths (N, Lmax, D), lengths (N,) int32) device tensors -> (paths, lengths, stats (N, 4)): n_iters shortcut attempts
+        per path against this task's obstacle geometry, checked at spacing check_step (ops.path_shortcut, which also takes the
+        keyword arguments draws, seed, problem_offset, with_log, out).  The in-kernel predicate knows obstacles only: a task with
+        a self_field or an sdf_field is refused by name."""
+        self.require_no_self_field('path shortcutting (mpb_path_shortcut)')
+        self.require_no_sdf_field('path shortcutting (mpb_path_shortcut)')
+        return ops.path_shortcut(paths, lengths, self.geom, n_iters, check_step, **kwargs)
+
 
 class IKResult:
     """What PlanningTask.inverse_kinematics returns: q (N, S, D), converged / free bool (N, S) (free = converged and not in collision
