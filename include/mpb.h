@@ -181,8 +181,9 @@ int mpb_cost_terms_grad(float *trajs, const float *grad_in, float *grad_out, con
  *   mpb_traj_resample          -- the warm start of HybridPlanner.optimize (hybrid_planner.py:42-66, over the
  *                                 external smoothen_trajectory / tensor_linspace_v1): N polylines of
  *                                 lengths[n] <= Lmax waypoints (paths (N,Lmax,D), rows beyond the length
- *                                 ignored) -> out (N,H,2D): H points uniform in arc length, linear in
- *                                 between, velocity = (last - first)/((H-1) dt) on interior points, 0 at ends.
+ *                                 ignored and never read; a length outside 1 .. Lmax is clamped into it)
+ *                                 -> out (N,H,2D): H points uniform in arc length, linear in between,
+ *                                 velocity = (last - first)/((H-1) dt) on interior points, 0 at ends.
  * ------------------------------------------------------------------------------------------- */
 int mpb_traj_resample(const float *paths, const int *lengths, float *out, int N, int Lmax, int H, int D, float dt,
                       void *stream);

@@ -333,8 +333,10 @@ __global__ __launch_bounds__(256) void traj_interpolate_kernel(const float* __re
     }
 }
 
+// velocities: the difference and 1 / 2dt in fp64, rounded once (an fp32 reciprocal and product cost three roundings of a value two
+// neighbours nearly cancel in)
 __global__ __launch_bounds__(256) void traj_fd_kernel(const float* __restrict__ pos, float* __restrict__ out, size_t total,
-                                                      int H, int D, float inv_2dt) {
+                                                      int H, int D, double inv_2dt) {
     for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (size_t)gridDim.x * blockDim.x) {
         const size_t row = e / (2 * D);
         const int i = (int)(e - row * 2 * D);
@@ -345,7 +347,7 @@ __global__ __launch_bounds__(256) void traj_fd_kernel(const float* __restrict__ 
             v = p[i];
         } else {
             const int j = i - D;
-            v = (t >= 1 && t + 1 < H) ? (p[D + j] - p[j - D]) * inv_2dt : 0.f;
+            v = (t >= 1 && t + 1 < H) ? (float)(((double)p[D + j] - (double)p[j - D]) * inv_2dt) : 0.f;
         }
         out[e] = v;
     }
@@ -373,7 +375,7 @@ extern "C" int mpb_traj_finite_difference(const float* pos, float* out, int B, i
     if (!pos || !out) return mpb_fail(MPB_E_INVALID, "mpb_traj_finite_difference: null pointer");
     const size_t total = (size_t)B * H * 2 * D;
     hipLaunchKernelGGL(traj_fd_kernel, dim3(stream_grid(total)), dim3(256), 0, (hipStream_t)stream, pos, out, total, H, D,
-                       1.f / (2.f * dt));
+                       1.0 / (2.0 * (double)dt));
     return mpb_check_launch("mpb_traj_finite_difference");
 }
 

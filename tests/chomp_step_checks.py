@@ -232,7 +232,8 @@ def same_bits(a, b):
 
 
 # ------------------------------------------------------------------------------------------------
-# the composite route: cost_terms_grad(apply=True) with a given incoming gradient and no cost term
+# the composite route: cost_terms_grad(apply=True) with a given incoming gradient and no cost term -- or, for
+# tests/test_gpu_cost_terms_elements.py, with the terms of tests/cost_terms_checks.py on
 # ------------------------------------------------------------------------------------------------
 COMPOSITE_SCENE = 'arm5'
 COMPOSITE_CASES = [(H, dmul, clipped) for H in (37, 150) for dmul in (1, 2) for clipped in (False, True)]
@@ -244,10 +245,20 @@ def _ulp32(t):
     return (torch.nextafter(t32, torch.full_like(t32, float('inf'))) - t32).double()
 
 
+COMPOSITE_TERM_CASES = [(H, dmul, clipped) for H in (37, 150, 256) for dmul in (2, 1) for clipped in (False, True)]
+COMPOSITE_TERMS = {2: 'all', 1: 'gp+smooth+jlim-fd'}     # cost_terms_checks.CONFIGS: stored velocities, finite-difference ones
+
+
 @functools.lru_cache(maxsize=None)
-def composite_reference(H, dmul, clipped):
+def composite_reference(H, dmul, clipped, terms=None):
     """x0 - lr * mask(clamp(grad_in + 2 B w (R x0))) in fp64 and in plain fp32; grad_in random at the scale of the scene's |g64|.
-    The unit is the prior-only one plus lr * ulp(grad_in): the sum is rounded to fp32 once more before the clamp."""
+    The unit is the prior-only one plus lr * ulp(grad_in): the sum is rounded to fp32 once more before the clamp.
+
+    terms: None, or a configuration of cost_terms_checks.CONFIGS switched on in the same call (the composite's last group).  The
+    incoming gradient of both restatements is then grad_in + g_terms64 (the oracle's fp64 gradient of the terms, jl_scale = B), which
+    the fp32 one rounds to fp32 once -- the kernel carries the terms in fp64 and rounds their sum with grad_in once -- and the unit's
+    ulp term is taken at that sum.  Under VEL_FD the unit also carries lr times the fp32 V tile's term of the gradient bar
+    (cost_terms_checks' docstring), the one fp32 rounding inside the terms that the contract names.  ns.spec: the terms' arguments."""
     bs = base(COMPOSITE_SCENE, H)
     D = bs.robot.q_dim
     d = dmul * D
@@ -257,10 +268,18 @@ def composite_reference(H, dmul, clipped):
     grad_in = (scale * torch.randn(K.B, H, d, generator=gen)).contiguous()
     interior = torch.zeros(K.B, H, d, dtype=torch.bool)
     interior[:, 1:-1] = True
-    unit = (unit_of(bs, x0, 0.0, W_PRIOR, K.B) + LR * _ulp32(grad_in.double())) * interior
+    incoming, extra, tref = grad_in.double(), 0.0, None
+    if terms is not None:
+        import cost_terms_checks as T
+        tref = T.reference(T.step_problem(H), terms)
+        assert tref.dmul == dmul and torch.equal(tref.x, x0) and tref.jl_scale == K.B
+        incoming = incoming + tref.g64
+        extra = LR * tref.vterm
+    unit = (unit_of(bs, x0, 0.0, W_PRIOR, K.B) + LR * _ulp32(incoming) + extra) * interior
 
     def run(dtype, clip):
-        x, R, gi = x0.to(dtype), bs.R.to(dtype), grad_in.to(dtype)
+        x, R = x0.to(dtype), bs.R.to(dtype)
+        gi = grad_in.to(dtype) if terms is None else incoming.to(dtype)
         g = gi + 2.0 * K.B * W_PRIOR * (R @ x)
         gc = g.clamp(-clip, clip) * interior
         return x + (-LR * gc), g * interior
@@ -270,7 +289,7 @@ def composite_reference(H, dmul, clipped):
     Eu = float(((x32u.double() - x64u).abs()[interior] / unit[interior]).max())
     ns = types.SimpleNamespace(H=H, D=D, d=d, x0=x0, R=bs.R, grad_in=grad_in, unit=unit, interior=interior, zero=~interior, g64=g64,
                                prior_bw=K.B * W_PRIOR, grad_clip=NO_CLIP, x64=x64u, x32=x32u, judged=interior, clamped=None,
-                               undecided_share=0.0, E32_unclipped=Eu)
+                               undecided_share=0.0, E32_unclipped=Eu, terms=terms, tref=tref)
     if clipped:
         clip = 2.0 ** round(float(torch.log2(g64.abs()[interior].median())))
         ns.grad_clip = clip
