@@ -1010,6 +1010,72 @@ int mpb_path_shortcut(const float *paths_in, const int *lengths_in, float *paths
                       int N, int Lmax, int D, int n_iters, float check_step,
                       uint64_t seed, uint32_t problem_offset, void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Batched PRM -- one roadmap of collision-free configurations, many start / goal queries (the reference has no roadmap
+ * planner: build-defined).  Three launches: the K nearest nodes, the edges' segment scans, the queries.
+ * Arithmetic shared by all three, rounded after every operation (no fma): d2(x, y) the sequential fp32 sum over the joints
+ * in index order of fl(fl(x_k - y_k)^2); dist = sqrtf(d2), the distance of the shortcut pass above.
+ *
+ * mpb_prm_knn: queries (Q,D), nodes (M,D) -> idx (Q,K) int32, dist (Q,K) fp32: row i holds the K nodes of smallest d2 to
+ *   query i in ascending order of (d2, index); a NaN d2 orders as +inf (and is written as +inf).  exclude_self != 0: the
+ *   queries ARE the nodes (Q == M) and node i is left out of row i.
+ *   Refusals, in this order, before the first HIP call: Q < 0 or D < 1: MPB_E_INVALID; D > MPB_MAX_DOF, M >
+ *   MPB_PRM_MAX_NODES, K > MPB_PRM_MAX_K: MPB_E_UNSUPPORTED; M < 2; exclude_self with Q != M; K < 1 or K > M - (1 with
+ *   exclude_self); a null pointer: MPB_E_INVALID.  Q == 0: MPB_OK, nothing launched.
+ *
+ * mpb_prm_edge_check: pts (P,D), pairs (E,2) int32 -> flag (E) int32, first (E) int32.  Pair (a,b) is scanned from point
+ *   min(a,b) to point max(a,b) -- (a,b) and (b,a) give the same bits -- exactly as the shortcut pass scans a candidate:
+ *   n_pts = (int)fl(dist / check_step) + 2 points of extend_path's linspace, a point in collision iff mpb_collision_check
+ *   says so (chained fields included), the scan stops after the 64 points that hold the first hit.  a == b checks that point.
+ *   flag: MPB_PRM_EDGE_FREE, first -1; MPB_PRM_EDGE_BLOCKED, first the index of the first point in collision;
+ *   MPB_PRM_EDGE_BAD_INDEX: a or b outside 0 .. P-1 (never dereferenced), first -1; MPB_PRM_EDGE_TOO_LONG:
+ *   fl(dist / check_step) not below 2^20 - 1 (a NaN included), first -1.
+ *   Refusals, in this order: E < 0, P < 1 or D < 1: MPB_E_INVALID; D > MPB_MAX_DOF: MPB_E_UNSUPPORTED; check_step not
+ *   finite or <= 0; a null pointer; geom not 16-byte aligned: MPB_E_INVALID.  E == 0: MPB_OK, nothing launched.
+ *
+ * mpb_prm_query: the roadmap as data -- nodes (M,D), nbr (M,K) int32, w (M,K) fp32 -- and per query starts, goals (Q,D), the
+ *   connection tables cs, cg (Q,Kc) int32 with ws, wg (Q,Kc) fp32, and direct (Q) fp32 -> paths (Q,Lmax,D), lengths (Q)
+ *   int32, costs (Q) fp32, status (Q) int32.  No geometry is read.  A table entry is FINITE when its weight's bits are below
+ *   +inf's (0 <= w < +inf, sign clear) and its index lies in 0 .. M-1; every other entry is absent (the caller writes +inf for
+ *   an edge that is not FREE or is shorter than MPB_PRM_MIN_EDGE: such nodes are duplicates for planning).
+ *   The graph is undirected: each finite entry (i, nbr[i][k], w[i][k]) relaxes both ways.  d is the least fixed point of
+ *   d[v] = min(init[v], min_u fl(d[u] + w_uv)), init[v] the smallest finite ws entry that names v (+inf: none); sweeps run
+ *   until one changes nothing (at most M).  fl(+) is monotone, so the fixed point -- the same bits on every run -- does not
+ *   depend on the order of the relaxations.  The goal's cost is c = min_k fl(d[cg_k] + wg_k) over the finite entries, ties to
+ *   the smallest k; the path is walked back from that cg_k after convergence, from d alone: the predecessor of v is the start
+ *   when init[v] == d[v], else the smallest-index neighbour u with fl(d[u] + w_uv) == d[v] and d[u] < d[v] (d falls strictly
+ *   along the walk: it cannot loop).  paths: start, the nodes, goal; rows at and past the length are zeros.
+ *   status: MPB_PRM_OK; MPB_PRM_NO_START / MPB_PRM_NO_GOAL: no finite ws / wg entry; MPB_PRM_DISCONNECTED: no finite c;
+ *   MPB_PRM_PATH_TOO_LONG: the path has more than Lmax rows; MPB_PRM_DEGENERATE: a node of the walk has no predecessor
+ *   (weights so small against d that fl(d + w) == d).  Every status but OK: lengths 0, costs +inf, a zeroed path.
+ *   A finite direct[q] (the start-goal distance where that segment is free, else +inf) wins before anything else: the path
+ *   [start, goal], cost direct, MPB_PRM_OK.
+ *   Refusals, in this order: Q < 0 or D < 1: MPB_E_INVALID; D > MPB_MAX_DOF, M > MPB_PRM_MAX_NODES, K or Kc >
+ *   MPB_PRM_MAX_K: MPB_E_UNSUPPORTED; M < 2; K < 1 or Kc < 1; Lmax outside 2 .. MPB_PRM_MAX_PATH_ROWS; a null pointer:
+ *   MPB_E_INVALID.  Q == 0: MPB_OK, nothing launched.
+ * ------------------------------------------------------------------------------------------- */
+#define MPB_PRM_MAX_NODES 16384
+#define MPB_PRM_MAX_K 32
+#define MPB_PRM_MAX_PATH_ROWS 1048576
+#define MPB_PRM_MIN_EDGE 1e-4f
+#define MPB_PRM_EDGE_FREE 0
+#define MPB_PRM_EDGE_BLOCKED 1
+#define MPB_PRM_EDGE_BAD_INDEX 2
+#define MPB_PRM_EDGE_TOO_LONG 3
+#define MPB_PRM_OK 0
+#define MPB_PRM_NO_START 1
+#define MPB_PRM_NO_GOAL 2
+#define MPB_PRM_DISCONNECTED 3
+#define MPB_PRM_PATH_TOO_LONG 4
+#define MPB_PRM_DEGENERATE 5
+int mpb_prm_knn(const float *queries, const float *nodes, int *idx, float *dist, int Q, int M, int D, int K,
+                int exclude_self, void *stream);
+int mpb_prm_edge_check(const float *pts, const int *pairs, int *flag, int *first, const float *geom, int geom_flags,
+                       int P, int E, int D, float check_step, void *stream);
+int mpb_prm_query(const float *nodes, const int *nbr, const float *w, const float *starts, const float *goals,
+                  const int *cs, const float *ws, const int *cg, const float *wg, const float *direct, float *paths,
+                  int *lengths, float *costs, int *status, int Q, int M, int K, int Kc, int D, int Lmax, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

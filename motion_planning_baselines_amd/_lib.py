@@ -93,6 +93,9 @@ SIGNATURES = {
     'mpb_rrt_star_init': [_p, ctypes.c_size_t, _p, _p, _p, _i, _i, _i, _i, _i, _p],
     'mpb_rrt_star_run': [_p, ctypes.c_size_t, _p, _i, _p, ctypes.c_size_t] + [_p] * 6 + [_i] * 11 + [_f] * 5 + [_u64, _u32, _p],
     'mpb_path_shortcut': [_p] * 7 + [_i, _p] + [_i] * 4 + [_f, _u64, _u32, _p],
+    'mpb_prm_knn': [_p] * 4 + [_i] * 5 + [_p],
+    'mpb_prm_edge_check': [_p] * 5 + [_i] * 4 + [_f, _p],
+    'mpb_prm_query': [_p] * 14 + [_i] * 6 + [_p],
 }
 
 # test aids (include/mpb_debug.h): a separate library, csrc/libmpb_hip_debug.so

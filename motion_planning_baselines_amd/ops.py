@@ -1663,3 +1663,90 @@ def path_shortcut(paths, lengths, geom, n_iters, check_step, draws=None, seed=0,
                                             _ptr(geom.buf), int(geom.flags), _ptr(draws), N, Lmax, D, n_iters, float(check_step),
                                             _seed64(seed), int(problem_offset) & 0xFFFFFFFF, _stream()), 'mpb_path_shortcut')
     return (paths_out, lengths_out, stats, log) if with_log else (paths_out, lengths_out, stats)
+
+
+# ---- batched PRM: one roadmap, many start / goal queries (csrc/mpb_prm.hip) ------------------------------------------------------------
+# include/mpb.h MPB_PRM_*: the limits, the edge flags, the query statuses, the shortest edge a roadmap keeps
+PRM_MAX_NODES, PRM_MAX_K, PRM_MAX_PATH_ROWS, PRM_MIN_EDGE = 16384, 32, 1 << 20, 1e-4
+PRM_EDGE_FLAGS = ('FREE', 'BLOCKED', 'BAD_INDEX', 'TOO_LONG')
+PRM_EDGE_FREE, PRM_EDGE_BLOCKED, PRM_EDGE_BAD_INDEX, PRM_EDGE_TOO_LONG = range(4)
+PRM_STATUS = ('OK', 'NO_START', 'NO_GOAL', 'DISCONNECTED', 'PATH_TOO_LONG', 'DEGENERATE')
+PRM_OK, PRM_NO_START, PRM_NO_GOAL, PRM_DISCONNECTED, PRM_PATH_TOO_LONG, PRM_DEGENERATE = range(6)
+
+
+def _rows(t, name):
+    if not (isinstance(t, torch.Tensor) and t.dim() == 2):
+        raise ValueError(f'{name} has shape {tuple(getattr(t, "shape", ()))}, expected two dimensions')
+    return t.shape
+
+
+@_on_tensor_device
+def prm_knn(queries, nodes, K, exclude_self=False):
+    """The K nearest rows of nodes (M, D) to every row of queries (Q, D) in one launch (mpb_prm_knn): -> (idx (Q, K) int32, dist (Q, K)
+    fp32), each row in ascending order of (squared distance, index); the distance is the sequential fp32 sum of the shortcut pass.
+    exclude_self: the queries are the nodes, and node i is left out of row i."""
+    Q, D = _rows(queries, 'queries')
+    M = _rows(nodes, 'nodes')[0]
+    _chk(queries, (Q, D), 'queries')
+    _chk(nodes, (M, D), 'nodes')
+    K = int(K)
+    idx = torch.empty(Q, max(K, 0), device=queries.device, dtype=torch.int32)
+    dist = torch.empty(Q, max(K, 0), device=queries.device, dtype=torch.float32)
+    if Q == 0 and 1 <= K <= PRM_MAX_K:                          # (an empty tensor has no address to hand over)
+        return idx, dist
+    _lib.check(_lib.lib().mpb_prm_knn(_ptr(queries), _ptr(nodes), _ptr(idx), _ptr(dist), Q, M, D, K, 1 if exclude_self else 0, _stream()),
+               'mpb_prm_knn')
+    return idx, dist
+
+
+@_on_tensor_device
+def prm_edge_check(pts, pairs, geom, check_step):
+    """The straight segments between rows of pts (P, D) that pairs (E, 2) int32 name, scanned as the shortcut pass scans a candidate at
+    spacing check_step, one wave per edge in one launch (mpb_prm_edge_check): -> (flag (E,) int32 PRM_EDGE_*, first (E,) int32: the index
+    of the first point in collision of a BLOCKED edge, else -1)."""
+    P, D = _rows(pts, 'pts')
+    E = _rows(pairs, 'pairs')[0]
+    _chk(pts, (P, D), 'pts')
+    _chk(pairs, (E, 2), 'pairs', dtype=torch.int32)
+    if D != geom.n_dof:
+        raise ValueError(f'pts has {D} columns, the geometry {geom.n_dof} degrees of freedom')
+    flag = torch.empty(E, device=pts.device, dtype=torch.int32)
+    first = torch.empty(E, device=pts.device, dtype=torch.int32)
+    if E == 0:                                                   # (an empty tensor has no address to hand over)
+        return flag, first
+    _lib.check(_lib.lib().mpb_prm_edge_check(_ptr(pts), _ptr(pairs), _ptr(flag), _ptr(first), _ptr(geom.buf), int(geom.flags), P, E, D,
+                                             float(check_step), _stream()), 'mpb_prm_edge_check')
+    return flag, first
+
+
+@_on_tensor_device
+def prm_query(nodes, nbr, w, starts, goals, cs, ws, cg, wg, direct, max_path_nodes):
+    """Q start / goal queries against one roadmap in one launch, one workgroup per query (mpb_prm_query; include/mpb.h has the
+    definition).  The roadmap: nodes (M, D), nbr (M, K) int32, w (M, K) (+inf: no edge); per query the connection tables cs, cg (Q, Kc)
+    int32 with ws, wg (Q, Kc) and direct (Q,) (the start-goal distance where that segment is free, else +inf).
+    -> (paths (Q, max_path_nodes, D), lengths (Q,) int32, costs (Q,), status (Q,) int32 PRM_*)."""
+    M, D = _rows(nodes, 'nodes')
+    K = _rows(nbr, 'nbr')[1]
+    Q = _rows(starts, 'starts')[0]
+    Kc = _rows(cs, 'cs')[1]
+    _chk(nodes, (M, D), 'nodes')
+    _chk(nbr, (M, K), 'nbr', dtype=torch.int32)
+    _chk(w, (M, K), 'w')
+    _chk(starts, (Q, D), 'starts')
+    _chk(goals, (Q, D), 'goals')
+    for t, name in ((cs, 'cs'), (cg, 'cg')):
+        _chk(t, (Q, Kc), name, dtype=torch.int32)
+    for t, name in ((ws, 'ws'), (wg, 'wg')):
+        _chk(t, (Q, Kc), name)
+    _chk(direct, (Q,), 'direct')
+    Lmax = int(max_path_nodes)
+    paths = torch.empty(Q, max(Lmax, 0), D, device=nodes.device, dtype=torch.float32)
+    lengths = torch.empty(Q, device=nodes.device, dtype=torch.int32)
+    costs = torch.empty(Q, device=nodes.device, dtype=torch.float32)
+    status = torch.empty(Q, device=nodes.device, dtype=torch.int32)
+    if Q == 0 and Lmax >= 2:                                     # (an empty tensor has no address to hand over)
+        return paths, lengths, costs, status
+    _lib.check(_lib.lib().mpb_prm_query(_ptr(nodes), _ptr(nbr), _ptr(w), _ptr(starts), _ptr(goals), _ptr(cs), _ptr(ws), _ptr(cg), _ptr(wg),
+                                        _ptr(direct), _ptr(paths), _ptr(lengths), _ptr(costs), _ptr(status), Q, M, K, Kc, D, Lmax, _stream()),
+               'mpb_prm_query')
+    return paths, lengths, costs, status

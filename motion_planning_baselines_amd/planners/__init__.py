@@ -1,1 +1,2 @@
+from .prm import PRM  # noqa: F401
 from .rrt_star import InfRRTStar, RRTStar  # noqa: F401
