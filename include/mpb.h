@@ -75,7 +75,8 @@ extern "C" {
  *                        occupancy voxels (mpb_sdf_grid_build_occupancy).  So were the end-effector pose and batched inverse
  *                        kinematics (mpb_fk_ee_pose, mpb_ik_solve): additive.  So was the
  *                        end-effector pose cost (mpb_ee_cost_eval, mpb_ee_cost_grad), and the SDF grid's build from triangle
- *                        meshes (mpb_mesh_check, mpb_sdf_grid_build_mesh). */
+ *                        meshes (mpb_mesh_check, mpb_sdf_grid_build_mesh), path shortcutting and the roadmap planner, and
+ *                        the time parameterisation under joint limits (mpb_traj_retime, mpb_traj_retime_sample). */
 #define MPB_ABI_VERSION 7
 #define MPB_VERSION_TUNING_BUILD 0x40000000
 int mpb_version(void);
@@ -1075,6 +1076,64 @@ int mpb_prm_edge_check(const float *pts, const int *pairs, int *flag, int *first
 int mpb_prm_query(const float *nodes, const int *nbr, const float *w, const float *starts, const float *goals,
                   const int *cs, const float *ws, const int *cg, const float *wg, const float *direct, float *paths,
                   int *lengths, float *costs, int *status, int Q, int M, int K, int Kc, int D, int Lmax, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Time parameterisation of a trajectory batch under per-joint velocity and acceleration limits (the reference has no retiming:
+ * build-defined): the time-optimal rest-to-rest timing along each path by reachability-based path
+ * parameterisation (TOPP-RA, Pham & Pham 2018), for limits symmetric about zero.  Two launches: the timing, then the trajectory
+ * sampled at a fixed control period.  No atomics: the same bits on every run.  Every operation below is rounded to fp32 on its
+ * own (no fma).
+ *
+ * mpb_traj_retime: trajs: N trajectories of H rows, read in place as mpb_traj_collision_stats reads them (row h of trajectory n
+ *   starts at trajs + (n*H + h)*row_stride, its first D floats are the joint positions q_h, the other columns are never read).
+ *   v_max, a_max (D) device fp32, finite and > 0; sdot_max > 0 caps the path speed where the path does not move.
+ *   Path parameter: the waypoint index.  Unknowns x_i = sdot^2 at the waypoints, u_i = sddot constant on [i, i+1]:
+ *   x_{i+1} = x_i + 2 u_i; rest to rest, x_0 = x_{H-1} = 0.
+ *   Path derivatives: p_i = (q_{i+1} - q_{i-1}) * 0.5, c_i = (q_{i+1} - q_i) - (q_i - q_{i-1}); p_0 = q_1 - q_0, p_{H-1} = q_{H-1} -
+ *   q_{H-2}, c_0 = c_{H-1} = 0.
+ *   Lines of interval i, each a u + b x <= c, in 2D + 1 pairs (a, b, c+, c-) that stand for a u + b x <= c+ and -a u - b x <= c-:
+ *     joint j at waypoint i:      (p_ij, c_ij, a_j, a_j);
+ *     joint j at waypoint i + 1:  (p_{i+1,j} + 2 c_{i+1,j}, c_{i+1,j}, a_j, a_j)       (the limit there, written in x_i);
+ *     reachability:               (2, 1, beta_{i+1}, 0)                                 (0 <= x_{i+1} <= beta_{i+1}).
+ *   Of a pair with a != 0 the line with a positive coefficient of u bounds u from above, the other from below; a pair with a == 0 and
+ *   b != 0 bounds x by c+ / |b|.
+ *   Speed limit: xv_i = min(sdot_max, min_j v_j / |p_ij| over p_ij != 0)^2.
+ *   Backward: beta_{H-1} = 0; for i = H-2 .. 1, beta_i = the minimum of xv_i, of the x-only bounds, and over every (upper line 1, lower
+ *   line 2) with k = a1 b2 - a2 b1 > 0 of (a1 c2 - a2 c1) / k.  (A minimum is exact in any order; (u, x) = (0, 0) satisfies every
+ *   line: there is no infeasible case.)
+ *   Forward: x_0 = 0; for i = 0 .. H-2, u_i = the minimum over the upper lines of (c - b x_i) / a, x_{i+1} = max(0, min(beta_{i+1},
+ *   x_i + 2 u_i)).  Times: t_0 = 0, t_{i+1} = t_i + 2 / (sqrt(x_i) + sqrt(x_{i+1})) (exact for constant sddot).
+ *   Outputs: x (N,H), u (N,H-1), t (N,H), qd (N,H,D) = p_i sqrt(x_i), status (N) int32: MPB_RETIME_OK, or MPB_RETIME_STALLED when two
+ *   adjacent x are 0 or t_{H-1} is not finite or exceeds t_max (repeated waypoints do this: the caller purges them); x, u, t, qd
+ *   are written as computed (t is +inf from the stall on).  A v_max / a_max entry that is not finite and > 0: STALLED, all four
+ *   outputs zero.
+ *   GUARANTEE: the limits hold at the waypoints (the acceleration at both ends of every interval), to rounding.  Between the
+ *   waypoints they do not: the answer to an overstep there is a denser input (mpb_traj_interpolate) or scaled limits.
+ *   Refusals, in this order, all before the first HIP call: D > MPB_MAX_DOF; H > MPB_MAX_H: MPB_E_UNSUPPORTED; H < 3, N < 0, D < 1
+ *   or row_stride < D; sdot_max, then t_max, not finite or <= 0; a null pointer: MPB_E_INVALID.  N == 0: MPB_OK, nothing launched.
+ *
+ * mpb_traj_retime_sample: trajs as above, x, u, t, retime_status as mpb_traj_retime wrote them -> out (N,T_rows,2D): row k of
+ *   trajectory n is the state (positions, velocities) at tau = fl32(k * dt); n_rows (N) int32, status (N) int32.  With T = t_{H-1}:
+ *   tau < T: i the interval with t_i <= tau < t_{i+1}, d = tau - t_i, r = sqrt(x_i), sigma = clamp(r d + ((u_i d) d) * 0.5, 0, 1),
+ *     sdot = max(0, r + u_i d); with dq = q_{i+1} - q_i, e2 = (3 dq - 2 p_i) - p_{i+1}, e3 = (p_i + p_{i+1}) - 2 dq -- the cubic Hermite of
+ *     (q_i, p_i, q_{i+1}, p_{i+1}) -- position q_i + sigma (p_i + sigma (e2 + sigma e3)), velocity (p_i + sigma (2 e2 + (3 sigma) e3))
+ *     sdot.
+ *   tau >= T: the last waypoint, zero velocity (the batch is padded by holding).
+ *   n_rows = ceil(T / dt) + 1, the quotient of the two fp32 values taken in fp64 (beyond an int: INT_MAX); n_rows > T_rows:
+ *   MPB_RETIME_TOO_LONG, the T_rows rows that fit are still written.  retime_status != MPB_RETIME_OK or T not finite:
+ *   MPB_RETIME_STALLED, n_rows = 0, every row holds the first waypoint with zero velocity.
+ *   Refusals, in this order, all before the first HIP call: D > MPB_MAX_DOF; H > MPB_MAX_H: MPB_E_UNSUPPORTED; H < 3, N < 0, D < 1
+ *   or row_stride < D; dt not finite or <= 0; T_rows < 1; N * ceil(T_rows / 256) beyond an int; a null pointer: MPB_E_INVALID.
+ *   N == 0: MPB_OK, nothing launched.
+ * ------------------------------------------------------------------------------------------- */
+#define MPB_RETIME_OK 0
+#define MPB_RETIME_STALLED 1
+#define MPB_RETIME_TOO_LONG 2
+int mpb_traj_retime(const float *trajs, size_t row_stride, const float *v_max, const float *a_max, float *x, float *u,
+                    float *t, float *qd, int *status, int N, int H, int D, float sdot_max, float t_max, void *stream);
+int mpb_traj_retime_sample(const float *trajs, size_t row_stride, const float *x, const float *u, const float *t,
+                           const int *retime_status, float *out, int *n_rows, int *status, int N, int H, int D, float dt,
+                           int T_rows, void *stream);
 
 #ifdef __cplusplus
 }

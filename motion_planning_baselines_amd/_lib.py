@@ -96,6 +96,8 @@ SIGNATURES = {
     'mpb_prm_knn': [_p] * 4 + [_i] * 5 + [_p],
     'mpb_prm_edge_check': [_p] * 5 + [_i] * 4 + [_f, _p],
     'mpb_prm_query': [_p] * 14 + [_i] * 6 + [_p],
+    'mpb_traj_retime': [_p, ctypes.c_size_t] + [_p] * 7 + [_i] * 3 + [_f, _f, _p],
+    'mpb_traj_retime_sample': [_p, ctypes.c_size_t] + [_p] * 7 + [_i] * 3 + [_f, _i, _p],
 }
 
 # test aids (include/mpb_debug.h): a separate library, csrc/libmpb_hip_debug.so

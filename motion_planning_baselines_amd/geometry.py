@@ -202,11 +202,21 @@ class Robot:
 
     kind = None
 
-    def __init__(self, q_dim, q_min, q_max, dt=None):
+    def __init__(self, q_dim, q_min, q_max, dt=None, dq_max=None, ddq_max=None):
         self.q_dim = int(q_dim)
         self.q_min_np = np.asarray(q_min, dtype=np.float32)
         self.q_max_np = np.asarray(q_max, dtype=np.float32)
         self.dt = dt
+        # per-joint velocity / acceleration limits, symmetric about zero (None: the robot carries none): what retiming reads
+        self.dq_max_np, self.ddq_max_np = (self._limit(v, name) for v, name in ((dq_max, 'dq_max'), (ddq_max, 'ddq_max')))
+
+    def _limit(self, v, name):
+        if v is None:
+            return None
+        v = np.asarray(v, dtype=np.float32)
+        if v.shape != (self.q_dim,) or not (np.all(np.isfinite(v)) and np.all(v > 0)):
+            raise ValueError(f'{name} must hold {self.q_dim} finite limits > 0 (got {v.tolist()})')
+        return v
 
     @property
     def q_min(self):
@@ -215,6 +225,14 @@ class Robot:
     @property
     def q_max(self):
         return torch.from_numpy(self.q_max_np)
+
+    @property
+    def dq_max(self):
+        return None if self.dq_max_np is None else torch.from_numpy(self.dq_max_np)
+
+    @property
+    def ddq_max(self):
+        return None if self.ddq_max_np is None else torch.from_numpy(self.ddq_max_np)
 
     # state slicing -- same meaning as torch_robotics' RobotBase (positions first, velocities last)
     def get_position(self, x):
@@ -232,8 +250,8 @@ class RobotPointMass(Robot):
 
     kind = KIND_POINT
 
-    def __init__(self, q_dim=2, radius=0.01, q_limits=(-1.0, 1.0), dt=None):
-        super().__init__(q_dim, [q_limits[0]] * q_dim, [q_limits[1]] * q_dim, dt=dt)
+    def __init__(self, q_dim=2, radius=0.01, q_limits=(-1.0, 1.0), dt=None, dq_max=None, ddq_max=None):
+        super().__init__(q_dim, [q_limits[0]] * q_dim, [q_limits[1]] * q_dim, dt=dt, dq_max=dq_max, ddq_max=ddq_max)
         assert q_dim in (2, 3)
         self.radius = float(radius)
 
@@ -252,7 +270,7 @@ class RobotSerialChain(Robot):
 
     kind = KIND_CHAIN
 
-    def __init__(self, joint_tf, link_frame, link_offset, link_radius, q_min, q_max, dt=None):
+    def __init__(self, joint_tf, link_frame, link_offset, link_radius, q_min, q_max, dt=None, dq_max=None, ddq_max=None):
         joint_tf = np.asarray(joint_tf, dtype=np.float32)
         n_dof = len(q_min)
         assert joint_tf.shape in ((n_dof, 3, 4), (n_dof + 1, 3, 4))
@@ -261,7 +279,7 @@ class RobotSerialChain(Robot):
             eye[0, :, :3] = np.eye(3)
             joint_tf = np.concatenate([joint_tf, eye], 0)
         assert n_dof <= MAX_DOF
-        super().__init__(n_dof, q_min, q_max, dt=dt)
+        super().__init__(n_dof, q_min, q_max, dt=dt, dq_max=dq_max, ddq_max=ddq_max)
         self.joint_tf = joint_tf
         self.link_frame = np.asarray(link_frame, dtype=np.int32)
         self.link_offset = np.asarray(link_offset, dtype=np.float32).reshape(-1, 3)
@@ -291,6 +309,9 @@ _PANDA_MDH = [
 _PANDA_FLANGE_D = 0.107
 _PANDA_Q_MIN = [-2.8973, -1.7628, -2.8973, -3.0718, -2.8973, -0.0175, -2.8973]
 _PANDA_Q_MAX = [2.8973, 1.7628, 2.8973, -0.0698, 2.8973, 3.7525, 2.8973]
+# the data sheet's joint velocity (rad/s) and acceleration (rad/s^2) limits
+_PANDA_DQ_MAX = [2.175, 2.175, 2.175, 2.175, 2.61, 2.61, 2.61]
+_PANDA_DDQ_MAX = [15.0, 7.5, 10.0, 12.5, 15.0, 20.0, 20.0]
 
 # Build-defined collision-sphere set: (frame, x, y, z, radius); frame j = link j (after joint j),
 # frame 8 = flange + hand (Tz(0.107) Rz(-pi/4)).
@@ -323,7 +344,7 @@ class RobotPanda(RobotSerialChain):
         super().__init__(
             joint_tf=np.stack(tfs), link_frame=sph[:, 0].astype(np.int32),
             link_offset=sph[:, 1:4], link_radius=sph[:, 4],
-            q_min=_PANDA_Q_MIN, q_max=_PANDA_Q_MAX, dt=dt)
+            q_min=_PANDA_Q_MIN, q_max=_PANDA_Q_MAX, dt=dt, dq_max=_PANDA_DQ_MAX, ddq_max=_PANDA_DDQ_MAX)
 
 
 class CollisionField:

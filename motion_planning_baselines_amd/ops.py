@@ -1750,3 +1750,89 @@ def prm_query(nodes, nbr, w, starts, goals, cs, ws, cg, wg, direct, max_path_nod
                                         _ptr(direct), _ptr(paths), _ptr(lengths), _ptr(costs), _ptr(status), Q, M, K, Kc, D, Lmax, _stream()),
                'mpb_prm_query')
     return paths, lengths, costs, status
+
+
+# ---- time parameterisation under joint limits (csrc/mpb_retime.hip) --------------------------------------------------------------------
+# include/mpb.h MPB_RETIME_*: the per-trajectory status of the timing and of the sampler
+RETIME_STATUS = ('OK', 'STALLED', 'TOO_LONG')
+RETIME_OK, RETIME_STALLED, RETIME_TOO_LONG = range(3)
+
+TrajTiming = collections.namedtuple('TrajTiming', 'x u t qd status duration')
+TrajTiming.__doc__ = """What traj_retime returns: x (N, H) = sdot^2 at the waypoints, u (N, H-1) = sddot on the intervals, t (N, H) the
+times of the waypoints, qd (N, H, D) the joint velocities there, status (N,) int32 RETIME_OK / RETIME_STALLED, duration (N,) = t[:, -1]
+(a view)."""
+
+
+def _retime_trajs(trajs, what):
+    if not (isinstance(trajs, torch.Tensor) and trajs.is_cuda):
+        raise _lib.MPBError(f'{what}: trajs must be a GPU tensor; there is no CPU fallback')
+    if trajs.dim() != 3:
+        raise ValueError(f'trajs has shape {tuple(trajs.shape)}, expected (N, H, W)')
+    _chk(trajs, tuple(trajs.shape), 'trajs')
+    return trajs.shape
+
+
+@_on_tensor_device
+def traj_retime(trajs, v_max, a_max, sdot_max=1e3, t_max=1e4):
+    """The time-optimal rest-to-rest timing along each of N waypoint trajectories under per-joint velocity / acceleration limits, in one
+    launch (mpb_traj_retime; include/mpb.h has the definition: TOPP-RA for limits symmetric about zero).  trajs (N, H, W) is read in
+    place, the first D = len(v_max) columns of a row are the joint positions (a planner's (N, H, 2D) state output is read as it is).
+    v_max, a_max: (D,) finite and > 0 (rad/s, rad/s^2); sdot_max caps the path speed (waypoints/s) where the path does not move; a
+    trajectory longer than t_max seconds is STALLED -- repeated waypoints do that, purge them.
+
+    GUARANTEE: the limits hold AT the waypoints, to rounding.  Between them they do not: a cubic through smooth Panda trajectories
+    sampled at 1 ms oversteps the velocity limit by 0.9 % at H = 64 and 10 % at H = 16, the acceleration limit by 28 % / 70 %, and a
+    polyline with corners by a factor 3.9 in acceleration.  The answer is a denser input (traj_interpolate) or scaled limits; nothing
+    is clamped here.  Returns a TrajTiming."""
+    N, H, W = _retime_trajs(trajs, 'traj_retime')
+    lim = []
+    for t, name in ((v_max, 'v_max'), (a_max, 'a_max')):
+        t = torch.as_tensor(t, dtype=torch.float32)
+        if t.dim() != 1 or not bool(torch.isfinite(t).all()) or not bool((t > 0).all()):
+            raise ValueError(f'{name} must be a vector of finite limits > 0 (got {t.tolist() if t.dim() == 1 else tuple(t.shape)})')
+        lim.append(t.to(trajs.device).contiguous())
+    D = lim[0].numel()
+    if lim[1].numel() != D or not 1 <= D <= W:
+        raise ValueError(f'v_max has {D} entries, a_max {lim[1].numel()}, the rows of trajs {W} columns')
+    dev = trajs.device
+    x, t = torch.empty(N, H, device=dev), torch.empty(N, H, device=dev)
+    u = torch.empty(N, max(H - 1, 0), device=dev)
+    qd = torch.empty(N, H, D, device=dev)
+    status = torch.empty(N, device=dev, dtype=torch.int32)
+    if N > 0:                                                    # (an empty tensor has no address to hand over)
+        _lib.check(_lib.lib().mpb_traj_retime(_ptr(trajs), W, _ptr(lim[0]), _ptr(lim[1]), _ptr(x), _ptr(u), _ptr(t), _ptr(qd), _ptr(status),
+                                              N, H, D, float(sdot_max), float(t_max), _stream()), 'mpb_traj_retime')
+    return TrajTiming(x, u, t, qd, status, t[:, -1] if H else t.reshape(N))
+
+
+@_on_tensor_device
+def traj_retime_sample(trajs, timing, dt, n_rows=None):
+    """trajs (N, H, W) and their TrajTiming -> the trajectories at the fixed control period dt, in one launch (mpb_traj_retime_sample):
+    (out (N, n_rows, 2D) positions and velocities, rows (N,) int32, status (N,) int32).  Row k is the state at k dt: a cubic Hermite of the
+    two waypoints around it; rows at and past a trajectory's own rows[n] = ceil(T / dt) + 1 hold its last waypoint at rest.  n_rows=None
+    reads the longest duration back (one synchronisation) and sizes the output to it.  A trajectory with more rows than n_rows is
+    RETIME_TOO_LONG (the rows that fit are written); a STALLED one has rows 0 and holds its first waypoint."""
+    N, H, W = _retime_trajs(trajs, 'traj_retime_sample')
+    D = timing.qd.shape[-1]
+    _chk(timing.x, (N, H), 'timing.x')
+    _chk(timing.u, (N, max(H - 1, 0)), 'timing.u')
+    _chk(timing.t, (N, H), 'timing.t')
+    _chk(timing.status, (N,), 'timing.status', dtype=torch.int32)
+    if D > W:
+        raise ValueError(f'the timing is of {D} joints, the rows of trajs have {W} columns')
+    dt = float(dt)
+    if n_rows is None:
+        if not (dt > 0 and math.isfinite(dt)):
+            raise ValueError(f'dt = {dt}: a finite period > 0')
+        ok = (timing.status == RETIME_OK) & torch.isfinite(timing.duration)
+        T = float(torch.where(ok, timing.duration, torch.zeros_like(timing.duration)).max()) if N else 0.0
+        n_rows = int(math.ceil(T / float(np.float32(dt)))) + 1
+    n_rows = int(n_rows)
+    out = torch.empty(N, max(n_rows, 0), 2 * D, device=trajs.device)
+    rows = torch.empty(N, device=trajs.device, dtype=torch.int32)
+    status = torch.empty(N, device=trajs.device, dtype=torch.int32)
+    if N > 0:
+        _lib.check(_lib.lib().mpb_traj_retime_sample(_ptr(trajs), W, _ptr(timing.x), _ptr(timing.u), _ptr(timing.t), _ptr(timing.status),
+                                                     _ptr(out), _ptr(rows), _ptr(status), N, H, D, dt, n_rows, _stream()),
+                   'mpb_traj_retime_sample')
+    return out, rows, status

@@ -346,6 +346,46 @@ class PlanningTask:
         self.require_no_sdf_field('path shortcutting (mpb_path_shortcut)')
         return ops.path_shortcut(paths, lengths, self.geom, n_iters, check_step, **kwargs)
 
+    # ---- time parameterisation of a trajectory batch (build-defined: DESIGN.md 10) -------------------------------------------------
+    def retime_trajs(self, trajs, dt=None, v_max=None, a_max=None, scale=1.0, **kwargs):
+        """trajs (..., H, W), W >= q_dim, leading dimensions flattened as in get_trajs_collision_and_free -> a TrajsRetimed: the
+        time-optimal rest-to-rest timing of every trajectory under per-joint velocity / acceleration limits (ops.traj_retime, which also
+        takes the keyword arguments sdot_max, t_max) and, with a control period dt, the batch sampled at it (ops.traj_retime_sample).
+        v_max, a_max default to the robot's dq_max, ddq_max; both are multiplied by `scale` (0 < scale: run slower than the data sheet
+        allows).  The limits hold AT the waypoints, not between them: ops.traj_retime says by how much."""
+        lim = {}
+        for name, given, own in (('v_max', v_max, 'dq_max'), ('a_max', a_max, 'ddq_max')):
+            v = getattr(self.robot, own, None) if given is None else given
+            if v is None:
+                raise ValueError(f'retime_trajs: no {name} given and the robot carries no {own}')
+            lim[name] = torch.as_tensor(v, dtype=torch.float32).reshape(-1)
+            if lim[name].numel() != self.q_dim:
+                raise ValueError(f'retime_trajs: {name} has {lim[name].numel()} entries, the robot {self.q_dim} joints')
+        scale = float(scale)
+        if not (scale > 0 and scale < float('inf')):
+            raise ValueError(f'retime_trajs: scale = {scale}, a finite factor > 0')
+        t = torch.as_tensor(trajs, dtype=torch.float32, device=self.device)
+        if t.dim() < 2 or t.shape[-1] < self.q_dim:
+            raise ValueError(f'trajs has shape {tuple(t.shape)}, expected (..., H, W) with W >= {self.q_dim}')
+        lead = tuple(t.shape[:-2])
+        t = t.reshape(-1, t.shape[-2], t.shape[-1]).contiguous()
+        timing = ops.traj_retime(t, lim['v_max'] * scale, lim['a_max'] * scale, **kwargs)
+        trajs_dt = n_rows = sample_status = None
+        if dt is not None:
+            out, rows, st = ops.traj_retime_sample(t, timing, dt)
+            trajs_dt, n_rows, sample_status = out.reshape(*lead, *out.shape[1:]), rows.reshape(lead), st.reshape(lead)
+        return TrajsRetimed(timing.duration.reshape(lead), timing.status.reshape(lead), timing, trajs_dt, n_rows, sample_status)
+
+
+class TrajsRetimed:
+    """What PlanningTask.retime_trajs returns, the leading dimensions of its input kept: durations (...) seconds, status (...) int32
+    (ops.RETIME_OK / RETIME_STALLED), timing (the flat ops.TrajTiming: x, u, t, qd); with a control period also trajs_dt (..., n_rows, 2D)
+    positions and velocities at k dt, n_rows (...) int32 the rows each trajectory needs, sample_status (...) int32; else None."""
+
+    def __init__(self, durations, status, timing, trajs_dt=None, n_rows=None, sample_status=None):
+        self.durations, self.status, self.timing = durations, status, timing
+        self.trajs_dt, self.n_rows, self.sample_status = trajs_dt, n_rows, sample_status
+
 
 class IKResult:
     """What PlanningTask.inverse_kinematics returns: q (N, S, D), converged / free bool (N, S) (free = converged and not in collision
