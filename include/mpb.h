@@ -76,7 +76,8 @@ extern "C" {
  *                        kinematics (mpb_fk_ee_pose, mpb_ik_solve): additive.  So was the
  *                        end-effector pose cost (mpb_ee_cost_eval, mpb_ee_cost_grad), and the SDF grid's build from triangle
  *                        meshes (mpb_mesh_check, mpb_sdf_grid_build_mesh), path shortcutting and the roadmap planner, and
- *                        the time parameterisation under joint limits (mpb_traj_retime, mpb_traj_retime_sample). */
+ *                        the time parameterisation under joint limits (mpb_traj_retime, mpb_traj_retime_sample), and Cartesian
+ *                        end-effector moves (mpb_cartesian_path). */
 #define MPB_ABI_VERSION 7
 #define MPB_VERSION_TUNING_BUILD 0x40000000
 int mpb_version(void);
@@ -823,6 +824,56 @@ int mpb_fk_ee_pose(const float *q, const float *geom, float *pose, float *jac, i
 int mpb_ik_solve(const float *target, const float *q_seed, const float *geom, const float *q_min, const float *q_max,
                  float *q_out, float *pos_err, float *rot_err, unsigned char *converged, int *iters_used,
                  int N, int S, int D, int n_iters, float damping, float pos_tol, float rot_tol, int position_only, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Cartesian end-effector moves: batched straight-line tracking (build-defined; what MoveIt calls computeCartesianPath).
+ * Serial chains only; geom as for mpb_fk_ee_pose (the first field's header and joint_tf alone, the header read back once per address).
+ * A problem is a pair (target n, start s): a goal pose [R* | t*], one per target and shared by its S starts, and a start configuration
+ * q_0.  [R_0 | t_0] is the pose mpb_fk_ee_pose returns for q_0 (the kernel walks with the same routine and sees those bits).
+ *   Once per problem, the rotation from R_0 to R* in the terms of mpb_ik_solve's error:  E = R* R_0^T,  w = vee(E - E^T) / 2,
+ *     c = (tr E - 1) / 2,  theta = atan2(|w|, c),  axis a = w / |w|.  theta > MPB_CART_MAX_TURN (the geodesic is ill-conditioned near
+ *     half a turn; a NaN angle counts): status MPB_CART_BAD_TARGET, n_ok = 0.  Otherwise theta is taken as 0 (no rotation) when
+ *     |w| < 1e-6.  With position_only the rotation is ignored altogether: no angle is computed, no target is bad, rot_err is 0.
+ *   Step k = 1 .. K, s_k = k / K:  t_k = t_0 + s_k (t* - t_0), evaluated as (1 - s_k) t_0 + s_k t* so that t_K is t* exactly;
+ *     R_k = Rod(a, s_k theta) R_0,  Rod(a, phi) = cos(phi) I + sin(phi) [a]x + (1 - cos(phi)) a a^T, computed in the lane: nothing
+ *     but the two end poses is read.
+ *   From the last accepted configuration at most n_inner iterations, each exactly mpb_ik_solve's against [R_k | t_k]: the same error
+ *     and tolerances, the same dq = J^T (J J^T + damping^2 I)^{-1} e, the same clamp onto q_min / q_max when given; a converged
+ *     problem is frozen.  The error is evaluated once more after the last iteration.  Then
+ *       not within (pos_tol, rot_tol):                      status MPB_CART_LOST, stop;
+ *       else max_j |q_k[j] - q_{k-1}[j]| > jump_max:        status MPB_CART_JUMP, stop (the arm would change branch);
+ *       else the step is accepted, n_ok = k.
+ *   A problem that accepts all K steps has status MPB_CART_OK.  MPB_CART_COLLISION is never written by the library: it is the status
+ *   of the callers that crop a path at its first colliding row (PlanningTask.cartesian_path).
+ * Outputs per problem: q_path (N, S, K+1, D): row 0 is q_0's bits, row k <= n_ok the accepted configuration, every row beyond n_ok
+ *   repeats row n_ok (always a valid trajectory, which holds still after the stop); pos_err, rot_err (N, S, K+1): the error of each
+ *   accepted row against its step's target, 0 in row 0, the rejected step's errors in row n_ok + 1 (LOST and JUMP), 0 after that;
+ *   n_ok (N, S) and status (N, S) int32.  When the geometry header has changed since the call: NaN in q_path (and the errors),
+ *   n_ok = 0, status MPB_CART_LOST.
+ * Bounds, so that a launch is bounded whatever the input, NaN included (a NaN problem never converges: it stops at step 1):
+ *   1 <= K <= MPB_CART_MAX_STEPS, 0 <= n_inner <= MPB_IK_MAX_ITERS, K * n_inner <= MPB_CART_MAX_WORK, damping >= MPB_IK_MIN_DAMPING,
+ *   jump_max > 0 (infinity turns the check off), tolerances not negative.  n_inner == 0 steps nowhere: a step is accepted only when
+ *   its target is already within tolerance of the held pose.
+ * One lane per problem; no LDS, no atomics, no cross-lane arithmetic: a problem's bits depend on its own inputs only.  A wave leaves
+ * the loops when none of its problems needs them.
+ * Refusals, in this order: (1) D > MPB_MAX_DOF: MPB_E_UNSUPPORTED; (2) N < 0, S < 0, D < 1, N * S beyond an int, K outside
+ * 1..MPB_CART_MAX_STEPS, n_inner outside 0..MPB_IK_MAX_ITERS, K * n_inner beyond MPB_CART_MAX_WORK, damping below MPB_IK_MIN_DAMPING or
+ * NaN, a negative or NaN tolerance, jump_max not positive or NaN: MPB_E_INVALID; (3) (N == 0 or S == 0: MPB_OK, nothing launched;)
+ * (4) a null required pointer, one of q_min / q_max without the other, geom not 16-byte aligned: MPB_E_INVALID; then what only the
+ * header tells: bad magic / version: MPB_E_INVALID; (5) a point robot: MPB_E_UNSUPPORTED; (6) D != n_dof: MPB_E_INVALID.
+ * ------------------------------------------------------------------------------------------- */
+#define MPB_CART_MAX_STEPS 4096
+#define MPB_CART_MAX_WORK 65536
+#define MPB_CART_MAX_TURN 3.04159265f /* pi - 0.1 */
+#define MPB_CART_OK 0
+#define MPB_CART_LOST 1
+#define MPB_CART_JUMP 2
+#define MPB_CART_BAD_TARGET 3
+#define MPB_CART_COLLISION 4
+int mpb_cartesian_path(const float *target, const float *q_start, const float *geom, const float *q_min, const float *q_max,
+                       float *q_path, float *pos_err, float *rot_err, int *n_ok, int *status,
+                       int N, int S, int D, int K, int n_inner, float damping, float pos_tol, float rot_tol, float jump_max,
+                       int position_only, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
  * End-effector pose cost of a trajectory batch and its gradient (build-defined): the task-space term of the planners --

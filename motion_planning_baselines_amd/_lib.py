@@ -84,6 +84,7 @@ SIGNATURES = {
     'mpb_sdf_grid_collision_check': [_p, _p, _p, _p, _i, _i, _i, _p],
     'mpb_fk_ee_pose': [_p, _p, _p, _p, _i, _i, _p],
     'mpb_ik_solve': [_p] * 10 + [_i] * 4 + [_f] * 3 + [_i, _p],
+    'mpb_cartesian_path': [_p] * 10 + [_i] * 5 + [_f] * 4 + [_i, _p],
     'mpb_ee_cost_eval': [_p] * 5 + [_i] * 9 + [_f, _f, _i] + [_f] * 4 + [_i, _p],
     'mpb_ee_cost_grad': [_p] * 5 + [_i] * 9 + [_f, _f, _i] + [_f] * 4 + [_i, _p],
     'mpb_rrt_connect_workspace_bytes': [_i, _i, _i, _i],

@@ -1,7 +1,8 @@
-// mpb_ee.h -- what the end-effector kernels share (mpb_ik.hip: the pose op and the IK solver; mpb_ee_cost.hip: the pose cost): the chain
-// of a geometry buffer as fk_advance reads it, the header guard of the kernels, the walk to the last frame, a column of the Jacobian's
-// upper half, and the launchers' cached read of a device buffer's header.  Every kernel that walks through ee_walk sees the bits
-// mpb_fk_ee_pose returns.
+// mpb_ee.h -- what the end-effector kernels share (mpb_ik.hip: the pose op and the IK solver; mpb_ee_cost.hip: the pose cost;
+// mpb_cartesian.hip: straight-line tracking): the chain of a geometry buffer as fk_advance reads it, the header guard of the kernels,
+// the walk to the last frame, a column of the Jacobian's upper half, the rotation error and one damped-least-squares step (the solver's
+// iteration, operation for operation, for the tracker), and the launchers' cached read of a device buffer's header.  Every kernel that walks
+// through ee_walk sees the bits mpb_fk_ee_pose returns.
 #pragma once
 #include "mpb_common.h"
 #include "mpb_geom.h"
@@ -42,6 +43,110 @@ __device__ __forceinline__ void ee_jv(const FKState<true>& F, int D, float& cx, 
     cx = on ? fmaf(F.zy[J], ez, -(F.zz[J] * ey)) : 0.f;
     cy = on ? fmaf(F.zz[J], ex, -(F.zx[J] * ez)) : 0.f;
     cz = on ? fmaf(F.zx[J], ey, -(F.zy[J] * ex)) : 0.f;
+}
+
+// ---- one damped-least-squares iteration of ik_solve_kernel (mpb_ik.hip, which keeps it written out: see there) as functions: what
+// cart_path_kernel (mpb_cartesian.hip) calls; spd_solve is shared by both --------------------------------------------------------
+// the rotation error of include/mpb.h against the target rotation (s00 .. s22): E = R* R^T, w = vee(E - E^T) / 2, c = (tr E - 1) / 2,
+// nw = |w|, th = atan2(|w|, c)
+__device__ __forceinline__ void ee_rot_error(float s00, float s01, float s02, float s10, float s11, float s12, float s20, float s21, float s22,
+                                             const FKState<true>& F, float& wx, float& wy, float& wz, float& nw, float& th) {
+    const float e00 = dot3(s00, F.r00, s01, F.r01, s02, F.r02), e01 = dot3(s00, F.r10, s01, F.r11, s02, F.r12),
+                e02 = dot3(s00, F.r20, s01, F.r21, s02, F.r22);
+    const float e10 = dot3(s10, F.r00, s11, F.r01, s12, F.r02), e11 = dot3(s10, F.r10, s11, F.r11, s12, F.r12),
+                e12 = dot3(s10, F.r20, s11, F.r21, s12, F.r22);
+    const float e20 = dot3(s20, F.r00, s21, F.r01, s22, F.r02), e21 = dot3(s20, F.r10, s21, F.r11, s22, F.r12),
+                e22 = dot3(s20, F.r20, s21, F.r21, s22, F.r22);
+    wx = 0.5f * (e21 - e12), wy = 0.5f * (e02 - e20), wz = 0.5f * (e10 - e01);
+    const float c = 0.5f * (((e00 + e11) + e22) - 1.0f);
+    nw = sqrtf(fmaf(wz, wz, fmaf(wy, wy, wx * wx)));
+    th = atan2f(nw, c);
+}
+
+// e_w = (theta / |w|) w into e[3..5]
+__device__ __forceinline__ void ee_rot_step_error(float wx, float wy, float wz, float nw, float th, float (&e)[6]) {
+    const float sc = (nw < 1e-6f) ? 1.0f : th / nw;  // (exactly half a turn away: w = 0, no rotation step)
+    e[3] = sc * wx; e[4] = sc * wy; e[5] = sc * wz;
+}
+
+// x = A^{-1} e for the SPD A given by its lower triangle (A[i][j], j <= i): unpivoted Cholesky A = L L^T with reciprocal pivots, the
+// two substitutions.  Fully unrolled, every index a compile-time constant.
+template <int NR>
+__device__ __forceinline__ void spd_solve(float (&A)[NR][NR], const float (&e)[NR], float (&x)[NR]) {
+    float inv[NR];
+#pragma unroll
+    for (int i = 0; i < NR; ++i) {
+#pragma unroll
+        for (int j = 0; j <= i; ++j) {
+            float s = A[i][j];
+#pragma unroll
+            for (int k = 0; k < j; ++k) s = fmaf(-A[i][k], A[j][k], s);
+            if (i == j) {
+                const float l = sqrtf(s);
+                inv[i] = 1.0f / l;
+                A[i][i] = l;
+            } else {
+                A[i][j] = s * inv[j];
+            }
+        }
+    }
+    float y[NR];
+#pragma unroll
+    for (int i = 0; i < NR; ++i) {
+        float s = e[i];
+#pragma unroll
+        for (int k = 0; k < i; ++k) s = fmaf(-A[i][k], y[k], s);
+        y[i] = s * inv[i];
+    }
+#pragma unroll
+    for (int i = NR - 1; i >= 0; --i) {
+        float s = y[i];
+#pragma unroll
+        for (int k = i + 1; k < NR; ++k) s = fmaf(-A[k][i], x[k], s);
+        x[i] = s * inv[i];
+    }
+}
+
+// q <- clamp(q + J^T (J J^T + lam2 I)^{-1} e) at the walk F of q; a frozen problem keeps its q.  PO: position only -- e is e_p, the
+// system the 3 x 3 of the Jacobian's upper half.
+template <bool PO>
+__device__ __forceinline__ void ee_dls_step(const FKState<true>& F, int D, const float (&e)[PO ? 3 : 6], float lam2, bool limits,
+                                            const float* q_min, const float* q_max, bool frozen,
+                                            float (&q)[MPB_MAX_DOF]) {
+    constexpr int NR = PO ? 3 : 6;
+    // A = J J^T + damping^2 I, lower triangle, joint by joint
+    float A[NR][NR];
+#pragma unroll
+    for (int a = 0; a < NR; ++a)
+#pragma unroll
+        for (int b = 0; b < NR; ++b) A[a][b] = 0.f;
+    static_for<0, MPB_MAX_DOF>([&](auto jc) {
+        constexpr int J = decltype(jc)::value;
+        float col[6];
+        ee_jv<J>(F, D, col[0], col[1], col[2]);
+        const bool on = J < D;
+        col[3] = on ? F.zx[J] : 0.f; col[4] = on ? F.zy[J] : 0.f; col[5] = on ? F.zz[J] : 0.f;
+#pragma unroll
+        for (int a = 0; a < NR; ++a)
+#pragma unroll
+            for (int b = 0; b <= a; ++b) A[a][b] = fmaf(col[a], col[b], A[a][b]);
+    });
+#pragma unroll
+    for (int a = 0; a < NR; ++a) A[a][a] += lam2;
+    float y[NR];
+    spd_solve<NR>(A, e, y);
+    static_for<0, MPB_MAX_DOF>([&](auto jc) {
+        constexpr int J = decltype(jc)::value;
+        if (J < D) {
+            float cx, cy, cz;
+            ee_jv<J>(F, D, cx, cy, cz);
+            float dq = fmaf(cz, y[2], fmaf(cy, y[1], cx * y[0]));
+            if constexpr (!PO) dq = fmaf(F.zz[J], y[5], fmaf(F.zy[J], y[4], fmaf(F.zx[J], y[3], dq)));
+            float qn = q[J] + dq;
+            if (limits) qn = fminf(fmaxf(qn, q_min[J]), q_max[J]);
+            q[J] = frozen ? q[J] : qn;
+        }
+    });
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------------

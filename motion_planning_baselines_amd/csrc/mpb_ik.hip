@@ -19,7 +19,8 @@
 //     joint loop of several hundred instructions each): a step is up to several radians long and multiplies their error.
 #include <limits.h>
 
-#include "mpb_ee.h"   // ik_chain_view, ik_header_matches, ee_walk, ee_jv and the launchers' ik_chain_check: shared with mpb_ee_cost.hip
+#include "mpb_ee.h"   // ik_chain_view, ik_header_matches, ee_walk, ee_jv, spd_solve and the launchers' ik_chain_check: shared with
+                      // mpb_ee_cost.hip and mpb_cartesian.hip
 
 __global__ __launch_bounds__(64) void fk_ee_pose_kernel(const float* __restrict__ q_in, const float* __restrict__ geom, float* __restrict__ pose,
                                                         float* __restrict__ jac, int N, int D) {
@@ -55,45 +56,11 @@ __global__ __launch_bounds__(64) void fk_ee_pose_kernel(const float* __restrict_
     }
 }
 
-// x = A^{-1} e for the SPD A given by its lower triangle (A[i][j], j <= i): unpivoted Cholesky A = L L^T with reciprocal pivots, the
-// two substitutions.  Fully unrolled, every index a compile-time constant.
-template <int NR>
-__device__ __forceinline__ void spd_solve(float (&A)[NR][NR], const float (&e)[NR], float (&x)[NR]) {
-    float inv[NR];
-#pragma unroll
-    for (int i = 0; i < NR; ++i) {
-#pragma unroll
-        for (int j = 0; j <= i; ++j) {
-            float s = A[i][j];
-#pragma unroll
-            for (int k = 0; k < j; ++k) s = fmaf(-A[i][k], A[j][k], s);
-            if (i == j) {
-                const float l = sqrtf(s);
-                inv[i] = 1.0f / l;
-                A[i][i] = l;
-            } else {
-                A[i][j] = s * inv[j];
-            }
-        }
-    }
-    float y[NR];
-#pragma unroll
-    for (int i = 0; i < NR; ++i) {
-        float s = e[i];
-#pragma unroll
-        for (int k = 0; k < i; ++k) s = fmaf(-A[i][k], y[k], s);
-        y[i] = s * inv[i];
-    }
-#pragma unroll
-    for (int i = NR - 1; i >= 0; --i) {
-        float s = y[i];
-#pragma unroll
-        for (int k = i + 1; k < NR; ++k) s = fmaf(-A[k][i], x[k], s);
-        x[i] = s * inv[i];
-    }
-}
-
 // PO: position only -- the error is e_p, the system the 3 x 3 of the Jacobian's upper half
+// (The iteration is written out here and once more as ee_rot_error / ee_rot_step_error / ee_dls_step of mpb_ee.h, which cart_path_kernel
+// calls: operation for operation the same.  Calling them here gives the same values but another register allocation -- 169 instead of
+// 179 VGPRs, other spill counts: the functions are optimised on their own before they are inlined -- and tests/test_ee_cost_cpu.py holds
+// this kernel to the figures it has.  tests/test_gpu_cartesian.py holds the two forms to the same bits.)
 template <bool PO>
 __global__ __launch_bounds__(64) void ik_solve_kernel(const float* __restrict__ target, const float* __restrict__ q_seed,
                                                       const float* __restrict__ geom, const float* __restrict__ q_min,

@@ -1395,6 +1395,58 @@ def ik_solve(target, q_seed, geom, q_min=None, q_max=None, n_iters=64, damping=0
     return q, pos_err, rot_err, conv, iters
 
 
+# ---- Cartesian end-effector moves: batched straight-line tracking (csrc/mpb_cartesian.hip) -----------------------------------------
+# include/mpb.h MPB_CART_*
+CART_OK, CART_LOST, CART_JUMP, CART_BAD_TARGET, CART_COLLISION = 0, 1, 2, 3, 4
+CART_MAX_STEPS, CART_MAX_WORK, CART_MAX_TURN = 4096, 65536, 3.04159265
+
+
+@_on_tensor_device
+def cartesian_path(target, q_start, geom, n_steps, n_inner=8, damping=0.1, pos_tol=1e-3, rot_tol=1e-2, jump_max=0.5, position_only=False,
+                   q_min=None, q_max=None):
+    """Straight-line end-effector moves from S start configurations per target (mpb_cartesian_path): target (N, 3, 4) = [R* | t*],
+    q_start (N, S, D), q_min / q_max (D,) both or neither -> q_path (N, S, K+1, D), pos_err, rot_err (N, S, K+1), n_ok int32 (N, S),
+    status int32 (N, S) (CART_OK / CART_LOST / CART_JUMP / CART_BAD_TARGET), K = n_steps.  Step k follows the pose interpolated between
+    the start's own pose and the target at k / K (straight line, geodesic), at most n_inner iterations of ik_solve from the last accepted
+    configuration; a problem stops where tracking is lost or a joint would move by more than jump_max in one step, and holds still from
+    there: rows beyond n_ok repeat row n_ok."""
+    if q_start.dim() != 3:
+        raise ValueError(f'q_start has shape {tuple(q_start.shape)}, expected (N, S, D)')
+    N, S, D = q_start.shape
+    _chk(q_start, (N, S, D), 'q_start')
+    _chk(target, (N, 3, 4), 'target')
+    _need_chain(geom, 'cartesian_path')
+    if D != geom.n_dof:
+        raise ValueError(f'q_start has {D} columns, the geometry {geom.n_dof} degrees of freedom')
+    if (q_min is None) != (q_max is None):
+        raise ValueError('q_min and q_max: both or neither')
+    _chk(q_min, (D,), 'q_min', allow_none=True)
+    _chk(q_max, (D,), 'q_max', allow_none=True)
+    K, n_inner, damping, pos_tol, rot_tol, jump_max = int(n_steps), int(n_inner), float(damping), float(pos_tol), float(rot_tol), float(jump_max)
+    if not 1 <= K <= CART_MAX_STEPS:
+        raise ValueError(f'n_steps = {K} outside 1..{CART_MAX_STEPS}')
+    if not 0 <= n_inner <= IK_MAX_ITERS:
+        raise ValueError(f'n_inner = {n_inner} outside 0..{IK_MAX_ITERS}')
+    if K * n_inner > CART_MAX_WORK:
+        raise ValueError(f'n_steps * n_inner = {K * n_inner} beyond {CART_MAX_WORK}')
+    if not damping >= IK_MIN_DAMPING:
+        raise ValueError(f'damping = {damping} below {IK_MIN_DAMPING}: the unpivoted fp32 Cholesky needs the floor')
+    if not (pos_tol >= 0.0 and rot_tol >= 0.0):
+        raise ValueError('pos_tol and rot_tol must not be negative')
+    if not jump_max > 0.0:
+        raise ValueError(f'jump_max = {jump_max}: must be positive (inf turns the check off)')
+    dev = q_start.device
+    q_path = torch.empty(N, S, K + 1, D, device=dev, dtype=torch.float32)
+    pos_err = torch.empty(N, S, K + 1, device=dev, dtype=torch.float32)
+    rot_err = torch.empty(N, S, K + 1, device=dev, dtype=torch.float32)
+    n_ok = torch.empty(N, S, device=dev, dtype=torch.int32)
+    status = torch.empty(N, S, device=dev, dtype=torch.int32)
+    _lib.check(_lib.lib().mpb_cartesian_path(_ptr(target), _ptr(q_start), _ptr(geom.buf), _ptr(q_min), _ptr(q_max), _ptr(q_path),
+                                             _ptr(pos_err), _ptr(rot_err), _ptr(n_ok), _ptr(status), N, S, D, K, n_inner, damping, pos_tol,
+                                             rot_tol, jump_max, 1 if position_only else 0, _stream()), 'mpb_cartesian_path')
+    return q_path, pos_err, rot_err, n_ok, status
+
+
 def _ee_cost_args(trajs, geom, target, k_pos, k_rot, axis, h_begin, h_end, target_per_waypoint, what):
     """The checks ee_cost_eval / ee_cost_grad share -> the C arguments after the pointers: (B, H, d, D, h_begin, h_end, group, stride_g,
     stride_h, k_pos, k_rot, use_axis, ax, ay, az)."""

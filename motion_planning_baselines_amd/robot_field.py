@@ -179,7 +179,9 @@ class PlanningTask:
 
     End-effector goals (serial chains): get_EE_pose / get_EE_position (the reference's robot.get_EE_position,
     panda_spheres_GPMP.py:63-64) and inverse_kinematics -- a pose in, many goal configurations out, filtered by the predicates above
-    (mpb_fk_ee_pose, mpb_ik_solve)."""
+    (mpb_fk_ee_pose, mpb_ik_solve) --, and cartesian_path: straight-line end-effector moves from those configurations, cropped at the
+    first row one of the predicates above refuses (mpb_cartesian_path; unlike validation and shortcutting it serves a task with a
+    self_field or an sdf_field)."""
 
     def __init__(self, robot, field, self_field=None, tensor_args=None, seed=0, sdf_field=None):
         from .planners.base import require_cuda
@@ -292,6 +294,45 @@ class PlanningTask:
             free &= ~self._in_collision(q.reshape(-1, D)).reshape(conv.shape)
         return IKResult(q, conv, free, pos_err, rot_err, iters, q_ref)
 
+    def cartesian_path(self, q_start, ee_goal, n_steps=32, n_inner=8, damping=0.1, pos_tol=1e-3, rot_tol=1e-2, jump_max=0.5,
+                       position_only=False, collision_free=True):
+        """Straight-line end-effector moves (the approach to a grasp, the retreat, a lift): from every start configuration follow the
+        pose interpolated between the start's own pose and the goal pose in n_steps steps, each warm-started from the last
+        (ops.cartesian_path, within the joint limits), then the task's own collision predicates -- obstacles, self_field, sdf_field --
+        ONCE over all rows; a path is cropped before its first colliding row (status CART_COLLISION).
+        q_start: (N, S, D), or (N, D) meaning S = 1.  ee_goal: (N, 3, 4) = [R* | t*], one per target and shared by its S starts, or
+        (N, 3) positions with position_only.  Returns a CartesianPathResult whose fields keep q_start's leading dimensions."""
+        q0 = torch.as_tensor(q_start, dtype=torch.float32, device=self.device)
+        if q0.dim() not in (2, 3) or q0.shape[-1] != self.q_dim:
+            raise ValueError(f'q_start has shape {tuple(q0.shape)}, expected (N, S, {self.q_dim}) or (N, {self.q_dim})')
+        lead = tuple(q0.shape[:-1])
+        q0 = q0.reshape(q0.shape[0], -1, self.q_dim).contiguous()
+        N, S, D = q0.shape
+        t = torch.as_tensor(ee_goal, dtype=torch.float32, device=self.device)
+        if position_only and t.dim() == 2 and t.shape[-1] == 3:
+            eye = torch.eye(3, device=self.device, dtype=torch.float32).expand(t.shape[0], 3, 3)
+            t = torch.cat([eye, t[:, :, None]], -1)
+        if t.dim() != 3 or tuple(t.shape) != (N, 3, 4):
+            raise ValueError(f'ee_goal has shape {tuple(t.shape)}, expected ({N}, 3, 4)' + (f' or ({N}, 3)' if position_only else ''))
+        q, pos_err, rot_err, n_ok, status = ops.cartesian_path(t.contiguous(), q0, self.geom, n_steps, n_inner=n_inner, damping=damping,
+                                                               pos_tol=pos_tol, rot_tol=rot_tol, jump_max=jump_max,
+                                                               position_only=position_only, q_min=self.q_min.contiguous(),
+                                                               q_max=self.q_max.contiguous())
+        K = q.shape[2] - 1
+        if collision_free and q.numel():
+            hit = self._in_collision(q.reshape(-1, D)).reshape(N, S, K + 1)
+            rows = torch.arange(K + 1, device=self.device, dtype=torch.int32)
+            first = torch.where(hit, rows, K + 1).amin(-1).to(torch.int32)           # the first colliding row, K + 1 when there is none
+            crop = first <= n_ok
+            keep = (first - 1).clamp_min(0)                                            # (r = 0: n_ok = 0, the rows are kept)
+            held = torch.gather(q, 2, keep.long()[:, :, None, None].expand(N, S, 1, D))
+            over = (crop & (first > 0))[:, :, None] & (rows >= first[:, :, None])
+            q = torch.where(over[..., None], held, q)
+            n_ok = torch.where(crop, keep, n_ok)
+            status = torch.where(crop, torch.full_like(status, ops.CART_COLLISION), status)
+        return CartesianPathResult(q.reshape(*lead, K + 1, D), n_ok.reshape(lead), status.reshape(lead), pos_err.reshape(*lead, K + 1),
+                                   rot_err.reshape(*lead, K + 1), K)
+
 
     # ---- validation of a trajectory batch (build-defined like the predicate: DESIGN.md 10) -----------------------------------
     def _trajs_stats(self, trajs, num_interpolation, with_flags=False):
@@ -385,6 +426,19 @@ class TrajsRetimed:
     def __init__(self, durations, status, timing, trajs_dt=None, n_rows=None, sample_status=None):
         self.durations, self.status, self.timing = durations, status, timing
         self.trajs_dt, self.n_rows, self.sample_status = trajs_dt, n_rows, sample_status
+
+
+class CartesianPathResult:
+    """What PlanningTask.cartesian_path returns, q_start's leading dimensions (...) kept: q (..., K+1, D) -- row 0 the start, rows beyond
+    n_ok repeat row n_ok: always a valid trajectory --, n_ok (...) int32 steps accepted, fraction (...) = n_ok / K, status (...) int32
+    (ops.CART_OK / CART_LOST / CART_JUMP / CART_BAD_TARGET / CART_COLLISION), complete (...) bool = status is CART_OK, pos_err / rot_err
+    (..., K+1) the tracking error of every row against its step's target as the tracker left it (the rejected step's in row n_ok + 1 of
+    a LOST or JUMP problem).  q[complete] is a trajectory batch for retime_trajs and the validation calls."""
+
+    def __init__(self, q, n_ok, status, pos_err, rot_err, n_steps):
+        self.q, self.n_ok, self.status, self.pos_err, self.rot_err, self.n_steps = q, n_ok, status, pos_err, rot_err, int(n_steps)
+        self.fraction = n_ok.to(torch.float32) / float(n_steps)
+        self.complete = status == ops.CART_OK
 
 
 class IKResult:
