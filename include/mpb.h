@@ -39,6 +39,8 @@
 /* the packed triangle-mesh buffer in numbers (generated from mesh_layout.py): header word indices MPB_MW_*, record words MPB_TRI_*,
  * feature codes MPB_FEAT_*, MPB_MESH_* */
 #include "mpb_mesh_layout.h"
+/* the packed moving-obstacle buffer in numbers (generated from moving_layout.py): header word indices MPB_VW_*, MPB_MOVING_* */
+#include "mpb_moving_layout.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -77,7 +79,8 @@ extern "C" {
  *                        end-effector pose cost (mpb_ee_cost_eval, mpb_ee_cost_grad), and the SDF grid's build from triangle
  *                        meshes (mpb_mesh_check, mpb_sdf_grid_build_mesh), path shortcutting and the roadmap planner, and
  *                        the time parameterisation under joint limits (mpb_traj_retime, mpb_traj_retime_sample), and Cartesian
- *                        end-effector moves (mpb_cartesian_path). */
+ *                        end-effector moves (mpb_cartesian_path), and the moving-obstacle field (mpb_moving_check,
+ *                        mpb_moving_invalidate, mpb_moving_collision_eval / _grad / _check). */
 #define MPB_ABI_VERSION 7
 #define MPB_VERSION_TUNING_BUILD 0x40000000
 int mpb_version(void);
@@ -726,6 +729,61 @@ int mpb_sdf_grid_grad(const float *trajs, const float *sdf, float *out, float *g
                       int B, int H, int d, int h_begin, float k_sigma, float weight, int accumulate, void *stream);
 int mpb_sdf_grid_collision_check(const float *q, const float *sdf, unsigned char *in_collision, float *gap,
                                  int N, int D, int or_into, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Moving-obstacle field: spheres and axis-aligned boxes whose centres depend on the ROW of the trajectory (build-defined, DESIGN.md
+ * 10).  Row h sees the world at one time t_h; the host has evaluated every centre c_{o,h} for every row (geometry.MovingObstacleField:
+ * piecewise linear between keyframes, in fp64, rounded once).  Boxes translate and do not rotate.
+ *   c_h(q) = sum_l relu(margin + r_l - min_o sd_{o,h}(x_l(q)))   over the robot's collision spheres (x_l: mpb_fk_collision_points; a
+ *          point robot has its one sphere at q, z = 0 with two coordinates); sd of a sphere |x - c_{o,h}| - R_o, of a box the
+ *          expression every cost kernel takes with centre c_{o,h}; spheres in table order, then boxes, a strict < keeps the first
+ *          minimum.  Row h is in collision iff c_h(q_h) > 0.
+ *   gradient: an active sphere contributes -grad sd of its nearest obstacle through J^T, with the conventions of the static field
+ *          (|x - c|^2 clamped at 1e-30; inside a box the unit axis of the largest component, the first on ties).  Time is fixed per
+ *          row: the obstacles' velocity is no part of d c / d q.
+ *
+ * The moving-obstacle buffer is ONE self-contained array of 32-bit words with a magic and version of its own (mpb_moving_layout.h,
+ * generated from moving_layout.py -- the one definition): a header of MPB_MOVING_HEADER_WORDS words (MPB_VW_MAGIC, _VERSION, _N_DOF,
+ * _N_TF = n_dof + 1 or 0 for a point robot, _N_LINKS, _N_ROWS, _N_SPHERES, _N_BOXES, _MARGIN, the section offsets _OFF_TF, _OFF_LINKS,
+ * _OFF_RADII, _OFF_HALF, _OFF_CENTRES, _TOTAL; the rest zero), then -- each at a multiple of MPB_MOVING_ALIGN words -- the joint
+ * transforms (n_tf x 12) and the link table (n_links x 8) in the row formats of the geometry buffer, EVERY link; the sphere radii
+ * (n_spheres, zero-padded to a multiple of MPB_MOVING_ALIGN); the box half extents (n_boxes x 4: hx, hy, hz, 0); the centres as
+ * [obstacle][x|y|z][row], spheres first, the row axis padded to a multiple of MPB_MOVING_ROW_PAD by repeating row n_rows - 1 (the
+ * lanes of a trip read 64 consecutive words and never past the table).  Limits: MPB_MOVING_MAX_ROWS rows, MPB_MOVING_MAX_SPHERES
+ * spheres, MPB_MOVING_MAX_BOXES boxes (at least one obstacle), MPB_MOVING_MAX_LINKS collision spheres of the robot.
+ *
+ * mpb_moving_check validates such a buffer held in HOST memory (n_words must equal its total): magic / version, limits, the transforms
+ * a robot kind needs, offsets and total, a finite margin, link frames sorted in [1, n_dof + 1], positive finite radii and half
+ * extents, finite centres, padding rows that repeat the last row.
+ *
+ * The device entry points take the buffer in DEVICE memory, 16-byte aligned, validated by the caller before the upload.  They read
+ * its 16 header words back ONCE per buffer address and device (a synchronous 64-byte copy on the first call with that pointer: make
+ * that call outside stream capture) and check the header alone.  H must equal the buffer's n_rows -- the centres were evaluated for
+ * exactly those rows --: otherwise MPB_E_INVALID, and mpb_last_error names both numbers.  The kernels form every centre index from
+ * the numbers they were launched with, compare the header (magic, n_dof, n_links, n_rows, n_spheres, n_boxes) with them and answer NaN
+ * (in_collision = 1) when it has changed since.  mpb_moving_invalidate(moving) forgets what was read at that address: call it whenever
+ * ANOTHER buffer is written at an address an earlier call may have seen.  Host only, never fails.
+ *
+ * mpb_moving_collision_eval / _grad: the signature and meaning of mpb_self_collision_eval / _grad with c_h as above: out[b] (+)= weight
+ *   * k_sigma * sum_{h >= h_begin} c_h(trajs[b, h, :n_dof]); per_waypoint (B, H) optional: c_h un-scaled, 0 for h < h_begin; grad
+ *   (B, H, d) (+)= d out[b] / d trajs[b], the velocity channels n_dof .. d-1 written 0 when not accumulating and left alone when
+ *   accumulating; accumulate != 0 adds the fresh value in ONE fp32 rounding.
+ * mpb_moving_collision_check: per ROW, because the predicate needs the row's time: trajs (B, H, d), d >= n_dof; in_collision (B * H)
+ *   bytes 0 / 1 = c_h > 0; gap (B * H) optional: c_h; or_into != 0 ORs into the existing flags and adds c_h onto the existing gap.
+ * One wave per trajectory, one lane per row, trips of 64; no LDS, no atomics; sums in fixed order (spheres in table order in fp32,
+ * a lane's rows ascending, a fixed wave reduction): the same bits on every run.
+ * Refusals, in this order: d > 2 MPB_MAX_DOF: MPB_E_UNSUPPORTED; B < 0, H < 1, d < 1, h_begin < 0: MPB_E_INVALID; (B == 0: MPB_OK,
+ * nothing launched;) a null required pointer, a buffer not 16-byte aligned: MPB_E_INVALID; the header: as mpb_moving_check says of
+ * it; d < n_dof: MPB_E_INVALID; H != n_rows: MPB_E_INVALID.
+ * ------------------------------------------------------------------------------------------- */
+int mpb_moving_check(const float *moving_host, int n_words);
+int mpb_moving_invalidate(const float *moving);
+int mpb_moving_collision_eval(const float *trajs, const float *moving, float *out, float *per_waypoint,
+                              int B, int H, int d, int h_begin, float k_sigma, float weight, int accumulate, void *stream);
+int mpb_moving_collision_grad(const float *trajs, const float *moving, float *out, float *grad,
+                              int B, int H, int d, int h_begin, float k_sigma, float weight, int accumulate, void *stream);
+int mpb_moving_collision_check(const float *trajs, const float *moving, unsigned char *in_collision, float *gap,
+                               int B, int H, int d, int or_into, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
  * SDF grid from triangle meshes: the exact signed distance to a mesh at every node (build-defined).

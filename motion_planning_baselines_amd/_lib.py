@@ -82,6 +82,11 @@ SIGNATURES = {
     'mpb_sdf_grid_eval': [_p, _p, _p, _p, _i, _i, _i, _i, _f, _f, _i, _p],
     'mpb_sdf_grid_grad': [_p, _p, _p, _p, _i, _i, _i, _i, _f, _f, _i, _p],
     'mpb_sdf_grid_collision_check': [_p, _p, _p, _p, _i, _i, _i, _p],
+    'mpb_moving_check': [_p, _i],
+    'mpb_moving_invalidate': [_p],
+    'mpb_moving_collision_eval': [_p, _p, _p, _p, _i, _i, _i, _i, _f, _f, _i, _p],
+    'mpb_moving_collision_grad': [_p, _p, _p, _p, _i, _i, _i, _i, _f, _f, _i, _p],
+    'mpb_moving_collision_check': [_p, _p, _p, _p, _i, _i, _i, _i, _p],
     'mpb_fk_ee_pose': [_p, _p, _p, _p, _i, _i, _p],
     'mpb_ik_solve': [_p] * 10 + [_i] * 4 + [_f] * 3 + [_i, _p],
     'mpb_cartesian_path': [_p] * 10 + [_i] * 5 + [_f] * 4 + [_i, _p],
@@ -196,6 +201,12 @@ def self_check(buf):
     """Validate a packed self-collision buffer (numpy fp32) on the host side of the C-ABI."""
     buf = np.ascontiguousarray(buf, dtype=np.float32)
     check(lib().mpb_self_check(buf.ctypes.data_as(ctypes.c_void_p), int(buf.size)), 'mpb_self_check')
+
+
+def moving_check(buf):
+    """Validate a packed moving-obstacle buffer (numpy fp32, geometry.pack_moving_obstacles) on the host side of the C-ABI."""
+    buf = np.ascontiguousarray(buf, dtype=np.float32)
+    check(lib().mpb_moving_check(buf.ctypes.data_as(ctypes.c_void_p), int(buf.size)), 'mpb_moving_check')
 
 
 def sdf_grid_check(buf, n_words=None):

@@ -495,6 +495,167 @@ def pack_self_collision(robot, field):
     return buf
 
 
+class MovingObstacleField:
+    """Obstacles that move (build-defined): spheres and axis-aligned boxes whose centres follow keyframes, seen by
+    row h of a trajectory at the time t_h of the field's clock.
+
+    t_key (K,): K >= 1 keyframe times, strictly ascending.  sphere_centers (K, Os, 3) with sphere_radii (Os,); box_centers (K, Ob, 3)
+    with box_half (Ob, 3): boxes translate and do not rotate.  Os + Ob >= 1.  Centres given with two coordinates get z = 0 (a planar
+    point mass), box half extents given with two get BOX_2D_HALF_Z, as CollisionField's 2-D forms do.  Every refusal is a ValueError that
+    names the argument.
+
+    Motion: centres are piecewise linear between keyframes, held at the first keyframe before t_key[0] and at the last after
+    t_key[-1], evaluated in fp64 on the host.
+    Clock: a trajectory of R >= 2 rows spans [t_start, t_end] uniformly, row h at t_start + h (t_end - t_start) / (R - 1); a single
+    row is at t_start.  The defaults are t_key[0] and t_key[-1].  The clock belongs to the field, not to a row count: the same field
+    serves a planner's support points, an interpolated trajectory and MPPI's rollouts.
+
+    Cost of row h:  c_h(q) = sum_l relu(margin + r_l - min_o sd_{o,h}(x_l(q)))  with CollisionField's signed distances and gradient
+    conventions about the centres c_{o,h}; spheres in the given order, then boxes.  Time is fixed per row: the obstacles' velocity is no
+    part of d c / d q.  A field whose keyframes are all equal means exactly the static CollisionField of at(t)."""
+
+    def __init__(self, t_key, sphere_centers=None, sphere_radii=None, box_centers=None, box_half=None, margin=0.05, t_start=None, t_end=None):
+        t = np.asarray(t_key, dtype=np.float64).reshape(-1)
+        if t.size < 1 or not np.all(np.isfinite(t)) or np.any(np.diff(t) <= 0):
+            raise ValueError('t_key must hold K >= 1 finite, strictly ascending keyframe times')
+        self.t_key = t
+        K = t.size
+
+        def centres(c, name):
+            if c is None:
+                return np.zeros((K, 0, 3))
+            c = np.asarray(c, dtype=np.float64)
+            if c.ndim != 3 or c.shape[0] != K or c.shape[2] not in (2, 3):
+                raise ValueError(f'{name} has shape {c.shape}, expected (K = {K}, O, 3) (or (K, O, 2): z = 0)')
+            if not np.all(np.isfinite(c)):
+                raise ValueError(f'{name} must be finite')
+            if c.shape[2] == 2:
+                c = np.concatenate([c, np.zeros(c.shape[:2] + (1,))], -1)
+            return np.ascontiguousarray(c)
+
+        def sizes(v, n, width, name, centres_name):
+            if v is None:
+                if n:
+                    raise ValueError(f'{name} is required with {centres_name}')
+                return np.zeros((0, width) if width > 1 else (0,))
+            v = np.asarray(v, dtype=np.float64)
+            if width == 3 and v.ndim == 2 and v.shape[1] == 2:
+                v = np.concatenate([v, np.full((v.shape[0], 1), BOX_2D_HALF_Z)], -1)
+            want = (n, width) if width > 1 else (n,)
+            if v.shape != want:
+                raise ValueError(f'{name} has shape {v.shape}, expected {want} to go with {centres_name}')
+            if not (np.all(np.isfinite(v)) and np.all(v > 0)):
+                raise ValueError(f'{name} must be finite and > 0')
+            return np.ascontiguousarray(v)
+
+        self.sphere_centers = centres(sphere_centers, 'sphere_centers')
+        self.sphere_radii = sizes(sphere_radii, self.sphere_centers.shape[1], 1, 'sphere_radii', 'sphere_centers')
+        self.box_centers = centres(box_centers, 'box_centers')
+        self.box_half = sizes(box_half, self.box_centers.shape[1], 3, 'box_half', 'box_centers')
+        if self.n_spheres + self.n_boxes < 1:
+            raise ValueError('sphere_centers / box_centers: a MovingObstacleField needs at least one obstacle')
+        self.margin = float(margin)
+        if not np.isfinite(self.margin):
+            raise ValueError('margin must be finite')
+        self.t_start = float(t[0] if t_start is None else t_start)
+        self.t_end = float(t[-1] if t_end is None else t_end)
+        if not np.isfinite(self.t_start):
+            raise ValueError('t_start must be finite')
+        if not (np.isfinite(self.t_end) and self.t_end >= self.t_start):
+            raise ValueError('t_end must be finite and >= t_start')
+
+    @property
+    def n_spheres(self):
+        return self.sphere_centers.shape[1]
+
+    @property
+    def n_boxes(self):
+        return self.box_centers.shape[1]
+
+    def times(self, R):
+        """(R,) fp64: the time of every row of a trajectory of R rows."""
+        R = int(R)
+        if R < 1:
+            raise ValueError(f'R = {R}: a trajectory has at least one row')
+        if R == 1:
+            return np.array([self.t_start])
+        return self.t_start + np.arange(R) * (self.t_end - self.t_start) / (R - 1)
+
+    def _centres(self, t):
+        """t (R,) -> ((R, Os, 3), (R, Ob, 3)) fp64: piecewise linear per component, held beyond the keyframes."""
+        t = np.asarray(t, dtype=np.float64).reshape(-1)
+        out = []
+        for keys in (self.sphere_centers, self.box_centers):
+            c = np.zeros((t.size,) + keys.shape[1:])
+            for o in range(keys.shape[1]):
+                for k in range(3):
+                    c[:, o, k] = np.interp(t, self.t_key, keys[:, o, k])
+            out.append(c)
+        return tuple(out)
+
+    def rows(self, R):
+        """The centres of every obstacle at every row of a trajectory of R rows: ((R, Os, 3), (R, Ob, 3)) fp64."""
+        return self._centres(self.times(R))
+
+    def at(self, t):
+        """The static CollisionField the obstacles form at time t, with the same margin (centres rounded once from fp64): for a
+        frozen-time RRT, for drawing, and what the tests restate the definition with."""
+        t = float(t)
+        if not np.isfinite(t):
+            raise ValueError('t must be finite')
+        sc, bc = self._centres(np.array([t]))
+        spheres = np.concatenate([sc[0], self.sphere_radii[:, None]], 1) if self.n_spheres else None
+        boxes = np.concatenate([bc[0], self.box_half], 1) if self.n_boxes else None
+        return CollisionField(spheres=spheres, boxes=boxes, margin=self.margin)
+
+    def shifted(self, delta):
+        """The same motion with the window [t_start, t_end] moved by `delta`: the receding-horizon step."""
+        delta = float(delta)
+        if not np.isfinite(delta):
+            raise ValueError('delta must be finite')
+        return MovingObstacleField(self.t_key, self.sphere_centers if self.n_spheres else None, self.sphere_radii if self.n_spheres else None,
+                                   self.box_centers if self.n_boxes else None, self.box_half if self.n_boxes else None, margin=self.margin,
+                                   t_start=self.t_start + delta, t_end=self.t_end + delta)
+
+    def zero_grad(self):
+        pass
+
+
+def pack_moving_obstacles(robot, field, n_rows):
+    """Pack a robot + a MovingObstacleField for trajectories of n_rows rows into ONE self-contained fp32 word buffer (moving_layout.py:
+    header, joint_tf rows, links rows -- both in the row formats of pack_geometry, every link kept --, the radii and half-extent tables,
+    then the centres as [obstacle][x|y|z][row], the row axis padded to a multiple of MOVING_ROW_PAD by repeating the last row; centres
+    rounded once from fp64)."""
+    from . import moving_layout as S
+    if not isinstance(field, MovingObstacleField):
+        raise TypeError('pack_moving_obstacles takes a MovingObstacleField')
+    rs = robot.spec()
+    n_rows = int(n_rows)
+    n_tf, n_links, ns, nb = rs['joint_tf'].shape[0], len(rs['link_radius']), field.n_spheres, field.n_boxes
+    for what, n, lo, name in (('n_rows', n_rows, 1, 'MOVING_MAX_ROWS'), ('moving spheres', ns, 0, 'MOVING_MAX_SPHERES'),
+                              ('moving boxes', nb, 0, 'MOVING_MAX_BOXES'), ('collision spheres of the robot', n_links, 1, 'MOVING_MAX_LINKS')):
+        if not lo <= n <= getattr(S, name):
+            raise ValueError(f'{what}: {n} outside {lo}..{name} = {getattr(S, name)}')
+    off = S.offsets(n_tf, n_links, n_rows, ns, nb)
+    buf = np.zeros((off['total'],), dtype=np.float32)
+    hdr = S.header(buf)
+    for name, value in dict(magic=S.MOVING_MAGIC, version=S.MOVING_VERSION, n_dof=rs['n_dof'], n_tf=n_tf, n_links=n_links, n_rows=n_rows,
+                            n_spheres=ns, n_boxes=nb, margin=field.margin, **off).items():
+        hdr[name] = value
+    sec = S.sections(buf)
+    sec['joint_tf'][...] = rs['joint_tf'].astype(np.float32)
+    sec['links'].view(np.int32)[:, 0] = rs['link_frame'] if rs['kind'] == KIND_CHAIN else 1
+    sec['links'][:, 1:4] = rs['link_offset']
+    sec['links'][:, 4] = rs['link_radius']
+    sec['radii'][...] = field.sphere_radii.astype(np.float32)
+    sec['half'][:, :3] = field.box_half.astype(np.float32)
+    sc, bc = field.rows(n_rows)
+    c = np.concatenate([sc, bc], 1).astype(np.float32)                 # (R, O, 3), spheres first
+    sec['centres'][:, :, :n_rows] = c.transpose(1, 2, 0)
+    sec['centres'][:, :, n_rows:] = sec['centres'][:, :, n_rows - 1:n_rows]
+    return buf
+
+
 class TriangleMesh:
     """A triangle mesh as the source of a GridSDFField (GridSDFField.from_mesh): `vertices` (nv, 3), `faces` (nt, 3) vertex indices,
     triangles counter-clockwise seen from outside.  The vertices are kept as the fp32 numbers the packed buffer carries; every check
@@ -1120,6 +1281,9 @@ def pack_geometry(robot, field, scales=None, prune_static=True, use_model=True, 
         for part in parts[:-1]:
             header(part)['next'] = part.size
         return np.concatenate(parts)
+    if isinstance(field, MovingObstacleField):
+        raise TypeError('a MovingObstacleField has no place in a geometry buffer (its centres carry a row axis): pack it with '
+                        'pack_moving_obstacles / ops.DeviceMovingObstacles, or freeze it with field.at(t)')
     rs, fs = robot.spec(), field.spec()
     from . import model_gen
     model_id, keep_mask = 0, 0

@@ -13,7 +13,7 @@ import numpy as np
 import torch
 
 from . import _lib, rrt_layout
-from .geometry import KIND_CHAIN, MAX_FIELDS, CollisionField, TriangleMesh, count_fields, mesh_pose, occupancy_bytes, pack_geometry, pack_mesh, pack_sdf_grid, pack_self_collision
+from .geometry import KIND_CHAIN, MAX_FIELDS, CollisionField, TriangleMesh, count_fields, mesh_pose, occupancy_bytes, pack_geometry, pack_mesh, pack_moving_obstacles, pack_sdf_grid, pack_self_collision
 from .geometry import header as geometry_header
 
 
@@ -391,11 +391,80 @@ def sdf_grid_check(q, sdf, with_gap=False, flag=None, gap=None):
     return _config_predicate('mpb_sdf_grid_collision_check', 'robot', q, sdf, with_gap, flag, gap)
 
 
+class DeviceMovingObstacles(_DeviceMemberBuffer):
+    """A robot + a MovingObstacleField for trajectories of `n_rows` rows as the packed moving-obstacle buffer
+    (geometry.pack_moving_obstacles) resident in HBM: packed, validated (mpb_moving_check) and uploaded once.  The buffer serves
+    exactly that row count: the centres are evaluated per row from the field's clock."""
+    INVALIDATE = 'mpb_moving_invalidate'
+
+    def __init__(self, robot, field, device, n_rows):
+        from .moving_layout import header as moving_header
+        self.robot, self.field = robot, field
+        self.host = pack_moving_obstacles(robot, field, n_rows)
+        _lib.moving_check(self.host)
+        hdr = moving_header(self.host)
+        self.n_dof, self.n_links, self.n_rows = int(hdr['n_dof']), int(hdr['n_links']), int(hdr['n_rows'])
+        self.n_spheres, self.n_boxes, self.off_centres = int(hdr['n_spheres']), int(hdr['n_boxes']), int(hdr['off_centres'])
+        self._adopt(torch.from_numpy(self.host.copy()).to(device))
+
+    def update(self, field):
+        """The obstacles of another field of the SAME shapes (counts, radii, half extents, margin) -- typically field.shifted(dt), the
+        receding-horizon step -- into the same device buffer: packed again on the host, only the centre section is uploaded, and the
+        library's cached header for the address is dropped.  Returns self."""
+        host = pack_moving_obstacles(self.robot, field, self.n_rows)
+        o = self.off_centres
+        if host.size != self.host.size or not np.array_equal(host[:o].view(np.uint32), self.host[:o].view(np.uint32)):
+            raise ValueError('update: the field must keep the obstacle counts, radii, half extents and margin the buffer was packed with')
+        _lib.moving_check(host)
+        self.field, self.host = field, host
+        self.buf[o:].copy_(torch.from_numpy(host[o:].copy()))
+        _lib.check(getattr(_lib.lib(), self.INVALIDATE)(_ptr(self.buf)), self.INVALIDATE)
+        return self
+
+
+@_on_tensor_device
+def moving_collision_eval(trajs, mo, k_sigma, weight=1.0, h_begin=1, per_waypoint=False, out=None, accumulate=False):
+    """trajs (B, H, d), H == mo.n_rows -> out (B,) (+)= weight * k_sigma * sum_{h >= h_begin} c_h(q_h) of a DeviceMovingObstacles
+    (mpb_moving_collision_eval); per_waypoint also returns c (B, H), un-scaled, 0 below h_begin."""
+    return _row_cost_eval('mpb_moving_collision_eval', 'robot', trajs, mo, k_sigma, weight, h_begin, per_waypoint, out, accumulate)
+
+
+@_on_tensor_device
+def moving_collision_grad(trajs, mo, k_sigma, weight=1.0, h_begin=1, out=None, grad=None, accumulate=False):
+    """(out (B,), grad (B, H, d)) (+)= the moving-obstacle cost and d out / d trajs (mpb_moving_collision_grad); accumulate adds onto the
+    given `out` AND `grad` (velocity channels left alone), otherwise both are written (velocity channels 0)."""
+    return _row_cost_grad('mpb_moving_collision_grad', 'robot', trajs, mo, k_sigma, weight, h_begin, out, grad, accumulate)
+
+
+@_on_tensor_device
+def moving_collision_check(trajs, mo, with_gap=False, flag=None, gap=None):
+    """trajs (B, H, d), H == mo.n_rows -> bool (B, H): row h collides with the obstacles as they stand at its time
+    (mpb_moving_collision_check); with_gap also returns the hinge sums (B, H).  Given `flag` (and `gap`), both (B, H), the answer is ORed
+    into the flags and added onto the gap."""
+    B, H, d = trajs.shape
+    _chk(trajs, (B, H, d), 'trajs')
+    if d < mo.n_dof:
+        raise ValueError(f'trajs has {d} columns, the robot {mo.n_dof} degrees of freedom')
+    or_into = flag is not None
+    if or_into:
+        _chk(flag, (B, H), 'flag', dtype=torch.bool)
+        _chk(gap, (B, H), 'gap', allow_none=True)
+        if with_gap and gap is None:
+            raise ValueError('with_gap next to flag= needs the gap= to add onto')
+    else:
+        flag = torch.empty(B, H, device=trajs.device, dtype=torch.bool)
+        gap = torch.empty(B, H, device=trajs.device, dtype=torch.float32) if with_gap else None
+    _lib.check(_lib.lib().mpb_moving_collision_check(_ptr(trajs), _ptr(mo.buf), _ptr(flag), _ptr(gap), B, H, d, int(or_into), _stream()),
+               'mpb_moving_collision_check')
+    return (flag, gap) if (with_gap or gap is not None) else flag
+
+
 # the wrappers that serve each member buffer, for the callers that hold one without caring which (CostCollision.own_eval / own_grad,
 # PlanningTask's predicate)
 MemberOps = collections.namedtuple('MemberOps', 'eval grad check')
 MEMBER_OPS = {DeviceSelfCollision: MemberOps(self_collision_eval, self_collision_grad, self_collision_check),
-              DeviceSDFGrid: MemberOps(sdf_grid_eval, sdf_grid_grad, sdf_grid_check)}
+              DeviceSDFGrid: MemberOps(sdf_grid_eval, sdf_grid_grad, sdf_grid_check),
+              DeviceMovingObstacles: MemberOps(moving_collision_eval, moving_collision_grad, moving_collision_check)}   # (check: per ROW of (B, H, d))
 
 
 @_on_tensor_device

@@ -14,7 +14,7 @@ import numpy as np
 import torch
 
 from ... import ops
-from ...geometry import GridSDFField, SelfCollisionField
+from ...geometry import GridSDFField, MovingObstacleField, SelfCollisionField
 
 
 class Cost(ABC):
@@ -74,8 +74,14 @@ class CostCollision(Cost):
     self-collision kernels (mpb_self_collision_*).  Such a member is never fused into a planner kernel.
 
     `field` may also be a geometry.GridSDFField (a precomputed grid of signed distances, the reference's precompute_sdf_obj_fixed=True):
-    the same three go to the SDF-grid kernels (mpb_sdf_grid_*).  Both kinds are "members with kernels of their own" (own_kernels): never
-    an obstacle member, never fused, served by own_eval / own_grad -- which is all a planner's device path needs to know of them.
+    the same three go to the SDF-grid kernels (mpb_sdf_grid_*).
+
+    `field` may also be a geometry.MovingObstacleField (obstacles whose centres follow keyframes; row h of whatever trajectory the member
+    is handed sees them at the time t_h of the field's clock): the same three go to the moving-obstacle kernels (mpb_moving_collision_*),
+    through one packed buffer per row count (device_own(device, rows)).
+
+    All three kinds are "members with kernels of their own" (own_kernels): never an obstacle member, never fused, served by own_eval /
+    own_grad -- which is all a planner's device path needs to know of them.
     """
 
     def __init__(self, robot, n_support_points, field=None, sigma_coll=None, **kwargs):
@@ -98,14 +104,28 @@ class CostCollision(Cost):
         return isinstance(self.field, GridSDFField)
 
     @property
-    def own_kernels(self):
-        """The member's field is no obstacle list: it has eval / gradient kernels of its own (own_eval, own_grad)."""
-        return self.is_self or self.is_grid
+    def is_moving(self):
+        return isinstance(self.field, MovingObstacleField)
 
-    def device_own(self, device):
-        """The packed buffer of a member with kernels of its own on `device` -- an ops.DeviceSelfCollision or an ops.DeviceSDFGrid: packed,
-        checked and uploaded (the grid, where it has no host values, built there) once."""
+    @property
+    def own_kernels(self):
+        """The member's field is no static obstacle list: it has eval / gradient kernels of its own (own_eval, own_grad)."""
+        return self.is_self or self.is_grid or self.is_moving
+
+    def device_own(self, device, rows=None):
+        """The packed buffer of a member with kernels of its own on `device` -- an ops.DeviceSelfCollision, an ops.DeviceSDFGrid or an
+        ops.DeviceMovingObstacles: packed, checked and uploaded (the grid, where it has no host values, built there) once.  `rows`: the
+        rows of the trajectories a MovingObstacleField member is to serve -- one buffer per row count is kept (the support points, an
+        interpolated trajectory and MPPI's rollouts each have their own); the other kinds ignore it."""
         assert self.own_kernels
+        if self.is_moving:
+            if rows is None:
+                raise TypeError('device_own of a MovingObstacleField member needs the row count: its buffer holds the centres per row')
+            cache = self.__dict__.setdefault('_own_rows', {})
+            key = (str(torch.device(device)), int(rows))
+            if key not in cache or cache[key].field is not self.field:
+                cache[key] = ops.DeviceMovingObstacles(self.robot, self.field, device, int(rows))
+            return cache[key]
         if self._own is None or self._own.buf.device != torch.device(device):
             self._own = (ops.DeviceSelfCollision if self.is_self else ops.DeviceSDFGrid)(self.robot, self.field, device)
         return self._own
@@ -121,14 +141,16 @@ class CostCollision(Cost):
         return self.device_own(device)
 
     def own_eval(self, trajs, weight=1.0, k_sigma=None, **kw):
-        """ops.self_collision_eval / ops.sdf_grid_eval of this member on (B, H, d) trajectories: h_begin, per_waypoint, out, accumulate
-        as those take them; k_sigma defaults to the member's."""
-        own = self.device_own(trajs.device)
+        """ops.self_collision_eval / ops.sdf_grid_eval / ops.moving_collision_eval of this member on (B, H, d) trajectories: h_begin,
+        per_waypoint, out, accumulate as those take them; k_sigma defaults to the member's.  A MovingObstacleField member takes the row
+        count, hence the times, from trajs.shape[1]."""
+        own = self.device_own(trajs.device, trajs.shape[1])
         return ops.MEMBER_OPS[type(own)].eval(trajs, own, self.k_sigma if k_sigma is None else k_sigma, weight=weight, **kw)
 
     def own_grad(self, trajs, weight=1.0, k_sigma=None, **kw):
-        """ops.self_collision_grad / ops.sdf_grid_grad of this member: h_begin, out, grad, accumulate as those take them."""
-        own = self.device_own(trajs.device)
+        """ops.self_collision_grad / ops.sdf_grid_grad / ops.moving_collision_grad of this member: h_begin, out, grad, accumulate as
+        those take them."""
+        own = self.device_own(trajs.device, trajs.shape[1])
         return ops.MEMBER_OPS[type(own)].grad(trajs, own, self.k_sigma if k_sigma is None else k_sigma, weight=weight, **kw)
 
     def device_geometry(self, device):
@@ -136,6 +158,8 @@ class CostCollision(Cost):
             raise TypeError('a SelfCollisionField has no obstacle geometry: use device_self()')
         if self.is_grid:
             raise TypeError('a GridSDFField has no obstacle geometry: use device_sdf()')
+        if self.is_moving:
+            raise TypeError('a MovingObstacleField has no static obstacle geometry: use device_own(device, rows)')
         if self._geom is None or self._geom.buf.device != torch.device(device):
             self._geom = ops.DeviceGeometry(self.robot, self.field, device)
         return self._geom
@@ -407,6 +431,7 @@ class CostEEPose(Cost):
     own_kernels = True
     is_self = False
     is_grid = False
+    is_moving = False
 
     def __init__(self, robot, n_support_points, target, sigma_pos=None, sigma_rot=None, axis=None, traj_range='goal',
                  target_per_waypoint=False, tensor_args=None, **kwargs):

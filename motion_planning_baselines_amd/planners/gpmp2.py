@@ -11,7 +11,7 @@ import torch
 import torch.distributed as dist
 
 from .. import ops
-from ..geometry import GridSDFField, SelfCollisionField
+from ..geometry import GridSDFField, MovingObstacleField, SelfCollisionField
 from .base import OptimizationPlanner
 from .costs.cost_functions import Cost, CostCollision, CostComposite, CostGP, CostGoalPrior, _TrajectoryTermCost
 
@@ -87,6 +87,9 @@ class GPMP2(OptimizationPlanner):
         if any(isinstance(f, GridSDFField) for f in collision_fields):
             raise NotImplementedError('GPMP2: a GridSDFField in collision_fields is not wired into the low-rank solve; pass it as '
                                       'extra_costs=[CostCollision(robot, H, field=GridSDFField(...), sigma_coll=...)] (the dense step)')
+        if any(isinstance(f, MovingObstacleField) for f in collision_fields):
+            raise NotImplementedError('GPMP2: a MovingObstacleField in collision_fields is not wired into the low-rank solve; pass it as '
+                                      'extra_costs=[CostCollision(robot, H, field=MovingObstacleField(...), sigma_coll=...)] (the dense step)')
         scales = [1.0] * len(collision_fields)
         n_fields_own = len(collision_fields)
         # the sigmas the block solve runs on: an extra CostGP / CostGoalPrior on the planner's OWN start / goal states is one

@@ -9,7 +9,7 @@ evaluated factor-wise (csrc/mpb_stoch_gpmp.hip).
 import torch
 
 from .. import ops
-from ..geometry import MAX_DOF, GridSDFField, SelfCollisionField
+from ..geometry import MAX_DOF, GridSDFField, MovingObstacleField, SelfCollisionField
 from .base import OptimizationPlanner, gp_prior_factor, gp_prior_scale_tril
 
 
@@ -39,6 +39,8 @@ class StochGPMP(OptimizationPlanner):
             raise NotImplementedError('StochGPMP: a SelfCollisionField in collision_fields is not wired into the fused StochGPMP cost')
         if any(isinstance(f, GridSDFField) for f in (collision_fields or [])):
             raise NotImplementedError('StochGPMP: a GridSDFField in collision_fields is not wired into the fused StochGPMP cost')
+        if any(isinstance(f, MovingObstacleField) for f in (collision_fields or [])):
+            raise NotImplementedError('StochGPMP: a MovingObstacleField in collision_fields is not wired into the fused StochGPMP cost')
         if not collision_fields or len(collision_fields) > 4:
             raise NotImplementedError('StochGPMP on the GPU takes one to four CollisionFields')
         assert multi_goal_states is not None, 'StochGPMP kernels need goal states'

@@ -177,6 +177,10 @@ class PlanningTask:
     sdf_field: a geometry.GridSDFField (a precomputed grid of signed distances: geometry the obstacle list cannot hold).  Its predicate
     (mpb_sdf_grid_collision_check with or_into) is ORed in the same way, and the same callers refuse such a task by name.
 
+    A geometry.MovingObstacleField is none of these: it is refused by name as field, self_field or sdf_field (the predicates and the
+    sample-based planners have no time axis).  check_trajs_moving(trajs, moving_field) validates trajectories against the task's static
+    predicates AND such a field, row by row at the field's clock.
+
     End-effector goals (serial chains): get_EE_pose / get_EE_position (the reference's robot.get_EE_position,
     panda_spheres_GPMP.py:63-64) and inverse_kinematics -- a pose in, many goal configurations out, filtered by the predicates above
     (mpb_fk_ee_pose, mpb_ik_solve) --, and cartesian_path: straight-line end-effector moves from those configurations, cropped at the
@@ -187,6 +191,12 @@ class PlanningTask:
         from .planners.base import require_cuda
         self.tensor_args = tensor_args
         self.device = require_cuda(tensor_args)
+        from .geometry import MovingObstacleField
+        for name, f in (('field', field), ('self_field', self_field), ('sdf_field', sdf_field)):
+            if any(isinstance(x, MovingObstacleField) for x in (f if isinstance(f, (list, tuple)) else [f])):
+                raise TypeError(f'PlanningTask({name}=...): a MovingObstacleField is no static field -- the task\'s predicates, samplers and '
+                                f'the RRT / PRM / shortcut kernels have no time axis.  Freeze it with field.at(t), give it to the optimisers '
+                                f'as CostCollision(field=...), and validate trajectories with check_trajs_moving(trajs, moving_field)')
         self.robot, self.field = robot, field
         self.geom = ops.DeviceGeometry(robot, field, self.device)
         self.self_field = self_field
@@ -212,6 +222,30 @@ class PlanningTask:
             if own is not None:
                 ops.MEMBER_OPS[type(own)].check(q2, own, flag=flag)
         return flag
+
+    def check_trajs_moving(self, trajs, moving_field):
+        """trajs (..., H, W), W >= q_dim, against the task's own static predicates AND a geometry.MovingObstacleField: returns
+        (in_collision (...), rows (..., H)), both bool.  rows[..., h] = the task's predicate on row h (_in_collision: obstacles,
+        self_field, sdf_field) ORed with the moving predicate of row h at the time t_h of the field's clock over H rows
+        (mpb_moving_collision_check); in_collision = any row.  The check is made AT THE ROWS only.  For a denser check interpolate the
+        trajectory first (ops.traj_interpolate) and call again: the clock follows the row count, so the denser rows are seen at their own
+        times.  One packed buffer per (field, H) is kept on the task."""
+        from .geometry import MovingObstacleField
+        if not isinstance(moving_field, MovingObstacleField):
+            raise TypeError('check_trajs_moving takes a geometry.MovingObstacleField')
+        t = torch.as_tensor(trajs, dtype=torch.float32, device=self.device)
+        if t.dim() < 2 or t.shape[-1] < self.q_dim:
+            raise ValueError(f'trajs has shape {tuple(t.shape)}, expected (..., H, W) with W >= {self.q_dim}')
+        lead, H = tuple(t.shape[:-2]), t.shape[-2]
+        t = t.reshape(-1, H, t.shape[-1]).contiguous()
+        cache = self.__dict__.setdefault('_moving_geoms', {})
+        key = (id(moving_field), H)
+        if key not in cache or cache[key].field is not moving_field:
+            cache[key] = ops.DeviceMovingObstacles(self.robot, moving_field, self.device, H)
+        rows = self._in_collision(t[..., :self.q_dim].reshape(-1, self.q_dim).contiguous()).reshape(t.shape[0], H).contiguous()
+        if t.shape[0]:
+            ops.moving_collision_check(t, cache[key], flag=rows)
+        return rows.any(-1).reshape(lead), rows.reshape(*lead, H)
 
     def require_no_sdf_field(self, what):
         if self.sdf_field is not None:
