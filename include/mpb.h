@@ -41,6 +41,9 @@
 #include "mpb_mesh_layout.h"
 /* the packed moving-obstacle buffer in numbers (generated from moving_layout.py): header word indices MPB_VW_*, MPB_MOVING_* */
 #include "mpb_moving_layout.h"
+/* the workspace and decision log of the space-time RRT-Connect in numbers (generated from strrt_layout.py): statuses MPB_STRRT_*, global
+ * word indices MPB_STG_*, header word indices MPB_STH_*, log record words MPB_STL_* */
+#include "mpb_strrt_layout.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -1010,6 +1013,62 @@ int mpb_rrt_connect_run(void *workspace, size_t workspace_bytes, const float *ge
                         int *lengths, int *status, int B, int max_nodes, int n_pre, int D, int Lmax, int iter0,
                         int n_iters, int total_iters, float step_size, float n_radius, uint64_t seed,
                         uint32_t problem_offset, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Space-time RRT-Connect among moving obstacles (build-defined: the reference has nothing like it) for B independent problems
+ * at once.  One persistent launch, one single-wave workgroup per problem; workgroups never wait on each other, there is no
+ * spin wait, every loop is bounded by n_iters, max_nodes, n_rows or Lmax, and a finished problem returns at once.
+ *
+ * Time lives on the row grid of a packed moving-obstacle buffer `moving` (mpb_moving_layout.h) packed for n_rows = R rows,
+ *   MPB_STRRT_MIN_ROWS <= R <= MPB_STRRT_MAX_ROWS: row h is the field's time t_start + h (t_end - t_start) / (R - 1).  Obstacle
+ *   positions are never interpolated: every check is made AT A ROW with the buffer's centres of that row, the statement
+ *   mpb_moving_collision_check makes of a trajectory.  A finer clock is a larger R.
+ * Problem b: start (b) at row 0, goal (b) at row R - 1; w (D): the most joint k may move per row, fp32(dq_max_k * dt_row).
+ * Predicate of (q, row): the static cost of geom (chained fields, as mpb_collision_check) is positive OR the moving cost of
+ *   that row (as mpb_moving_collision_check) is.
+ * Tree: nodes (q, row, parent); tree 0 is rooted at (start, 0) and grows forward in time (a child's row is greater than its
+ *   parent's), tree 1 at (goal, R - 1) and grows backward.  Waiting is an ordinary edge with little or no motion.
+ * Metric from node n to a target (q_r, h_r) on the tree's growing side, dh = |h_r - h_n| >= 1:
+ *   tau = max_k (|q_r[k] - q_n[k]| / w_k), m = max(tau, (float)dh); nearest = least m, lowest index on ties.
+ * Extension from n: s = min(dh, max_step_rows) rows (a connect target: s = dh); f = tau > dh ? dh / tau : 1;
+ *   dl = (q_r - q_n) * f; point j (1 <= j <= s) = fma(dl, (float)j / (float)dh, q_n) at row h_n +- j; point j = dh with f == 1
+ *   is q_r's own bits.  The first colliding point j0 == 1 fails the extension; otherwise point j0 - 1 (or s) is appended.
+ * Iteration it: tree it & 1 extends towards (pre_samples[idx], row): sample_idx / sample_row NULL -> idx = mulhi(x, n_pre),
+ *   row = 1 + mulhi(y, R - 2) of Philox4x32-10(counter = (problem_offset + b, it, MPB_STRRT_MAGIC, 0), key = seed); else
+ *   (B, total_iters) int32 recorded draws, clamped to 0 .. n_pre - 1 and 1 .. R - 2.  Then the other tree extends towards
+ *   the new node; when it appends that very node (same row, every coordinate allclose, and arrived at with f == 1: an allclose
+ *   near miss with tau slightly above dh would put an edge faster than w into the plan) the trees are joined: vertices = tree
+ *   0's chain from its root to its new node, then tree 1's chain from the PARENT of its new node to its root; the dense
+ *   trajectory is fma(q_b - q_a, (float)(h - h_a) / (float)(h_b - h_a), q_a) between consecutive vertices, the vertex rows
+ *   their own bits; every one of the R rows is then checked again.  A failing row discards the join (MPB_STH_REJECTED_JOINS
+ *   goes up, the search continues); otherwise FOUND: every row of the output is free by the kernel's own predicate.
+ * workspace: mpb_strrt_workspace_bytes(B, max_nodes, D) bytes, 16-byte aligned (0 = shape refused).  mpb_strrt_layout.h
+ *   (generated from strrt_layout.py): MPB_STRRT_GLOBAL_WORDS words -- MPB_STG_MAGIC, _B, _MAX_NODES, _D, _DP (D rounded up to
+ *   4), _N_ROWS --; per problem MPB_STRRT_HDR_WORDS words -- MPB_STH_STATUS (MPB_STRRT_*), _ITERS (iterations begun), _COUNTS
+ *   (two words: nodes of tree 0, of tree 1), _REJECTED_JOINS --; then nodes (B, 2, max_nodes, Dp) fp32 zero padded, rows
+ *   (B, 2, max_nodes) int32, parents (B, 2, max_nodes) int32 (-1: root).
+ * mpb_strrt_init: roots, counts, status: START_OR_GOAL_IN_COLLISION (start at row 0, goal at row R - 1), else
+ *   HORIZON_TOO_SHORT when tau(goal, start) > R - 1, else RUNNING.
+ * mpb_strrt_run: iterations iter0 .. min(iter0 + n_iters, total_iters) - 1 of every problem still RUNNING, resumed from the
+ *   workspace.  trajs (B,R,D); vertex_q (B,Lmax,D), vertex_row (B,Lmax), n_vertices (B): written for FOUND problems (trajs may
+ *   hold the rows of a discarded join otherwise); more than Lmax vertices: PATH_TOO_LONG; a full tree: TREE_FULL; total_iters
+ *   used up: EXHAUSTED_ITERS.  status (B): copy of the status words.  log: NULL or (B, total_iters, MPB_STRRT_LOG_WORDS) int32
+ *   the caller has filled with MPB_STRRT_LOG_NONE: per iteration the extension towards the sample at word 0 and the connect
+ *   extension at word MPB_STRRT_LOG_EXT_WORDS, each MPB_STL_TREE, _NEAREST, _DH, _S, _FIRST (first colliding point or -1),
+ *   _APPENDED (node index or -1), and at word MPB_STRRT_LOG_JOIN the first failing row of a join's re-check or -1.
+ * Refusals: D > MPB_MAX_DOF, n_rows > MPB_STRRT_MAX_ROWS: MPB_E_UNSUPPORTED; n_rows < MPB_STRRT_MIN_ROWS, bad shapes, null
+ *   pointers, misaligned buffers, a small workspace, one recorded-draw array without the other: MPB_E_INVALID; then the moving
+ *   buffer's header (through the cache mpb_moving_invalidate serves): n_rows and n_dof must equal the call's, and the message
+ *   names both numbers.
+ * ------------------------------------------------------------------------------------------- */
+size_t mpb_strrt_workspace_bytes(int B, int max_nodes, int D);
+int mpb_strrt_init(void *workspace, size_t workspace_bytes, const float *start, const float *goal, const float *w,
+                   const float *geom, int geom_flags, const float *moving, int B, int max_nodes, int D, int n_rows, void *stream);
+int mpb_strrt_run(void *workspace, size_t workspace_bytes, const float *geom, int geom_flags, const float *moving, const float *w,
+                  const float *pre_samples, size_t pre_stride, const int *sample_idx, const int *sample_row, float *trajs,
+                  float *vertex_q, int *vertex_row, int *n_vertices, int *status, int *log, int B, int max_nodes, int n_pre, int D,
+                  int n_rows, int Lmax, int max_step_rows, int iter0, int n_iters, int total_iters, uint64_t seed,
+                  uint32_t problem_offset, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Batched RRT* and informed RRT* -- replaces RRTStar._run_optimization (rrt_star.py:133-261) with OptimalNode's cost

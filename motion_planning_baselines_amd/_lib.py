@@ -95,6 +95,9 @@ SIGNATURES = {
     'mpb_rrt_connect_workspace_bytes': [_i, _i, _i, _i],
     'mpb_rrt_connect_init': [_p, ctypes.c_size_t, _p, _p, _p, _i, _i, _i, _i, _i, _p],
     'mpb_rrt_connect_run': [_p, ctypes.c_size_t, _p, _i, _p, ctypes.c_size_t, _p, _p, _p, _p] + [_i] * 8 + [_f, _f, _u64, _u32, _p],
+    'mpb_strrt_workspace_bytes': [_i, _i, _i],
+    'mpb_strrt_init': [_p, ctypes.c_size_t] + [_p] * 4 + [_i, _p] + [_i] * 4 + [_p],
+    'mpb_strrt_run': [_p, ctypes.c_size_t, _p, _i, _p, _p, _p, ctypes.c_size_t] + [_p] * 8 + [_i] * 10 + [_u64, _u32, _p],
     'mpb_rrt_star_workspace_bytes': [_i, _i, _i, _i],
     'mpb_rrt_star_init': [_p, ctypes.c_size_t, _p, _p, _p, _i, _i, _i, _i, _i, _p],
     'mpb_rrt_star_run': [_p, ctypes.c_size_t, _p, _i, _p, ctypes.c_size_t] + [_p] * 6 + [_i] * 11 + [_f] * 5 + [_u64, _u32, _p],
@@ -149,7 +152,7 @@ def lib():
         fn.argtypes = argtypes
         fn.restype = (ctypes.c_char_p if name == 'mpb_last_error' else
                       ctypes.c_size_t if name in ('mpb_gpmp2_workspace_bytes', 'mpb_stomp_workspace_bytes', 'mpb_rrt_connect_workspace_bytes',
-                                                         'mpb_rrt_star_workspace_bytes') else ctypes.c_int)
+                                                         'mpb_rrt_star_workspace_bytes', 'mpb_strrt_workspace_bytes') else ctypes.c_int)
     if (h.mpb_version() & 0xFFFF) != ABI_VERSION:
         # signatures change positionally between ABI versions: calling across them would pass pointers as ints
         raise MPBError(f'{LIB_PATH} reports ABI version {h.mpb_version() & 0xFFFF}, this binding is written for {ABI_VERSION} '

@@ -12,7 +12,7 @@ import warnings
 import numpy as np
 import torch
 
-from . import _lib, rrt_layout
+from . import _lib, rrt_layout, strrt_layout
 from .geometry import KIND_CHAIN, MAX_FIELDS, CollisionField, TriangleMesh, count_fields, mesh_pose, occupancy_bytes, pack_geometry, pack_mesh, pack_moving_obstacles, pack_sdf_grid, pack_self_collision
 from .geometry import header as geometry_header
 
@@ -1744,6 +1744,103 @@ def rrt_star_tree(ws):
     `rewires`, `informed_rejections`, `best_cost_iters`, `iters_after_first_success`, and the first success: `first_cost`,
     `first_iter`, `first_count` (all (B,))."""
     return _rrt_read('star', ws, hidden=('goal_q', 'cand', 'best_cost_eps'))
+
+
+# ---- space-time RRT-Connect among moving obstacles (csrc/mpb_strrt.hip; layout: strrt_layout.py) ------------------------------------
+STRRT_STATUS_NAMES = strrt_layout.STATUS
+(STRRT_RUNNING, STRRT_FOUND, STRRT_EXHAUSTED_ITERS, STRRT_START_OR_GOAL_IN_COLLISION, STRRT_HORIZON_TOO_SHORT, STRRT_TREE_FULL,
+ STRRT_PATH_TOO_LONG) = range(len(STRRT_STATUS_NAMES))
+STRRT_MIN_ROWS, STRRT_MAX_ROWS, STRRT_MAX_PRE_SAMPLES = strrt_layout.STRRT_MIN_ROWS, strrt_layout.STRRT_MAX_ROWS, strrt_layout.STRRT_MAX_PRE_SAMPLES
+STRRT_LOG_WORDS, STRRT_LOG_NONE = strrt_layout.STRRT_LOG_WORDS, strrt_layout.STRRT_LOG_NONE
+
+
+class STRRTWorkspace:
+    """The caller-allocated state of a batch of space-time RRT-Connect problems: two trees per problem (configuration, row, parent), counts,
+    status words (layout: strrt_layout.py)."""
+
+    def __init__(self, B, max_nodes, D, n_rows, device):
+        nbytes = int(_lib.lib().mpb_strrt_workspace_bytes(int(B), int(max_nodes), int(D)))
+        if nbytes == 0:
+            msg = _lib.lib().mpb_last_error()
+            raise _lib.MPBError(f'mpb_strrt_workspace_bytes: {msg.decode() if msg else "?"}')
+        self.B, self.max_nodes, self.D, self.n_rows = int(B), int(max_nodes), int(D), int(n_rows)
+        self.nbytes = nbytes
+        self.buf = torch.zeros(nbytes // 4, device=device, dtype=torch.int32)
+
+
+def _strrt_scene(ws, geom, mo, w):
+    """The checks both STRRT wrappers make of the scene: the static geometry, the moving buffer's rows, the per-row step limits."""
+    if ws.D != geom.n_dof or ws.D != mo.n_dof:
+        raise ValueError(f'the problems have {ws.D} columns, the geometry {geom.n_dof} and the moving-obstacle buffer {mo.n_dof} degrees of freedom')
+    if ws.n_rows != mo.n_rows:
+        raise ValueError(f'n_rows = {ws.n_rows}, the moving-obstacle buffer was packed for n_rows = {mo.n_rows}')
+    _chk(w, (ws.D,), 'w')
+
+
+@_on_tensor_device
+def strrt_init(ws_buf, ws, start, goal, w, geom, mo):
+    """Roots (start at row 0, goal at row n_rows - 1), counts and the first status word of every problem (mpb_strrt_init):
+    START_OR_GOAL_IN_COLLISION by the predicate of those two rows, HORIZON_TOO_SHORT when max_k |goal - start|_k / w_k > n_rows - 1.
+    w (D,) fp32: the most a joint may move per row.  `ws_buf` is ws.buf (passed so that the launch lands on its device)."""
+    _chk(start, (ws.B, ws.D), 'start')
+    _chk(goal, (ws.B, ws.D), 'goal')
+    _strrt_scene(ws, geom, mo, w)
+    _lib.check(_lib.lib().mpb_strrt_init(_ptr(ws_buf), ws.nbytes, _ptr(start), _ptr(goal), _ptr(w), _ptr(geom.buf), int(geom.flags),
+                                         _ptr(mo.buf), ws.B, ws.max_nodes, ws.D, ws.n_rows, _stream()), 'mpb_strrt_init')
+
+
+@_on_tensor_device
+def strrt_run(ws_buf, ws, geom, mo, w, pre_samples, sample_idx, sample_row, trajs, vertex_q, vertex_row, n_vertices, status, iter0, n_iters,
+              total_iters, max_step_rows, seed=0, problem_offset=0, log=None):
+    """Iterations iter0 .. min(iter0 + n_iters, total_iters) - 1 of every problem still RUNNING (mpb_strrt_run).  pre_samples (n_pre, D)
+    shared or (B, n_pre, D); sample_idx and sample_row both None (device Philox) or both (B, total_iters) int32; trajs (B, n_rows, D);
+    vertex_q (B, Lmax, D), vertex_row (B, Lmax) and n_vertices (B,) int32; log None or (B, total_iters, STRRT_LOG_WORDS) int32 filled with
+    STRRT_LOG_NONE by the caller."""
+    B, D = ws.B, ws.D
+    _strrt_scene(ws, geom, mo, w)
+    n_pre = pre_samples.shape[-2]
+    if pre_samples.ndim == 2:
+        _chk(pre_samples, (n_pre, D), 'pre_samples')
+        stride = 0
+    else:
+        _chk(pre_samples, (B, n_pre, D), 'pre_samples')
+        stride = n_pre * D
+    if (sample_idx is None) != (sample_row is None):
+        raise ValueError('sample_idx and sample_row are given together or not at all')
+    _chk(sample_idx, (B, total_iters), 'sample_idx', allow_none=True, dtype=torch.int32)
+    _chk(sample_row, (B, total_iters), 'sample_row', allow_none=True, dtype=torch.int32)
+    Lmax = vertex_q.shape[1]
+    _chk(trajs, (B, ws.n_rows, D), 'trajs')
+    _chk(vertex_q, (B, Lmax, D), 'vertex_q')
+    _chk(vertex_row, (B, Lmax), 'vertex_row', dtype=torch.int32)
+    _chk(n_vertices, (B,), 'n_vertices', dtype=torch.int32)
+    _chk(status, (B,), 'status', dtype=torch.int32)
+    _chk(log, (B, total_iters, STRRT_LOG_WORDS), 'log', allow_none=True, dtype=torch.int32)
+    _lib.check(_lib.lib().mpb_strrt_run(
+        _ptr(ws_buf), ws.nbytes, _ptr(geom.buf), int(geom.flags), _ptr(mo.buf), _ptr(w), _ptr(pre_samples), stride, _ptr(sample_idx),
+        _ptr(sample_row), _ptr(trajs), _ptr(vertex_q), _ptr(vertex_row), _ptr(n_vertices), _ptr(status), _ptr(log), B, ws.max_nodes, n_pre, D,
+        ws.n_rows, Lmax, int(max_step_rows), int(iter0), int(n_iters), int(total_iters), _seed64(seed), int(problem_offset) & 0xFFFFFFFF,
+        _stream()), 'mpb_strrt_run')
+
+
+def strrt_trees(ws):
+    """The trees of a workspace, for tests and rendering: dict of `nodes` (B, 2, max_nodes, D) fp32, `rows` and `parents`
+    (B, 2, max_nodes) int32 (-1: root), `counts` (B, 2), `iters` (B,) iterations used, `status` (B,) and `rejected_joins` (B,).  Tree 0 is
+    rooted at (start, row 0), tree 1 at (goal, row n_rows - 1)."""
+    lay = strrt_layout.offsets(ws.B, ws.max_nodes, ws.D)
+    w = ws.buf
+    glob = dict(zip(strrt_layout.GLOBAL, w[:len(strrt_layout.GLOBAL)].tolist()))
+    if glob != dict(magic=strrt_layout.STRRT_MAGIC, B=ws.B, max_nodes=ws.max_nodes, D=ws.D, Dp=lay.Dp, n_rows=ws.n_rows):
+        raise ValueError('the workspace was not initialised for these shapes (strrt_init)')
+    out = {}
+    for name, (o, typ, shape) in lay.sections.items():
+        t = w[o:o + math.prod(shape)]
+        out[name] = (t.view(torch.float32) if typ == 'f4' else t).reshape(shape)
+    hdr = out.pop('hdr')
+    for name, (i, typ, n) in strrt_layout.header_index().items():
+        out[name] = hdr[:, i:i + n] if n > 1 else hdr[:, i]
+    out['nodes'] = out['nodes'][..., :ws.D]
+    return out
 
 
 # ---- path shortcutting between the tree and the optimiser (csrc/mpb_path_shortcut.hip) ---------------------------------------------

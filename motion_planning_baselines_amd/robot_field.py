@@ -195,7 +195,8 @@ class PlanningTask:
         for name, f in (('field', field), ('self_field', self_field), ('sdf_field', sdf_field)):
             if any(isinstance(x, MovingObstacleField) for x in (f if isinstance(f, (list, tuple)) else [f])):
                 raise TypeError(f'PlanningTask({name}=...): a MovingObstacleField is no static field -- the task\'s predicates, samplers and '
-                                f'the RRT / PRM / shortcut kernels have no time axis.  Freeze it with field.at(t), give it to the optimisers '
+                                f'the RRT / PRM / shortcut kernels have no time axis.  Plan among it with planners.STRRTConnect(task, moving_field, n_rows, ...), '
+                                f'freeze it with field.at(t), give it to the optimisers '
                                 f'as CostCollision(field=...), and validate trajectories with check_trajs_moving(trajs, moving_field)')
         self.robot, self.field = robot, field
         self.geom = ops.DeviceGeometry(robot, field, self.device)

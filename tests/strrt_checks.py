@@ -1,0 +1,523 @@
+"""The space-time RRT-Connect (planners.STRRTConnect, csrc/mpb_strrt.hip; definition: include/mpb.h) restated on the CPU
+(helper module, no tests; imported like path_shortcut_checks.py and moving_obstacle_checks.py).
+
+The whole planner in numpy fp32, in the operation order the definition fixes (numpy float32 scalars and arrays round after every
+operation; the two fused multiply-adds of the definition are fma32 below, exact):
+    draws     one Philox4x32-10 call per iteration, counter (problem_offset + b, it, STRRT_MAGIC, 0), key = seed:
+              idx = mulhi(x, n_pre), row = 1 + mulhi(y, R - 2); or recorded draws, clamped into 0 .. n_pre - 1 / 1 .. R - 2
+    metric    dh = |h_r - h_n| >= 1 on the tree's growing side; tau = max_k (|q_r[k] - q_n[k]| / w_k), starting from 0;
+              m = max(tau, (float)dh); nearest = least m, lowest index on ties
+    steering  s = min(dh, max_step_rows) (connect: s = dh); f = tau > dh ? dh / tau : 1; dl = (q_r - q_n) * f;
+              point j = fma(dl, (float)j / (float)dh, q_n) at row h_n +- j; point j = dh with f == 1 is q_r's own bits
+    append    first colliding point j0 == 1 fails; otherwise point j0 - 1 (or s) is appended; a full tree: TREE_FULL
+    join      the other tree appended the new node itself (same row, |a - b| <= fma(1e-5, |b|, 1e-8) per coordinate, b the later node,
+              and the connect extension ARRIVED: f == 1 and its last point j = dh was appended, so that no edge of the plan exceeds w);
+              vertices = tree 0's chain root -> its last node, then tree 1's chain from the PARENT of its last node to its root
+    fill      row h between vertices (q_a, h_a), (q_b, h_b): fma(q_b - q_a, (float)(h - h_a) / (float)(h_b - h_a), q_a); vertex rows: own bits
+    re-check  every one of the R rows with the same predicate; the first failing row discards the join (rejected_joins)
+    statuses  init: START_OR_GOAL_IN_COLLISION before HORIZON_TOO_SHORT (tau(goal, start) > R - 1); then FOUND, TREE_FULL, PATH_TOO_LONG,
+              EXHAUSTED_ITERS; `iters` counts the iterations begun
+    log       per iteration two extension records (tree, nearest, dh, s, first, appended) and the join word, NONE where nothing happened.
+
+The predicate of (q, row) three ways:
+    fp32      the fp32 oracle (oracle/geometry_ref.py in float32): static cost of every field > 0, or the cost of row `row` > 0 against
+              the obstacles of field.at(t_row) -- the per-row restatement of moving_obstacle_checks.py, its expressions evaluated for a
+              batch of points at different rows at once (rows_field; test_strrt_cpu.py holds it to RefCollisionField bit for bit)
+    fp64      the same in float64, as the hinge argument m = max over fields and spheres of margin + r_l - sd: positive = in collision
+    follow    the collision outcomes are taken from a log (the kernel's), everything else is recomputed; with audit=True every logged
+              decision is held against fp64: over the points up to the logged first hit, E32 = max |m32 - m64| and the decision is
+              DECIDABLE when min |m64| > collision_kinks.bar(E32) (path_shortcut_checks.py's rule); a decidable decision must equal fp64's.
+"""
+import functools
+import types
+
+import numpy as np
+import torch
+
+from collision_kinks import bar
+from oracle.geometry_ref import RefCollisionField, _safe_norm, make_ref_geometry
+
+from motion_planning_baselines_amd import strrt_layout as SL
+
+F32 = dict(device='cpu', dtype=torch.float32)
+F64 = dict(device='cpu', dtype=torch.float64)
+f32 = np.float32
+(RUNNING, FOUND, EXHAUSTED_ITERS, START_OR_GOAL_IN_COLLISION, HORIZON_TOO_SHORT, TREE_FULL, PATH_TOO_LONG) = range(len(SL.STATUS))
+NONE, EXT, JOIN, LOGW = SL.STRRT_LOG_NONE, SL.STRRT_LOG_EXT_WORDS, SL.STRRT_LOG_JOIN, SL.STRRT_LOG_WORDS
+VEL_SLACK = 1e-5           # |q[h+1] - q[h]|_k <= w_k (1 + VEL_SLACK): fewer than ten fp32 roundings at 6e-8 each
+
+
+# ------------------------------------------------------------------------------------------------
+# arithmetic
+# ------------------------------------------------------------------------------------------------
+def fma32(a, b, c):
+    """fl32(a * b + c) of float32 values, exactly: the product is exact in float64, the sum is taken there with its rounding error
+    (TwoSum) and rounded to odd, which a second rounding to 24 bits cannot get wrong."""
+    a, b, c = (np.asarray(v, np.float32).astype(np.float64) for v in (a, b, c))
+    p = a * b
+    s = p + c
+    bb = s - p
+    e = (p - (s - bb)) + (c - bb)
+    inexact = e != 0
+    s = np.where(inexact & ((e > 0) != (s > 0)), np.nextafter(s, 0.0), s)     # truncate towards zero ...
+    bits = np.ascontiguousarray(s).view(np.int64) | inexact.astype(np.int64)   # ... and make the last bit sticky
+    return bits.view(np.float64).astype(np.float32)
+
+
+def close(a, b):
+    """rrt_close per coordinate (atol + rtol |b| is one fma), all coordinates"""
+    return bool(np.all(np.abs(a - b) <= fma32(f32(1e-5), np.abs(b), f32(1e-8))))
+
+
+def philox4x32_10(ctr, key):
+    """Philox4x32-10 (Random123) of one counter (4 words) and key (2 words) -> 4 words."""
+    c, k = [int(v) & 0xFFFFFFFF for v in ctr], [int(v) & 0xFFFFFFFF for v in key]
+    for _ in range(10):
+        p0, p1 = 0xD2511F53 * c[0], 0xCD9E8D57 * c[2]
+        c = [(p1 >> 32) ^ c[1] ^ k[0], p1 & 0xFFFFFFFF, (p0 >> 32) ^ c[3] ^ k[1], p0 & 0xFFFFFFFF]
+        k = [(k[0] + 0x9E3779B9) & 0xFFFFFFFF, (k[1] + 0xBB67AE85) & 0xFFFFFFFF]
+    return c
+
+
+def device_draws(p, B=None, offset=0):
+    """(sample_idx, sample_row), both (B, n_iters) int32: what the kernel draws for problems offset .. offset + B - 1 of p's seed."""
+    B = p.B if B is None else B
+    idx, row = np.zeros((B, p.n_iters), np.int32), np.zeros((B, p.n_iters), np.int32)
+    for b in range(B):
+        for it in range(p.n_iters):
+            x, y, _, _ = philox4x32_10((offset + b, it, SL.STRRT_MAGIC, 0), (p.seed & 0xFFFFFFFF, (p.seed >> 32) & 0xFFFFFFFF))
+            idx[b, it], row[b, it] = (x * p.n_pre) >> 32, 1 + ((y * (p.R - 2)) >> 32)
+    return idx, row
+
+
+def tau32(qr, qn, w):
+    return f32(max(f32(0.0), np.max(np.abs(qr - qn) / w)))
+
+
+# ------------------------------------------------------------------------------------------------
+# the predicate
+# ------------------------------------------------------------------------------------------------
+def rows_field(robot, field, R, ta):
+    """The obstacles of every row as the oracle's per-row static fields hold them (RefCollisionField of field.at(t_h), the restatement
+    of moving_obstacle_checks.row_fields), stacked: spheres (R, Os, 4), boxes (R, Ob, 6), margin, link radii."""
+    radius = robot.spec()['link_radius']
+    per = [RefCollisionField(field.at(t).spec(), radius, tensor_args=ta) for t in field.times(R)]
+    return types.SimpleNamespace(per=per, spheres=torch.stack([f.spheres for f in per]), boxes=torch.stack([f.boxes for f in per]),
+                                 margin=per[0].margin, link_radius=per[0].link_radius)
+
+
+def sd_rows(mf, x, rows):
+    """x (n, L, 3), rows (n,) -> (n, L): RefCollisionField.signed_distance's expressions with point i against the obstacles of rows[i]."""
+    rows = torch.as_tensor(rows, dtype=torch.long)
+    sds = []
+    if mf.spheres.shape[1]:
+        S = mf.spheres[rows].unsqueeze(1)                           # (n, 1, Os, 4)
+        sds.append(_safe_norm(x.unsqueeze(-2) - S[..., :3]) - S[..., 3])
+    if mf.boxes.shape[1]:
+        Bx = mf.boxes[rows].unsqueeze(1)
+        qv = (x.unsqueeze(-2) - Bx[..., :3]).abs() - Bx[..., 3:6]
+        sds.append(_safe_norm(torch.clamp(qv, min=0.0)) + torch.clamp(qv.max(dim=-1)[0], max=0.0))
+    return torch.cat(sds, dim=-1).min(dim=-1)[0]
+
+
+def hinge(p, prec, q, rows):
+    """q (n, D) float32 numpy, rows (n,) -> (n,) in `prec` (32 / 64): max over fields (static, then the row's moving obstacles) and
+    collision spheres of margin + r_l - sd: positive = in collision."""
+    rr, rfs, mf, ta = (p.rr32, p.rf32, p.mv32, F32) if prec == 32 else (p.rr64, p.rf64, p.mv64, F64)
+    threads = torch.get_num_threads()
+    torch.set_num_threads(1)                    # (a few dozen points per call: a thread pool costs fifty times the arithmetic)
+    try:
+        x = rr.fk_map_collision(torch.from_numpy(np.ascontiguousarray(q, f32)).to(**ta))
+        m = (mf.margin + mf.link_radius - sd_rows(mf, x, rows)).max(-1)[0]
+        for f in rfs:
+            m = torch.maximum(m, (f.margin + f.link_radius - f.signed_distance(x)).max(-1)[0])
+    finally:
+        torch.set_num_threads(threads)
+    return m.numpy()
+
+
+def collides32(p, q, rows):
+    """The fp32 predicate: the fp32 oracle's static cost of any field or its moving cost of the row is positive (a sum of hinges is
+    positive iff the largest hinge argument is)."""
+    return hinge(p, 32, q, rows) > 0
+
+
+# ------------------------------------------------------------------------------------------------
+# problems
+# ------------------------------------------------------------------------------------------------
+def make_problem(name, robot, fields, moving, R, dq_max, starts, goals, pre, n_iters, max_step, seed=0, max_nodes=None, Lmax=512):
+    fields = list(fields)
+    dt_row = (moving.t_end - moving.t_start) / (R - 1)
+    w = (np.asarray(dq_max, np.float64) * dt_row).astype(f32)
+    p = types.SimpleNamespace(name=name, robot=robot, fields=fields, moving=moving, R=int(R), dq_max=np.asarray(dq_max, np.float64), w=w,
+                              starts=np.ascontiguousarray(starts, f32), goals=np.ascontiguousarray(goals, f32),
+                              pre=np.ascontiguousarray(pre, f32), n_iters=int(n_iters), max_step=int(max_step), seed=int(seed),
+                              max_nodes=int(max_nodes or n_iters + 1), Lmax=int(Lmax))
+    p.B, p.D = p.starts.shape
+    p.n_pre = len(p.pre)
+    p.rr32, p.rr64 = make_ref_geometry(robot, fields[0], F32)[0], make_ref_geometry(robot, fields[0], F64)[0]
+    p.rf32 = [make_ref_geometry(robot, f, F32)[1] for f in fields]
+    p.rf64 = [make_ref_geometry(robot, f, F64)[1] for f in fields]
+    p.mv32, p.mv64 = rows_field(robot, moving, R, F32), rows_field(robot, moving, R, F64)
+    return p
+
+
+def variant(p, **kw):
+    """p with other numbers (the geometry shared; R and the moving field must stay)."""
+    q = types.SimpleNamespace(**vars(p))
+    for k, v in kw.items():
+        setattr(q, k, v)
+    q.B, q.n_pre = len(q.starts), len(q.pre)
+    return q
+
+
+def _free_static(p_like, rng, n, lo, hi, clear=1e-3):
+    """n configurations uniform in [lo, hi] whose fp64 static hinge argument is below -clear."""
+    out = []
+    while len(out) < n:
+        q = rng.uniform(lo, hi, (4 * n, len(lo))).astype(f32)
+        x = p_like.rr64.fk_map_collision(torch.from_numpy(q).double())
+        m = torch.stack([(f.margin + f.link_radius - f.signed_distance(x)).max(-1)[0] for f in p_like.rf64]).max(0)[0].numpy()
+        out += list(q[m < -clear])
+    return np.array(out[:n], f32)
+
+
+def _endpoints(p, rng, lo, hi, clear=1e-2):
+    """B starts free at row 0 and B goals free at row R - 1 (fp64 hinge argument below -clear), within the horizon of w."""
+    starts, goals = [], []
+    while len(starts) < p.B:
+        s, g = _free_static(p, rng, 1, lo, hi), _free_static(p, rng, 1, lo, hi)
+        if hinge(p, 64, s, [0])[0] < -clear and hinge(p, 64, g, [p.R - 1])[0] < -clear and tau32(g[0], s[0], p.w) <= 0.4 * (p.R - 1):
+            starts.append(s[0])
+            goals.append(g[0])
+    return np.array(starts, f32), np.array(goals, f32)
+
+
+GATE_R, GATE_B, GATE_ITERS, GATE_SEED = 33, 16, 256, 3
+GATE_BLOCKED = (11, 21)      # the rows (inclusive) at which the moving sphere sits in the gap
+GATE_W = 0.13                # per row: the straight constant-speed line moves 1.4 / 32 = 0.044 per row and is at the gap at row 16
+
+
+GATE = (GATE_R, GATE_B, GATE_ITERS, GATE_W)
+
+
+def _gate_static():
+    from motion_planning_baselines_amd import geometry as G
+    return G.CollisionField(boxes=np.array([[0.0, 0.6, 0.05, 0.45], [0.0, -0.6, 0.05, 0.45]], f32), margin=0.02)
+
+
+PARITY_R, PARITY_B, PARITY_ITERS, PARITY_W = 32, 4, 64, 0.2   # R even: reversing a row (R - 1 - h) flips its parity
+
+
+# the gate scene on a four times finer clock: R = 129 rows -- a join's dense fill and its re-check take more than two trips of 64 --, the
+# same motion in the same time (keyframes at 4 x the rows, the sphere in the gap during rows 44 .. 84), w a quarter
+GATE129_R, GATE129_B, GATE129_ITERS, GATE129_W = 129, 8, 256, GATE_W / 4
+GATE129_BLOCKED = (44, 84)
+
+
+def _gate_moving(parity=False, scale=1.0):
+    """One sphere of radius 0.12: in the gap (0, 0) during rows 11 .. 21, inside the upper wall (0, 0.7) otherwise (scale: the keyframe
+    times multiplied, for a finer row grid); parity: a sphere of radius 0.03 in the gap at every ODD row, in the wall at every even one
+    (a keyframe per row)."""
+    from motion_planning_baselines_amd import geometry as G
+    if parity:
+        t = np.arange(PARITY_R, dtype=np.float64)
+        y = np.where(np.arange(PARITY_R) % 2 == 1, 0.0, 0.7)
+    else:
+        t = scale * np.array([0.0, 10.0, 11.0, 21.0, 22.0, 32.0])
+        y = np.array([0.7, 0.7, 0.0, 0.0, 0.7, 0.7])
+    c = np.stack([np.zeros_like(y), y], -1)[:, None, :]
+    return G.MovingObstacleField(t, sphere_centers=c, sphere_radii=[0.03 if parity else 0.12], margin=0.02, t_start=0.0, t_end=float(t[-1]))
+
+
+def _shell_field(seed, K, n_sph, n_box, margin=0.02, dt_key=1.0):
+    """Small moving obstacles for a chain at the origin: keyframe k at time k dt_key, every centre in the shell 0.45 .. 0.75 m around the base
+    axis at heights 0.15 .. 0.9 m -- away from the links next to the base, which every configuration shares."""
+    from motion_planning_baselines_amd import geometry as G
+    rng = np.random.RandomState(seed)
+    O = n_sph + n_box
+    r, th, z = rng.uniform(0.45, 0.75, (K, O)), rng.uniform(-np.pi, np.pi, (K, O)), rng.uniform(0.15, 0.9, (K, O))
+    c = np.stack([r * np.cos(th), r * np.sin(th), z], -1)
+    return G.MovingObstacleField(dt_key * np.arange(K, dtype=np.float64), c[:, :n_sph], rng.uniform(0.04, 0.07, n_sph), c[:, n_sph:],
+                                 rng.uniform(0.04, 0.07, (n_box, 3)), margin=margin)
+
+
+@functools.lru_cache(maxsize=None)
+def problem(name):
+    """The input set `name`; treat as read-only.  gate / parity / gate129: the 2-D point mass between two static boxes that leave a gap, one moving
+    sphere (gate129: R = 129); panda_R_S: Panda, 5 static + 3 moving spheres + 1 moving box, R rows, max_step_rows S (pandaslow_R_S: the
+    same obstacle paths in four times the time); arm12: the 12-joint table-driven chain."""
+    from motion_planning_baselines_amd import geometry as G
+    if name in ('gate', 'parity', 'gate129'):
+        par = name == 'parity'
+        GATE_R, GATE_B, GATE_ITERS, GATE_W = {'gate': GATE, 'parity': (PARITY_R, PARITY_B, PARITY_ITERS, PARITY_W),
+                                              'gate129': (GATE129_R, GATE129_B, GATE129_ITERS, GATE129_W)}[name]
+        robot = G.RobotPointMass(2, radius=0.03, dq_max=[GATE_W, GATE_W])
+        rng = np.random.RandomState(5)
+        p = make_problem(name, robot, [_gate_static()], _gate_moving(par, 4.0 if name == 'gate129' else 1.0), GATE_R, robot.dq_max_np, np.zeros((GATE_B, 2)),
+                         np.zeros((GATE_B, 2)), np.zeros((1, 2)), GATE_ITERS, 8, seed=GATE_SEED)
+        starts = np.stack([rng.uniform(-0.75, -0.65, GATE_B), rng.uniform(-0.3, 0.3, GATE_B)], -1)
+        goals = np.stack([rng.uniform(0.65, 0.75, GATE_B), rng.uniform(-0.3, 0.3, GATE_B)], -1)
+        starts[0], goals[0] = (-0.7, 0.0), (0.7, 0.0)                  # the straight line through the middle of the gap
+        return variant(p, starts=starts.astype(f32), goals=goals.astype(f32), pre=_free_static(p, rng, 512, [-1, -1], [1, 1]))
+    if name.startswith(('panda_', 'pandaslow_')):
+        R, S = (int(v) for v in name.split('_')[1:])
+        robot = G.RobotPanda(dt=0.04)
+        moving = _shell_field(31, 4, 3, 1, dt_key=4.0 if name.startswith('pandaslow_') else 1.0)    # pandaslow: the same paths in 12 s, not 3
+        p = make_problem(name, robot, [G.env_spheres_3d(seed=4, n_spheres=5)], moving, R, robot.dq_max_np, np.zeros((8, 7)), np.zeros((8, 7)),
+                         np.zeros((1, 7)), 128, S, seed=7)
+        rng = np.random.RandomState(9)
+        lo, hi = 0.5 * robot.q_min_np, 0.5 * robot.q_max_np         # (half the joint range: the horizon of 3 s leaves time to detour)
+        starts, goals = _endpoints(p, rng, lo, hi)
+        return variant(p, starts=starts, goals=goals, pre=_free_static(p, rng, 256, lo, hi))
+    if name == 'arm12':
+        from path_shortcut_checks import _arm_field
+        from test_gpu_generic_dof import make_arm
+        robot = make_arm(12)
+        moving = _shell_field(23, 3, 2, 1)
+        p = make_problem(name, robot, [_arm_field()], moving, 24, np.full(12, 4.0), np.zeros((4, 12)), np.zeros((4, 12)), np.zeros((1, 12)),
+                         96, 6, seed=11)
+        rng = np.random.RandomState(13)
+        lo, hi = 0.3 * robot.q_min_np, 0.3 * robot.q_max_np
+        starts, goals = _endpoints(p, rng, lo, hi)
+        return variant(p, starts=starts, goals=goals, pre=_free_static(p, rng, 256, lo, hi))
+    raise KeyError(name)
+
+
+# ------------------------------------------------------------------------------------------------
+# the planner
+# ------------------------------------------------------------------------------------------------
+def _points(q1, tq, dl, dh, whole, js):
+    """The points js (1-based) of an extension, (len(js), D) float32."""
+    out = np.zeros((len(js), len(q1)), f32)
+    for i, j in enumerate(js):
+        out[i] = tq if (whole and j == dh) else fma32(dl, f32(j) / f32(dh), q1)
+    return out
+
+
+def run(p, judge_ext, judge_join, init_hit, draws=None, offset=0, row_of=None):
+    """The definition over the input set p.
+    judge_ext(b, it, e, pts (s, D), rows (s,)) -> the first colliding point 1 .. s or -1 (e: 0 the sample extension, 1 the connect one);
+    judge_join(b, it, traj (R, D)) -> the first colliding row or -1; init_hit(b) -> the start at row 0 or the goal at row R - 1 collides.
+    draws: None (Philox of p.seed, stream offset + b) or (sample_idx, sample_row).  row_of(t, row) -> the row the predicate is asked
+    about (identity; the variants of tests/test_strrt_cpu.py's row-index conditions pass others).
+    -> SimpleNamespace of nodes (B, 2, M, D), rows, parents (B, 2, M), counts (B, 2), status, iters, rejected_joins (B,), trajs (B, R, D),
+    vertex_q (B, Lmax, D), vertex_row (B, Lmax), n_vertices (B,), log (B, n_iters, LOGW)."""
+    B, D, R, M, T, w = p.B, p.D, p.R, p.max_nodes, p.n_iters, p.w
+    if draws is None:
+        draws = device_draws(p, B, offset)
+    o = types.SimpleNamespace(nodes=np.zeros((B, 2, M, D), f32), rows=np.zeros((B, 2, M), np.int32), parents=np.zeros((B, 2, M), np.int32),
+                              counts=np.ones((B, 2), np.int32), status=np.zeros(B, np.int32), iters=np.zeros(B, np.int32),
+                              rejected_joins=np.zeros(B, np.int32), trajs=np.zeros((B, R, D), f32), vertex_q=np.zeros((B, p.Lmax, D), f32),
+                              vertex_row=np.zeros((B, p.Lmax), np.int32), n_vertices=np.zeros(B, np.int32),
+                              log=np.full((B, T, LOGW), NONE, np.int32))
+    row_of = row_of or (lambda t, row: row)
+    for b in range(B):
+        nodes, rows, parents, cnt = o.nodes[b], o.rows[b], o.parents[b], o.counts[b]
+        nodes[0, 0], nodes[1, 0] = p.starts[b], p.goals[b]
+        rows[0, 0], rows[1, 0] = 0, R - 1
+        parents[0, 0] = parents[1, 0] = -1
+        status = RUNNING
+        if tau32(p.goals[b], p.starts[b], w) > f32(R - 1):
+            status = HORIZON_TOO_SHORT
+        if init_hit(b):
+            status = START_OR_GOAL_IN_COLLISION
+        state = types.SimpleNamespace(status=status)
+
+        def extend(t, tq, hr, connect, it, e):
+            rec = o.log[b, it, e * EXT:(e + 1) * EXT]
+            n = cnt[t]
+            dhs = (hr - rows[t, :n]) if t == 0 else (rows[t, :n] - hr)
+            tau = np.maximum(f32(0.0), np.max(np.abs(tq[None] - nodes[t, :n]) / w[None], axis=1)).astype(f32)
+            m = np.where(dhs >= 1, np.maximum(tau, dhs.astype(f32)), f32(np.inf))
+            bi = int(np.argmin(m))                                     # (the first of equal minima)
+            rec[0] = t
+            if not dhs[bi] >= 1:
+                rec[1:] = (-1, 0, 0, -1, -1)
+                return None
+            hn, dh = int(rows[t, bi]), int(dhs[bi])
+            s = dh if connect else min(dh, p.max_step)
+            q1 = nodes[t, bi].copy()
+            ta = tau32(tq, q1, w)
+            whole = not ta > f32(dh)
+            f = f32(1.0) if whole else f32(dh) / ta
+            dl = ((tq - q1) * f).astype(f32)
+            js = np.arange(1, s + 1)
+            prow = hn + js if t == 0 else hn - js
+            first = judge_ext(b, it, e, _points(q1, tq, dl, dh, whole, js), np.array([row_of(t, r) for r in prow]))
+            rec[1:] = (bi, dh, s, first, -1)
+            if first == 1:
+                return None
+            jend = s if first < 0 else first - 1
+            nq, nrow = _points(q1, tq, dl, dh, whole, [jend])[0], int(prow[jend - 1])
+            if n >= M:
+                state.status = TREE_FULL
+                return None
+            nodes[t, n], rows[t, n], parents[t, n] = nq, nrow, bi
+            cnt[t] = n + 1
+            rec[5] = n
+            return nq, nrow, whole and jend == dh
+
+        it = 0
+        while it < T and state.status == RUNNING:
+            this, it = it, it + 1                                      # (`it` counts the iterations begun, as the kernel's header word)
+            t1 = this & 1
+            idx = min(max(int(draws[0][b, this]), 0), p.n_pre - 1)
+            hs = min(max(int(draws[1][b, this]), 1), R - 2)
+            got = extend(t1, p.pre[idx], hs, False, this, 0)
+            if got is None:
+                continue
+            n1, h1, _ = got
+            got = extend(t1 ^ 1, n1, h1, True, this, 1)
+            if got is None or got[1] != h1 or not got[2] or not close(n1, got[0]):
+                continue
+            chain0, j = [], cnt[0] - 1
+            while j >= 0:
+                chain0.append(j)
+                j = parents[0, j]
+            chain1, j = [], parents[1, cnt[1] - 1]
+            while j >= 0:
+                chain1.append(j)
+                j = parents[1, j]
+            nv = len(chain0) + len(chain1)
+            if nv > p.Lmax:
+                state.status = PATH_TOO_LONG
+                break
+            vq = np.concatenate([nodes[0, chain0[::-1]], nodes[1, chain1]]).astype(f32)
+            vr = np.concatenate([rows[0, chain0[::-1]], rows[1, chain1]]).astype(np.int32)
+            o.vertex_q[b, :nv], o.vertex_row[b, :nv] = vq, vr
+            traj = o.trajs[b]
+            for i in range(nv - 1):
+                ha, hb = int(vr[i]), int(vr[i + 1])
+                traj[ha] = vq[i]
+                for h in range(ha + 1, hb):
+                    traj[h] = fma32(vq[i + 1] - vq[i], f32(h - ha) / f32(hb - ha), vq[i])
+            traj[R - 1] = vq[nv - 1]
+            bad = judge_join(b, this, traj)
+            o.log[b, this, JOIN] = bad
+            if bad >= 0:
+                o.rejected_joins[b] += 1
+                continue
+            o.n_vertices[b] = nv
+            state.status = FOUND
+        if state.status == RUNNING:
+            state.status = EXHAUSTED_ITERS
+        o.status[b], o.iters[b] = state.status, it
+        if state.status != FOUND:
+            o.trajs[b] = 0
+    return o
+
+
+def restate32(p, draws=None, offset=0, row_of=None):
+    """The planner running on its own fp32 predicate."""
+    def judge_ext(b, it, e, pts, rows):
+        hit = np.nonzero(collides32(p, pts, rows))[0]
+        return int(hit[0]) + 1 if len(hit) else -1
+
+    def judge_join(b, it, traj):
+        hit = np.nonzero(collides32(p, traj, np.arange(p.R)))[0]
+        return int(hit[0]) if len(hit) else -1
+
+    def init_hit(b):
+        return bool(collides32(p, np.stack([p.starts[b], p.goals[b]]), [0, p.R - 1]).any())
+    return run(p, judge_ext, judge_join, init_hit, draws, offset, row_of)
+
+
+def follow(p, log, status, draws=None, offset=0, audit=False):
+    """The planner with the collision outcomes of `log` (and, for the two rows the init kernel checks, of `status`); audit: every logged
+    decision is held against fp64 as the module docstring says (raises AssertionError naming the first decidable one that differs).
+    -> (the run, [SimpleNamespace(b, it, kind, decidable, margin, E32, bar)] (empty without audit))."""
+    log, status, seen = np.asarray(log), np.asarray(status), []
+
+    def audit_points(b, it, kind, pts, rows, logged):
+        m64, m32 = hinge(p, 64, pts, rows), hinge(p, 32, pts, rows).astype(np.float64)
+        hit = np.nonzero(m64 > 0)[0]
+        first64 = int(hit[0]) if len(hit) else -1                     # 0-based; `logged` too
+        n = max(first64, logged) + 1 if max(first64, logged) >= 0 else len(pts)
+        E32, margin = float(np.abs(m32[:n] - m64[:n]).max()), float(np.abs(m64[:n]).min())
+        c = types.SimpleNamespace(b=b, it=it, kind=kind, decidable=margin > bar(E32), margin=margin, E32=E32, bar=bar(E32))
+        seen.append(c)
+        if c.decidable:
+            assert logged == first64, (f'{p.name}: problem {b} iteration {it} {kind}: decidable (margin {margin:.3e} > bar {c.bar:.3e}), fp64 '
+                                       f'says first collision {first64}, the log {logged}')
+
+    def judge_ext(b, it, e, pts, rows):
+        rec = log[b, it, e * EXT:(e + 1) * EXT]
+        assert rec[0] != NONE, f'{p.name}: problem {b} iteration {it}: the definition makes extension {e}, the log has none'
+        first = int(rec[4])
+        assert first == -1 or 1 <= first <= len(pts), (p.name, b, it, e, first)
+        if audit:
+            audit_points(b, it, f'extension {e}', pts, rows, first - 1 if first > 0 else -1)
+        return first
+
+    def judge_join(b, it, traj):
+        bad = int(log[b, it, JOIN])
+        assert bad != NONE and -1 <= bad < p.R, f'{p.name}: problem {b} iteration {it}: the definition re-checks a join, the log says {bad}'
+        if audit:
+            audit_points(b, it, 'join', traj, np.arange(p.R), bad)
+        return bad
+
+    def init_hit(b):
+        return int(status[b]) == START_OR_GOAL_IN_COLLISION
+    return run(p, judge_ext, judge_join, init_hit, draws, offset), seen
+
+
+def undecidable_share(seen):
+    return sum(not c.decidable for c in seen) / max(len(seen), 1)
+
+
+def same_bits(a, b, what=''):
+    """Two runs (SimpleNamespace of run(), or dicts of the kernel's arrays under the same names) agree bit for bit: trees up to their
+    counts, counts, statuses, iterations, rejected joins, vertex lists, the trajectories of FOUND problems and -- where both have one --
+    the log."""
+    a, b = (types.SimpleNamespace(**x) if isinstance(x, dict) else x for x in (a, b))
+    for k in ('status', 'iters', 'counts', 'rejected_joins', 'n_vertices'):
+        assert np.array_equal(np.asarray(getattr(a, k)), np.asarray(getattr(b, k))), f'{what}: {k} differs: {getattr(a, k)} vs {getattr(b, k)}'
+    for i in range(len(a.status)):
+        for t in (0, 1):
+            n = int(a.counts[i, t])
+            assert np.array_equal(a.rows[i, t, :n], b.rows[i, t, :n]) and np.array_equal(a.parents[i, t, :n], b.parents[i, t, :n]), (what, i, t)
+            assert np.array_equal(np.ascontiguousarray(a.nodes[i, t, :n]).view(np.uint32), np.ascontiguousarray(b.nodes[i, t, :n]).view(np.uint32)), \
+                f'{what}: problem {i} tree {t}: node bits differ'
+        if a.status[i] == FOUND:
+            n = int(a.n_vertices[i])
+            assert np.array_equal(a.vertex_row[i, :n], b.vertex_row[i, :n]), (what, i)
+            assert np.array_equal(np.ascontiguousarray(a.vertex_q[i, :n]).view(np.uint32), np.ascontiguousarray(b.vertex_q[i, :n]).view(np.uint32)), (what, i)
+            assert np.array_equal(np.ascontiguousarray(a.trajs[i]).view(np.uint32), np.ascontiguousarray(b.trajs[i]).view(np.uint32)), \
+                f'{what}: problem {i}: trajectory bits differ'
+    la, lb = getattr(a, 'log', None), getattr(b, 'log', None)
+    if la is not None and lb is not None:
+        assert np.array_equal(la, lb), f'{what}: the logs differ at (problem, iteration, word) {np.argwhere(np.asarray(la) != np.asarray(lb))[:5].tolist()}'
+
+
+def check_properties(p, r, collides=None):
+    """What every run must satisfy: a FOUND trajectory starts at the start and ends at the goal bit for bit, is free on every row by
+    `collides` (default: the fp32 predicate), moves joint k by at most w_k (1 + VEL_SLACK) per row, its vertex rows ascend strictly from 0
+    to R - 1; in both trees a child's row lies strictly on the growing side of its parent's."""
+    collides = collides or (lambda q, rows: collides32(p, q, rows))
+    for b in range(p.B):
+        for t in (0, 1):
+            n = int(r.counts[b, t])
+            par = r.parents[b, t, 1:n]
+            assert (par >= 0).all() and (par < np.arange(1, n)).all(), (p.name, b, t)
+            d = r.rows[b, t, 1:n] - r.rows[b, t, par]
+            assert ((d > 0) if t == 0 else (d < 0)).all(), f'{p.name}: problem {b} tree {t}: a child is not on the growing side of its parent'
+        if r.status[b] != FOUND:
+            continue
+        tr = r.trajs[b]
+        assert np.array_equal(tr[0].view(np.uint32), p.starts[b].view(np.uint32)) and np.array_equal(tr[-1].view(np.uint32), p.goals[b].view(np.uint32))
+        assert not collides(tr, np.arange(p.R)).any(), f'{p.name}: problem {b}: a FOUND trajectory collides at rows {np.nonzero(collides(tr, np.arange(p.R)))[0]}'
+        step = np.abs(np.diff(tr.astype(np.float64), axis=0))
+        assert (step <= p.w.astype(np.float64) * (1 + VEL_SLACK)).all(), f'{p.name}: problem {b}: per-row step {(step / p.w).max():.7f} w'
+        n = int(r.n_vertices[b])
+        vr = r.vertex_row[b, :n]
+        assert vr[0] == 0 and vr[-1] == p.R - 1 and (np.diff(vr) > 0).all(), (p.name, b, vr)
+
+
+@functools.lru_cache(maxsize=None)
+def reference(name):
+    """restate32 of the input set and its own log followed and audited in fp64, computed once and shared.  Treat as read-only."""
+    p = problem(name)
+    r32 = restate32(p)
+    r64, seen = follow(p, r32.log, r32.status, audit=True)
+    return types.SimpleNamespace(p=p, r32=r32, r64=r64, seen=seen)

@@ -1,0 +1,157 @@
+"""The space-time RRT-Connect on the GPU (planners.STRRTConnect, csrc/mpb_strrt.hip) against its restatement (strrt_checks.py): bit for
+bit following the kernel's own decision log, every decidable decision against fp64, the output against the existing moving-obstacle
+predicate kernels, the draws, chunking and copies, a frozen field, and the refusals by name."""
+import numpy as np
+import pytest
+import torch
+
+import strrt_checks as S
+
+pytestmark = pytest.mark.gpu
+CAP = 0.02                 # undecidable decisions among those audited: the shortcutter's cap
+REPLAY = ('gate', 'parity', 'gate129', 'panda_16_1', 'panda_16_8', 'panda_16_80', 'panda_65_1', 'panda_65_8', 'panda_65_80', 'panda_130_200', 'pandaslow_130_200', 'arm12')
+
+
+def _task(p, dev, fields=None):
+    from motion_planning_baselines_amd.robot_field import PlanningTask
+    fields = p.fields if fields is None else fields
+    return PlanningTask(p.robot, fields if len(fields) > 1 else fields[0], tensor_args=dict(device=dev, dtype=torch.float32))
+
+
+def _planner(p, dev, task=None, **kw):
+    from motion_planning_baselines_amd.planners import STRRTConnect
+    args = dict(task=task or _task(p, dev), moving_field=p.moving, n_rows=p.R, start_state_pos=torch.from_numpy(p.starts),
+                goal_state_pos=torch.from_numpy(p.goals), n_iters=p.n_iters, max_step_rows=p.max_step, dq_max=p.dq_max, n_pre_samples=p.n_pre,
+                pre_samples=torch.from_numpy(p.pre), seed=p.seed, max_nodes=p.max_nodes, max_path_nodes=p.Lmax)
+    args.update(kw)
+    return STRRTConnect(**args)
+
+
+def _arrays(planner, rec, rows=None):
+    """Host copies of everything a run leaves behind, under the names of strrt_checks.run() (rows: a slice of the problems)."""
+    from motion_planning_baselines_amd import ops
+    out = {k: v.cpu().numpy() for k, v in ops.strrt_trees(planner.workspace).items()}
+    out.update(trajs=rec.trajs.cpu().numpy(), vertex_q=rec.vertex_q.cpu().numpy(), vertex_row=rec.vertex_row.cpu().numpy(),
+               n_vertices=rec.n_vertices.cpu().numpy(), status_out=rec.status.cpu().numpy(), found=rec.found.cpu().numpy())
+    if rec.log is not None:
+        out['log'] = rec.log.cpu().numpy()
+    assert np.array_equal(out['status'], out['status_out']) and np.array_equal(out['found'], out['status'] == S.FOUND)
+    return {k: v[rows] for k, v in out.items()} if rows is not None else out
+
+
+@pytest.mark.parametrize('name', REPLAY)
+def test_kernel_equals_restatement_following_its_log(gpu_device, name):
+    """The restatement fed the kernel's collision outcomes reproduces trees (q, row, parent), counts, statuses, vertex lists, trajectories
+    and the log itself bit for bit; every decidable logged decision equals fp64's; undecidable ones stay under the cap.  On the gate
+    scenes, whose decisions are far from any surface, the kernel also equals the free-running fp32 restatement; every problem of gate
+    and of gate129 (R = 129: more than one trip of rows in a join) is FOUND."""
+    p = S.problem(name)
+    planner = _planner(p, gpu_device)
+    got = _arrays(planner, planner.optimize_batched(with_log=True))
+    want, seen = S.follow(p, got['log'], got['status'], audit=True)
+    S.same_bits(got, want, name)
+    share = S.undecidable_share(seen)
+    n_found = int((got['status'] == S.FOUND).sum())
+    print(f'{name}: {len(seen)} decisions audited, {share:.4f} undecidable, {n_found} of {p.B} found, statuses {got["status"].tolist()}, '
+          f'rejected joins {got["rejected_joins"].tolist()}')
+    assert len(seen) > 0 and share <= CAP
+    S.check_properties(p, want)
+    if name in ('gate', 'parity', 'gate129'):
+        S.same_bits(got, S.reference(name).r32, name + ' free-running')
+    if name in ('gate', 'gate129'):                  # gate129: joins whose dense fill and re-check take three trips of 64 rows
+        assert n_found == p.B
+    if name == 'pandaslow_130_200':                  # the Panda with a 12 s horizon: one problem joins, over three trips of rows
+        assert n_found >= 1
+
+
+@pytest.mark.parametrize('name', ('gate', 'gate129', 'panda_16_8', 'pandaslow_130_200'))
+def test_found_rows_are_free_by_the_existing_kernels_and_within_the_velocity_bound(gpu_device, name):
+    p = S.problem(name)
+    task = _task(p, gpu_device)
+    planner = _planner(p, gpu_device, task=task)
+    rec = planner.optimize_batched()
+    found = rec.found.cpu().numpy()
+    assert found.any()
+    hit, rows = task.check_trajs_moving(rec.trajs, p.moving)
+    assert not rows.cpu().numpy()[found].any(), np.argwhere(rows.cpu().numpy()[found])
+    tr = rec.trajs.cpu().numpy()[found].astype(np.float64)
+    step = np.abs(np.diff(tr, axis=1))
+    print(f'{name}: {int(found.sum())} found, largest per-row step {(step / p.w).max():.7f} w')
+    assert (step <= p.w.astype(np.float64) * (1 + S.VEL_SLACK)).all()
+    assert np.array_equal(tr[:, 0], p.starts[found]) and np.array_equal(tr[:, -1], p.goals[found])
+
+
+def test_recorded_draws_runs_chunks_and_copies(gpu_device):
+    p = S.problem('panda_16_8')
+    task = _task(p, gpu_device)
+    planner = _planner(p, gpu_device, task=task)
+    base = _arrays(planner, planner.optimize_batched(with_log=True))
+    S.same_bits(base, _arrays(planner, planner.optimize_batched(with_log=True)), 'second run')
+    idx, row = S.device_draws(p)
+    S.same_bits(base, _arrays(planner, planner.optimize_batched(sample_idx=idx, sample_row=row, with_log=True)), 'recorded draws')
+    wild = _arrays(planner, planner.optimize_batched(sample_idx=idx + np.where(idx == p.n_pre - 1, 5, 0), sample_row=np.where(row == 1, -3, row),
+                                                     with_log=True))
+    S.same_bits(base, wild, 'recorded draws out of range are clamped')
+    chunked = _planner(p, gpu_device, task=task, chunk_iters=7)
+    S.same_bits(base, _arrays(chunked, chunked.optimize_batched(with_log=True)), 'chunks of 7 iterations')
+    three = _arrays(planner, planner.optimize_batched(n_copies=3, with_log=True))
+    S.same_bits(base, {k: v[:p.B] for k, v in three.items()}, 'copy 0')
+    for c in (1, 2):
+        shifted = _arrays(planner, planner.optimize_batched(problem_offset=c * p.B, with_log=True))
+        S.same_bits(shifted, {k: v[c * p.B:(c + 1) * p.B] for k, v in three.items()}, f'copy {c} draws from stream offset + b')
+        assert not np.array_equal(shifted['log'], base['log'])
+        S.same_bits(shifted, S.follow(p, shifted['log'], shifted['status'], offset=c * p.B)[0], f'copy {c} against the restatement of its stream')
+
+
+def test_frozen_field_behaves_as_the_static_scene(gpu_device):
+    """A field whose keyframes are all equal is the static CollisionField of at(t): the plan is free of the static obstacles AND of that
+    field at every row by mpb_traj_collision_stats, and the kernel equals the restatement as in the replay test."""
+    from motion_planning_baselines_amd import geometry as G, ops
+    g = S.problem('gate')
+    c = np.array([[[-0.35, 0.45]], [[-0.35, 0.45]]])
+    frozen = G.MovingObstacleField([0.0, float(g.R - 1)], sphere_centers=c, sphere_radii=[0.2], margin=0.02)
+    p = S.make_problem('frozen', g.robot, g.fields, frozen, g.R, g.dq_max, g.starts, g.goals, g.pre, g.n_iters, g.max_step, seed=g.seed)
+    planner = _planner(p, gpu_device)
+    rec = planner.optimize_batched(with_log=True)
+    got = _arrays(planner, rec)
+    S.same_bits(got, S.follow(p, got['log'], got['status'])[0], 'frozen')
+    assert rec.found.all()
+    both = _task(p, gpu_device, fields=[g.fields[0], frozen.at(0.0)])
+    count, first, gap = ops.traj_collision_stats(rec.trajs, both.geom, n_interp=0)
+    assert int(count.sum()) == 0 and float(gap.max()) == 0.0
+    one = planner.optimize()
+    assert isinstance(one, list) and len(one) == p.B and all(torch.equal(t, rec.trajs[b]) for b, t in enumerate(one))
+
+
+def test_refusals_by_name(gpu_device):
+    from motion_planning_baselines_amd import geometry as G, ops
+    from motion_planning_baselines_amd.robot_field import PlanningTask
+    p = S.problem('gate')
+    task = _task(p, gpu_device)
+    for R in (2, 1025):
+        with pytest.raises(ValueError, match='n_rows'):
+            _planner(p, gpu_device, task=task, n_rows=R)
+    with pytest.raises(ValueError, match='dq_max'):
+        _planner(p, gpu_device, task=PlanningTask(G.RobotPointMass(2, radius=0.03), p.fields[0], tensor_args=task.tensor_args), dq_max=None)
+    with pytest.raises(ValueError, match='same shape'):
+        _planner(p, gpu_device, task=task, goal_state_pos=torch.from_numpy(p.goals[:3]))
+    with pytest.raises(TypeError, match='MovingObstacleField'):
+        _planner(p, gpu_device, task=task, moving_field=p.fields[0])
+    # a buffer packed for another row count: the wrapper and the library both name the two numbers
+    planner = _planner(p, gpu_device, task=task)
+    other = ops.DeviceMovingObstacles(p.robot, p.moving, gpu_device, p.R + 1)
+    ws = ops.STRRTWorkspace(p.B, p.max_nodes, p.D, p.R, gpu_device)
+    with pytest.raises(ValueError, match=f'n_rows = {p.R}.*n_rows = {p.R + 1}'):
+        ops.strrt_init(ws.buf, ws, planner.starts, planner.goals, planner.w, task.geom, other)
+    from motion_planning_baselines_amd import _lib
+    rc = _lib.lib().mpb_strrt_init(ops._ptr(ws.buf), ws.nbytes, ops._ptr(planner.starts), ops._ptr(planner.goals), ops._ptr(planner.w),
+                                   ops._ptr(task.geom.buf), int(task.geom.flags), ops._ptr(other.buf), p.B, p.max_nodes, p.D, p.R, None)
+    assert rc != 0 and f'n_rows = {p.R}' in _lib.lib().mpb_last_error().decode() and f'n_rows = {p.R + 1}' in _lib.lib().mpb_last_error().decode()
+    # self_field / sdf_field: refused by name like the RRT planners refuse them
+    panda = S.problem('panda_16_8')
+    ta = dict(device=gpu_device, dtype=torch.float32)
+    with pytest.raises(NotImplementedError, match='self_field'):
+        _planner(panda, gpu_device, task=PlanningTask(panda.robot, panda.fields[0], self_field=G.SelfCollisionField(panda.robot), tensor_args=ta))
+    sdf = G.GridSDFField.from_field(panda.fields[0], lo=(-1, -1, -1), hi=(1, 1, 1), cell=0.1)
+    with pytest.raises(NotImplementedError, match='sdf_field'):
+        _planner(panda, gpu_device, task=PlanningTask(panda.robot, panda.fields[0], sdf_field=sdf, tensor_args=ta))

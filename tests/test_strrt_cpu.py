@@ -1,0 +1,164 @@
+"""The space-time RRT-Connect without a GPU: the properties of its restatement (strrt_checks.py) on its own fp32 predicate, the gate scene,
+the row-index conditions the GPU replay rests on, the status cases, and the generated layout and what the compiler made of the kernels."""
+import json
+
+import numpy as np
+import pytest
+import torch
+
+import strrt_checks as S
+
+SCENES = ('gate', 'parity', 'gate129', 'panda_16_8', 'panda_65_80', 'pandaslow_130_200', 'arm12')
+# VGPRs / SGPRs / scratch of the three moving-obstacle kernels as the parent commit's build recorded them: moving their device code into
+# csrc/mpb_moving.h is a pure move
+MOVING_PARENT = {'_Z18moving_cost_kernelILb0EEvPKfS1_PfS2_S2_iiiffiiiii': (106, 106, 0), '_Z18moving_cost_kernelILb1EEvPKfS1_PfS2_S2_iiiffiiiii': (226, 106, 0),
+                 '_Z19moving_check_kernelPKfS0_PhPfiiiiiii': (105, 106, 0)}
+
+
+@pytest.mark.parametrize('name', SCENES)
+def test_restatement_properties_and_fp64_audit(name):
+    """FOUND trajectories start at q_s, end at q_g, are free on every row by the fp32 predicate and keep |dq_k| <= w_k (1 + 1e-5) per row;
+    parents' rows are strictly ordered in both trees; following its own log reproduces the run; the fp32 predicate's undecidable decisions
+    against fp64 stay within the 2 % the GPU replay allows."""
+    ref = S.reference(name)
+    S.check_properties(ref.p, ref.r32)
+    S.same_bits(ref.r32, ref.r64, name)
+    assert len(ref.seen) > 0 and S.undecidable_share(ref.seen) <= 0.02, S.undecidable_share(ref.seen)
+    if name in ('gate129', 'pandaslow_130_200'):                     # the scenes that exercise a join over more than one trip of 64 rows
+        assert ref.p.R > 128 and (ref.r32.status == S.FOUND).any()
+
+
+def test_rows_field_equals_the_per_row_oracle_fields():
+    p = S.problem('panda_16_8')
+    q = torch.from_numpy(p.pre[:p.R])
+    for mf, ta in ((p.mv32, S.F32), (p.mv64, S.F64)):
+        x = (p.rr32 if ta is S.F32 else p.rr64).fk_map_collision(q.to(**ta))
+        want = torch.stack([mf.per[h].signed_distance(x[h]) for h in range(p.R)])
+        assert torch.equal(S.sd_rows(mf, x, np.arange(p.R)), want)
+
+
+def test_gate_scene():
+    """Seed GATE_SEED = 3 (chosen here on the CPU): all B = 16 problems are solved within 256 iterations; the straight constant-speed line
+    collides under the moving predicate; every plan crosses the gap outside the blocked rows."""
+    ref = S.reference('gate')
+    p, r = ref.p, ref.r32
+    line = (p.starts[0][None] + (p.goals[0] - p.starts[0])[None] * (np.arange(p.R, dtype=np.float32) / np.float32(p.R - 1))[:, None]).astype(np.float32)
+    assert np.abs(np.diff(line, axis=0)).max() <= p.w.min() and S.collides32(p, line, np.arange(p.R))[p.R // 2]
+    assert (r.status == S.FOUND).all() and (r.iters <= 256).all(), r.status
+    lo, hi = S.GATE_BLOCKED
+    for b in range(p.B):
+        x = r.trajs[b, :, 0]
+        cross = np.nonzero((x[:-1] < 0) != (x[1:] < 0))[0]
+        assert len(cross) >= 1 and all(h + 1 < lo or h > hi for h in cross), (b, cross)
+        near = np.nonzero(np.abs(x) < 0.1)[0]
+        assert all(h < lo or h > hi for h in near), (b, near)
+
+
+def test_gate_scene_on_129_rows_joins_over_more_than_one_trip():
+    """gate129: the same motion on R = 129 rows.  Every problem is FOUND, so the joins' dense fill and re-check (trips of 64 rows) are
+    exercised beyond one trip; every plan crosses the gap outside the blocked rows 44 .. 84."""
+    ref = S.reference('gate129')
+    p, r = ref.p, ref.r32
+    assert p.R == 129 and (r.status == S.FOUND).all(), r.status
+    lo, hi = S.GATE129_BLOCKED
+    for b in range(p.B):
+        near = np.nonzero(np.abs(r.trajs[b, :, 0]) < 0.1)[0]
+        assert len(near) and all(h < lo or h > hi for h in near), (b, near)
+        assert (np.diff(r.vertex_row[b, :r.n_vertices[b]]) > 0).all() and r.vertex_row[b, r.n_vertices[b] - 1] == 128
+
+
+def test_row_index_conditions():
+    """The parity scene (the sphere sits in the gap at odd rows only): a predicate that ignores, shifts or reverses the row of the
+    backward tree grows other trees than the definition's, so a kernel that did could not pass the replay."""
+    p = S.problem('parity')
+    true = S.reference('parity').r32
+    for what, row_of in (('ignores', lambda t, row: row if t == 0 else 0), ('shifts', lambda t, row: row if t == 0 else max(row - 1, 0)),
+                         ('reverses', lambda t, row: row if t == 0 else p.R - 1 - row)):
+        other = S.restate32(p, row_of=row_of)
+        with pytest.raises(AssertionError):
+            S.same_bits(true, other, what)
+
+
+def test_status_cases():
+    from motion_planning_baselines_amd import geometry as G
+    g = S.problem('gate')
+    one = dict(starts=g.starts[:1], goals=g.goals[:1])
+    far = S.restate32(S.variant(g, starts=np.array([[-0.9, -0.9]], np.float32), goals=np.array([[0.9, 0.9]], np.float32), w=np.full(2, 0.05, np.float32)))
+    assert far.status[0] == S.HORIZON_TOO_SHORT and far.iters[0] == 0          # 1.8 / 0.05 = 36 rows > R - 1 = 32
+    edge = S.restate32(S.variant(g, **one, w=np.full(2, np.float32(1.4) / np.float32(32), np.float32), n_iters=1))
+    assert edge.status[0] != S.HORIZON_TOO_SHORT                               # tau == R - 1 exactly is served
+    for at_start in (True, False):
+        where, t = (g.starts[0], [0.0, 1.0, 32.0]) if at_start else (g.goals[0], [0.0, 31.0, 32.0])
+        park = np.array([0.0, 0.7])
+        c = np.array([[where if at_start else park], [park], [park if at_start else where]])
+        mv = G.MovingObstacleField(t, sphere_centers=c, sphere_radii=[0.05], margin=0.02)
+        q = S.make_problem('hit', g.robot, g.fields, mv, g.R, g.dq_max, g.starts[:1], g.goals[:1], g.pre, 8, 8)
+        rows = np.arange(g.R)
+        hit = S.collides32(q, np.repeat(where[None], g.R, 0), rows)
+        assert hit[0 if at_start else -1] and hit.sum() == 1                    # the endpoint collides at its own row only
+        assert S.restate32(q).status[0] == S.START_OR_GOAL_IN_COLLISION
+    full = S.restate32(S.variant(g, max_nodes=3))
+    assert (full.status == S.TREE_FULL).any() and (full.counts <= 3).all()
+    S.check_properties(g, full)
+    long = S.restate32(S.variant(g, **one, Lmax=2))
+    assert long.status[0] == S.PATH_TOO_LONG
+    # a discarded join could not be constructed from geometry (every interpolated row lies within rounding of a point an extension
+    # checked, so a failing re-check needs a surface within a few ulp); the bookkeeping is exercised with a judge that refuses the first join
+    seen = []
+
+    def judge_join(b, it, traj):
+        seen.append(it)
+        return 5 if len(seen) == 1 else -1
+    q = S.variant(g, **one)
+    ext = lambda b, it, e, pts, rows: (lambda hit: int(hit[0]) + 1 if len(hit) else -1)(np.nonzero(S.collides32(q, pts, rows))[0])
+    r = S.run(q, ext, judge_join, lambda b: False)
+    assert r.rejected_joins[0] == 1 and r.status[0] == S.FOUND and len(seen) == 2 and r.log[0, seen[0], S.JOIN] == 5 and r.log[0, seen[1], S.JOIN] == -1
+    S.check_properties(q, r)
+
+
+def test_draws_are_philox_known_answers():
+    """Random123's known-answer vectors for philox4x32_10 (the ones tests/test_gpu_rng.py holds the device generator to)."""
+    assert S.philox4x32_10((0, 0, 0, 0), (0, 0)) == [0x6627e8d5, 0xe169c58d, 0xbc57ac4c, 0x9b00dbd8]
+    assert S.philox4x32_10((0xffffffff,) * 4, (0xffffffff,) * 2) == [0x408f276d, 0x41c83b0e, 0xa20bc7c6, 0x6d5451fd]
+    idx, row = S.device_draws(S.problem('gate'))
+    assert idx.min() >= 0 and idx.max() < 512 and row.min() >= 1 and row.max() <= S.GATE_R - 2
+
+
+def test_layout_header_is_generated():
+    from motion_planning_baselines_amd import build, model_gen, strrt_layout as L
+    assert open(model_gen.STRRT_LAYOUT_HEADER).read() == model_gen.strrt_layout_header_text()
+    assert not model_gen.stale_headers()
+    text = open(model_gen.STRRT_LAYOUT_HEADER).read()
+    for line in ('#define MPB_STRRT_MAGIC 0x53545252', '#define MPB_STRRT_HORIZON_TOO_SHORT 4', '#define MPB_STRRT_MAX_ROWS 1024', 'MPB_STH_REJECTED_JOINS = 4,',
+                 'MPB_STG_N_ROWS = 5,', 'MPB_STL_APPENDED = 5,', '#define MPB_STRRT_LOG_JOIN 12', '#define MPB_STRRT_LOG_NONE (-2)'):
+        assert line in text, line
+    assert L.STRRT_MAGIC.to_bytes(4, 'big') == b'STRR'
+    lay = L.offsets(3, 10, 7)
+    assert lay.Dp == 8 and lay.sections['nodes'][0] == 16 + 3 * 16 and lay.total == 16 + 48 + 3 * 2 * 10 * (8 + 2)
+    assert 'mpb_strrt_layout.h' in open(build.__file__).read() and 'mpb_strrt.hip' in build.SOURCES
+    assert '#include "mpb_strrt_layout.h"' in open(model_gen.STRRT_LAYOUT_HEADER.replace('mpb_strrt_layout.h', 'mpb.h')).read()
+
+
+def test_kernel_resources():
+    """csrc/kernel_resources.json: the new kernels (two init, five run instantiations) have 0 B of scratch and no vector spills; the three
+    moving-obstacle kernels came out with the parent commit's registers."""
+    from motion_planning_baselines_amd import build
+    build.build(verbose=False)
+    res = json.load(open(build.RESOURCES))
+    new = {k: v for k, v in res.items() if k.startswith(('_Z17strrt_init_kernel', '_Z12strrt_kernel'))}
+    assert len(new) == 7, list(new)
+    for name, r in new.items():
+        assert r['scratch'] == 0 and r['vgpr_spill'] == 0, (name, r)
+    for name, (vgprs, sgprs, scratch) in MOVING_PARENT.items():
+        assert (res[name]['vgprs'], res[name]['sgprs'], res[name]['scratch']) == (vgprs, sgprs, scratch), (name, res[name])
+
+
+def test_library_exports_the_entry_points():
+    import os
+    from conftest import ROOT
+    from motion_planning_baselines_amd import _lib
+    text = open(os.path.join(ROOT, 'include', 'mpb.h')).read()
+    for name in ('mpb_strrt_workspace_bytes', 'mpb_strrt_init', 'mpb_strrt_run'):
+        assert hasattr(_lib.lib(), name) and name + '(' in text, name
+    assert _lib.lib().mpb_strrt_workspace_bytes(3, 10, 7) == 4 * (16 + 48 + 3 * 2 * 10 * 10)
+    assert _lib.lib().mpb_strrt_workspace_bytes(3, 1, 7) == 0 and b'max_nodes' in _lib.lib().mpb_last_error()
