@@ -7,6 +7,7 @@
 #include <stdarg.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <string.h>
 
 #include <mutex>
 
@@ -127,6 +128,21 @@ static inline int mpb_raise_lds_limit(const void* kernel, int dev, size_t bytes,
     if (e != hipSuccess) return mpb_failf(MPB_E_HIP, "%s: raising the LDS limit to %zu bytes failed: %s", who, bytes, hipGetErrorString(e));
     if (slot < 64) raised[slot] = {kernel, dev, bytes};                               // (a full table only costs the call again)
     return MPB_OK;
+}
+// ... on the current device, as a launcher asks for it (at or below 48 KB no runtime call is made)
+template <class Kernel>
+static inline int mpb_raise_lds_limit(Kernel kernel, size_t bytes, const char* who) {
+    if (bytes <= 48 * 1024) return MPB_OK;
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return mpb_failf(MPB_E_HIP, "%s: hipGetDevice failed", who);
+    return mpb_raise_lds_limit(reinterpret_cast<const void*>(kernel), dev, bytes, who);
+}
+
+// a step size a launcher refuses: not finite or not positive, decided on the bits (the build assumes finite math)
+static inline bool mpb_bad_step(float step) {
+    uint32_t bits;
+    memcpy(&bits, &step, 4);
+    return (bits >> 31) != 0u || (bits << 1) == 0u || (bits & 0x7F800000u) == 0x7F800000u;
 }
 
 // Trajectory rows (B, H, d) against a packed robot buffer, "the <noun> buffer": the refusals that need no header, in the order

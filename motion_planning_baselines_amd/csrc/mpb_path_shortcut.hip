@@ -5,19 +5,16 @@
 //
 // ONE launch, one single-wave workgroup per path, the path in LDS as (Lmax, Dp) floats (Dp = D rounded up to 4) for the
 // whole launch.  Per iteration: two uniforms pick two positions on the polyline, the segment between them is checked exactly
-// as the RRT kernels check an extension without the max_dist clamp (the sequential fp32 distance, dist / check_step + 2
+// as the RRT kernels check an extension without the max_dist clamp (the rounded fp32 distance, dist / check_step + 2
 // points, rrt_linspace_point, rrt_first_collision with rrt_config_cost > 0: mpb_rrt.h), and a free segment replaces the
 // nodes between the two positions; the tail moves in LDS by a parallel shift, as rrt_pool_delete moves its list.
 //   - workgroups never wait on each other, every loop is bounded by n_iters, Lmax or the point count of one candidate;
 //   - no atomics, a fixed order: the same bits on every run, and a path's bits depend on its own inputs only;
-//   - the arithmetic of this file is rounded after every operation: plain operators under #pragma clang fp contract(off).  (The
-//     __f*_rn intrinsics are inline functions of plain operators compiled under the default contraction: hipcc fuses
-//     __fadd_rn(a, __fmul_rn(b, c)) into one fma whatever the caller's pragma says.  What this file calls in mpb_rrt.h is
-//     compiled as it stands there: rrt_linspace_point and rrt_close do contract.)
+//   - the arithmetic of this file is rounded after every operation: plain operators under #pragma clang fp contract(off).  What
+//     it calls in mpb_rrt.h is what stands there: rrt_d2_rounded rounds after every operation too, rrt_linspace_point and
+//     rrt_close say fmaf where they take one rounding;
 //   - every value that steers control flow (the length, the positions, the verdicts) is computed alike by all 64 lanes
 //     from LDS broadcasts: the control flow is block-uniform, as rrt_config_cost's __syncthreads() needs.
-#include <string.h>
-
 #include "mpb_common.h"
 #include "mpb_rrt.h"
 #include "mpb_rrt_host.h"
@@ -46,25 +43,6 @@ __device__ __forceinline__ float sc_unit(float u) {
     return fminf(fmaxf(u, 0.f), 0x1.fffffep-1f);
 }
 
-// the RRT kernels' distance (rrt_connect_kernel's nearest-node scan): a sequential fp32 sum in index order, no contraction
-template <int DM>
-__device__ __forceinline__ float sc_dist(const float (&x)[MPB_MAX_DOF], const float (&y)[MPB_MAX_DOF]) {
-#pragma clang fp contract(off)
-    float d2 = 0.f;
-#pragma unroll
-    for (int k = 0; k < DM; ++k) {
-        const float df = x[k] - y[k];
-        d2 = d2 + df * df;
-    }
-    return sqrtf(d2);
-}
-
-template <int DM>
-__device__ __forceinline__ void sc_row(const float* P, int Dp, int D, int r, float (&q)[MPB_MAX_DOF]) {
-#pragma unroll
-    for (int k = 0; k < MPB_MAX_DOF; ++k) q[k] = (k < DM && k < D) ? P[r * Dp + k] : 0.f;
-}
-
 template <int DM>
 __device__ __forceinline__ bool sc_allclose(const float (&x)[MPB_MAX_DOF], const float (&y)[MPB_MAX_DOF], int D) {
     bool c = true;
@@ -74,14 +52,16 @@ __device__ __forceinline__ bool sc_allclose(const float (&x)[MPB_MAX_DOF], const
     return c;
 }
 
-// the polyline's joint-space length: the segments' distances summed in fp32 in path order (every lane the whole sum)
+// the polyline's joint-space length: the segments' distances (the square root of rrt_d2_rounded) summed in fp32 in path order
+// (every lane the whole sum)
 template <int DM>
 __device__ __forceinline__ float sc_length(const float* P, int Dp, int D, int L) {
+#pragma clang fp contract(off)
     float len = 0.f, x[MPB_MAX_DOF], y[MPB_MAX_DOF];
-    if (L > 0) sc_row<DM>(P, Dp, D, 0, x);
+    if (L > 0) rrt_load_row<DM>(P, D, x);
     for (int j = 1; j < L; ++j) {
-        sc_row<DM>(P, Dp, D, j, y);
-        len = len + sc_dist<DM>(x, y);
+        rrt_load_row<DM>(P + j * Dp, D, y);
+        len = len + sqrtf(rrt_d2_rounded<DM>(x, y));
 #pragma unroll
         for (int k = 0; k < MPB_MAX_DOF; ++k) x[k] = y[k];
     }
@@ -103,8 +83,8 @@ template <int DM>
 __device__ __forceinline__ bool sc_point(const float* P, int Dp, int D, int a, float t, float (&pt)[MPB_MAX_DOF], int& node) {
 #pragma clang fp contract(off)
     float q0[MPB_MAX_DOF], q1[MPB_MAX_DOF];
-    sc_row<DM>(P, Dp, D, a, q0);
-    sc_row<DM>(P, Dp, D, a + 1, q1);
+    rrt_load_row<DM>(P + a * Dp, D, q0);
+    rrt_load_row<DM>(P + (a + 1) * Dp, D, q1);
 #pragma unroll
     for (int k = 0; k < MPB_MAX_DOF; ++k) pt[k] = q0[k] + t * (q1[k] - q0[k]);
     const bool at0 = t == 0.f || sc_allclose<DM>(pt, q0, D);
@@ -170,7 +150,7 @@ __global__ __launch_bounds__(64) void path_shortcut_kernel(const ScArgs a) {
                 const bool ins2 = sc_point<DM>(P, Dp, D, a2, t2, p2, n2);
                 const int lo = ins1 ? a1 : n1;             // the last node kept before the shortcut
                 const int hi = ins2 ? a2 + 1 : n2;         // the first node kept after it
-                const float dist = sc_dist<DM>(p1, p2);
+                const float dist = sqrtf(rrt_d2_rounded<DM>(p1, p2));
                 const float cntf = dist / a.step;
                 // (hi - lo < 2: after the snap to nodes both points lie on one segment)
                 if (hi - lo >= 2 && !sc_allclose<DM>(p1, p2, D) && cntf < (float)(RRT_MAX_PTS - 1)) {
@@ -234,18 +214,6 @@ __global__ __launch_bounds__(64) void path_shortcut_kernel(const ScArgs a) {
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------------
-template <int DT, int MODEL>
-static int sc_launch(const ScArgs& a, int N, size_t lds, hipStream_t s) {
-    if (lds > 48 * 1024) {
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess) return mpb_fail(MPB_E_HIP, "mpb_path_shortcut: hipGetDevice failed");
-        const int rc = mpb_raise_lds_limit(reinterpret_cast<const void*>(path_shortcut_kernel<DT, MODEL>), dev, lds, "mpb_path_shortcut");
-        if (rc) return rc;
-    }
-    hipLaunchKernelGGL((path_shortcut_kernel<DT, MODEL>), dim3(N), dim3(64), lds, s, a);
-    return mpb_check_launch("mpb_path_shortcut");
-}
-
 extern "C" int mpb_path_shortcut(const float* paths_in, const int* lengths_in, float* paths_out, int* lengths_out, float* stats,
                                  int* log, const float* geom, int geom_flags, const float* draws, int N, int Lmax, int D,
                                  int n_iters, float check_step, uint64_t seed, uint32_t problem_offset, void* stream) {
@@ -257,20 +225,17 @@ extern "C" int mpb_path_shortcut(const float* paths_in, const int* lengths_in, f
         return mpb_failf(MPB_E_INVALID, "mpb_path_shortcut: Lmax = %d outside 2 .. %d (the path of D = %d lives in LDS)", Lmax, max_rows, D);
     if (n_iters < 0 || n_iters > MPB_SHORTCUT_MAX_ITERS)
         return mpb_failf(MPB_E_INVALID, "mpb_path_shortcut: n_iters = %d outside 0 .. %d", n_iters, MPB_SHORTCUT_MAX_ITERS);
-    uint32_t step_bits;
-    memcpy(&step_bits, &check_step, 4);                      // (on the bits: the build assumes finite math)
-    if ((step_bits >> 31) != 0u || (step_bits << 1) == 0u || (step_bits & 0x7F800000u) == 0x7F800000u)
-        return mpb_fail(MPB_E_INVALID, "mpb_path_shortcut: check_step must be finite and positive");
+    if (mpb_bad_step(check_step)) return mpb_fail(MPB_E_INVALID, "mpb_path_shortcut: check_step must be finite and positive");
     if (!paths_in || !lengths_in || !paths_out || !lengths_out || !stats || !geom) return mpb_fail(MPB_E_INVALID, "mpb_path_shortcut: null pointer");
     if (mpb_misaligned16(geom)) return mpb_fail(MPB_E_INVALID, "mpb_path_shortcut: geom must be 16-byte aligned");
     if (N == 0) return MPB_OK;
     const ScArgs a = {paths_in, lengths_in, paths_out, lengths_out, stats, log, geom, draws, Lmax, D, n_iters, check_step,
                       (uint32_t)seed, (uint32_t)(seed >> 32), problem_offset};
     const size_t lds = (size_t)Lmax * Dp * sizeof(float);
-    const hipStream_t s = (hipStream_t)stream;
-    if (rrt_use_model(geom_flags, D)) return sc_launch<7, PandaModel::ID>(a, N, lds, s);
-    if (D == 2) return sc_launch<2, 0>(a, N, lds, s);
-    if (D == 3) return sc_launch<3, 0>(a, N, lds, s);
-    if (D == 7) return sc_launch<7, 0>(a, N, lds, s);
-    return sc_launch<0, 0>(a, N, lds, s);
+    return rrt_dispatch<2, 3, 7>(geom_flags, D, [&](auto dt, auto model) {
+        const int rl = mpb_raise_lds_limit(path_shortcut_kernel<dt.value, model.value>, lds, "mpb_path_shortcut");
+        if (rl) return rl;
+        hipLaunchKernelGGL((path_shortcut_kernel<dt.value, model.value>), dim3(N), dim3(64), lds, (hipStream_t)stream, a);
+        return mpb_check_launch("mpb_path_shortcut");
+    });
 }

@@ -11,9 +11,7 @@
 //     build assumes finite math and +inf is a value here, and an LDS atomic min on the bits is exact.  The relaxation order of a sweep is
 //     not fixed, the fixed point is: fl(d + w) is monotone in d, so every run ends with the same bits;
 //   - the arithmetic of this file is rounded after every operation: plain operators under #pragma clang fp contract(off) (what it calls
-//     in mpb_rrt.h is compiled as it stands there: mpb_path_shortcut.hip has the note).
-#include <string.h>
-
+//     in mpb_rrt.h is what stands there: rrt_d2_rounded rounds alike, rrt_linspace_point says fmaf where it takes one rounding).
 #include "mpb_common.h"
 #include "mpb_rrt.h"
 #include "mpb_rrt_host.h"
@@ -22,26 +20,7 @@
 #define PRM_QUERY_THREADS 256
 #define PRM_NO_PRED 0xFFFFFFFFu
 
-// ---- the distance: mpb_path_shortcut.hip's sc_dist before its square root ---------------------------------------------------------------
-template <int DM>
-__device__ __forceinline__ float prm_d2(const float (&x)[MPB_MAX_DOF], const float (&y)[MPB_MAX_DOF]) {
-#pragma clang fp contract(off)
-    float d2 = 0.f;
-#pragma unroll
-    for (int k = 0; k < DM; ++k) {
-        const float df = x[k] - y[k];
-        d2 = d2 + df * df;
-    }
-    return d2;
-}
-
-template <int DM>
-__device__ __forceinline__ void prm_row(const float* __restrict__ p, int D, float (&q)[MPB_MAX_DOF]) {
-#pragma unroll
-    for (int k = 0; k < MPB_MAX_DOF; ++k) q[k] = (k < DM && k < D) ? p[k] : 0.f;
-}
-
-// the key a d2 is ordered by: its bits (d2 is a sum of squares: never negative), a NaN as +inf
+// the key a d2 (rrt_d2_rounded of mpb_rrt.h) is ordered by: its bits (d2 is a sum of squares: never negative), a NaN as +inf
 __device__ __forceinline__ unsigned prm_key(float d2) { return min(__float_as_uint(d2) & 0x7FFFFFFFu, PRM_INF_BITS); }
 
 // ---- 1. k nearest nodes ---------------------------------------------------------------------------------------------------------------
@@ -62,7 +41,7 @@ __global__ __launch_bounds__(64) void prm_knn_kernel(const PrmKnnArgs a) {
     const int D = DT ? DT : a.D;
     const int i = blockIdx.x, lane = threadIdx.x, M = a.M;
     float q[MPB_MAX_DOF], x[MPB_MAX_DOF];
-    prm_row<DM>(a.queries + (size_t)i * D, D, q);
+    rrt_load_row<DM>(a.queries + (size_t)i * D, D, q);
     for (int base = 0; base < M; base += 64) {
         const int rows = min(64, M - base);
         __syncthreads();
@@ -70,8 +49,8 @@ __global__ __launch_bounds__(64) void prm_knn_kernel(const PrmKnnArgs a) {
         __syncthreads();
         const int j = base + lane;
         if (lane < rows) {
-            prm_row<DM>(tile + lane * D, D, x);
-            prm_keys[j] = (a.exclude_self && j == i) ? 0xFFFFFFFFu : prm_key(prm_d2<DM>(q, x));
+            rrt_load_row<DM>(tile + lane * D, D, x);
+            prm_keys[j] = (a.exclude_self && j == i) ? 0xFFFFFFFFu : prm_key(rrt_d2_rounded<DM>(q, x));
         }
     }
     __syncthreads();
@@ -124,9 +103,9 @@ __global__ __launch_bounds__(64) void prm_edge_kernel(const PrmEdgeArgs a) {
             code = MPB_PRM_EDGE_BAD_INDEX;
         } else {
             float p1[MPB_MAX_DOF], p2[MPB_MAX_DOF], dl[MPB_MAX_DOF];
-            prm_row<DM>(a.pts + (size_t)min(ia, ib) * D, D, p1);
-            prm_row<DM>(a.pts + (size_t)max(ia, ib) * D, D, p2);
-            const float cntf = sqrtf(prm_d2<DM>(p1, p2)) / a.step;
+            rrt_load_row<DM>(a.pts + (size_t)min(ia, ib) * D, D, p1);
+            rrt_load_row<DM>(a.pts + (size_t)max(ia, ib) * D, D, p2);
+            const float cntf = sqrtf(rrt_d2_rounded<DM>(p1, p2)) / a.step;
             // (on the bits: cntf is never negative, and a NaN or +inf counts as too long)
             if (!(__float_as_uint(cntf) < __float_as_uint((float)(RRT_MAX_PTS - 1)))) {
                 code = MPB_PRM_EDGE_TOO_LONG;
@@ -310,12 +289,6 @@ __global__ __launch_bounds__(PRM_QUERY_THREADS) void prm_query_kernel(const PrmQ
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------------------------------
-static bool prm_bad_step(float step) {
-    uint32_t bits;
-    memcpy(&bits, &step, 4);                                 // (on the bits: the build assumes finite math)
-    return (bits >> 31) != 0u || (bits << 1) == 0u || (bits & 0x7F800000u) == 0x7F800000u;
-}
-
 // the shape and limit refusals the entry points share, in the order include/mpb.h gives them (rows: the count that may be 0)
 static int prm_shape_check(const char* who, int rows, int D, int M, int K) {
     if (rows < 0 || D < 1) return mpb_failf(MPB_E_INVALID, "%s: bad shape (rows %d, D %d)", who, rows, D);
@@ -324,23 +297,6 @@ static int prm_shape_check(const char* who, int rows, int D, int M, int K) {
     if (K > MPB_PRM_MAX_K) return mpb_failf(MPB_E_UNSUPPORTED, "%s: K = %d exceeds MPB_PRM_MAX_K = %d", who, K, MPB_PRM_MAX_K);
     if (M < 2) return mpb_failf(MPB_E_INVALID, "%s: M = %d, a roadmap has at least 2 nodes", who, M);
     return MPB_OK;
-}
-
-template <class Kernel>
-static int prm_lds_limit(Kernel kernel, size_t lds, const char* who) {
-    if (lds <= 48 * 1024) return MPB_OK;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return mpb_failf(MPB_E_HIP, "%s: hipGetDevice failed", who);
-    return mpb_raise_lds_limit(reinterpret_cast<const void*>(kernel), dev, lds, who);
-}
-
-template <int DT>
-static int prm_knn_launch(const PrmKnnArgs& a, int Q, hipStream_t s) {
-    const size_t lds = (size_t)a.M * sizeof(unsigned);
-    const int rc = prm_lds_limit(prm_knn_kernel<DT>, lds, "mpb_prm_knn");
-    if (rc) return rc;
-    hipLaunchKernelGGL((prm_knn_kernel<DT>), dim3(Q), dim3(64), lds, s, a);
-    return mpb_check_launch("mpb_prm_knn");
 }
 
 extern "C" int mpb_prm_knn(const float* queries, const float* nodes, int* idx, float* dist, int Q, int M, int D, int K, int exclude_self,
@@ -353,35 +309,29 @@ extern "C" int mpb_prm_knn(const float* queries, const float* nodes, int* idx, f
     if (!queries || !nodes || !idx || !dist) return mpb_fail(MPB_E_INVALID, "mpb_prm_knn: null pointer");
     if (Q == 0) return MPB_OK;
     const PrmKnnArgs a = {queries, nodes, idx, dist, M, D, K, exclude_self ? 1 : 0};
-    const hipStream_t s = (hipStream_t)stream;
-    if (D == 2) return prm_knn_launch<2>(a, Q, s);
-    if (D == 3) return prm_knn_launch<3>(a, Q, s);
-    if (D == 7) return prm_knn_launch<7>(a, Q, s);
-    return prm_knn_launch<0>(a, Q, s);
-}
-
-template <int DT, int MODEL>
-static int prm_edge_launch(const PrmEdgeArgs& a, hipStream_t s) {
-    const int blocks = min(a.E, 8 * mpb_device_cu_count());
-    hipLaunchKernelGGL((prm_edge_kernel<DT, MODEL>), dim3(blocks), dim3(64), 0, s, a);
-    return mpb_check_launch("mpb_prm_edge_check");
+    const size_t lds = (size_t)M * sizeof(unsigned);
+    return rrt_dispatch<2, 3, 7>(0, D, [&](auto dt, auto) {                  // (no geometry: DT alone, never the model's branch)
+        const int rl = mpb_raise_lds_limit(prm_knn_kernel<dt.value>, lds, "mpb_prm_knn");
+        if (rl) return rl;
+        hipLaunchKernelGGL((prm_knn_kernel<dt.value>), dim3(Q), dim3(64), lds, (hipStream_t)stream, a);
+        return mpb_check_launch("mpb_prm_knn");
+    });
 }
 
 extern "C" int mpb_prm_edge_check(const float* pts, const int* pairs, int* flag, int* first, const float* geom, int geom_flags, int P, int E,
                                   int D, float check_step, void* stream) {
     if (E < 0 || P < 1 || D < 1) return mpb_failf(MPB_E_INVALID, "mpb_prm_edge_check: bad shape (P %d, E %d, D %d)", P, E, D);
     if (D > MPB_MAX_DOF) return mpb_failf(MPB_E_UNSUPPORTED, "mpb_prm_edge_check: D = %d exceeds MPB_MAX_DOF = %d", D, MPB_MAX_DOF);
-    if (prm_bad_step(check_step)) return mpb_fail(MPB_E_INVALID, "mpb_prm_edge_check: check_step must be finite and positive");
+    if (mpb_bad_step(check_step)) return mpb_fail(MPB_E_INVALID, "mpb_prm_edge_check: check_step must be finite and positive");
     if (!pts || !pairs || !flag || !first || !geom) return mpb_fail(MPB_E_INVALID, "mpb_prm_edge_check: null pointer");
     if (mpb_misaligned16(geom)) return mpb_fail(MPB_E_INVALID, "mpb_prm_edge_check: geom must be 16-byte aligned");
     if (E == 0) return MPB_OK;
     const PrmEdgeArgs a = {pts, pairs, geom, flag, first, P, E, D, check_step};
-    const hipStream_t s = (hipStream_t)stream;
-    if (rrt_use_model(geom_flags, D)) return prm_edge_launch<7, PandaModel::ID>(a, s);
-    if (D == 2) return prm_edge_launch<2, 0>(a, s);
-    if (D == 3) return prm_edge_launch<3, 0>(a, s);
-    if (D == 7) return prm_edge_launch<7, 0>(a, s);
-    return prm_edge_launch<0, 0>(a, s);
+    const int blocks = min(E, 8 * mpb_device_cu_count());
+    return rrt_dispatch<2, 3, 7>(geom_flags, D, [&](auto dt, auto model) {
+        hipLaunchKernelGGL((prm_edge_kernel<dt.value, model.value>), dim3(blocks), dim3(64), 0, (hipStream_t)stream, a);
+        return mpb_check_launch("mpb_prm_edge_check");
+    });
 }
 
 extern "C" int mpb_prm_query(const float* nodes, const int* nbr, const float* w, const float* starts, const float* goals, const int* cs,
@@ -396,7 +346,7 @@ extern "C" int mpb_prm_query(const float* nodes, const int* nbr, const float* w,
     if (Q == 0) return MPB_OK;
     const PrmQueryArgs a = {nodes, nbr, w, starts, goals, cs, ws, cg, wg, direct, paths, lengths, costs, status, M, K, Kc, D, Lmax};
     const size_t lds = 2 * (size_t)M * sizeof(unsigned);
-    const int rl = prm_lds_limit(prm_query_kernel, lds, "mpb_prm_query");
+    const int rl = mpb_raise_lds_limit(prm_query_kernel, lds, "mpb_prm_query");
     if (rl) return rl;
     hipLaunchKernelGGL(prm_query_kernel, dim3(Q), dim3(PRM_QUERY_THREADS), lds, (hipStream_t)stream, a);
     return mpb_check_launch("mpb_prm_query");

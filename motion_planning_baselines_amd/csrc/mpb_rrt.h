@@ -1,9 +1,15 @@
-// mpb_rrt.h -- the pieces the sample-based planner kernels share (mpb_rrt_connect.hip, mpb_rrt_star.hip): the collision
-// cost of one configuration per lane, torch.allclose, extend_path's linspace point (utils.py:4-14), safe_path's scan for
-// the first point in collision (utils.py:17-30), purge_duplicates_from_traj (utils.py:33-50) and the order-preserving
-// deletion of a pool entry (rrt_base.py:59-63), and what the two init kernels have in common.  Every function is
-// block-uniform: all 64 lanes of the single-wave workgroup call it.  The workspace in numbers (status values, header word
-// indices, the pool limit MPB_RRT_MAX_PRE_SAMPLES) is include/mpb_rrt_layout.h, generated from rrt_layout.py.
+// mpb_rrt.h -- the pieces the sample-based planner kernels share (mpb_rrt_connect.hip, mpb_rrt_star.hip, mpb_strrt.hip,
+// mpb_prm.hip, mpb_path_shortcut.hip; mpb_traj_validate.hip takes the predicate): the collision cost of one configuration
+// per lane, the row loads, the two distances, torch.allclose's element, extend_path's point count and linspace point
+// (utils.py:4-14), safe_path's scan for the first point in collision (utils.py:17-30), purge_duplicates_from_traj
+// (utils.py:33-50) and the order-preserving deletion of a pool entry (rrt_base.py:59-63), and what the init kernels have
+// in common.  Every function is block-uniform: all 64 lanes of the
+// single-wave workgroup call it.  The workspace in numbers (status values, header word indices, the pool limit
+// MPB_RRT_MAX_PRE_SAMPLES) is include/mpb_rrt_layout.h, generated from rrt_layout.py.
+// Arithmetic: every function below that rounds carries #pragma clang fp contract(off) in its body and says what the device
+// runs -- fmaf where one rounding is the definition, plain operators where every operation rounds; rrt_dist alone does
+// not, and says why.  (The pragma is per function body, never at file scope: the collision walk of mpb_geom.h is compiled
+// under the build's fast contraction.)
 #pragma once
 #include "../../include/mpb_rrt_layout.h"
 #include "mpb_common.h"
@@ -39,17 +45,80 @@ __device__ __forceinline__ float rrt_config_cost(const float* __restrict__ geom,
     return c;
 }
 
-// torch.allclose(a, b) element: |a - b| <= atol + rtol |b| with the defaults rtol 1e-5, atol 1e-8
-__device__ __forceinline__ bool rrt_close(float a, float b) { return fabsf(a - b) <= 1e-8f + 1e-5f * fabsf(b); }
+// a configuration row of D floats into registers, zeros past D
+template <int DM>
+__device__ __forceinline__ void rrt_load_row(const float* p, int D, float (&q)[MPB_MAX_DOF]) {
+#pragma unroll
+    for (int k = 0; k < MPB_MAX_DOF; ++k) q[k] = (k < DM && k < D) ? p[k] : 0.f;
+}
 
-// point p of  q1 + dl * linspace(0, 1, n_pts)  as ATen's CPU kernel evaluates the linspace (from the near end of each
-// half); lstep = 1 / (n_pts - 1)
+// a padded row (Dp floats, float4-aligned, zero padded) into registers
+template <int DM>
+__device__ __forceinline__ void rrt_load_row4(const float* row, int Dp, float (&q)[MPB_MAX_DOF]) {
+    const float4* r = reinterpret_cast<const float4*>(row);
+#pragma unroll
+    for (int kk = 0; kk < (DM + 3) / 4; ++kk) {
+        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (4 * kk < Dp) v = r[kk];
+        const float e[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+        for (int c = 0; c < 4; ++c)
+            if (4 * kk + c < MPB_MAX_DOF) q[4 * kk + c] = (4 * kk + c < DM) ? e[c] : 0.f;
+    }
+#pragma unroll
+    for (int k = (DM + 3) / 4 * 4; k < MPB_MAX_DOF; ++k) q[k] = 0.f;
+}
+
+// RRT*'s distance: the squares summed in index order, symmetric in its arguments ((a - b)^2 == (b - a)^2); a distance between
+// the same two bit patterns is the same number wherever it is computed.  The ONE expression of this file left under the
+// build's contraction (plain operators, no pragma), because no single form is what the device runs: the compile-time-D
+// instantiations of rrt_star_kernel take fma(df0, df0, fl(df1 df1)) and ONE fma per later term at every call, while in
+// rrt_star_kernel<0, 0> the calls disagree (the informed test's two distances take that form, the nearest-node scan takes
+// fl(df0 df0) and ONE fma per later term).  tests/test_gpu_sample_based_bits.py holds every instantiation to its bits.
+template <int DM>
+__device__ __forceinline__ float rrt_dist(const float (&x)[MPB_MAX_DOF], const float (&y)[MPB_MAX_DOF]) {
+    float d2 = 0.f;
+#pragma unroll
+    for (int k = 0; k < DM; ++k) {
+        const float df = x[k] - y[k];
+        d2 = d2 + df * df;
+    }
+    return sqrtf(d2);
+}
+
+// The roadmap's and the shortcut pass's squared distance: the same sum rounded after every operation (tests/*_checks.py dist32)
+template <int DM>
+__device__ __forceinline__ float rrt_d2_rounded(const float (&x)[MPB_MAX_DOF], const float (&y)[MPB_MAX_DOF]) {
+#pragma clang fp contract(off)
+    float d2 = 0.f;
+#pragma unroll
+    for (int k = 0; k < DM; ++k) {
+        const float df = x[k] - y[k];
+        d2 = d2 + df * df;
+    }
+    return d2;
+}
+
+// torch.allclose(a, b) element: |a - b| <= atol + rtol |b| with the defaults rtol 1e-5, atol 1e-8; the right side is ONE fma
+__device__ __forceinline__ bool rrt_close(float a, float b) {
+#pragma clang fp contract(off)
+    return fabsf(a - b) <= fmaf(1e-5f, fabsf(b), 1e-8f);
+}
+
+// extend_path's point count (utils.py:9-11), from the UNCLAMPED distance
+__device__ __forceinline__ int rrt_point_count(float dist, float step) {
+    return (int)fminf(dist / step, (float)(RRT_MAX_PTS - 2)) + 2;
+}
+
+// point p of  q1 + dl * linspace(0, 1, n_pts)  as ATen's CPU kernel walks the linspace (from the near end of each half),
+// lstep = 1 / (n_pts - 1), with one rounding where ATen has two: 1 - lstep * j and q1 + dl * al are ONE fma each
 template <int DM>
 __device__ __forceinline__ void rrt_linspace_point(const float (&q1)[MPB_MAX_DOF], const float (&dl)[MPB_MAX_DOF], int n_pts,
                                                    float lstep, int p, float (&q)[MPB_MAX_DOF]) {
-    const float al = (p < n_pts / 2) ? __fmul_rn(lstep, (float)p) : __fsub_rn(1.0f, __fmul_rn(lstep, (float)(n_pts - 1 - p)));
+#pragma clang fp contract(off)
+    const float al = (p < n_pts / 2) ? lstep * (float)p : fmaf(-lstep, (float)(n_pts - 1 - p), 1.0f);
 #pragma unroll
-    for (int k = 0; k < MPB_MAX_DOF; ++k) q[k] = (k < DM) ? __fadd_rn(q1[k], __fmul_rn(dl[k], al)) : 0.f;
+    for (int k = 0; k < MPB_MAX_DOF; ++k) q[k] = (k < DM) ? fmaf(dl[k], al, q1[k]) : 0.f;
 }
 
 // safe_path's scan: the index of the first of the n_pts points of an extension that is in collision, -1 when none is;
@@ -117,7 +186,7 @@ __device__ __forceinline__ int rrt_purge(float* path_b, int Lraw, int D, int lan
     return out;
 }
 
-// What the init kernels of both planners do alike, for problem b: the global words (block 0), the full pool list
+// What the init kernels of RRT-Connect and RRT* do alike, for problem b: the global words (block 0), the full pool list
 // 0 .. n_pre - 1 at `pool`, and the collision check of the start (lane 0) and the goal (every other lane).  Returns the
 // problem's first status word.
 template <int MODEL>
@@ -137,8 +206,7 @@ __device__ __forceinline__ int rrt_init_shared(int* __restrict__ ws, int magic, 
     }
     const float* row = (lane == 0 ? start : goal) + (size_t)b * D;
     float q[MPB_MAX_DOF];
-#pragma unroll
-    for (int k = 0; k < MPB_MAX_DOF; ++k) q[k] = (k < D) ? row[k] : 0.f;
+    rrt_load_row<MPB_MAX_DOF>(row, D, q);
     const float* staged = nullptr;
     const float c = rrt_config_cost<MODEL>(geom, gridw, otab, staged, q);
     const bool hit = __ballot(c > 0.f) != 0ull;

@@ -53,8 +53,7 @@ __global__ __launch_bounds__(256) void collision_check_kernel(const float* __res
     const int i = blockIdx.x * 256 + threadIdx.x;
     const float* row = q_in + (size_t)min(i, N - 1) * D;
     float q[MPB_MAX_DOF];
-#pragma unroll
-    for (int k = 0; k < MPB_MAX_DOF; ++k) q[k] = (k < D) ? row[k] : 0.f;
+    rrt_load_row<MPB_MAX_DOF>(row, D, q);
     const float* staged = nullptr;
     const float c = rrt_config_cost<MODEL>(geom, gridw, otab, staged, q);
     if (i < N) {
@@ -92,6 +91,31 @@ __global__ __launch_bounds__(64) void rrt_init_kernel(int* __restrict__ ws, cons
     }
 }
 
+// The squared distance of the padded tree row `row` to tq (node minus target, index order): RRT-Connect's nearest-node metric.
+// Left under the build's contraction like rrt_dist of mpb_rrt.h (plain operators, no pragma): the compile-time-D instantiations
+// of rrt_connect_kernel round the first product and take ONE fma per later term; rrt_connect_kernel<0, 0> fuses the first product
+// onto the rounded second, fma(df0, df0, fl(df1 df1)), and takes ONE fma per later term.
+template <int DM>
+__device__ __forceinline__ float rrtc_row_d2(const float* row, int Dp, const float (&tq)[MPB_MAX_DOF]) {
+    const float4* r = reinterpret_cast<const float4*>(row);
+    float d2 = 0.f;
+#pragma unroll
+    for (int kk = 0; kk < (DM + 3) / 4; ++kk) {
+        if (4 * kk < Dp) {
+            const float4 v = r[kk];
+            const float e[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                if (4 * kk + c < DM) {
+                    const float df = e[c] - tq[4 * kk + c];
+                    d2 = d2 + df * df;
+                }
+            }
+        }
+    }
+    return d2;
+}
+
 struct RrtArgs {
     int* ws;
     const float* geom;
@@ -109,11 +133,11 @@ struct RrtArgs {
 // ---- the persistent kernel ------------------------------------------------------------------------------------------
 template <int DT, int MODEL>
 __global__ __launch_bounds__(64) void rrt_connect_kernel(const RrtArgs a) {
+#pragma clang fp contract(off)
     __shared__ unsigned gridw[MPB_GRID_MAX_CELLS];
     __shared__ float4 otab[MPB_GRID_MAX_SPH + 1];
     __shared__ unsigned short pool[MPB_RRT_MAX_PRE_SAMPLES];
     constexpr int DM = DT ? DT : MPB_MAX_DOF;
-    constexpr int DM4 = (DM + 3) / 4;
     const int D = DT ? DT : a.D;
     const int b = blockIdx.x, lane = threadIdx.x;
     const RrtLayout L = rrt_layout(a.B, a.max_nodes, a.n_pre, D);
@@ -143,23 +167,7 @@ __global__ __launch_bounds__(64) void rrt_connect_kernel(const RrtArgs a) {
         float best = 3.0e38f;
         int bi = 0x7FFFFFFF;
         for (int i = lane; i < n; i += 64) {
-            const float4* r = reinterpret_cast<const float4*>(nd + (size_t)i * L.Dp);
-            float d2 = 0.f;
-#pragma unroll
-            for (int kk = 0; kk < DM4; ++kk) {
-                if (4 * kk < L.Dp) {
-                    const float4 v = r[kk];
-                    const float e[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-                    for (int c = 0; c < 4; ++c) {
-                        if (4 * kk + c < DM) {
-                            const float df = __fsub_rn(e[c], tq[4 * kk + c]);
-                            d2 = __fadd_rn(d2, __fmul_rn(df, df));
-                        }
-                    }
-                }
-            }
-            const float ds = sqrtf(d2);
+            const float ds = sqrtf(rrtc_row_d2<DM>(nd + (size_t)i * L.Dp, L.Dp, tq));
             if (ds < best) { best = ds; bi = i; }
         }
 #pragma unroll
@@ -174,13 +182,12 @@ __global__ __launch_bounds__(64) void rrt_connect_kernel(const RrtArgs a) {
 #pragma unroll
         for (int k = 0; k < MPB_MAX_DOF; ++k) {
             q1[k] = (k < DM && k < D) ? nd[(size_t)bi * L.Dp + k] : 0.f;
-            const float df = __fsub_rn(tq[k], q1[k]);
+            const float df = tq[k] - q1[k];
             // (utils.py:7-8: the far end clamped to n_radius; the point count below is from the UNCLAMPED distance)
-            const float q2 = (dist > a.radius) ? __fadd_rn(q1[k], __fmul_rn(df, f)) : tq[k];
-            dl[k] = __fsub_rn(q2, q1[k]);
+            const float q2 = (dist > a.radius) ? fmaf(df, f, q1[k]) : tq[k];
+            dl[k] = q2 - q1[k];
         }
-        const float cntf = fminf(dist / a.step, (float)(RRT_MAX_PTS - 2));
-        const int n_pts = (int)cntf + 2;
+        const int n_pts = rrt_point_count(dist, a.step);
         const float lstep = 1.0f / (float)(n_pts - 1);
         const int first = rrt_first_collision<DM, MODEL>(a.geom, gridw, otab, staged, q1, dl, n_pts, lstep, lane);
         if (first == 0) return false;
@@ -302,13 +309,10 @@ extern "C" int mpb_rrt_connect_run(void* workspace, size_t workspace_bytes, cons
     if (rc != MPB_OK || B == 0) return rc;
     const RrtArgs a = {(int*)workspace, geom, pre_samples, pre_stride, sample_idx, paths, lengths, status, B, D, max_nodes, n_pre, Lmax,
                        iter0, n_iters, total_iters, step_size, n_radius, (uint32_t)seed, (uint32_t)(seed >> 32), problem_offset};
-    const hipStream_t s = (hipStream_t)stream;
-    if (rrt_use_model(geom_flags, D)) hipLaunchKernelGGL((rrt_connect_kernel<7, PandaModel::ID>), dim3(B), dim3(64), 0, s, a);
-    else if (D == 2) hipLaunchKernelGGL((rrt_connect_kernel<2, 0>), dim3(B), dim3(64), 0, s, a);
-    else if (D == 3) hipLaunchKernelGGL((rrt_connect_kernel<3, 0>), dim3(B), dim3(64), 0, s, a);
-    else if (D == 7) hipLaunchKernelGGL((rrt_connect_kernel<7, 0>), dim3(B), dim3(64), 0, s, a);
-    else hipLaunchKernelGGL((rrt_connect_kernel<0, 0>), dim3(B), dim3(64), 0, s, a);
-    return mpb_check_launch("mpb_rrt_connect_run");
+    return rrt_dispatch<2, 3, 7>(geom_flags, D, [&](auto dt, auto model) {
+        hipLaunchKernelGGL((rrt_connect_kernel<dt.value, model.value>), dim3(B), dim3(64), 0, (hipStream_t)stream, a);
+        return mpb_check_launch("mpb_rrt_connect_run");
+    });
 }
 
 extern "C" int mpb_collision_check(const float* q, const float* geom, int geom_flags, unsigned char* in_collision, float* gap,

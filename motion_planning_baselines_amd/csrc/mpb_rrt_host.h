@@ -1,7 +1,10 @@
-// mpb_rrt_host.h -- the host side the launchers of the sample-based planners share (mpb_rrt_connect.hip, mpb_rrt_star.hip): the shape
-// check, the model predicate and the argument checks of *_init and *_run.  Every check reports under the entry point's name `who`; the
-// order of the checks is part of the ABI (a call wrong in two ways gets the earlier message).  No device code.
+// mpb_rrt_host.h -- the host side the launchers of the sample-based planners share (RRT-Connect, RRT*, STRRT, PRM, the shortcut pass, the
+// trajectory validation): the shape check, the model predicate, the <DT, MODEL> dispatch and the argument checks of *_init and *_run.
+// Every check reports under the entry point's name `who`; the order of the checks is part of the ABI (a call wrong in two ways gets the
+// earlier message).  No device code.
 #pragma once
+#include <type_traits>
+
 #include "mpb_host.h"
 #include "mpb_model_panda.h"
 
@@ -17,6 +20,17 @@ static int rrt_shape_check(const char* who, double words_per_node, int B, int ma
 
 // may a launcher pick the kernels instantiated for the compile-time Panda?
 static bool rrt_use_model(int geom_flags, int D) { return mpb_flags_model_on_grids(geom_flags, PandaModel::ID) && D == PandaModel::N_DOF; }
+
+// The <DT, MODEL> instantiation a launcher picks -- the compile-time Panda where rrt_use_model allows, else the D among DTS... a kernel is
+// instantiated for, else the run-time-D form <0, 0>: returns launch(DT, MODEL), both handed over as std::integral_constant values.
+template <int... DTS, class Launch>
+static int rrt_dispatch(int geom_flags, int D, Launch launch) {
+    using std::integral_constant;
+    if (rrt_use_model(geom_flags, D)) return launch(integral_constant<int, PandaModel::N_DOF>{}, integral_constant<int, PandaModel::ID>{});
+    int rc = MPB_OK;
+    if (((D == DTS && (rc = launch(integral_constant<int, DTS>{}, integral_constant<int, 0>{}), true)) || ...)) return rc;
+    return launch(integral_constant<int, 0>{}, integral_constant<int, 0>{});
+}
 
 // what every *_init checks, and every *_run first: the shapes, the pointers (any_null: one of the call's required pointers is null;
 // draws_unpaired: RRT*'s two recorded-draw arrays, one given without the other), the alignment, the workspace's size (need: the bytes

@@ -17,7 +17,7 @@
 //   - cost propagation: the reference keeps cost[i] == fl32(cost[parent[i]] + d[i]) at all times (root: 0); given parents
 //     and d that fixed point is unique, so relaxation sweeps over all nodes, repeated until a ballot reports no change
 //     (at most node-count sweeps), reproduce the reference's bits although parent < child no longer holds.
-// ONE distance routine (rrt_dist) serves nearest node, extension, neighbours, rewire, goal and informed tests: a distance
+// ONE distance routine (rrt_dist of mpb_rrt.h) serves nearest node, extension, neighbours, rewire, goal and informed tests: a distance
 // between the same two bit patterns is the same number wherever it is computed, which is what resolves the reference's
 // exact ties (new.cost + d == n.cost when the new node duplicates its parent) the way the reference does.
 #include "mpb_rrt.h"
@@ -45,39 +45,6 @@ __host__ __device__ static inline RrsLayout rrs_layout(int B, int max_nodes, int
     L.pool = L.cand + (size_t)B * 3 * max_nodes;
     L.total = L.pool + (size_t)B * L.pool_words;
     return L;
-}
-
-// a tree row (Dp floats, float4-aligned, zero padded) into registers
-template <int DM>
-__device__ __forceinline__ void rrs_load_row(const float* row, int Dp, float (&q)[MPB_MAX_DOF]) {
-    const float4* r = reinterpret_cast<const float4*>(row);
-#pragma unroll
-    for (int kk = 0; kk < (DM + 3) / 4; ++kk) {
-        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (4 * kk < Dp) v = r[kk];
-        const float e[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-        for (int c = 0; c < 4; ++c)
-            if (4 * kk + c < MPB_MAX_DOF) q[4 * kk + c] = (4 * kk + c < DM) ? e[c] : 0.f;
-    }
-#pragma unroll
-    for (int k = (DM + 3) / 4 * 4; k < MPB_MAX_DOF; ++k) q[k] = 0.f;
-}
-
-// THE distance: sequential sum over the coordinates in index order, symmetric in its arguments ((a - b)^2 == (b - a)^2)
-template <int DM>
-__device__ __forceinline__ float rrt_dist(const float (&x)[MPB_MAX_DOF], const float (&y)[MPB_MAX_DOF]) {
-    float d2 = 0.f;
-#pragma unroll
-    for (int k = 0; k < DM; ++k) {
-        const float df = __fsub_rn(x[k], y[k]);
-        d2 = __fadd_rn(d2, __fmul_rn(df, df));
-    }
-    return sqrtf(d2);
-}
-
-__device__ __forceinline__ int rrs_point_count(float dist, float step) {
-    return (int)fminf(dist / step, (float)(RRT_MAX_PTS - 2)) + 2;
 }
 
 // ---- workspace initialisation: root, goal, counters, pool list, start / goal collision check -------------------------
@@ -132,6 +99,7 @@ struct RrsArgs {
 // ---- the persistent kernel ------------------------------------------------------------------------------------------
 template <int DT, int MODEL>
 __global__ __launch_bounds__(64) void rrt_star_kernel(const RrsArgs a) {
+#pragma clang fp contract(off)
     __shared__ unsigned gridw[MPB_GRID_MAX_CELLS];
     __shared__ float4 otab[MPB_GRID_MAX_SPH + 1];
     __shared__ unsigned short pool[MPB_RRT_MAX_PRE_SAMPLES];
@@ -164,8 +132,8 @@ __global__ __launch_bounds__(64) void rrt_star_kernel(const RrsArgs a) {
     float* path_b = a.paths + (size_t)b * a.Lmax * D;
     const float* staged = nullptr;
     float sq[MPB_MAX_DOF], gq[MPB_MAX_DOF];
-    rrs_load_row<DM>(nodes_b, L.Dp, sq);
-    rrs_load_row<DM>(wf + L.goalq + (size_t)b * L.Dp, L.Dp, gq);
+    rrt_load_row4<DM>(nodes_b, L.Dp, sq);
+    rrt_load_row4<DM>(wf + L.goalq + (size_t)b * L.Dp, L.Dp, gq);
     __syncthreads();
 
     const int it_end = min(a.iter0 + a.n_iters, a.total_iters);
@@ -174,7 +142,7 @@ __global__ __launch_bounds__(64) void rrt_star_kernel(const RrsArgs a) {
         if (bci >= a.max_bci) { stop = MPB_RRT_STOP_COST_CONVERGED; ++it; break; }
         if (goal >= 0) {
             const float gc = cost_b[goal];
-            if (gc < __fsub_rn(best, a.cost_eps)) { best = gc; bci = 0; }
+            if (gc < best - a.cost_eps) { best = gc; bci = 0; }
             else ++bci;
             ++iafs;
         }
@@ -204,19 +172,20 @@ __global__ __launch_bounds__(64) void rrt_star_kernel(const RrsArgs a) {
         }
         // ---- :197-199: informed rejection (a goal node exists, so this was a sample draw)
         if (a.informed && goal >= 0) {
-            if (__fadd_rn(rrt_dist<DM>(sq, tq), rrt_dist<DM>(tq, gq)) >= cost_b[goal]) {
+            if (rrt_dist<DM>(sq, tq) + rrt_dist<DM>(tq, gq) >= cost_b[goal]) {
                 rrt_pool_delete(pool, idx, plen, lane);
                 --plen;
                 ++rejected;
                 continue;
             }
         }
-        // ---- :202: nearest node (the lowest index wins a tie, as torch.argmin does)
+        // ---- :202: nearest node (the lowest index wins a tie, as torch.argmin does).  (The other pieces of mpb_rrt.h are spelled out in
+        // this kernel: called here they cost SGPR spills in the run-time-D form or 1.5 % of the time -- DESIGN.md, the RRT open items.)
         float bestd = 3.0e38f;
         int bi = 0x7FFFFFFF;
         for (int i = lane; i < cnt; i += 64) {
             float r[MPB_MAX_DOF];
-            rrs_load_row<DM>(nodes_b + (size_t)i * L.Dp, L.Dp, r);
+            rrt_load_row4<DM>(nodes_b + (size_t)i * L.Dp, L.Dp, r);
             const float ds = rrt_dist<DM>(r, tq);
             if (ds < bestd) { bestd = ds; bi = i; }
         }
@@ -229,16 +198,16 @@ __global__ __launch_bounds__(64) void rrt_star_kernel(const RrsArgs a) {
         // ---- :205-208: extend_path (the far end clamped to n_radius, the point count from the UNCLAMPED distance), safe_path
         const float dist = bestd;
         float q1[MPB_MAX_DOF], dl[MPB_MAX_DOF], nq[MPB_MAX_DOF];
-        rrs_load_row<DM>(nodes_b + (size_t)bi * L.Dp, L.Dp, q1);
+        rrt_load_row4<DM>(nodes_b + (size_t)bi * L.Dp, L.Dp, q1);
         // (max_dist / dist with a Python float on the left is Tensor.__rtruediv__: dist.reciprocal() * max_dist, two roundings)
-        const float f = (dist > a.radius) ? __fmul_rn(__fdiv_rn(1.0f, dist), a.radius) : 1.0f;
+        const float f = (dist > a.radius) ? (1.0f / dist) * a.radius : 1.0f;
 #pragma unroll
         for (int k = 0; k < MPB_MAX_DOF; ++k) {
-            const float df = __fsub_rn(tq[k], q1[k]);
-            const float q2 = (dist > a.radius) ? __fadd_rn(q1[k], __fmul_rn(df, f)) : tq[k];
-            dl[k] = __fsub_rn(q2, q1[k]);
+            const float df = tq[k] - q1[k];
+            const float q2 = (dist > a.radius) ? fmaf(df, f, q1[k]) : tq[k];
+            dl[k] = q2 - q1[k];
         }
-        const int n_pts = rrs_point_count(dist, a.step);
+        const int n_pts = rrt_point_count(dist, a.step);
         const float lstep = 1.0f / (float)(n_pts - 1);
         const int first = rrt_first_collision<DM, MODEL>(a.geom, gridw, otab, staged, q1, dl, n_pts, lstep, lane);
         if (first == 0) continue;
@@ -258,7 +227,7 @@ __global__ __launch_bounds__(64) void rrt_star_kernel(const RrsArgs a) {
         const int n = cnt;
         if (n >= a.max_nodes) { status = MPB_RRT_TREE_FULL; break; }
         const float dn = rrt_dist<DM>(q1, nq);
-        const float cn = __fadd_rn(cost_b[bi], dn);
+        const float cn = cost_b[bi] + dn;
         {
             float v = 0.f;
 #pragma unroll
@@ -279,9 +248,9 @@ __global__ __launch_bounds__(64) void rrt_star_kernel(const RrsArgs a) {
         for (int base = 0; base < cnt; base += 64) {
             const int i = base + lane;
             float r[MPB_MAX_DOF];
-            rrs_load_row<DM>(nodes_b + (size_t)min(i, cnt - 1) * L.Dp, L.Dp, r);
+            rrt_load_row4<DM>(nodes_b + (size_t)min(i, cnt - 1) * L.Dp, L.Dp, r);
             const float di = rrt_dist<DM>(r, nq);
-            const bool c = i < cnt && di < a.radius && __fadd_rn(cn, di) < cost_b[min(i, cnt - 1)];
+            const bool c = i < cnt && di < a.radius && cn + di < cost_b[min(i, cnt - 1)];
             const unsigned long long m = __ballot(c);
             if (c) {
                 const int pos = ncand + __popcll(m & ((1ull << lane) - 1ull));
@@ -298,7 +267,7 @@ __global__ __launch_bounds__(64) void rrt_star_kernel(const RrsArgs a) {
             const bool cv = c < ncand;
             const int ci = cand_i[min(c, ncand - 1)];
             const float cd = cand_d[min(c, ncand - 1)];
-            const int np = cv ? rrs_point_count(cd, a.step) : 0;
+            const int np = cv ? rrt_point_count(cd, a.step) : 0;
             int inc = np;
 #pragma unroll
             for (int off = 1; off < 64; off <<= 1) {
@@ -318,10 +287,10 @@ __global__ __launch_bounds__(64) void rrt_star_kernel(const RrsArgs a) {
                 const int p = fl - s_excl[j];
                 const int cj = min(cb + j, ncand - 1);
                 float tj[MPB_MAX_DOF], dj[MPB_MAX_DOF], q[MPB_MAX_DOF];
-                rrs_load_row<DM>(nodes_b + (size_t)cand_i[cj] * L.Dp, L.Dp, tj);
+                rrt_load_row4<DM>(nodes_b + (size_t)cand_i[cj] * L.Dp, L.Dp, tj);
 #pragma unroll
-                for (int k = 0; k < MPB_MAX_DOF; ++k) dj[k] = __fsub_rn(tj[k], nq[k]);
-                const int npj = rrs_point_count(cand_d[cj], a.step);
+                for (int k = 0; k < MPB_MAX_DOF; ++k) dj[k] = tj[k] - nq[k];
+                const int npj = rrt_point_count(cand_d[cj], a.step);
                 rrt_linspace_point<DM>(nq, dj, npj, 1.0f / (float)(npj - 1), min(p, npj - 1), q);
                 const float cc = rrt_config_cost<MODEL>(a.geom, gridw, otab, staged, q);
                 if (fb + lane < total && cc > 0.f) atomicMin(&s_first[j], p);
@@ -332,9 +301,9 @@ __global__ __launch_bounds__(64) void rrt_star_kernel(const RrsArgs a) {
             bool ok = false;
             if (cv && fc != 0) {
                 float tj[MPB_MAX_DOF], dj[MPB_MAX_DOF], q[MPB_MAX_DOF];
-                rrs_load_row<DM>(nodes_b + (size_t)ci * L.Dp, L.Dp, tj);
+                rrt_load_row4<DM>(nodes_b + (size_t)ci * L.Dp, L.Dp, tj);
 #pragma unroll
-                for (int k = 0; k < MPB_MAX_DOF; ++k) dj[k] = __fsub_rn(tj[k], nq[k]);
+                for (int k = 0; k < MPB_MAX_DOF; ++k) dj[k] = tj[k] - nq[k];
                 rrt_linspace_point<DM>(nq, dj, np, 1.0f / (float)(np - 1), fc == 0x7FFFFFFF ? np - 1 : fc - 1, q);
                 ok = rrt_dist<DM>(tj, q) < a.eps;
             }
@@ -346,7 +315,7 @@ __global__ __launch_bounds__(64) void rrt_star_kernel(const RrsArgs a) {
             if (cand_ok[c] == 0) continue;
             const int ci = cand_i[c];
             const float cd = cand_d[c];
-            if (!(__fadd_rn(cn, cd) < cost_b[ci])) continue;
+            if (!(cn + cd < cost_b[ci])) continue;
             __syncthreads();
             if (lane == 0) { parents_b[ci] = n; d_b[ci] = cd; }
             ++rewires;
@@ -356,7 +325,7 @@ __global__ __launch_bounds__(64) void rrt_star_kernel(const RrsArgs a) {
                 for (int base = 1; base < cnt; base += 64) {
                     const int i = base + lane;
                     if (i < cnt) {
-                        const float want = __fadd_rn(cost_b[parents_b[i]], d_b[i]);
+                        const float want = cost_b[parents_b[i]] + d_b[i];
                         if (want != cost_b[i]) { cost_b[i] = want; changed = true; }
                     }
                     __syncthreads();
@@ -427,10 +396,8 @@ extern "C" int mpb_rrt_star_run(void* workspace, size_t workspace_bytes, const f
     const RrsArgs a = {(int*)workspace, geom, pre_samples, pre_stride, sample_idx, goal_draw, paths, lengths, costs, status,
                        B, D, max_nodes, n_pre, Lmax, iter0, n_iters, total_iters, max_best_cost_iters, n_iters_after_success,
                        informed, step_size, n_radius, goal_prob, cost_eps, eps, (uint32_t)seed, (uint32_t)(seed >> 32), problem_offset};
-    const hipStream_t s = (hipStream_t)stream;
-    if (rrt_use_model(geom_flags, D)) hipLaunchKernelGGL((rrt_star_kernel<7, PandaModel::ID>), dim3(B), dim3(64), 0, s, a);
-    else if (D == 2) hipLaunchKernelGGL((rrt_star_kernel<2, 0>), dim3(B), dim3(64), 0, s, a);
-    else if (D == 7) hipLaunchKernelGGL((rrt_star_kernel<7, 0>), dim3(B), dim3(64), 0, s, a);
-    else hipLaunchKernelGGL((rrt_star_kernel<0, 0>), dim3(B), dim3(64), 0, s, a);
-    return mpb_check_launch("mpb_rrt_star_run");
+    return rrt_dispatch<2, 7>(geom_flags, D, [&](auto dt, auto model) {      // (no form of its own for D = 3)
+        hipLaunchKernelGGL((rrt_star_kernel<dt.value, model.value>), dim3(B), dim3(64), 0, (hipStream_t)stream, a);
+        return mpb_check_launch("mpb_rrt_star_run");
+    });
 }

@@ -162,7 +162,7 @@ def unit(u):
 
 
 def close(x, y):
-    """torch.allclose(x, y) with the defaults, in fp32, as rrt_close is compiled (atol + rtol |y| is one fma)"""
+    """torch.allclose(x, y) with the defaults, in fp32, as rrt_close states it (atol + rtol |y| is one fmaf)"""
     return bool(np.all(np.abs(x - y) <= fma32(f32(1e-5), np.abs(y), f32(1e-8))))
 
 
@@ -199,14 +199,14 @@ def point(path, a, t):
 
 
 def fma32(a, b, c):
-    """fl32(a * b + c) of float32 arrays: the product of two float32 is exact in float64 (the sum is rounded twice, to 53 bits and
+    """fmaf of csrc/mpb_rrt.h (rrt_close, rrt_linspace_point): fl32(a * b + c) of float32 arrays.  The product of two float32 is exact in float64 (the sum is rounded twice, to 53 bits and
     to 24: it differs from the fused result only where the first rounding lands on a tie of the second)"""
     return (np.asarray(a, np.float64) * np.asarray(b, np.float64) + np.asarray(c, np.float64)).astype(f32)
 
 
 def dense_points(p1, p2, n_pts):
-    """extend_path's linspace (from the near end of each half) as rrt_linspace_point is compiled: 1 - lstep * j and q1 + dl * al are
-    one fma each (csrc/mpb_rrt.h's __f*_rn intrinsics are plain operators to hipcc, which contracts them).  The points are data to
+    """extend_path's linspace (from the near end of each half) as rrt_linspace_point of csrc/mpb_rrt.h states it: 1 - lstep * j and
+    q1 + dl * al are one fmaf each, the rest plain operators under #pragma clang fp contract(off).  The points are data to
     both restatements; a decision that fp64 can decide does not depend on their last bit."""
     dl = p2 - p1
     lstep = f32(1.0) / f32(n_pts - 1)

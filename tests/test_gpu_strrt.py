@@ -9,7 +9,7 @@ import strrt_checks as S
 
 pytestmark = pytest.mark.gpu
 CAP = 0.02                 # undecidable decisions among those audited: the shortcutter's cap
-REPLAY = ('gate', 'parity', 'gate129', 'panda_16_1', 'panda_16_8', 'panda_16_80', 'panda_65_1', 'panda_65_8', 'panda_65_80', 'panda_130_200', 'pandaslow_130_200', 'arm12')
+REPLAY = ('gate', 'parity', 'gate129', 'panda_16_1', 'panda_16_8', 'panda_16_80', 'panda_65_1', 'panda_65_8', 'panda_65_80', 'panda_130_200', 'pandaslow_130_200', 'arm12', 'pm3d', 'panda_16_8:generic')
 
 
 def _task(p, dev, fields=None):
@@ -44,9 +44,14 @@ def test_kernel_equals_restatement_following_its_log(gpu_device, name):
     """The restatement fed the kernel's collision outcomes reproduces trees (q, row, parent), counts, statuses, vertex lists, trajectories
     and the log itself bit for bit; every decidable logged decision equals fp64's; undecidable ones stay under the cap.  On the gate
     scenes, whose decisions are far from any surface, the kernel also equals the free-running fp32 restatement; every problem of gate
-    and of gate129 (R = 129: more than one trip of rows in a join) is FOUND."""
+    and of gate129 (R = 129: more than one trip of rows in a join) is FOUND.  `:generic`: the Panda packed without its compile-time model."""
+    name, _, form = name.partition(':')
     p = S.problem(name)
-    planner = _planner(p, gpu_device)
+    task = _task(p, gpu_device)
+    if form == 'generic':
+        from motion_planning_baselines_amd import ops
+        task.geom = ops.DeviceGeometry(p.robot, p.fields if len(p.fields) > 1 else p.fields[0], gpu_device, use_model=False)
+    planner = _planner(p, gpu_device, task=task)
     got = _arrays(planner, planner.optimize_batched(with_log=True))
     want, seen = S.follow(p, got['log'], got['status'], audit=True)
     S.same_bits(got, want, name)

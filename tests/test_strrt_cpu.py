@@ -8,7 +8,7 @@ import torch
 
 import strrt_checks as S
 
-SCENES = ('gate', 'parity', 'gate129', 'panda_16_8', 'panda_65_80', 'pandaslow_130_200', 'arm12')
+SCENES = ('gate', 'parity', 'gate129', 'panda_16_8', 'panda_65_80', 'pandaslow_130_200', 'arm12', 'pm3d')
 # VGPRs / SGPRs / scratch of the three moving-obstacle kernels as the parent commit's build recorded them: moving their device code into
 # csrc/mpb_moving.h is a pure move
 MOVING_PARENT = {'_Z18moving_cost_kernelILb0EEvPKfS1_PfS2_S2_iiiffiiiii': (106, 106, 0), '_Z18moving_cost_kernelILb1EEvPKfS1_PfS2_S2_iiiffiiiii': (226, 106, 0),
