@@ -44,6 +44,8 @@
 /* the workspace and decision log of the space-time RRT-Connect in numbers (generated from strrt_layout.py): statuses MPB_STRRT_*, global
  * word indices MPB_STG_*, header word indices MPB_STH_*, log record words MPB_STL_* */
 #include "mpb_strrt_layout.h"
+/* path timing among moving obstacles in numbers (generated from path_timing_layout.py): statuses and limits MPB_PT_*, the LDS of a launch */
+#include "mpb_path_timing_layout.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -83,7 +85,8 @@ extern "C" {
  *                        meshes (mpb_mesh_check, mpb_sdf_grid_build_mesh), path shortcutting and the roadmap planner, and
  *                        the time parameterisation under joint limits (mpb_traj_retime, mpb_traj_retime_sample), and Cartesian
  *                        end-effector moves (mpb_cartesian_path), and the moving-obstacle field (mpb_moving_check,
- *                        mpb_moving_invalidate, mpb_moving_collision_eval / _grad / _check). */
+ *                        mpb_moving_invalidate, mpb_moving_collision_eval / _grad / _check), and the timing of geometric paths among
+ *                        moving obstacles (mpb_path_time_plan): additive. */
 #define MPB_ABI_VERSION 7
 #define MPB_VERSION_TUNING_BUILD 0x40000000
 int mpb_version(void);
@@ -1069,6 +1072,47 @@ int mpb_strrt_run(void *workspace, size_t workspace_bytes, const float *geom, in
                   float *vertex_q, int *vertex_row, int *n_vertices, int *status, int *log, int B, int max_nodes, int n_pre, int D,
                   int n_rows, int Lmax, int max_step_rows, int iter0, int n_iters, int total_iters, uint64_t seed,
                   uint32_t problem_offset, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Timing of geometric paths among moving obstacles: path-velocity decomposition (build-defined, DESIGN.md 10: the reference has
+ * nothing like it).  N paths of S samples each keep their shape; each gets the rows of the clock at which to stand on which sample --
+ * advancing or waiting, never going back -- so that every row is free at its own time.  One workgroup per path, no workspace.
+ *
+ * paths (N, S, D) fp32: sample 0 the start, sample S - 1 the goal; MPB_PT_MIN_SAMPLES <= S <= MPB_PT_MAX_SAMPLES.  The clock is the row
+ *   grid of `moving` (mpb_moving_layout.h) packed for n_rows = R rows, MPB_PT_MIN_ROWS <= R <= MPB_PT_MAX_ROWS: the clock of
+ *   mpb_strrt_run and mpb_moving_collision_check.  w (D): the most joint k may move per row, fp32(dq_max_k * dt_row), finite and positive.
+ *   blocked: NULL or (N, S) bytes, nonzero = the sample is refused by a static predicate of the caller's.
+ * 1 segment cost   c_i = max over k of fl(fl(|fl(P[i+1,k] - P[i,k])|) / w_k), starting from 0, every operation rounded, none contracted
+ *                  (the tau of mpb_strrt_run); cfix_i = (uint32) ceilf(c_i * MPB_PT_COST_ONE).  A term above 1 or not finite:
+ *                  MPB_PT_SEGMENT_TOO_LONG -- no single row can cross that segment, resample the path more densely.
+ * 2 prefix sums    C_i = sum of cfix_m over m < i, in integers (at most 255 * MPB_PT_COST_ONE).
+ * 3 advance rule   in one row from sample i to sample i' >= i iff C_i' - C_i <= MPB_PT_COST_ONE (waiting: i' = i).  The sum of the
+ *                  per-segment maxima bounds every joint's travel along the polyline, so a row step moves joint k by at most w_k up to
+ *                  fp32 rounding: the plan definition of mpb_strrt_run.  lo_i' = the smallest i the rule admits.
+ * 4 free table     F[j][i] = !blocked[i] && !(the predicate of mpb_moving_collision_check for P[i] at row j), the buffer's centres of
+ *                  row j; nothing is interpolated between rows.
+ * 5 reachability   reach[0][i] = (i == 0) && F[0][0];  reach[j][i'] = F[j][i'] && OR over i in [lo_i', i'] of reach[j-1][i].
+ * 6 arrival        hold[j] = F[j'][S-1] for every j' >= j; the arrival row j* = the least j with reach[j][S-1] && hold[j].
+ * 7 backtrack      idx[j*] = S - 1; for j = j* .. 1: idx[j-1] = the largest i in [lo_idx[j], idx[j]] with reach[j-1][i]; idx[j] = S - 1
+ *                  for j > j* (held at the goal).
+ * 8 output         trajs (N, R, D): row j = P[idx[j]], the sample's own bits; all zero where no timing was found.
+ * 9 status (N)     MPB_PT_FOUND, or the first that applies of MPB_PT_BUFFER_CHANGED (the header of `moving` differs from what the
+ *                  launcher read -- through the cache mpb_moving_invalidate serves --: nothing of it is trusted, the table reads all
+ *                  zero), MPB_PT_SEGMENT_TOO_LONG, MPB_PT_START_BLOCKED (!F[0][0]), MPB_PT_GOAL_NOT_HOLDABLE (!F[R-1][S-1]), MPB_PT_NO_TIMING.
+ * Exact on this lattice: MPB_PT_FOUND arrives at the earliest row any monotone timing under the advance rule can; MPB_PT_NO_TIMING
+ * means none exists on it.  No random draws; every run gives the same bits.
+ * Optional outputs (NULL: not written): idx (N, R) int32, -1 where no timing was found; arrival_row (N) int32, -1 likewise; free_table
+ *   (N, R, S) bytes, F as above (with MPB_PT_SEGMENT_TOO_LONG the table is evaluated only when it is asked for).
+ * Not built: backward motion along the path, obstacle interpolation between rows, acceleration limits, arrival trade-offs other than
+ *   the earliest row.
+ * Refusals: D > MPB_MAX_DOF, S > MPB_PT_MAX_SAMPLES, n_rows > MPB_PT_MAX_ROWS, shapes beyond 2e9 elements: MPB_E_UNSUPPORTED; S or n_rows
+ *   below their minimum, bad shapes, (N > 0:) a null required pointer, a moving buffer not 16-byte aligned: MPB_E_INVALID; the buffer's
+ *   header: n_rows and n_dof must equal the call's, the message names both numbers; an LDS need -- MPB_PT_LDS_WORDS of the robot's
+ *   collision spheres, S and n_rows, in 32-bit words -- above MPB_PT_MAX_LDS_BYTES: MPB_E_UNSUPPORTED, by that name.
+ * ------------------------------------------------------------------------------------------- */
+int mpb_path_time_plan(const float *paths, const float *moving, const float *w, const unsigned char *blocked, float *trajs,
+                       int *idx, int *arrival_row, int *status, unsigned char *free_table, int N, int S, int D, int n_rows,
+                       void *stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Batched RRT* and informed RRT* -- replaces RRTStar._run_optimization (rrt_star.py:133-261) with OptimalNode's cost

@@ -12,7 +12,7 @@ import warnings
 import numpy as np
 import torch
 
-from . import _lib, rrt_layout, strrt_layout
+from . import _lib, path_timing_layout, rrt_layout, strrt_layout
 from .geometry import KIND_CHAIN, MAX_FIELDS, CollisionField, TriangleMesh, count_fields, mesh_pose, occupancy_bytes, pack_geometry, pack_mesh, pack_moving_obstacles, pack_sdf_grid, pack_self_collision
 from .geometry import header as geometry_header
 
@@ -1841,6 +1841,53 @@ def strrt_trees(ws):
         out[name] = hdr[:, i:i + n] if n > 1 else hdr[:, i]
     out['nodes'] = out['nodes'][..., :ws.D]
     return out
+
+
+# ---- timing of geometric paths among moving obstacles (csrc/mpb_path_timing.hip; numbers: path_timing_layout.py) ----------------------
+PT_STATUS_NAMES = path_timing_layout.STATUS
+PT_FOUND, PT_START_BLOCKED, PT_GOAL_NOT_HOLDABLE, PT_SEGMENT_TOO_LONG, PT_NO_TIMING, PT_BUFFER_CHANGED = range(len(PT_STATUS_NAMES))
+PathTiming = collections.namedtuple('PathTiming', 'trajs found status arrival_row idx free_table')
+
+
+@_on_tensor_device
+def path_time_plan(paths, mo, w, blocked=None, with_table=False):
+    """paths (N, S, D) fp32 -- sample 0 the start, sample S - 1 the goal -- timed on the row grid of a DeviceMovingObstacles `mo`
+    (mpb_path_time_plan; include/mpb.h has the definition): at which row to stand on which sample, advancing or waiting, so that every
+    row is free at its own time.  w (D,) fp32: the most a joint may move per row.  blocked: None or (N, S) bool / uint8, True = the sample
+    is refused by a static predicate of the caller's.  Returns a PathTiming: trajs (N, n_rows, D) (zero where no timing was found), found
+    (N,) bool, status (N,) int32 (PT_*), arrival_row (N,) int32 and idx (N, n_rows) int32 (-1 where none was found), free_table
+    (N, n_rows, S) bool with with_table, else None."""
+    if not isinstance(mo, DeviceMovingObstacles):
+        raise TypeError('path_time_plan takes a DeviceMovingObstacles')
+    if paths.dim() != 3:
+        raise ValueError(f'paths has shape {tuple(paths.shape)}, expected (N, S, D)')
+    N, S, D = paths.shape
+    _chk(paths, (N, S, D), 'paths')
+    R = mo.n_rows
+    if D != mo.n_dof:
+        raise ValueError(f'paths has D = {D} columns, the moving-obstacle buffer\'s robot {mo.n_dof} degrees of freedom')
+    L = path_timing_layout
+    if not L.PT_MIN_SAMPLES <= S <= L.PT_MAX_SAMPLES:
+        raise ValueError(f'n_samples = {S} outside {L.PT_MIN_SAMPLES} .. PT_MAX_SAMPLES = {L.PT_MAX_SAMPLES}')
+    if not L.PT_MIN_ROWS <= R <= L.PT_MAX_ROWS:
+        raise ValueError(f'n_rows = {R} outside {L.PT_MIN_ROWS} .. PT_MAX_ROWS = {L.PT_MAX_ROWS}')
+    need = L.lds_bytes(mo.n_links, S, R)
+    if need > L.PT_MAX_LDS_BYTES:
+        raise ValueError(f'{mo.n_links} collision spheres x {S} samples over {R} rows need {need} bytes of LDS, above PT_MAX_LDS_BYTES = '
+                         f'{L.PT_MAX_LDS_BYTES}: fewer samples or a robot with fewer spheres')
+    _chk(w, (D,), 'w')
+    if blocked is not None:
+        if blocked.dtype not in (torch.bool, torch.uint8):
+            raise ValueError(f'blocked must be bool or uint8 (got {blocked.dtype})')
+        _chk(blocked, (N, S), 'blocked', dtype=blocked.dtype)
+    dev = paths.device
+    trajs = torch.empty(N, R, D, device=dev, dtype=torch.float32)
+    idx = torch.empty(N, R, device=dev, dtype=torch.int32)
+    arrival, status = torch.empty(N, device=dev, dtype=torch.int32), torch.empty(N, device=dev, dtype=torch.int32)
+    table = torch.empty(N, R, S, device=dev, dtype=torch.bool) if with_table else None
+    _lib.check(_lib.lib().mpb_path_time_plan(_ptr(paths), _ptr(mo.buf), _ptr(w), _ptr(blocked), _ptr(trajs), _ptr(idx), _ptr(arrival),
+                                             _ptr(status), _ptr(table), N, S, D, R, _stream()), 'mpb_path_time_plan')
+    return PathTiming(trajs, status == PT_FOUND, status, arrival, idx, table)
 
 
 # ---- path shortcutting between the tree and the optimiser (csrc/mpb_path_shortcut.hip) ---------------------------------------------

@@ -7,6 +7,7 @@ package's geometry; forward kinematics and the field cost are HIP kernels (csrc/
 differentiates through them by their hand-written vector-Jacobian products.  The planners of this package do NOT go
 through these objects: they use the fused evaluators.
 """
+import numpy as np
 import torch
 
 from . import ops
@@ -239,14 +240,63 @@ class PlanningTask:
             raise ValueError(f'trajs has shape {tuple(t.shape)}, expected (..., H, W) with W >= {self.q_dim}')
         lead, H = tuple(t.shape[:-2]), t.shape[-2]
         t = t.reshape(-1, H, t.shape[-1]).contiguous()
-        cache = self.__dict__.setdefault('_moving_geoms', {})
-        key = (id(moving_field), H)
-        if key not in cache or cache[key].field is not moving_field:
-            cache[key] = ops.DeviceMovingObstacles(self.robot, moving_field, self.device, H)
+        mo = self._moving_geom(moving_field, H)
         rows = self._in_collision(t[..., :self.q_dim].reshape(-1, self.q_dim).contiguous()).reshape(t.shape[0], H).contiguous()
         if t.shape[0]:
-            ops.moving_collision_check(t, cache[key], flag=rows)
+            ops.moving_collision_check(t, mo, flag=rows)
         return rows.any(-1).reshape(lead), rows.reshape(*lead, H)
+
+    def _moving_geom(self, moving_field, n_rows):
+        """The packed buffer of (moving_field, n_rows), one per pair kept on the task (check_trajs_moving, time_paths_moving)."""
+        cache = self.__dict__.setdefault('_moving_geoms', {})
+        key = (id(moving_field), int(n_rows))
+        if key not in cache or cache[key].field is not moving_field:
+            cache[key] = ops.DeviceMovingObstacles(self.robot, moving_field, self.device, int(n_rows))
+        return cache[key]
+
+    # ---- timing of geometric paths among moving obstacles (build-defined: DESIGN.md 10) ------------------------------------------------
+    def time_paths_moving(self, paths, moving_field, n_rows, lengths=None, n_samples=None, dq_max=None):
+        """Path-velocity decomposition: geometric paths -- from RRTConnect on this task or on field.at(t), shortcut_paths -- keep their
+        shape and get their timing among a geometry.MovingObstacleField on a clock of n_rows rows (ops.path_time_plan, which has the
+        definition): when to advance along the path and when to wait, so that every row is free at its own time.
+        paths (N, S, D) samples, sample 0 the start and sample S - 1 the goal; or, with lengths (N,) int32, padded polylines (N, Lmax, D)
+        that are first resampled uniformly in arc length to n_samples samples (ops.traj_resample, its position half).  A sample this
+        task's own predicate refuses (_in_collision: obstacles, self_field, sdf_field) is never stood on.  dq_max (D,) rad/s defaults to
+        the robot's; a row may move joint k by dq_max_k * (t_end - t_start) / (n_rows - 1).  Returns an ops.PathTiming; its trajs
+        (N, n_rows, D) are accepted by check_trajs_moving(trajs, moving_field) wherever found is set.  One packed buffer per
+        (field, n_rows) is kept on the task."""
+        from .geometry import MovingObstacleField
+        if not isinstance(moving_field, MovingObstacleField):
+            raise TypeError('time_paths_moving takes a geometry.MovingObstacleField')
+        if not moving_field.t_end > moving_field.t_start:
+            raise ValueError(f'time_paths_moving: the MovingObstacleField has t_end = {moving_field.t_end} <= t_start = {moving_field.t_start}: '
+                             f'a clock needs a positive span')
+        n_rows = int(n_rows)
+        if n_rows < 2:
+            raise ValueError(f'time_paths_moving: n_rows = {n_rows}, the clock needs at least 2 rows')
+        dq = getattr(self.robot, 'dq_max_np', None) if dq_max is None else dq_max
+        if dq is None:
+            raise ValueError('time_paths_moving: no dq_max given and the robot carries none')
+        dq = np.asarray(dq.detach().cpu().numpy() if isinstance(dq, torch.Tensor) else dq, np.float64).reshape(-1)
+        if dq.size != self.q_dim or not (np.isfinite(dq).all() and (dq > 0).all()):
+            raise ValueError(f'time_paths_moving: dq_max must hold {self.q_dim} finite positive entries')
+        dt_row = (float(moving_field.t_end) - float(moving_field.t_start)) / (n_rows - 1)
+        w = torch.from_numpy((dq * dt_row).astype(np.float32)).to(self.device)
+        p = torch.as_tensor(paths, dtype=torch.float32, device=self.device)
+        if p.dim() != 3 or p.shape[-1] != self.q_dim:
+            raise ValueError(f'paths has shape {tuple(p.shape)}, expected (N, S, D) with D = {self.q_dim}')
+        p = p.contiguous()
+        if lengths is not None:
+            if n_samples is None:
+                raise ValueError('time_paths_moving: lengths needs n_samples, the samples to resample every polyline to')
+            ln = torch.as_tensor(lengths, device=self.device).to(torch.int32).contiguous()
+            p = ops.traj_resample(p, ln, int(n_samples), 1.0)[..., :self.q_dim].contiguous() if p.shape[0] else p[:, :0]
+        elif n_samples is not None and int(n_samples) != p.shape[1]:
+            raise ValueError(f'time_paths_moving: n_samples = {n_samples} without lengths, and paths holds {p.shape[1]} samples')
+        N, S = p.shape[0], p.shape[1]
+        mo = self._moving_geom(moving_field, n_rows)
+        blocked = self._in_collision(p.reshape(-1, self.q_dim).contiguous()).reshape(N, S).contiguous()
+        return ops.path_time_plan(p, mo, w, blocked=blocked)
 
     def require_no_sdf_field(self, what):
         if self.sdf_field is not None:
