@@ -46,6 +46,9 @@
 #include "mpb_strrt_layout.h"
 /* path timing among moving obstacles in numbers (generated from path_timing_layout.py): statuses and limits MPB_PT_*, the LDS of a launch */
 #include "mpb_path_timing_layout.h"
+/* space-time shortcutting among moving obstacles in numbers (generated from st_shortcut_layout.py): statuses MPB_STS_*, log codes
+ * MPB_STS_LOG_*, the Philox tag, the input gate's limit, limits, the LDS of a launch */
+#include "mpb_st_shortcut_layout.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -86,7 +89,7 @@ extern "C" {
  *                        the time parameterisation under joint limits (mpb_traj_retime, mpb_traj_retime_sample), and Cartesian
  *                        end-effector moves (mpb_cartesian_path), and the moving-obstacle field (mpb_moving_check,
  *                        mpb_moving_invalidate, mpb_moving_collision_eval / _grad / _check), and the timing of geometric paths among
- *                        moving obstacles (mpb_path_time_plan): additive. */
+ *                        moving obstacles (mpb_path_time_plan), and space-time shortcutting (mpb_st_shortcut): additive. */
 #define MPB_ABI_VERSION 7
 #define MPB_VERSION_TUNING_BUILD 0x40000000
 int mpb_version(void);
@@ -1113,6 +1116,63 @@ int mpb_strrt_run(void *workspace, size_t workspace_bytes, const float *geom, in
 int mpb_path_time_plan(const float *paths, const float *moving, const float *w, const unsigned char *blocked, float *trajs,
                        int *idx, int *arrival_row, int *status, unsigned char *free_table, int N, int S, int D, int n_rows,
                        void *stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Space-time shortcutting: the pass between a planner on the moving-obstacle clock (mpb_strrt_run, mpb_path_time_plan) and the
+ * optimiser (build-defined, DESIGN.md 10: the reference has nothing like it).  N dense trajectories keep their row count -- and so their
+ * clock --; an iteration replaces the rows BETWEEN two rows by the constant-velocity straight piece, and keeps the replacement only when
+ * every new row is free at its own time and the piece respects the per-row velocity bound.  One single-wave workgroup per trajectory,
+ * the trajectory in LDS for the whole launch, no workspace.
+ *
+ * trajs_in (N, R, D) fp32, MPB_STS_MIN_ROWS <= R <= MPB_STS_MAX_ROWS, finite; trajs_out (N, R, D), may be trajs_in (in place).  geom: the
+ *   packed geometry of the static scene (chained fields allowed), geom_flags its mpb_geom_flags.  moving: a packed moving-obstacle buffer
+ *   for n_rows = R (mpb_moving_layout.h): row h is seen at the time of the buffer's row h.  w (D): the most joint k may move per row,
+ *   fp32(dq_max_k * dt_row) as mpb_strrt_run takes it, finite and positive.  valid: NULL or (N) bytes, 0 = pass the trajectory through.
+ *   draws: NULL or (N, n_iters, 2) int32 recorded rows.  max_span: 0 (no limit) or the most rows a piece may span.
+ * 1 predicate      of (q, row): the static cost of geom is positive (the predicate of mpb_collision_check) OR the moving cost of that
+ *                  row is (the predicate of mpb_moving_collision_check): the predicate of mpb_strrt_run, exactly.  Rows are checked at
+ *                  the rows only; obstacle positions are never interpolated.
+ * 2 input gate     per trajectory, before any iteration: all R rows by the predicate, then every step
+ *                  tau(q[h+1], q[h]) <= MPB_STS_GATE_LIMIT = 1 + 2^-16, tau(x, y) = max over k of fl(fl(|fl(x_k - y_k)|) / w_k) from 0
+ *                  (the tau of mpb_strrt_run).  The slack is derived: both producers keep every step within w (1 + 1e-5), tau's own three
+ *                  roundings add under 2e-7, 2^-16 = 1.53e-5 clears the sum.
+ * 3 status (N)     the first that applies of MPB_STS_NOT_VALID (valid[n] == 0), MPB_STS_BUFFER_CHANGED (the header of `moving` differs
+ *                  from what the launcher read -- through the cache mpb_moving_invalidate serves --: nothing of it is read),
+ *                  MPB_STS_INPUT_IN_COLLISION, MPB_STS_INPUT_TOO_FAST; else MPB_STS_OK.  first_bad (N): the first colliding row, or
+ *                  the row h + 1 of the first step h -> h + 1 above the limit; else -1.  Only MPB_STS_OK trajectories are edited: every
+ *                  other one comes out with its input bits.
+ * 4 draws          iteration `it` of trajectory n: ONE Philox4x32-10 call, counter (problem_offset + n, it, MPB_STS_PHILOX_TAG, 0),
+ *                  key = seed; r0 = mulhi(x, R), r1 = mulhi(y, R).  Recorded draws: the two ints clamped into 0 .. R - 1.
+ *                  a = min(r0, r1), b = max(r0, r1); with max_span > 0: b = min(b, a + max_span).
+ * 5 decisions      in this order: b - a < 2: MPB_STS_LOG_SKIP_SHORT.  tau(q_b, q_a) > (float)(b - a): MPB_STS_LOG_SKIP_FAST (the
+ *                  f == 1 condition of mpb_strrt_run's steering: the filled rows obey the rounding argument of its fill).  Candidate
+ *                  row h, a < h < b: fma(q_b - q_a, (float)(h - a) / (float)(b - a), q_a) -- the subtraction and the division rounded,
+ *                  ONE fused multiply-add: the dense-row expression of mpb_strrt_run, bit for bit; rows a and b keep their bits.  Every
+ *                  candidate row within |c - o| <= fma(1e-5, |o|, 1e-8) of the row o it would replace, in every coordinate:
+ *                  MPB_STS_LOG_SKIP_STRAIGHT, nothing is evaluated.  Rows a + 1 .. b - 1 by the predicate at their own rows, ascending: a
+ *                  hit is MPB_STS_LOG_REJECT | first colliding row << MPB_STS_LOG_INDEX_SHIFT.  Otherwise MPB_STS_LOG_ACCEPT: the
+ *                  candidate rows replace the old ones.  Rows 0 and R - 1 never change.
+ * 6 outputs        stats (N, 4) fp32: candidates checked (REJECT + ACCEPT), accepted, joint-space length before, after -- per-row
+ *                  distances, the squares summed in index order with every operation rounded, square-rooted and summed in row order --;
+ *                  NaN where the trajectory is not MPB_STS_OK.  log: NULL or (N, n_iters) int32, one word per iteration as above,
+ *                  MPB_STS_LOG_IDLE where the trajectory is not MPB_STS_OK.
+ * No atomics, a fixed order: the same bits on every run; a trajectory's bits depend on its own inputs only.
+ * Guarantee: an MPB_STS_OK output is free on every row by the predicate above; starts and ends on the input's bits; every step the pass
+ *   wrote is within w_k (1 + 1e-5) (a step of a piece is |q_b - q_a| / (b - a) <= w up to the roundings of tau, the division and the
+ *   fma); and its fp64 length is no longer than the input's up to rounding: a candidate row differs per coordinate from the exact chord
+ *   point by at most 6 * 2^-24 * M (the rounded difference and quotient, the fma's one rounding; M the largest |coordinate| of the input),
+ *   the exact chord is no longer than the rows it replaces, and a row moved by e lengthens its two steps by at most 2 e, so
+ *   len(out) <= len(in) + 2 W * 6 * 2^-24 * sqrt(D) * M with W the rows written, at most accepted * (R - 2).
+ * Not built: self_field / sdf_field members in the predicate, obstacle interpolation between rows, acceleration limits, changing the
+ *   arrival row, per-joint shortcutting, cost-aware acceptance.
+ * Refusals: D > MPB_MAX_DOF, n_rows > MPB_STS_MAX_ROWS, shapes beyond 2e9 elements: MPB_E_UNSUPPORTED; n_rows < MPB_STS_MIN_ROWS, bad
+ *   shapes, n_iters outside 0 .. MPB_STS_MAX_ITERS, max_span < 0, (N > 0:) a null required pointer, geom or moving not 16-byte aligned:
+ *   MPB_E_INVALID; the buffer's header: n_rows and n_dof must equal the call's, the message names both numbers; an LDS need --
+ *   MPB_STS_LDS_BYTES(n_rows, D) -- above MPB_STS_MAX_LDS_BYTES: MPB_E_UNSUPPORTED, by that name.
+ * ------------------------------------------------------------------------------------------- */
+int mpb_st_shortcut(const float *trajs_in, float *trajs_out, const float *geom, int geom_flags, const float *moving, const float *w,
+                    const unsigned char *valid, const int *draws, int *status, int *first_bad, float *stats, int *log, int N,
+                    int n_rows, int D, int n_iters, int max_span, uint64_t seed, uint32_t problem_offset, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Batched RRT* and informed RRT* -- replaces RRTStar._run_optimization (rrt_star.py:133-261) with OptimalNode's cost

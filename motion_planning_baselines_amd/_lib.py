@@ -99,6 +99,7 @@ SIGNATURES = {
     'mpb_strrt_init': [_p, ctypes.c_size_t] + [_p] * 4 + [_i, _p] + [_i] * 4 + [_p],
     'mpb_strrt_run': [_p, ctypes.c_size_t, _p, _i, _p, _p, _p, ctypes.c_size_t] + [_p] * 8 + [_i] * 10 + [_u64, _u32, _p],
     'mpb_path_time_plan': [_p] * 9 + [_i] * 4 + [_p],
+    'mpb_st_shortcut': [_p, _p, _p, _i] + [_p] * 8 + [_i] * 5 + [_u64, _u32, _p],
     'mpb_rrt_star_workspace_bytes': [_i, _i, _i, _i],
     'mpb_rrt_star_init': [_p, ctypes.c_size_t, _p, _p, _p, _i, _i, _i, _i, _i, _p],
     'mpb_rrt_star_run': [_p, ctypes.c_size_t, _p, _i, _p, ctypes.c_size_t] + [_p] * 6 + [_i] * 11 + [_f] * 5 + [_u64, _u32, _p],

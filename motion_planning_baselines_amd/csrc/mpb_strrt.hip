@@ -21,11 +21,13 @@
 //   on; FOUND therefore means every row of the output is free by this file's predicate, bit for bit.
 // Mapping: one single-wave workgroup per problem; workgroups never wait on each other, there is no spin wait, every loop is bounded by
 // n_iters, max_nodes, R or Lmax, and a finished problem returns at once.  The trees (configurations padded to float4s, int32 row, int32
-// parent) live in the caller's workspace (include/mpb_strrt_layout.h, generated from strrt_layout.py).
+// parent) live in the caller's workspace (include/mpb_strrt_layout.h, generated from strrt_layout.py).  The predicate strrt_collides, the
+// metric strrt_tau and the scene record StMoving are in mpb_strrt.h, shared with mpb_st_shortcut.hip.
 #include "mpb_common.h"
 #include "mpb_rrt.h"
 #include "mpb_rrt_host.h"
 #include "mpb_moving.h"
+#include "mpb_strrt.h"
 #include "../../include/mpb_strrt_layout.h"
 
 #define STRRT_WORDS_PER_NODE 32.0   // the size bound of the shape check: two trees, at most 12 + 2 words per node
@@ -44,33 +46,6 @@ __host__ __device__ static inline StLayout st_layout(int B, int max_nodes, int D
     L.parents = L.rows + (size_t)B * 2 * max_nodes;
     L.total = L.parents + (size_t)B * 2 * max_nodes;
     return L;
-}
-
-// the moving half of the scene as the launcher read it from the buffer's header
-struct StMoving {
-    const float* mob;
-    int L, n_sph, n_box;
-};
-
-// the predicate of (q, row), row < R: block-uniform (every lane of the workgroup calls it; a lane without work passes any valid pair)
-template <int MODEL>
-__device__ __forceinline__ bool strrt_collides(const float* __restrict__ geom, unsigned* gridw, float4* otab, const float*& staged,
-                                               const GeomView& G, const MovingTables& T, int L, bool ok, int row,
-                                               const float (&q)[MPB_MAX_DOF]) {
-    const float cs = rrt_config_cost<MODEL>(geom, gridw, otab, staged, q);
-    const bool hs = cs > 0.f;
-    float dq[MPB_MAX_DOF];
-    const float cm = moving_row_cost<false>(G, T, L, row, q, dq);
-    return !ok || hs || cm > 0.f;          // (a buffer whose header changed since the launcher read it: everything collides)
-}
-
-// tau of the definition between two configurations held in registers
-__device__ __forceinline__ float strrt_tau(const float (&qr)[MPB_MAX_DOF], const float (&qn)[MPB_MAX_DOF], const float (&w)[MPB_MAX_DOF]) {
-#pragma clang fp contract(off)
-    float tau = 0.f;
-#pragma unroll
-    for (int k = 0; k < MPB_MAX_DOF; ++k) tau = fmaxf(tau, fabsf(qr[k] - qn[k]) / w[k]);
-    return tau;
 }
 
 // ---- workspace initialisation: global words, roots, counts, status (start at row 0, goal at row R - 1, the horizon) ----------------------

@@ -12,7 +12,7 @@ import warnings
 import numpy as np
 import torch
 
-from . import _lib, path_timing_layout, rrt_layout, strrt_layout
+from . import _lib, path_timing_layout, rrt_layout, st_shortcut_layout, strrt_layout
 from .geometry import KIND_CHAIN, MAX_FIELDS, CollisionField, TriangleMesh, count_fields, mesh_pose, occupancy_bytes, pack_geometry, pack_mesh, pack_moving_obstacles, pack_sdf_grid, pack_self_collision
 from .geometry import header as geometry_header
 
@@ -1888,6 +1888,72 @@ def path_time_plan(paths, mo, w, blocked=None, with_table=False):
     _lib.check(_lib.lib().mpb_path_time_plan(_ptr(paths), _ptr(mo.buf), _ptr(w), _ptr(blocked), _ptr(trajs), _ptr(idx), _ptr(arrival),
                                              _ptr(status), _ptr(table), N, S, D, R, _stream()), 'mpb_path_time_plan')
     return PathTiming(trajs, status == PT_FOUND, status, arrival, idx, table)
+
+
+# ---- space-time shortcutting of timed trajectories among moving obstacles (csrc/mpb_st_shortcut.hip; numbers: st_shortcut_layout.py) --
+STS_STATUS_NAMES = st_shortcut_layout.STATUS
+STS_OK, STS_NOT_VALID, STS_BUFFER_CHANGED, STS_INPUT_IN_COLLISION, STS_INPUT_TOO_FAST = range(len(STS_STATUS_NAMES))
+STS_LOG_CODES = st_shortcut_layout.LOG_CODES
+STS_LOG_IDLE, STS_LOG_SKIP_SHORT, STS_LOG_SKIP_FAST, STS_LOG_SKIP_STRAIGHT, STS_LOG_REJECT, STS_LOG_ACCEPT = range(len(STS_LOG_CODES))
+STS_LOG_INDEX_SHIFT, STS_MAX_ITERS = st_shortcut_layout.STS_LOG_INDEX_SHIFT, st_shortcut_layout.STS_MAX_ITERS
+STShortcut = collections.namedtuple('STShortcut', 'trajs ok status first_bad stats log')
+
+
+@_on_tensor_device
+def st_shortcut(trajs, geom, mo, w, n_iters, draws=None, seed=0, problem_offset=0, valid=None, max_span=0, with_log=False, out=None):
+    """Shortcut N dense trajectories (N, R, D) fp32 on the clock of a DeviceMovingObstacles `mo` packed for R rows in one launch
+    (mpb_st_shortcut; include/mpb.h has the definition): n_iters times per trajectory two rows a < b are drawn and the rows between them
+    are replaced by the constant-velocity straight piece when that piece moves no joint k by more than w_k per row and every new row is
+    free at its own time -- of geom's static obstacles and of mo's obstacles of that row.  The row count, and so the clock, never changes.
+    geom: the DeviceGeometry of the static scene.  w (D,) fp32: the most a joint may move per row.  draws: None (device Philox;
+    trajectory n draws from stream problem_offset + n of `seed`) or (N, n_iters, 2) int32 recorded rows.  valid: None or (N,) bool /
+    uint8, False = pass the trajectory through.  max_span: 0 (no limit) or the most rows a piece may span.  out: None (a new tensor) or
+    the (N, R, D) tensor to write into; it may be `trajs` itself (in place).
+    Returns an STShortcut: trajs (N, R, D); ok (N,) bool; status (N,) int32 (STS_*: only OK trajectories are edited, every other one
+    comes out with its input bits); first_bad (N,) int32, the first row the input gate refuses or -1; stats (N, 4) fp32: candidates
+    checked, accepted, length before, length after (NaN where not OK); log (N, n_iters) int32 with with_log (STS_LOG_* | first colliding
+    row << STS_LOG_INDEX_SHIFT), else None."""
+    if not isinstance(geom, DeviceGeometry):
+        raise TypeError('st_shortcut takes the DeviceGeometry of the static scene')
+    if not isinstance(mo, DeviceMovingObstacles):
+        raise TypeError('st_shortcut takes a DeviceMovingObstacles')
+    if not (isinstance(trajs, torch.Tensor) and trajs.dim() == 3):
+        raise ValueError(f'trajs has shape {tuple(getattr(trajs, "shape", ()))}, expected (N, R, D)')
+    N, R, D = trajs.shape
+    _chk(trajs, (N, R, D), 'trajs')
+    L = st_shortcut_layout
+    if D != geom.n_dof or D != mo.n_dof:
+        raise ValueError(f'trajs has D = {D} columns, the geometry {geom.n_dof} and the moving-obstacle buffer {mo.n_dof} degrees of freedom')
+    if R != mo.n_rows:
+        raise ValueError(f'trajs has n_rows = {R}, the moving-obstacle buffer was packed for n_rows = {mo.n_rows}')
+    if not L.STS_MIN_ROWS <= R <= L.STS_MAX_ROWS:
+        raise ValueError(f'n_rows = {R} outside {L.STS_MIN_ROWS} .. STS_MAX_ROWS = {L.STS_MAX_ROWS}')
+    n_iters, max_span = int(n_iters), int(max_span)
+    if not 0 <= n_iters <= L.STS_MAX_ITERS:
+        raise ValueError(f'n_iters = {n_iters} outside 0 .. STS_MAX_ITERS = {L.STS_MAX_ITERS}')
+    if max_span < 0:
+        raise ValueError(f'max_span = {max_span}: 0 (no limit) or a positive row count')
+    need = L.lds_bytes(R, D)
+    if need > L.STS_MAX_LDS_BYTES:
+        raise ValueError(f'{R} rows of D = {D} need {need} bytes of LDS, above STS_MAX_LDS_BYTES = {L.STS_MAX_LDS_BYTES}: fewer rows')
+    _chk(w, (D,), 'w')
+    _chk(draws, (N, n_iters, 2), 'draws', allow_none=True, dtype=torch.int32)
+    if valid is not None:
+        if valid.dtype not in (torch.bool, torch.uint8):
+            raise ValueError(f'valid must be bool or uint8 (got {valid.dtype})')
+        _chk(valid, (N,), 'valid', dtype=valid.dtype)
+    if out is None:
+        out = torch.empty_like(trajs)
+    else:
+        _chk(out, (N, R, D), 'out')
+    dev = trajs.device
+    status, first_bad = torch.empty(N, device=dev, dtype=torch.int32), torch.empty(N, device=dev, dtype=torch.int32)
+    stats = torch.empty(N, 4, device=dev, dtype=torch.float32)
+    log = torch.empty(N, n_iters, device=dev, dtype=torch.int32) if with_log else None
+    _lib.check(_lib.lib().mpb_st_shortcut(_ptr(trajs), _ptr(out), _ptr(geom.buf), int(geom.flags), _ptr(mo.buf), _ptr(w), _ptr(valid),
+                                          _ptr(draws), _ptr(status), _ptr(first_bad), _ptr(stats), _ptr(log), N, R, D, n_iters, max_span,
+                                          _seed64(seed), int(problem_offset) & 0xFFFFFFFF, _stream()), 'mpb_st_shortcut')
+    return STShortcut(out, status == STS_OK, status, first_bad, stats, log)
 
 
 # ---- path shortcutting between the tree and the optimiser (csrc/mpb_path_shortcut.hip) ---------------------------------------------

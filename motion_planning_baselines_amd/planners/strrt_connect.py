@@ -15,6 +15,9 @@ and n_radius, n_iters + 1 loop bodies, a pre-sample pool kept as a list in LDS a
 lengths as outputs), and it must not change here; what fits is restated below with the same names and meaning -- `chunk_iters`, `max_time`
 between launches, copy-major `n_copies` with `problem_offset`, reset()'s top-up of the pre-samples, PATH_TOO_LONG raising.
 
+shortcut(result) -- or shortcut_iters > 0 at construction -- runs the space-time shortcut pass (ops.st_shortcut) over the found plans: a
+plan is a chain of random tree vertices joined by straight pieces, and the pass straightens it on the same clock.
+
 The result seeds the optimisers: CHOMP(initial_particle_means=trajs) with a CostCollision(field=moving_field) member at
 n_support_points = n_rows sees row h at the same time the plan was checked at.
 """
@@ -35,7 +38,7 @@ class STRRTConnect(MPPlanner):
 
     def __init__(self, task=None, moving_field=None, n_rows=None, start_state_pos=None, goal_state_pos=None, n_iters=None, max_step_rows=8,
                  dq_max=None, n_pre_samples=4096, pre_samples=None, seed=0, chunk_iters=1024, max_nodes=None, max_path_nodes=512,
-                 max_time=60., tensor_args=None, **kwargs):
+                 max_time=60., tensor_args=None, shortcut_iters=0, **kwargs):
         assert start_state_pos is not None and goal_state_pos is not None
         super().__init__(name=self.NAME, tensor_args=tensor_args if tensor_args is not None else getattr(task, 'tensor_args', None))
         self.device = require_cuda(self.tensor_args)
@@ -81,6 +84,9 @@ class STRRTConnect(MPPlanner):
         self.seed, self.chunk_iters, self.max_time = int(seed), max(1, int(chunk_iters)), float(max_time)
         self.max_nodes = int(max_nodes) if max_nodes is not None else self.total_iters + 1   # a tree gains at most one node per iteration
         self.max_path_nodes = int(max_path_nodes)
+        self.shortcut_iters = int(shortcut_iters)            # 0: no shortcut pass, the planner as it is without the argument
+        if not 0 <= self.shortcut_iters <= ops.STS_MAX_ITERS:
+            raise ValueError(f'shortcut_iters = {self.shortcut_iters} outside 0 .. {ops.STS_MAX_ITERS}')
         self.moving = ops.DeviceMovingObstacles(task.robot, moving_field, self.device, self.n_rows)
         self.workspace = self.status = None
         self.reset()
@@ -100,7 +106,8 @@ class STRRTConnect(MPPlanner):
         record: trajs (B, R, D) (zero where not found), found (B,) bool, status (B,) int32 (ops.STRRT_*), vertex_q (B, max_path_nodes, D),
         vertex_row (B, max_path_nodes) and n_vertices (B,) int32 -- the plan's tree nodes in ascending rows, from (start, 0) to
         (goal, R - 1) --, log (B, n_iters, ops.STRRT_LOG_WORDS) int32 with with_log, else None.  The trees stay readable through
-        ops.strrt_trees(self.workspace)."""
+        ops.strrt_trees(self.workspace).  With shortcut_iters > 0 the found plans then go through shortcut(): trajs are the shortcut
+        plans, raw_trajs the plans as joined, shortcut the ops.STShortcut record."""
         n_copies = int(n_copies)
         starts = self.starts.repeat(n_copies, 1) if n_copies > 1 else self.starts
         goals = self.goals.repeat(n_copies, 1) if n_copies > 1 else self.goals
@@ -135,8 +142,20 @@ class STRRTConnect(MPPlanner):
                            f'construct the planner with a larger max_path_nodes')
         found = status == ops.STRRT_FOUND
         trajs[~found] = 0.                                          # (a discarded join leaves its rows behind)
-        return types.SimpleNamespace(trajs=trajs, found=found, status=status, vertex_q=vertex_q, vertex_row=vertex_row, n_vertices=n_vertices,
-                                     log=log)
+        result = types.SimpleNamespace(trajs=trajs, found=found, status=status, vertex_q=vertex_q, vertex_row=vertex_row,
+                                       n_vertices=n_vertices, log=log)
+        if self.shortcut_iters > 0:
+            result.raw_trajs = trajs
+            result.shortcut = self.shortcut(result, self.shortcut_iters, problem_offset=problem_offset)
+            result.trajs = result.shortcut.trajs
+        return result
+
+    def shortcut(self, result, n_iters=64, **kw):
+        """Shortcut the found trajectories of an optimize_batched record on their own clock (ops.st_shortcut with valid=result.found,
+        this planner's static geometry, moving-obstacle buffer and w; the seed defaults to the planner's).  The vertex lists of the record
+        describe the plan before the pass.  Returns an ops.STShortcut; rows of problems that were not found pass through (zeros)."""
+        kw.setdefault('seed', self.seed)
+        return ops.st_shortcut(result.trajs, self.task.geom, self.moving, self.w, n_iters, valid=result.found, **kw)
 
     def optimize(self, opt_iters=None, **observation):
         """One problem: the (R, D) trajectory or None; several: a list of those."""

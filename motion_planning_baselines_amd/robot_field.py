@@ -298,6 +298,45 @@ class PlanningTask:
         blocked = self._in_collision(p.reshape(-1, self.q_dim).contiguous()).reshape(N, S).contiguous()
         return ops.path_time_plan(p, mo, w, blocked=blocked)
 
+    # ---- space-time shortcutting of timed trajectories (build-defined: DESIGN.md 10) ---------------------------------------------------
+    def shortcut_trajs_moving(self, trajs, moving_field, n_iters=64, dq_max=None, valid=None, **kw):
+        """The pass between a planner on the moving-obstacle clock and the optimiser: trajs (N, R, D) -- STRRTConnect plans, or the
+        trajs of time_paths_moving -- are shortcut on their own clock of R rows among the task's static obstacles AND a
+        geometry.MovingObstacleField (ops.st_shortcut, which has the definition): rows between two drawn rows are replaced by the
+        constant-velocity straight piece when it is free at every row's own time and within the per-row velocity bound.  dq_max (D,)
+        rad/s defaults to the robot's; a row may move joint k by dq_max_k * (t_end - t_start) / (R - 1), formed as time_paths_moving
+        forms it.  valid: None or (N,) bool, False = pass the trajectory through (the `found` of either producer).  **kw: draws, seed,
+        problem_offset, max_span, with_log, out of ops.st_shortcut.  Returns an ops.STShortcut; its trajs are accepted by
+        check_trajs_moving(trajs, moving_field) wherever ok is set.  One packed buffer per (field, R) is kept on the task."""
+        from .geometry import MovingObstacleField
+        what = 'shortcut_trajs_moving (the space-time shortcut kernel)'
+        self.require_no_self_field(what)
+        self.require_no_sdf_field(what)
+        if not isinstance(moving_field, MovingObstacleField):
+            raise TypeError('shortcut_trajs_moving takes a geometry.MovingObstacleField')
+        if not moving_field.t_end > moving_field.t_start:
+            raise ValueError(f'shortcut_trajs_moving: the MovingObstacleField has t_end = {moving_field.t_end} <= t_start = '
+                             f'{moving_field.t_start}: a clock needs a positive span')
+        t = torch.as_tensor(trajs, dtype=torch.float32, device=self.device)
+        if t.dim() != 3 or t.shape[-1] != self.q_dim:
+            raise ValueError(f'trajs has shape {tuple(t.shape)}, expected (N, R, D) with D = {self.q_dim}')
+        n_rows = int(t.shape[1])
+        if n_rows < 3:
+            raise ValueError(f'shortcut_trajs_moving: n_rows = {n_rows}, a trajectory needs at least 3 rows')
+        dq = getattr(self.robot, 'dq_max_np', None) if dq_max is None else dq_max
+        if dq is None:
+            raise ValueError('shortcut_trajs_moving: no dq_max given and the robot carries none')
+        dq = np.asarray(dq.detach().cpu().numpy() if isinstance(dq, torch.Tensor) else dq, np.float64).reshape(-1)
+        if dq.size != self.q_dim or not (np.isfinite(dq).all() and (dq > 0).all()):
+            raise ValueError(f'shortcut_trajs_moving: dq_max must hold {self.q_dim} finite positive entries')
+        dt_row = (float(moving_field.t_end) - float(moving_field.t_start)) / (n_rows - 1)
+        w = torch.from_numpy((dq * dt_row).astype(np.float32)).to(self.device)
+        if valid is not None:
+            valid = torch.as_tensor(valid, device=self.device)
+            valid = (valid if valid.dtype in (torch.bool, torch.uint8) else valid != 0).contiguous()
+        mo = self._moving_geom(moving_field, n_rows)
+        return ops.st_shortcut(t.contiguous(), self.geom, mo, w, n_iters, valid=valid, **kw)
+
     def require_no_sdf_field(self, what):
         if self.sdf_field is not None:
             raise NotImplementedError(f'{what} reads the obstacle geometry alone: it does not serve a task with an sdf_field '
