@@ -49,6 +49,9 @@
 /* space-time shortcutting among moving obstacles in numbers (generated from st_shortcut_layout.py): statuses MPB_STS_*, log codes
  * MPB_STS_LOG_*, the Philox tag, the input gate's limit, limits, the LDS of a launch */
 #include "mpb_st_shortcut_layout.h"
+/* path certification by clearance bisection in numbers (generated from certify_layout.py): statuses MPB_CERT_*, the interval word, limits,
+ * the reach buffer's header, the default slack */
+#include "mpb_certify_layout.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -89,7 +92,8 @@ extern "C" {
  *                        the time parameterisation under joint limits (mpb_traj_retime, mpb_traj_retime_sample), and Cartesian
  *                        end-effector moves (mpb_cartesian_path), and the moving-obstacle field (mpb_moving_check,
  *                        mpb_moving_invalidate, mpb_moving_collision_eval / _grad / _check), and the timing of geometric paths among
- *                        moving obstacles (mpb_path_time_plan), and space-time shortcutting (mpb_st_shortcut): additive. */
+ *                        moving obstacles (mpb_path_time_plan), and space-time shortcutting (mpb_st_shortcut): additive.  So were
+ *                        the clearance op and the path certifier (mpb_clearance, mpb_path_certify). */
 #define MPB_ABI_VERSION 7
 #define MPB_VERSION_TUNING_BUILD 0x40000000
 int mpb_version(void);
@@ -1406,6 +1410,54 @@ int mpb_traj_retime(const float *trajs, size_t row_stride, const float *v_max, c
 int mpb_traj_retime_sample(const float *trajs, size_t row_stride, const float *x, const float *u, const float *t,
                            const int *retime_status, float *out, int *n_rows, int *status, int N, int H, int D, float dt,
                            int T_rows, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Clearance, and the certificate that a joint-space polyline is free BETWEEN its samples (build-defined; definition, proof and
+ * what is not built: DESIGN.md 10).  Obstacle geometry only: spheres and axis-aligned boxes, chained fields included.
+ *   eta_l(q) = min_f (sd_f(x_l(q)) - margin_f) - r_l,   eta(q) = min_l eta_l(q)
+ * sd_f the exact signed distance of field f (the minimum over its obstacles, walked exhaustively: the broad-phase grids only know
+ * obstacles within the margin), x_l the collision-sphere centres, r_l their radii; fscale plays no part.  eta_l < 0 is the
+ * predicate of mpb_collision_check.  Every chained field must carry the robot's WHOLE link table (pack_geometry with
+ * prune_static=False): the walk reads the first field's.
+ *
+ * mpb_clearance: q (N, D) -> eta (N) and link (N) int, the arg-min sphere (lowest index on a tie; may be NULL).  One lane per
+ *   configuration.  A geometry header that does not hold D joints: eta = NaN, link = -1.
+ *   Refusals: D > MPB_MAX_DOF: MPB_E_UNSUPPORTED; N < 0, D < 1: MPB_E_INVALID; (N == 0: MPB_OK;) a null q / geom / eta, geom not
+ *   16-byte aligned: MPB_E_INVALID.
+ *
+ * mpb_path_certify: N paths of H rows read in place as mpb_traj_collision_stats reads them (row h of path n starts at
+ *   paths + (n*H + h)*row_stride, its first D floats are read); lengths (N) or NULL (every path has H rows); path n is the polyline
+ *   through its first lengths[n] rows.  reach: the device buffer of MPB_REACH_HEADER_WORDS header words (MPB_REACH_MAGIC, n_dof,
+ *   n_links, kind) and rho as [n_dof][n_links] floats -- sphere l is never farther than rho_il from the origin of joint i when joint
+ *   i moves it, 0 when it does not (certify_layout.reach_table builds it in fp64, rounded up); n_links: its sphere count.
+ *   On the segment a -> b sphere l moves at most w * Lambda_l while the parameter moves by w, Lambda_l = sum_i |b_i - a_i| rho_il
+ *   (a point robot: |b - a|_2); the device multiplies its fp32 sum by MPB_CERT_LAMBDA_INFLATE.
+ *   Level -1: every node; eta - c_req < -S at a node: MPB_CERT_COLLISION, witness (node index, t = 0).  Then level d = 0, 1, ...:
+ *   the intervals of a level in (segment, j) order, interval j of segment s at level d has the midpoint parameter
+ *   t = (2j + 1) 2^-(d+1), the half-width w = 2^-(d+1) and the midpoint m = fmaf(b - a, t, a) per joint, and is
+ *     FREE       when eta_l(m) - w Lambda_l - c_req > S for every l  (then eta_l - c_req > S on the closed interval),
+ *     COLLISION  when eta_l(m) - c_req < -S for some l,
+ *     else split into (2j, 2j + 1) at level d + 1; at d == max_depth it stays undecided.
+ *   A path ends at the first level that holds a COLLISION interval (witness: the smallest (segment, t) of that level, the arg-min
+ *   sphere and its eta); else MPB_CERT_UNDECIDED_QUEUE when the next level would hold more than max_intervals intervals (level 0:
+ *   more than max_intervals segments), nothing further being evaluated; else MPB_CERT_UNDECIDED_DEPTH when an interval of level
+ *   max_depth stayed undecided, else MPB_CERT_FREE.  MPB_CERT_BAD_INPUT: a length outside 1 .. H or a non-finite coordinate;
+ *   MPB_CERT_BUFFER_CHANGED: a geometry or reach header that differs from (D, n_links) -- nothing else of either buffer is read.
+ *   out_i (N, MPB_CERT_OUT_INTS): status, witness segment, witness link, n_evals (configurations evaluated), depth_max (the deepest
+ *   level evaluated, -1: nodes only); out_f (N, MPB_CERT_OUT_FLOATS): witness t, witness eta, margin_cert -- the minimum over the
+ *   FREE intervals of eta_l - w Lambda_l - c_req (a path of one row: its node's eta - c_req), a lower bound of the path's clearance
+ *   minus c_req up to S; -inf unless the status is MPB_CERT_FREE.  Without a witness: segment = link = -1, t = eta = 0.
+ *   One single-wave workgroup per path, the level's queue in LDS, no atomics, every loop bounded: the same bits on every run.
+ *   Refusals, in this order, all before the launch: D > MPB_MAX_DOF: MPB_E_UNSUPPORTED; H outside 1 .. MPB_CERT_MAX_ROWS (the
+ *   segment field of the interval word), max_depth outside 0 .. MPB_CERT_MAX_DEPTH (its j field), max_intervals outside
+ *   1 .. MPB_CERT_MAX_INTERVALS, n_links outside 1 .. MPB_CERT_MAX_LINKS: MPB_E_UNSUPPORTED, each by name; N < 0, D < 1,
+ *   row_stride < D, S not finite or negative, c_req not finite: MPB_E_INVALID; (N == 0: MPB_OK;) a null required pointer, geom or
+ *   reach not 16-byte aligned: MPB_E_INVALID.
+ * ------------------------------------------------------------------------------------------- */
+int mpb_clearance(const float *q, const float *geom, float *eta, int *link, int N, int D, void *stream);
+int mpb_path_certify(const float *paths, size_t row_stride, const int *lengths, const float *geom, const float *reach, int n_links,
+                     float S, float c_req, int max_depth, int max_intervals, int *out_i, float *out_f, int N, int H, int D,
+                     void *stream);
 
 #ifdef __cplusplus
 }

@@ -12,7 +12,7 @@ import warnings
 import numpy as np
 import torch
 
-from . import _lib, path_timing_layout, rrt_layout, st_shortcut_layout, strrt_layout
+from . import _lib, certify_layout, path_timing_layout, rrt_layout, st_shortcut_layout, strrt_layout
 from .geometry import KIND_CHAIN, MAX_FIELDS, CollisionField, TriangleMesh, count_fields, mesh_pose, occupancy_bytes, pack_geometry, pack_mesh, pack_moving_obstacles, pack_sdf_grid, pack_self_collision
 from .geometry import header as geometry_header
 
@@ -2167,3 +2167,113 @@ def traj_retime_sample(trajs, timing, dt, n_rows=None):
                                                      _ptr(out), _ptr(rows), _ptr(status), N, H, D, dt, n_rows, _stream()),
                    'mpb_traj_retime_sample')
     return out, rows, status
+
+
+# ---- clearance and path certification (csrc/mpb_certify.hip; the definition: include/mpb.h) ---------------------------
+CERT_STATUS_NAMES = certify_layout.STATUS
+CERT_FREE, CERT_COLLISION, CERT_UNDECIDED_DEPTH, CERT_UNDECIDED_QUEUE, CERT_BAD_INPUT, CERT_BUFFER_CHANGED = range(len(CERT_STATUS_NAMES))
+CERT_DEFAULT_SLACK = certify_layout.CERT_DEFAULT_SLACK
+
+
+class DeviceReach:
+    """The reach buffer of a robot (certify_layout.pack_reach: how far each collision sphere can be from each joint that moves it)
+    resident in HBM: what path_certify forms its motion bounds from."""
+
+    def __init__(self, robot, device):
+        rs = robot.spec()
+        self.robot, self.host = robot, certify_layout.pack_reach(rs)
+        self.n_dof, self.n_links, self.kind = int(rs['n_dof']), len(rs['link_radius']), int(rs['kind'])
+        self.buf = torch.from_numpy(self.host.copy()).to(device)
+
+
+def _need_whole_link_table(geom, what):
+    if not geom.all_links:
+        raise ValueError(f'{what} needs every collision sphere of the robot in every chained field: build the DeviceGeometry with '
+                         f'keep_all_links=True')
+
+
+@_on_tensor_device
+def clearance(q, geom, with_link=False):
+    """(N, D) configurations -> eta fp32 (N,): the clearance min_l (min_f (sd_f(x_l) - margin_f) - r_l) over the obstacle geometry,
+    every obstacle of every chained field walked exhaustively (mpb_clearance); eta < 0 is collision_check's predicate.  with_link
+    also returns the arg-min collision sphere, int32 (N,), the lowest index on a tie."""
+    if not (isinstance(q, torch.Tensor) and q.is_cuda):
+        raise _lib.MPBError('clearance: q must be a GPU tensor; there is no CPU fallback')
+    if q.dim() != 2:
+        raise ValueError(f'q has shape {tuple(q.shape)}, expected (N, D)')
+    N, D = q.shape
+    _chk(q, (N, D), 'q')
+    if D != geom.n_dof:
+        raise ValueError(f'q has {D} columns, the geometry {geom.n_dof} degrees of freedom')
+    _need_whole_link_table(geom, 'clearance')
+    eta = torch.empty(N, device=q.device, dtype=torch.float32)
+    link = torch.empty(N, device=q.device, dtype=torch.int32) if with_link else None
+    _lib.check(_lib.lib().mpb_clearance(_ptr(q), _ptr(geom.buf), _ptr(eta), _ptr(link), N, D, _stream()), 'mpb_clearance')
+    return (eta, link) if with_link else eta
+
+
+class PathCertificate:
+    """What path_certify returns, per path (N,): status int32 (CERT_FREE / CERT_COLLISION / CERT_UNDECIDED_DEPTH / CERT_UNDECIDED_QUEUE /
+    CERT_BAD_INPUT / CERT_BUFFER_CHANGED), free / collision / undecided bool; the witness of a COLLISION -- witness_segment int32,
+    witness_t fp32 (a node: its index and t = 0), witness_link int32, witness_eta fp32; -1, 0, -1, 0 without one --; n_evals int32
+    configurations evaluated, depth_max int32 the deepest level evaluated (-1: nodes only), margin_cert fp32 a certified lower bound
+    of the path's clearance minus c_req, up to the slack (-inf unless FREE); slack, c_req as the launch took them.  The certificate
+    covers the joint-space POLYLINE through the rows, not a spline through them."""
+
+    def __init__(self, out_i, out_f, slack, c_req):
+        self.status, self.witness_segment, self.witness_link, self.n_evals, self.depth_max = (out_i[:, k] for k in range(5))
+        self.witness_t, self.witness_eta, self.margin_cert = (out_f[:, k] for k in range(3))
+        self.free, self.collision = self.status == CERT_FREE, self.status == CERT_COLLISION
+        self.undecided = (self.status == CERT_UNDECIDED_DEPTH) | (self.status == CERT_UNDECIDED_QUEUE)
+        self.slack, self.c_req = float(slack), float(c_req)
+
+    def witness_q(self, paths):
+        """(N, D) the witness configurations on paths (N, H, W): fmaf(b - a, t, a) on the witness segment, the node itself for t = 0;
+        rows without a witness hold row 0."""
+        H = paths.shape[1]
+        s = self.witness_segment.clamp_min(0).long()
+        idx = torch.arange(paths.shape[0], device=paths.device)
+        a, b = paths[idx, s], paths[idx, (s + 1).clamp_max(H - 1)]
+        t = self.witness_t[:, None]
+        return torch.where(t == 0, a, torch.addcmul(a, b - a, t))
+
+
+@_on_tensor_device
+def path_certify(paths, geom, reach, lengths=None, slack=None, c_req=0.0, max_depth=certify_layout.CERT_DEFAULT_MAX_DEPTH,
+                 max_intervals=certify_layout.CERT_DEFAULT_MAX_INTERVALS):
+    """(N, H, W) paths, W >= the geometry's degrees of freedom, read in place (the first D columns of a row) -> a PathCertificate: is
+    the joint-space polyline through the first lengths[n] rows (every row without lengths) free of the obstacle geometry over its
+    whole continuum, with clearance above c_req?  Bisection with the motion bound of `reach` (a DeviceReach of the same robot),
+    mpb_path_certify: include/mpb.h has the definition.  slack: the S of the definition, CERT_DEFAULT_SLACK (measured: certify_layout.py)
+    when None.  UNDECIDED_DEPTH: raise max_depth (<= 20); UNDECIDED_QUEUE: raise max_intervals (<= 4096)."""
+    if not (isinstance(paths, torch.Tensor) and paths.is_cuda):
+        raise _lib.MPBError('path_certify: paths must be a GPU tensor; there is no CPU fallback')
+    if paths.dim() != 3:
+        raise ValueError(f'paths has shape {tuple(paths.shape)}, expected (N, H, W)')
+    N, H, W = paths.shape
+    _chk(paths, (N, H, W), 'paths')
+    D = geom.n_dof
+    if W < D:
+        raise ValueError(f'paths has {W} columns, the geometry {D} degrees of freedom')
+    _need_whole_link_table(geom, 'path_certify')
+    if (reach.n_dof, reach.n_links, reach.kind) != (geom.n_dof, geom.n_links, geom.kind):
+        raise ValueError(f'path_certify: the reach buffer is of a robot with {reach.n_dof} joints and {reach.n_links} collision spheres '
+                         f'(kind {reach.kind}), the geometry of one with {geom.n_dof} and {geom.n_links} (kind {geom.kind})')
+    if reach.buf.device != paths.device or geom.buf.device != paths.device:
+        raise ValueError('path_certify: paths, the geometry and the reach buffer must live on one device')
+    _chk(lengths, (N,), 'lengths', allow_none=True, dtype=torch.int32)
+    if H > certify_layout.CERT_MAX_ROWS:
+        raise ValueError(f'path_certify: H = {H} exceeds CERT_MAX_ROWS = {certify_layout.CERT_MAX_ROWS} (the segment field of the interval word)')
+    if not 0 <= int(max_depth) <= certify_layout.CERT_MAX_DEPTH:
+        raise ValueError(f'path_certify: max_depth = {max_depth} outside 0 .. CERT_MAX_DEPTH = {certify_layout.CERT_MAX_DEPTH} (the j field of the interval word)')
+    if not 1 <= int(max_intervals) <= certify_layout.CERT_MAX_INTERVALS:
+        raise ValueError(f'path_certify: max_intervals = {max_intervals} outside 1 .. CERT_MAX_INTERVALS = {certify_layout.CERT_MAX_INTERVALS} (the queue lives in LDS)')
+    slack = CERT_DEFAULT_SLACK if slack is None else float(slack)
+    if not (math.isfinite(slack) and slack >= 0.0 and math.isfinite(float(c_req))):
+        raise ValueError(f'path_certify: slack = {slack} must be finite and >= 0, c_req = {c_req} finite')
+    out_i = torch.empty(N, certify_layout.CERT_OUT_INTS, device=paths.device, dtype=torch.int32)
+    out_f = torch.empty(N, certify_layout.CERT_OUT_FLOATS, device=paths.device, dtype=torch.float32)
+    _lib.check(_lib.lib().mpb_path_certify(_ptr(paths), W, _ptr(lengths), _ptr(geom.buf), _ptr(reach.buf), int(reach.n_links), slack,
+                                           float(c_req), int(max_depth), int(max_intervals), _ptr(out_i), _ptr(out_f), N, H, D, _stream()),
+               'mpb_path_certify')
+    return PathCertificate(out_i, out_f, slack, c_req)

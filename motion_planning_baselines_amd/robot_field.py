@@ -501,6 +501,52 @@ class PlanningTask:
         _, (count, _, _) = self._trajs_stats(trajs, kwargs.get('num_interpolation', 5))
         return 1 if bool((count == 0).any()) else 0
 
+    # ---- clearance and the certificate between the samples (build-defined: DESIGN.md 10) ----------------------------------------------
+    def _certify_buffers(self, what):
+        """(geometry with the whole link table in every field, reach buffer) of this task's robot and obstacle field(s), built on first
+        use and kept.  The clearance walk knows the obstacle geometry alone: a self_field or an sdf_field is refused by name."""
+        self.require_no_self_field(what)
+        self.require_no_sdf_field(what)
+        if '_certify_geom' not in self.__dict__:
+            self._certify_geom = (ops.DeviceGeometry(self.robot, self.field, self.device, keep_all_links=True, use_model=False),
+                                  ops.DeviceReach(self.robot, self.device))
+        return self._certify_geom
+
+    def compute_clearance(self, qs, return_link=False):
+        """(..., D) configurations -> eta (...): the signed clearance of the robot's collision spheres from the obstacles, margins taken
+        off (ops.clearance): eta < 0 is compute_collision's answer, eta is how far it is from flipping.  return_link adds the arg-min
+        collision sphere, int32 (...)."""
+        geom, _ = self._certify_buffers('compute_clearance (mpb_clearance)')
+        q = torch.as_tensor(qs, dtype=torch.float32, device=self.device)
+        if q.dim() < 1 or q.shape[-1] != self.q_dim:
+            raise ValueError(f'qs has shape {tuple(q.shape)}, expected (..., {self.q_dim})')
+        lead = tuple(q.shape[:-1])
+        eta, link = ops.clearance(q.reshape(-1, self.q_dim).contiguous(), geom, with_link=True)
+        return (eta.reshape(lead), link.reshape(lead)) if return_link else eta.reshape(lead)
+
+    def certify_paths(self, paths, lengths=None, **kwargs):
+        """(paths (N, Lmax, D), lengths (N,) int32 or None) -- what the RRT planners and shortcut_paths emit -> an ops.PathCertificate:
+        which joint-space polylines are free of the obstacles over their whole continuum, not only at check_step samples
+        (ops.path_certify, which also takes slack, c_req, max_depth, max_intervals).  The certificate covers the polyline, not a spline
+        through it."""
+        geom, reach = self._certify_buffers('certify_paths (mpb_path_certify)')
+        p = torch.as_tensor(paths, dtype=torch.float32, device=self.device)
+        if p.dim() != 3 or p.shape[-1] < self.q_dim:
+            raise ValueError(f'paths has shape {tuple(p.shape)}, expected (N, Lmax, W) with W >= {self.q_dim}')
+        if lengths is not None:
+            lengths = torch.as_tensor(lengths, device=self.device).to(torch.int32).contiguous()
+        return ops.path_certify(p.contiguous(), geom, reach, lengths=lengths, **kwargs)
+
+    def certify_trajs(self, trajs, **kwargs):
+        """trajs (..., H, W), W >= q_dim, leading dimensions flattened as in get_trajs_collision_and_free and read in place -> an
+        ops.PathCertificate over the N flattened trajectories: free BETWEEN the waypoints too, where get_trajs_collision_and_free
+        looks at num_interpolation points per segment.  The certificate covers the polyline through the waypoints, not a spline."""
+        geom, reach = self._certify_buffers('certify_trajs (mpb_path_certify)')
+        t = torch.as_tensor(trajs, dtype=torch.float32, device=self.device)
+        if t.dim() < 2 or t.shape[-1] < self.q_dim:
+            raise ValueError(f'trajs has shape {tuple(t.shape)}, expected (..., H, W) with W >= {self.q_dim}')
+        return ops.path_certify(t.reshape(-1, t.shape[-2], t.shape[-1]).contiguous(), geom, reach, **kwargs)
+
     # ---- shortcutting of a path batch (build-defined: DESIGN.md 10) ------------------------------------------------------------
     def shortcut_paths(self, paths, lengths, n_iters=64, check_step=0.05, **kwargs):
         """(paths (N, Lmax, D), lengths (N,) int32) device tensors -> (paths, lengths, stats (N, 4)): n_iters shortcut attempts
