@@ -93,7 +93,9 @@ extern "C" {
  *                        end-effector moves (mpb_cartesian_path), and the moving-obstacle field (mpb_moving_check,
  *                        mpb_moving_invalidate, mpb_moving_collision_eval / _grad / _check), and the timing of geometric paths among
  *                        moving obstacles (mpb_path_time_plan), and space-time shortcutting (mpb_st_shortcut): additive.  So were
- *                        the clearance op and the path certifier (mpb_clearance, mpb_path_certify). */
+ *                        the clearance op and the path certifier (mpb_clearance, mpb_path_certify), and the world predicate and the
+ *                        *_world entries (mpb_world_collision_check, mpb_rrt_connect_init_world / _run_world, mpb_path_shortcut_world,
+ *                        mpb_traj_collision_stats_world). */
 #define MPB_ABI_VERSION 7
 #define MPB_VERSION_TUNING_BUILD 0x40000000
 int mpb_version(void);
@@ -1458,6 +1460,51 @@ int mpb_clearance(const float *q, const float *geom, float *eta, int *link, int 
 int mpb_path_certify(const float *paths, size_t row_stride, const int *lengths, const float *geom, const float *reach, int n_links,
                      float S, float c_req, int max_depth, int max_intervals, int *out_i, float *out_f, int N, int H, int D,
                      void *stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * The world: ONE in-kernel collision predicate over a whole planning task (build-defined).  A configuration is in
+ * collision iff  c_obs(q) > 0  or  c_sdf(q) > 0  or  c_self(q) > 0,  where c_obs is mpb_collision_check's gap on geom, c_sdf is
+ * mpb_sdf_grid_collision_check's gap on the packed SDF-grid buffer sdfb, c_self is mpb_self_collision_check's gap on the packed self
+ * buffer selfb: the answer of the three stand-alone predicates ORed, in one launch and inside the kernels that decide collisions in
+ * a loop.  sdfb and selfb are device buffers as those predicates take them (validated on the host by mpb_sdf_grid_check /
+ * mpb_self_check; their headers are read once per address, mpb_sdf_grid_invalidate / mpb_self_invalidate announce another buffer at
+ * an address); EITHER MAY BE NULL: that part is absent.  With both null every entry below launches its old entry's kernels and gives
+ * its outputs bit for bit (mpb_world_collision_check: mpb_collision_check's flags, and its gap as part 0).
+ * A buffer whose header no longer holds what the launcher read puts every configuration in collision (the stand-alone predicates'
+ * rule; its part reads NaN, a validation max_gap 3e38): an RRT problem then ends START_OR_GOAL_IN_COLLISION, a shortcut candidate is
+ * REJECTed at point 0; no status word is added and nothing is read through a header word the launcher has not checked.
+ * Every *_world entry takes its old entry's arguments plus (sdfb, selfb) after geom_flags, makes the old entry's refusals first, in the
+ * old order and under its own name, then: sdfb or selfb not 16-byte aligned: MPB_E_INVALID; the SDF header's refusals
+ * (mpb_sdf_grid_check's, of the header), its n_dof != D: MPB_E_INVALID; the self header's refusals, its n_dof != D: MPB_E_INVALID.
+ * LDS: the self part keeps 768 B per collision sphere and wave next to what the old kernel takes (mpb_path_shortcut_world refuses
+ * an Lmax whose path does not fit beside it).
+ *
+ * mpb_world_collision_check: q (N, D); in_collision (N) bytes, 0 / 1; parts (N, 3) optional (may be NULL): (c_obs, c_sdf, c_self), an
+ *   absent part 0 -- the bits of the three stand-alone gaps.  Refusals as mpb_collision_check's, then the above.
+ * mpb_rrt_connect_init_world / mpb_rrt_connect_run_world: mpb_rrt_connect_init / _run with the world predicate for the start / goal
+ *   check and for every point of an extension.  Workspace layout, magic and status values are those of mpb_rrt_connect_*; a
+ *   workspace may be initialised and advanced by either pair of entries as long as one world is used throughout.  (The world kernels
+ *   are instantiated for the compile-time Panda and for run-time D: the bits of a D = 2, 3, 7 tree on a world are those of the
+ *   run-time-D kernel, which rounds the nearest-node distance as rrt_connect_kernel<0, 0> does.)
+ * mpb_path_shortcut_world: mpb_path_shortcut with the world predicate on a candidate's points.
+ * mpb_traj_collision_stats_world: mpb_traj_collision_stats with the world predicate on the dense points; max_gap is the largest
+ *   (c_obs + c_sdf) + c_self, every addition rounded.  Workgroups of 256 threads, of 64 where selfb is given (one self block).
+ * ------------------------------------------------------------------------------------------- */
+int mpb_world_collision_check(const float *q, const float *geom, int geom_flags, const float *sdfb, const float *selfb,
+                              unsigned char *in_collision, float *parts, int N, int D, void *stream);
+int mpb_rrt_connect_init_world(void *workspace, size_t workspace_bytes, const float *start, const float *goal, const float *geom,
+                               int geom_flags, const float *sdfb, const float *selfb, int B, int max_nodes, int n_pre, int D,
+                               void *stream);
+int mpb_rrt_connect_run_world(void *workspace, size_t workspace_bytes, const float *geom, int geom_flags, const float *sdfb,
+                              const float *selfb, const float *pre_samples, size_t pre_stride, const int *sample_idx, float *paths,
+                              int *lengths, int *status, int B, int max_nodes, int n_pre, int D, int Lmax, int iter0, int n_iters,
+                              int total_iters, float step_size, float n_radius, uint64_t seed, uint32_t problem_offset, void *stream);
+int mpb_path_shortcut_world(const float *paths_in, const int *lengths_in, float *paths_out, int *lengths_out, float *stats, int *log,
+                            const float *geom, int geom_flags, const float *sdfb, const float *selfb, const float *draws, int N,
+                            int Lmax, int D, int n_iters, float check_step, uint64_t seed, uint32_t problem_offset, void *stream);
+int mpb_traj_collision_stats_world(const float *trajs, size_t row_stride, const float *geom, int geom_flags, const float *sdfb,
+                                   const float *selfb, int n_interp, int *n_in_collision, int *first_in_collision, float *max_gap,
+                                   unsigned char *point_in_collision, int N, int H, int D, void *stream);
 
 #ifdef __cplusplus
 }

@@ -15,9 +15,12 @@
 //     rrt_close say fmaf where they take one rounding;
 //   - every value that steers control flow (the length, the positions, the verdicts) is computed alike by all 64 lanes
 //     from LDS broadcasts: the control flow is block-uniform, as rrt_config_cost's __syncthreads() needs.
+// On a world (mpb_world.h) shortcut_world_kernel runs the same body with the world predicate; its self block sits behind the path.
 #include "mpb_common.h"
 #include "mpb_rrt.h"
 #include "mpb_rrt_host.h"
+#include "mpb_world.h"
+#include "mpb_world_host.h"
 
 #define SC_TAG 0x53484354u                                   // the Philox stream of this kernel (the RRT kernels': their magics)
 #define SC_STAGING_BYTES (4 * MPB_GRID_MAX_CELLS + 16 * (MPB_GRID_MAX_SPH + 1))   // gridw + otab, static LDS
@@ -95,8 +98,10 @@ __device__ __forceinline__ bool sc_point(const float* P, int Dp, int D, int a, f
     return !at0 && !at1;
 }
 
-template <int DT, int MODEL>
-__global__ __launch_bounds__(64) void path_shortcut_kernel(const ScArgs a) {
+// (the body of path_shortcut_kernel and of its world form shortcut_world_kernel; W: null with WORLD == 0, whose self block sits in the
+// dynamic LDS behind the path)
+template <int DT, int MODEL, int WORLD>
+__device__ __forceinline__ void path_shortcut_body(const ScArgs& a, const WorldView* W) {
 #pragma clang fp contract(off)
     __shared__ unsigned gridw[MPB_GRID_MAX_CELLS];
     __shared__ float4 otab[MPB_GRID_MAX_SPH + 1];
@@ -158,7 +163,7 @@ __global__ __launch_bounds__(64) void path_shortcut_kernel(const ScArgs a) {
                     const float lstep = 1.0f / (float)(n_pts - 1);
 #pragma unroll
                     for (int k = 0; k < MPB_MAX_DOF; ++k) dl[k] = p2[k] - p1[k];
-                    first = rrt_first_collision<DM, MODEL>(a.geom, gridw, otab, staged, p1, dl, n_pts, lstep, lane);
+                    first = rrt_first_collision<DM, MODEL, WORLD>(a.geom, gridw, otab, staged, p1, dl, n_pts, lstep, lane, W);
                     ++tested;
                     const int n_ins = (ins1 ? 1 : 0) + (ins2 ? 1 : 0);
                     const int new_len = lo + 1 + n_ins + (L - hi);
@@ -213,29 +218,72 @@ __global__ __launch_bounds__(64) void path_shortcut_kernel(const ScArgs a) {
     if (lane == 0) a.lengths_out[b] = L;
 }
 
+template <int DT, int MODEL>
+__global__ __launch_bounds__(64) void path_shortcut_kernel(const ScArgs a) {
+    path_shortcut_body<DT, MODEL, 0>(a, nullptr);
+}
+
+// the same pass on a world: a candidate's points are decided by the world predicate (mpb_world.h)
+template <int DT, int MODEL>
+__global__ __launch_bounds__(64) void shortcut_world_kernel(const ScArgs a, const WorldArgs w) {
+    extern __shared__ float sc_path[];
+    const int Dp = ((DT ? DT : a.D) + 3) & ~3;
+    const WorldView W = world_view(a.geom, w, sc_path + (size_t)a.Lmax * Dp);
+    path_shortcut_body<DT, MODEL, 1>(a, &W);
+}
+
 // ---- host side ------------------------------------------------------------------------------------------------------
-extern "C" int mpb_path_shortcut(const float* paths_in, const int* lengths_in, float* paths_out, int* lengths_out, float* stats,
-                                 int* log, const float* geom, int geom_flags, const float* draws, int N, int Lmax, int D,
-                                 int n_iters, float check_step, uint64_t seed, uint32_t problem_offset, void* stream) {
-    if (D > MPB_MAX_DOF) return mpb_failf(MPB_E_UNSUPPORTED, "mpb_path_shortcut: D = %d exceeds MPB_MAX_DOF = %d", D, MPB_MAX_DOF);
-    if (N < 0 || D < 1) return mpb_failf(MPB_E_INVALID, "mpb_path_shortcut: bad shape (N %d, D %d)", N, D);
+static int path_shortcut_impl(const char* who, const float* paths_in, const int* lengths_in, float* paths_out, int* lengths_out, float* stats,
+                              int* log, const float* geom, int geom_flags, const float* sdfb, const float* selfb, const float* draws, int N,
+                              int Lmax, int D, int n_iters, float check_step, uint64_t seed, uint32_t problem_offset, void* stream) {
+    if (D > MPB_MAX_DOF) return mpb_failf(MPB_E_UNSUPPORTED, "%s: D = %d exceeds MPB_MAX_DOF = %d", who, D, MPB_MAX_DOF);
+    if (N < 0 || D < 1) return mpb_failf(MPB_E_INVALID, "%s: bad shape (N %d, D %d)", who, N, D);
     const int Dp = (D + 3) & ~3;
     const int max_rows = (SC_LDS_BYTES - SC_STAGING_BYTES) / (4 * Dp);
     if (Lmax < 2 || Lmax > max_rows)
-        return mpb_failf(MPB_E_INVALID, "mpb_path_shortcut: Lmax = %d outside 2 .. %d (the path of D = %d lives in LDS)", Lmax, max_rows, D);
+        return mpb_failf(MPB_E_INVALID, "%s: Lmax = %d outside 2 .. %d (the path of D = %d lives in LDS)", who, Lmax, max_rows, D);
     if (n_iters < 0 || n_iters > MPB_SHORTCUT_MAX_ITERS)
-        return mpb_failf(MPB_E_INVALID, "mpb_path_shortcut: n_iters = %d outside 0 .. %d", n_iters, MPB_SHORTCUT_MAX_ITERS);
-    if (mpb_bad_step(check_step)) return mpb_fail(MPB_E_INVALID, "mpb_path_shortcut: check_step must be finite and positive");
-    if (!paths_in || !lengths_in || !paths_out || !lengths_out || !stats || !geom) return mpb_fail(MPB_E_INVALID, "mpb_path_shortcut: null pointer");
-    if (mpb_misaligned16(geom)) return mpb_fail(MPB_E_INVALID, "mpb_path_shortcut: geom must be 16-byte aligned");
+        return mpb_failf(MPB_E_INVALID, "%s: n_iters = %d outside 0 .. %d", who, n_iters, MPB_SHORTCUT_MAX_ITERS);
+    if (mpb_bad_step(check_step)) return mpb_failf(MPB_E_INVALID, "%s: check_step must be finite and positive", who);
+    if (!paths_in || !lengths_in || !paths_out || !lengths_out || !stats || !geom) return mpb_failf(MPB_E_INVALID, "%s: null pointer", who);
+    if (mpb_misaligned16(geom)) return mpb_failf(MPB_E_INVALID, "%s: geom must be 16-byte aligned", who);
     if (N == 0) return MPB_OK;
     const ScArgs a = {paths_in, lengths_in, paths_out, lengths_out, stats, log, geom, draws, Lmax, D, n_iters, check_step,
                       (uint32_t)seed, (uint32_t)(seed >> 32), problem_offset};
     const size_t lds = (size_t)Lmax * Dp * sizeof(float);
-    return rrt_dispatch<2, 3, 7>(geom_flags, D, [&](auto dt, auto model) {
-        const int rl = mpb_raise_lds_limit(path_shortcut_kernel<dt.value, model.value>, lds, "mpb_path_shortcut");
+    if (!world_present(sdfb, selfb))
+        return rrt_dispatch<2, 3, 7>(geom_flags, D, [&](auto dt, auto model) {
+            const int rl = mpb_raise_lds_limit(path_shortcut_kernel<dt.value, model.value>, lds, who);
+            if (rl) return rl;
+            hipLaunchKernelGGL((path_shortcut_kernel<dt.value, model.value>), dim3(N), dim3(64), lds, (hipStream_t)stream, a);
+            return mpb_check_launch(who);
+        });
+    WorldArgs w;
+    const int rc = world_args(who, sdfb, selfb, D, w);
+    if (rc) return rc;
+    const size_t lds_w = lds + world_self_lds_bytes(w, 1);
+    if (lds_w > (size_t)(SC_LDS_BYTES - SC_STAGING_BYTES))
+        return mpb_failf(MPB_E_INVALID, "%s: Lmax = %d rows of D = %d and the self block of %d spheres take %zu bytes of LDS, %d are there", who, Lmax,
+                         D, w.self_links, lds_w, SC_LDS_BYTES - SC_STAGING_BYTES);
+    return rrt_dispatch<>(geom_flags, D, [&](auto dt, auto model) {
+        const int rl = mpb_raise_lds_limit(shortcut_world_kernel<dt.value, model.value>, lds_w, who);
         if (rl) return rl;
-        hipLaunchKernelGGL((path_shortcut_kernel<dt.value, model.value>), dim3(N), dim3(64), lds, (hipStream_t)stream, a);
-        return mpb_check_launch("mpb_path_shortcut");
+        hipLaunchKernelGGL((shortcut_world_kernel<dt.value, model.value>), dim3(N), dim3(64), lds_w, (hipStream_t)stream, a, w);
+        return mpb_check_launch(who);
     });
+}
+
+extern "C" int mpb_path_shortcut(const float* paths_in, const int* lengths_in, float* paths_out, int* lengths_out, float* stats,
+                                 int* log, const float* geom, int geom_flags, const float* draws, int N, int Lmax, int D,
+                                 int n_iters, float check_step, uint64_t seed, uint32_t problem_offset, void* stream) {
+    return path_shortcut_impl(__func__, paths_in, lengths_in, paths_out, lengths_out, stats, log, geom, geom_flags, nullptr, nullptr, draws, N,
+                              Lmax, D, n_iters, check_step, seed, problem_offset, stream);
+}
+
+extern "C" int mpb_path_shortcut_world(const float* paths_in, const int* lengths_in, float* paths_out, int* lengths_out, float* stats,
+                                       int* log, const float* geom, int geom_flags, const float* sdfb, const float* selfb,
+                                       const float* draws, int N, int Lmax, int D, int n_iters, float check_step, uint64_t seed,
+                                       uint32_t problem_offset, void* stream) {
+    return path_shortcut_impl(__func__, paths_in, lengths_in, paths_out, lengths_out, stats, log, geom, geom_flags, sdfb, selfb, draws, N, Lmax,
+                              D, n_iters, check_step, seed, problem_offset, stream);
 }

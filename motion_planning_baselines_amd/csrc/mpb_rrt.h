@@ -45,6 +45,14 @@ __device__ __forceinline__ float rrt_config_cost(const float* __restrict__ geom,
     return c;
 }
 
+// The predicate over the whole task (mpb_world.h, which defines both): obstacles, SDF grid and the robot against itself.  The
+// functions below take WORLD as a compile-time switch and a WorldView; with WORLD == 0 they make the rrt_config_cost call above and
+// nothing else, and the view is never looked at.
+struct WorldView;
+template <int MODEL, int WORLD>
+__device__ __forceinline__ bool world_in_collision(const WorldView& W, unsigned* gridw, float4* otab, const float*& staged,
+                                                   const float (&q)[MPB_MAX_DOF]);
+
 // a configuration row of D floats into registers, zeros past D
 template <int DM>
 __device__ __forceinline__ void rrt_load_row(const float* p, int D, float (&q)[MPB_MAX_DOF]) {
@@ -123,16 +131,22 @@ __device__ __forceinline__ void rrt_linspace_point(const float (&q1)[MPB_MAX_DOF
 
 // safe_path's scan: the index of the first of the n_pts points of an extension that is in collision, -1 when none is;
 // one lane per point, 64 points per trip, and the trips after the first hit are never evaluated
-template <int DM, int MODEL>
+template <int DM, int MODEL, int WORLD = 0>
 __device__ __forceinline__ int rrt_first_collision(const float* __restrict__ geom, unsigned* gridw, float4* otab,
                                                    const float*& staged, const float (&q1)[MPB_MAX_DOF],
-                                                   const float (&dl)[MPB_MAX_DOF], int n_pts, float lstep, int lane) {
+                                                   const float (&dl)[MPB_MAX_DOF], int n_pts, float lstep, int lane,
+                                                   const WorldView* W = nullptr) {
     for (int base = 0; base < n_pts; base += 64) {
         const int p = base + lane;
         float q[MPB_MAX_DOF];
         rrt_linspace_point<DM>(q1, dl, n_pts, lstep, min(p, n_pts - 1), q);
-        const float c = rrt_config_cost<MODEL>(geom, gridw, otab, staged, q);
-        const unsigned long long m = __ballot(p < n_pts && c > 0.f);
+        unsigned long long m;
+        if constexpr (WORLD == 0) {
+            const float c = rrt_config_cost<MODEL>(geom, gridw, otab, staged, q);
+            m = __ballot(p < n_pts && c > 0.f);
+        } else {
+            m = __ballot(world_in_collision<MODEL, WORLD>(*W, gridw, otab, staged, q) && p < n_pts);
+        }
         if (m != 0ull) return base + (int)__builtin_ctzll(m);
     }
     return -1;
@@ -189,11 +203,11 @@ __device__ __forceinline__ int rrt_purge(float* path_b, int Lraw, int D, int lan
 // What the init kernels of RRT-Connect and RRT* do alike, for problem b: the global words (block 0), the full pool list
 // 0 .. n_pre - 1 at `pool`, and the collision check of the start (lane 0) and the goal (every other lane).  Returns the
 // problem's first status word.
-template <int MODEL>
+template <int MODEL, int WORLD = 0>
 __device__ __forceinline__ int rrt_init_shared(int* __restrict__ ws, int magic, int B, int max_nodes, int n_pre, int D, int Dp,
                                                unsigned* __restrict__ pool, int pool_words, const float* __restrict__ start,
                                                const float* __restrict__ goal, const float* __restrict__ geom, unsigned* gridw,
-                                               float4* otab, int b, int lane) {
+                                               float4* otab, int b, int lane, const WorldView* W = nullptr) {
     if (b == 0 && lane < MPB_RRT_GLOBAL_WORDS) {
         int v = 0;
         if (lane == MPB_RRTG_MAGIC) v = magic;
@@ -208,8 +222,13 @@ __device__ __forceinline__ int rrt_init_shared(int* __restrict__ ws, int magic, 
     float q[MPB_MAX_DOF];
     rrt_load_row<MPB_MAX_DOF>(row, D, q);
     const float* staged = nullptr;
-    const float c = rrt_config_cost<MODEL>(geom, gridw, otab, staged, q);
-    const bool hit = __ballot(c > 0.f) != 0ull;
+    bool hit;
+    if constexpr (WORLD == 0) {
+        const float c = rrt_config_cost<MODEL>(geom, gridw, otab, staged, q);
+        hit = __ballot(c > 0.f) != 0ull;
+    } else {
+        hit = __ballot(world_in_collision<MODEL, WORLD>(*W, gridw, otab, staged, q)) != 0ull;
+    }
     for (int w = lane; w < pool_words; w += 64)
         pool[w] = (unsigned)(2 * w) | ((unsigned)(2 * w + 1) << MPB_RRT_POOL_INDEX_BITS);
     return hit ? MPB_RRT_START_OR_GOAL_IN_COLLISION : MPB_RRT_RUNNING;

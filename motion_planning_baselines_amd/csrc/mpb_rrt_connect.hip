@@ -20,9 +20,13 @@
 // per-waypoint collision cost  sum_f s_f sum_l relu(margin + r_l - min_o sdf_o(x_l))  is positive; evaluated with the
 // evaluators of mpb_geom.h (broad-phase grid where the field has one, the compile-time Panda model where geom_flags
 // allows, the exhaustive walk otherwise; chained fields in turn).
+// On a world (mpb_world.h: obstacles OR SDF grid OR the robot against itself) the same tree is grown by rrtc_world_init_kernel /
+// rrtc_world_kernel, and world_check_kernel is the world predicate stand-alone: the *_world entries at the end of this file.
 #include "mpb_common.h"
 #include "mpb_rrt.h"
 #include "mpb_rrt_host.h"
+#include "mpb_world.h"
+#include "mpb_world_host.h"
 
 #define RRT_WORDS_PER_NODE 32.0  // the size bound of rrt_shape_check: two trees, 16 words per node
 
@@ -62,18 +66,43 @@ __global__ __launch_bounds__(256) void collision_check_kernel(const float* __res
     }
 }
 
+// ---- the world predicate (mpb_world.h) stand-alone: flag (N) and the three parts (N, 3) = (c_obs, c_sdf, c_self), one lane per
+// configuration, single-wave workgroups (the self block is per wave).  WORLD == 0 serves a call without either buffer.
+template <int MODEL, int WORLD>
+__global__ __launch_bounds__(64) void world_check_kernel(const float* __restrict__ q_in, const float* __restrict__ geom, const WorldArgs w,
+                                                         unsigned char* __restrict__ flag, float* __restrict__ parts, int N, int D) {
+    __shared__ unsigned gridw[MPB_GRID_MAX_CELLS];
+    __shared__ float4 otab[MPB_GRID_MAX_SPH + 1];
+    extern __shared__ __align__(16) float world_lds[];
+    const int i = blockIdx.x * 64 + threadIdx.x;
+    const float* row = q_in + (size_t)min(i, N - 1) * D;
+    float q[MPB_MAX_DOF];
+    rrt_load_row<MPB_MAX_DOF>(row, D, q);
+    const float* staged = nullptr;
+    const WorldView W = world_view(geom, w, world_lds);
+    const WorldCost c = world_config_cost<MODEL, WORLD>(W, gridw, otab, staged, q);
+    if (i < N) {
+        flag[i] = world_hit(c) ? 1 : 0;
+        if (parts != nullptr) {
+            parts[3 * (size_t)i] = c.obs;
+            parts[3 * (size_t)i + 1] = c.sdf;
+            parts[3 * (size_t)i + 2] = c.self;
+        }
+    }
+}
+
 // ---- workspace initialisation: roots, counts, pool lists, status, start / goal collision check ---------------------
-template <int MODEL>
-__global__ __launch_bounds__(64) void rrt_init_kernel(int* __restrict__ ws, const float* __restrict__ start,
-                                                      const float* __restrict__ goal, const float* __restrict__ geom, int B,
-                                                      int max_nodes, int n_pre, int D) {
+// (the body of rrt_init_kernel and of its world form rrtc_world_init_kernel; W: null with WORLD == 0)
+template <int MODEL, int WORLD>
+__device__ __forceinline__ void rrt_init_body(int* __restrict__ ws, const float* __restrict__ start, const float* __restrict__ goal,
+                                              const float* __restrict__ geom, int B, int max_nodes, int n_pre, int D, const WorldView* W) {
     __shared__ unsigned gridw[MPB_GRID_MAX_CELLS];
     __shared__ float4 otab[MPB_GRID_MAX_SPH + 1];
     const int b = blockIdx.x, lane = threadIdx.x;
     const RrtLayout L = rrt_layout(B, max_nodes, n_pre, D);
     unsigned* pool = reinterpret_cast<unsigned*>(ws) + L.pool + (size_t)b * L.pool_words;
-    const int status = rrt_init_shared<MODEL>(ws, MPB_RRT_CONNECT_MAGIC, B, max_nodes, n_pre, D, L.Dp, pool, L.pool_words, start, goal,
-                                              geom, gridw, otab, b, lane);
+    const int status = rrt_init_shared<MODEL, WORLD>(ws, MPB_RRT_CONNECT_MAGIC, B, max_nodes, n_pre, D, L.Dp, pool, L.pool_words, start, goal,
+                                                     geom, gridw, otab, b, lane, W);
     float* nodes = reinterpret_cast<float*>(ws) + L.nodes + (size_t)b * 2 * max_nodes * L.Dp;
     int* parents = ws + L.parents + (size_t)b * 2 * max_nodes;
     if (lane < L.Dp) {
@@ -89,6 +118,23 @@ __global__ __launch_bounds__(64) void rrt_init_kernel(int* __restrict__ ws, cons
         if (lane == MPB_RRTC_POOL_LEN) v = n_pre;
         H[lane] = v;
     }
+}
+
+template <int MODEL>
+__global__ __launch_bounds__(64) void rrt_init_kernel(int* __restrict__ ws, const float* __restrict__ start,
+                                                      const float* __restrict__ goal, const float* __restrict__ geom, int B,
+                                                      int max_nodes, int n_pre, int D) {
+    rrt_init_body<MODEL, 0>(ws, start, goal, geom, B, max_nodes, n_pre, D, nullptr);
+}
+
+// the same on a world: the start / goal check is the world predicate (a refused header puts every problem in START_OR_GOAL_IN_COLLISION)
+template <int MODEL>
+__global__ __launch_bounds__(64) void rrtc_world_init_kernel(int* __restrict__ ws, const float* __restrict__ start,
+                                                             const float* __restrict__ goal, const float* __restrict__ geom, int B,
+                                                             int max_nodes, int n_pre, int D, const WorldArgs w) {
+    extern __shared__ __align__(16) float world_lds[];
+    const WorldView W = world_view(geom, w, world_lds);
+    rrt_init_body<MODEL, 1>(ws, start, goal, geom, B, max_nodes, n_pre, D, &W);
 }
 
 // The squared distance of the padded tree row `row` to tq (node minus target, index order): RRT-Connect's nearest-node metric.
@@ -131,152 +177,27 @@ struct RrtArgs {
 };
 
 // ---- the persistent kernel ------------------------------------------------------------------------------------------
+// (its body is mpb_rrt_connect_loop.h, which says why it is text included by both kernels)
 template <int DT, int MODEL>
 __global__ __launch_bounds__(64) void rrt_connect_kernel(const RrtArgs a) {
-#pragma clang fp contract(off)
-    __shared__ unsigned gridw[MPB_GRID_MAX_CELLS];
-    __shared__ float4 otab[MPB_GRID_MAX_SPH + 1];
-    __shared__ unsigned short pool[MPB_RRT_MAX_PRE_SAMPLES];
-    constexpr int DM = DT ? DT : MPB_MAX_DOF;
-    const int D = DT ? DT : a.D;
-    const int b = blockIdx.x, lane = threadIdx.x;
-    const RrtLayout L = rrt_layout(a.B, a.max_nodes, a.n_pre, D);
-    int* H = a.ws + L.hdr + (size_t)b * MPB_RRT_CONNECT_HDR_WORDS;
-    int status = H[MPB_RRTC_STATUS];
-    if (status != MPB_RRT_RUNNING) {                       // block-uniform: a finished problem costs nothing
-        if (lane == 0) a.status[b] = status;
-        return;
+    const WorldView* W = nullptr;
+    {
+#define RRT_WORLD 0
+#include "mpb_rrt_connect_loop.h"
+#undef RRT_WORLD
     }
-    int cnt[2] = {H[MPB_RRTC_COUNTS], H[MPB_RRTC_COUNTS + 1]};
-    int bit = H[MPB_RRTC_SWAP], plen = H[MPB_RRTC_POOL_LEN];
-    float* nodes_b = reinterpret_cast<float*>(a.ws) + L.nodes + (size_t)b * 2 * a.max_nodes * L.Dp;
-    int* parents_b = a.ws + L.parents + (size_t)b * 2 * a.max_nodes;
-    unsigned short* pool_g = reinterpret_cast<unsigned short*>(a.ws + L.pool + (size_t)b * L.pool_words);
-    for (int i = lane; i < plen; i += 64) pool[i] = pool_g[i];
-    const float* pre_b = a.pre + (size_t)b * a.pre_stride;
-    float* path_b = a.paths + (size_t)b * a.Lmax * D;
-    const float* staged = nullptr;
-    __syncthreads();
+}
 
-    // one extension (extend_path + safe_path + the append): grows tree t from its node nearest to `tq` towards `tq`;
-    // returns false when the extension's first point is in collision (safe_path's []) or the tree is full
-    float nq[MPB_MAX_DOF];
-    auto extend = [&](int t, const float (&tq)[MPB_MAX_DOF]) -> bool {
-        const float* nd = nodes_b + (size_t)t * a.max_nodes * L.Dp;
-        const int n = cnt[t];
-        float best = 3.0e38f;
-        int bi = 0x7FFFFFFF;
-        for (int i = lane; i < n; i += 64) {
-            const float ds = sqrtf(rrtc_row_d2<DM>(nd + (size_t)i * L.Dp, L.Dp, tq));
-            if (ds < best) { best = ds; bi = i; }
-        }
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            const float od = __shfl_xor(best, off, 64);
-            const int oi = __shfl_xor(bi, off, 64);
-            if (od < best || (od == best && oi < bi)) { best = od; bi = oi; }
-        }
-        const float dist = best;
-        float q1[MPB_MAX_DOF], dl[MPB_MAX_DOF];
-        const float f = (dist > a.radius) ? a.radius / dist : 1.0f;
-#pragma unroll
-        for (int k = 0; k < MPB_MAX_DOF; ++k) {
-            q1[k] = (k < DM && k < D) ? nd[(size_t)bi * L.Dp + k] : 0.f;
-            const float df = tq[k] - q1[k];
-            // (utils.py:7-8: the far end clamped to n_radius; the point count below is from the UNCLAMPED distance)
-            const float q2 = (dist > a.radius) ? fmaf(df, f, q1[k]) : tq[k];
-            dl[k] = q2 - q1[k];
-        }
-        const int n_pts = rrt_point_count(dist, a.step);
-        const float lstep = 1.0f / (float)(n_pts - 1);
-        const int first = rrt_first_collision<DM, MODEL>(a.geom, gridw, otab, staged, q1, dl, n_pts, lstep, lane);
-        if (first == 0) return false;
-        rrt_linspace_point<DM>(q1, dl, n_pts, lstep, first < 0 ? n_pts - 1 : first - 1, nq);
-        if (n >= a.max_nodes) {
-            status = MPB_RRT_TREE_FULL;
-            return false;
-        }
-        float* dst = nodes_b + ((size_t)t * a.max_nodes + n) * L.Dp;
-        float v = 0.f;
-#pragma unroll
-        for (int k = 0; k < DM; ++k) v = (lane == k) ? nq[k] : v;
-        if (lane < L.Dp) dst[lane] = v;
-        if (lane == 0) parents_b[(size_t)t * a.max_nodes + n] = bi;
-        cnt[t] = n + 1;
-        __syncthreads();                                   // the node is read back by the next nearest-node scan
-        return true;
-    };
-
-    int it = a.iter0;
-    const int it_end = min(a.iter0 + a.n_iters, a.total_iters);
-    for (; it < it_end && status == MPB_RRT_RUNNING; ++it) {
-        if (plen == 0) { status = MPB_RRT_POOL_EMPTY; break; }
-        bit ^= 1;                                          // rrt_connect.py:126-128
-        const int t1 = bit, t2 = bit ^ 1;
-        int idx;
-        if (a.sample_idx != nullptr) {
-            idx = a.sample_idx[(size_t)b * a.total_iters + it];
-            idx = min(max(idx, 0), plen - 1);
-        } else {
-            const uint4 r = philox4x32_10(make_uint4(a.problem_offset + (uint32_t)b, (uint32_t)it, MPB_RRT_CONNECT_MAGIC, 0u),
-                                          make_uint2(a.seed_lo, a.seed_hi));
-            idx = (int)__umulhi(r.x, (uint32_t)plen);
-        }
-        const float* trow = pre_b + (size_t)pool[idx] * D;
-        float tq[MPB_MAX_DOF];
-#pragma unroll
-        for (int k = 0; k < MPB_MAX_DOF; ++k) tq[k] = (k < DM && k < D) ? trow[k] : 0.f;
-        if (!extend(t1, tq)) continue;                     // :142-143 -- BEFORE the swap-back (Q15)
-        float n1[MPB_MAX_DOF];
-        bool reached = true;
-#pragma unroll
-        for (int k = 0; k < MPB_MAX_DOF; ++k) {
-            n1[k] = nq[k];
-            if (k < DM && k < D) reached = reached && rrt_close(n1[k], tq[k]);
-        }
-        if (reached) {                                     // :149-150, rrt_base.py:59-63: delete entry idx, keep the order
-            rrt_pool_delete(pool, idx, plen, lane);
-            --plen;
-        }
-        if (!extend(t2, n1)) continue;                     // :161-162
-        bit ^= 1;                                          // :168-170
-        bool joined = true;
-#pragma unroll
-        for (int k = 0; k < MPB_MAX_DOF; ++k)
-            if (k < DM && k < D) joined = joined && rrt_close(n1[k], nq[k]);
-        if (!joined) continue;
-        // ---- :173-185: retrace(n2)[:-1] + reversed(retrace(n1)), then purge_duplicates_from_traj (utils.py:33-50)
-        const float* ndA = nodes_b + (size_t)t2 * a.max_nodes * L.Dp;
-        const float* ndB = nodes_b + (size_t)t1 * a.max_nodes * L.Dp;
-        const int* paA = parents_b + (size_t)t2 * a.max_nodes;
-        const int* paB = parents_b + (size_t)t1 * a.max_nodes;
-        int lenA = 0, lenB = 0;
-        for (int j = paA[cnt[t2] - 1]; j >= 0 && lenA < cnt[t2]; j = paA[j]) ++lenA;
-        for (int j = cnt[t1] - 1; j >= 0 && lenB < cnt[t1]; j = paB[j]) ++lenB;
-        const int Lraw = lenA + lenB;
-        ++it;
-        if (Lraw > a.Lmax) { status = MPB_RRT_PATH_TOO_LONG; break; }
-        {
-            int pos = lenA - 1;
-            for (int j = paA[cnt[t2] - 1]; j >= 0 && pos >= 0; j = paA[j], --pos)
-                if (lane < D) path_b[(size_t)pos * D + lane] = ndA[(size_t)j * L.Dp + lane];
-            pos = lenA;
-            for (int j = cnt[t1] - 1; j >= 0 && pos < Lraw; j = paB[j], ++pos)
-                if (lane < D) path_b[(size_t)pos * D + lane] = ndB[(size_t)j * L.Dp + lane];
-        }
-        __syncthreads();
-        const int len = rrt_purge(path_b, Lraw, D, lane);
-        if (lane == 0) a.lengths[b] = len;
-        status = MPB_RRT_FOUND;
-        break;
-    }
-    if (status == MPB_RRT_RUNNING && it >= a.total_iters) status = MPB_RRT_EXHAUSTED_ITERS;
-    __syncthreads();
-    for (int i = lane; i < plen; i += 64) pool_g[i] = pool[i];
-    if (lane == 0) {
-        H[MPB_RRTC_STATUS] = status; H[MPB_RRTC_ITERS] = it; H[MPB_RRTC_COUNTS] = cnt[0]; H[MPB_RRTC_COUNTS + 1] = cnt[1];
-        H[MPB_RRTC_SWAP] = bit; H[MPB_RRTC_POOL_LEN] = plen;
-        a.status[b] = status;
+// the same tree on a world: every extension point is decided by the world predicate (mpb_world.h); the self blocks are dynamic LDS
+template <int DT, int MODEL>
+__global__ __launch_bounds__(64) void rrtc_world_kernel(const RrtArgs a, const WorldArgs w) {
+    extern __shared__ __align__(16) float world_lds[];
+    const WorldView Wv = world_view(a.geom, w, world_lds);
+    const WorldView* W = &Wv;
+    {
+#define RRT_WORLD 1
+#include "mpb_rrt_connect_loop.h"
+#undef RRT_WORLD
     }
 }
 
@@ -286,16 +207,68 @@ extern "C" size_t mpb_rrt_connect_workspace_bytes(int B, int max_nodes, int n_pr
     return 4 * rrt_layout(B, max_nodes, n_pre, D).total;
 }
 
+// both forms of *_init and *_run: the old entry's checks under the name `who`, then (a buffer given) world_args and the world kernels
+static int rrt_connect_init_impl(const char* who, void* workspace, size_t workspace_bytes, const float* start, const float* goal,
+                                 const float* geom, int geom_flags, const float* sdfb, const float* selfb, int B, int max_nodes, int n_pre,
+                                 int D, void* stream) {
+    int rc = rrt_init_check(who, RRT_WORDS_PER_NODE, B, max_nodes, n_pre, D, !workspace || !start || !goal || !geom, false, workspace, geom,
+                            workspace_bytes, 4 * rrt_layout(B, max_nodes, n_pre, D).total);
+    if (rc != MPB_OK || B == 0) return rc;
+    if (!world_present(sdfb, selfb)) {
+        if (rrt_use_model(geom_flags, D))
+            hipLaunchKernelGGL(rrt_init_kernel<PandaModel::ID>, dim3(B), dim3(64), 0, (hipStream_t)stream, (int*)workspace, start, goal, geom, B, max_nodes, n_pre, D);
+        else
+            hipLaunchKernelGGL(rrt_init_kernel<0>, dim3(B), dim3(64), 0, (hipStream_t)stream, (int*)workspace, start, goal, geom, B, max_nodes, n_pre, D);
+        return mpb_check_launch(who);
+    }
+    WorldArgs w;
+    if ((rc = world_args(who, sdfb, selfb, D, w))) return rc;
+    const size_t lds = world_self_lds_bytes(w, 1);
+    return rrt_dispatch<>(geom_flags, D, [&](auto, auto model) {
+        const int rl = mpb_raise_lds_limit(rrtc_world_init_kernel<model.value>, lds, who);
+        if (rl) return rl;
+        hipLaunchKernelGGL(rrtc_world_init_kernel<model.value>, dim3(B), dim3(64), lds, (hipStream_t)stream, (int*)workspace, start, goal, geom, B,
+                           max_nodes, n_pre, D, w);
+        return mpb_check_launch(who);
+    });
+}
+
+static int rrt_connect_run_impl(const char* who, void* workspace, size_t workspace_bytes, const float* geom, int geom_flags, const float* sdfb,
+                                const float* selfb, const float* pre_samples, size_t pre_stride, const int* sample_idx, float* paths,
+                                int* lengths, int* status, int B, int max_nodes, int n_pre, int D, int Lmax, int iter0, int n_iters,
+                                int total_iters, float step_size, float n_radius, uint64_t seed, uint32_t problem_offset, void* stream) {
+    int rc = rrt_init_check(who, RRT_WORDS_PER_NODE, B, max_nodes, n_pre, D, !workspace || !geom || !pre_samples || !paths || !lengths || !status,
+                            false, workspace, geom, workspace_bytes, 4 * rrt_layout(B, max_nodes, n_pre, D).total);
+    if (rc == MPB_OK) rc = rrt_run_check(who, Lmax, iter0, n_iters, total_iters, true, step_size, n_radius);
+    if (rc != MPB_OK || B == 0) return rc;
+    const RrtArgs a = {(int*)workspace, geom, pre_samples, pre_stride, sample_idx, paths, lengths, status, B, D, max_nodes, n_pre, Lmax,
+                       iter0, n_iters, total_iters, step_size, n_radius, (uint32_t)seed, (uint32_t)(seed >> 32), problem_offset};
+    if (!world_present(sdfb, selfb))
+        return rrt_dispatch<2, 3, 7>(geom_flags, D, [&](auto dt, auto model) {
+            hipLaunchKernelGGL((rrt_connect_kernel<dt.value, model.value>), dim3(B), dim3(64), 0, (hipStream_t)stream, a);
+            return mpb_check_launch(who);
+        });
+    WorldArgs w;
+    if ((rc = world_args(who, sdfb, selfb, D, w))) return rc;
+    const size_t lds = world_self_lds_bytes(w, 1);
+    // (the world kernel is instantiated for the compile-time Panda and for run-time D: DESIGN.md 10)
+    return rrt_dispatch<>(geom_flags, D, [&](auto dt, auto model) {
+        const int rl = mpb_raise_lds_limit(rrtc_world_kernel<dt.value, model.value>, lds, who);
+        if (rl) return rl;
+        hipLaunchKernelGGL((rrtc_world_kernel<dt.value, model.value>), dim3(B), dim3(64), lds, (hipStream_t)stream, a, w);
+        return mpb_check_launch(who);
+    });
+}
+
 extern "C" int mpb_rrt_connect_init(void* workspace, size_t workspace_bytes, const float* start, const float* goal,
                                     const float* geom, int geom_flags, int B, int max_nodes, int n_pre, int D, void* stream) {
-    const int rc = rrt_init_check("mpb_rrt_connect_init", RRT_WORDS_PER_NODE, B, max_nodes, n_pre, D, !workspace || !start || !goal || !geom, false,
-                                  workspace, geom, workspace_bytes, 4 * rrt_layout(B, max_nodes, n_pre, D).total);
-    if (rc != MPB_OK || B == 0) return rc;
-    if (rrt_use_model(geom_flags, D))
-        hipLaunchKernelGGL(rrt_init_kernel<PandaModel::ID>, dim3(B), dim3(64), 0, (hipStream_t)stream, (int*)workspace, start, goal, geom, B, max_nodes, n_pre, D);
-    else
-        hipLaunchKernelGGL(rrt_init_kernel<0>, dim3(B), dim3(64), 0, (hipStream_t)stream, (int*)workspace, start, goal, geom, B, max_nodes, n_pre, D);
-    return mpb_check_launch("mpb_rrt_connect_init");
+    return rrt_connect_init_impl(__func__, workspace, workspace_bytes, start, goal, geom, geom_flags, nullptr, nullptr, B, max_nodes, n_pre, D, stream);
+}
+
+extern "C" int mpb_rrt_connect_init_world(void* workspace, size_t workspace_bytes, const float* start, const float* goal,
+                                          const float* geom, int geom_flags, const float* sdfb, const float* selfb, int B, int max_nodes,
+                                          int n_pre, int D, void* stream) {
+    return rrt_connect_init_impl(__func__, workspace, workspace_bytes, start, goal, geom, geom_flags, sdfb, selfb, B, max_nodes, n_pre, D, stream);
 }
 
 extern "C" int mpb_rrt_connect_run(void* workspace, size_t workspace_bytes, const float* geom, int geom_flags,
@@ -303,16 +276,19 @@ extern "C" int mpb_rrt_connect_run(void* workspace, size_t workspace_bytes, cons
                                    int* lengths, int* status, int B, int max_nodes, int n_pre, int D, int Lmax, int iter0,
                                    int n_iters, int total_iters, float step_size, float n_radius, uint64_t seed,
                                    uint32_t problem_offset, void* stream) {
-    int rc = rrt_init_check("mpb_rrt_connect_run", RRT_WORDS_PER_NODE, B, max_nodes, n_pre, D, !workspace || !geom || !pre_samples || !paths || !lengths || !status,
-                            false, workspace, geom, workspace_bytes, 4 * rrt_layout(B, max_nodes, n_pre, D).total);
-    if (rc == MPB_OK) rc = rrt_run_check("mpb_rrt_connect_run", Lmax, iter0, n_iters, total_iters, true, step_size, n_radius);
-    if (rc != MPB_OK || B == 0) return rc;
-    const RrtArgs a = {(int*)workspace, geom, pre_samples, pre_stride, sample_idx, paths, lengths, status, B, D, max_nodes, n_pre, Lmax,
-                       iter0, n_iters, total_iters, step_size, n_radius, (uint32_t)seed, (uint32_t)(seed >> 32), problem_offset};
-    return rrt_dispatch<2, 3, 7>(geom_flags, D, [&](auto dt, auto model) {
-        hipLaunchKernelGGL((rrt_connect_kernel<dt.value, model.value>), dim3(B), dim3(64), 0, (hipStream_t)stream, a);
-        return mpb_check_launch("mpb_rrt_connect_run");
-    });
+    return rrt_connect_run_impl(__func__, workspace, workspace_bytes, geom, geom_flags, nullptr, nullptr, pre_samples, pre_stride, sample_idx, paths,
+                                lengths, status, B, max_nodes, n_pre, D, Lmax, iter0, n_iters, total_iters, step_size, n_radius, seed,
+                                problem_offset, stream);
+}
+
+extern "C" int mpb_rrt_connect_run_world(void* workspace, size_t workspace_bytes, const float* geom, int geom_flags, const float* sdfb,
+                                         const float* selfb, const float* pre_samples, size_t pre_stride, const int* sample_idx,
+                                         float* paths, int* lengths, int* status, int B, int max_nodes, int n_pre, int D, int Lmax,
+                                         int iter0, int n_iters, int total_iters, float step_size, float n_radius, uint64_t seed,
+                                         uint32_t problem_offset, void* stream) {
+    return rrt_connect_run_impl(__func__, workspace, workspace_bytes, geom, geom_flags, sdfb, selfb, pre_samples, pre_stride, sample_idx, paths,
+                                lengths, status, B, max_nodes, n_pre, D, Lmax, iter0, n_iters, total_iters, step_size, n_radius, seed,
+                                problem_offset, stream);
 }
 
 extern "C" int mpb_collision_check(const float* q, const float* geom, int geom_flags, unsigned char* in_collision, float* gap,
@@ -328,4 +304,30 @@ extern "C" int mpb_collision_check(const float* q, const float* geom, int geom_f
     else
         hipLaunchKernelGGL(collision_check_kernel<0>, grid, dim3(256), 0, (hipStream_t)stream, q, geom, in_collision, gap, N, D);
     return mpb_check_launch("mpb_collision_check");
+}
+
+extern "C" int mpb_world_collision_check(const float* q, const float* geom, int geom_flags, const float* sdfb, const float* selfb,
+                                         unsigned char* in_collision, float* parts, int N, int D, void* stream) {
+    if (D > MPB_MAX_DOF) return mpb_failf(MPB_E_UNSUPPORTED, "%s: D = %d exceeds MPB_MAX_DOF = %d", __func__, D, MPB_MAX_DOF);
+    if (N < 0 || D < 1) return mpb_failf(MPB_E_INVALID, "%s: bad shape", __func__);
+    if (N == 0) return MPB_OK;
+    if (!q || !geom || !in_collision) return mpb_failf(MPB_E_INVALID, "%s: null pointer", __func__);
+    if (mpb_misaligned16(geom)) return mpb_failf(MPB_E_INVALID, "%s: geom must be 16-byte aligned", __func__);
+    WorldArgs w = {};
+    w.n_dof = D;
+    const dim3 grid((N + 63) / 64);
+    if (!world_present(sdfb, selfb))
+        return rrt_dispatch<>(geom_flags, D, [&](auto, auto model) {
+            hipLaunchKernelGGL((world_check_kernel<model.value, 0>), grid, dim3(64), 0, (hipStream_t)stream, q, geom, w, in_collision, parts, N, D);
+            return mpb_check_launch("mpb_world_collision_check");
+        });
+    const int rc = world_args(__func__, sdfb, selfb, D, w);
+    if (rc) return rc;
+    const size_t lds = world_self_lds_bytes(w, 1);
+    return rrt_dispatch<>(geom_flags, D, [&](auto, auto model) {
+        const int rl = mpb_raise_lds_limit(world_check_kernel<model.value, 1>, lds, "mpb_world_collision_check");
+        if (rl) return rl;
+        hipLaunchKernelGGL((world_check_kernel<model.value, 1>), grid, dim3(64), lds, (hipStream_t)stream, q, geom, w, in_collision, parts, N, D);
+        return mpb_check_launch("mpb_world_collision_check");
+    });
 }

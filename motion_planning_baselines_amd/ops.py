@@ -42,7 +42,7 @@ def _on_tensor_device(fn):
     def run(*args, **kw):
         dev = None
         for a in list(args) + list(kw.values()):
-            t = a.buf if isinstance(a, (DeviceGeometry, _DeviceMemberBuffer)) else a
+            t = a.buf if isinstance(a, (DeviceGeometry, _DeviceMemberBuffer, DeviceWorld)) else a
             if isinstance(t, torch.Tensor) and t.is_cuda:
                 if dev is None:
                     dev = t.device
@@ -1402,6 +1402,96 @@ def collision_check(q, geom, with_gap=False):
     return (flag, gap) if with_gap else flag
 
 
+# ---- the world: one in-kernel predicate over obstacles, SDF grid and the robot against itself (csrc/mpb_world.h) --------------------
+def _robot_tables(host, hdr):
+    """(kind, n_dof, joint_tf words, link rows (n_links, 5): frame, offset, radius) of a packed buffer's robot, from its host words."""
+    f = np.asarray(host).view(np.float32)
+    n_tf, n_links, o_tf, o_l = int(hdr['n_tf']), int(hdr['n_links']), int(hdr['off_tf']), int(hdr['off_links'])
+    return (int(hdr['kind']) if 'kind' in hdr.dtype.names else KIND_CHAIN, int(hdr['n_dof']),
+            f[o_tf:o_tf + 12 * n_tf].view(np.uint32), f[o_l:o_l + 8 * n_links].reshape(n_links, 8)[:, :5].view(np.uint32))
+
+
+def check_world_parts(geom_host, sdf_host=None, self_host=None):
+    """The robot-consistency check of DeviceWorld on HOST words (packed geometry, packed SDF-grid buffer or its words before the node
+    section, packed self buffer): every part given must have been packed for the same robot -- kind, n_dof, the joint transforms bit
+    for bit, and link rows (frame, offset, radius) that agree: the SDF and self buffers hold the whole link table and must hold the
+    same one, the geometry's (statically pruned) rows must all be rows of it.  Raises ValueError naming the part."""
+    from .sdf_layout import header as sdf_header
+    from .self_layout import header as self_header
+    kind, n_dof, tf, links = _robot_tables(geom_host, geometry_header(geom_host))
+    whole = None
+    for noun, host, hdr_of in (('SDF-grid', sdf_host, sdf_header), ('self-collision', self_host, self_header)):
+        if host is None:
+            continue
+        k2, d2, tf2, links2 = _robot_tables(host, hdr_of(host))
+        if d2 != n_dof:
+            raise ValueError(f'DeviceWorld: the {noun} buffer was packed for a robot of n_dof = {d2}, the geometry for n_dof = {n_dof}')
+        if k2 != kind:
+            raise ValueError(f'DeviceWorld: the {noun} buffer was packed for another kind of robot (point / chain) than the geometry')
+        if tf2.shape != tf.shape or not np.array_equal(tf2, tf):
+            raise ValueError(f'DeviceWorld: the {noun} buffer was packed for another robot than the geometry (joint transforms differ)')
+        if whole is not None and (links2.shape != whole.shape or not np.array_equal(links2, whole)):
+            raise ValueError(f'DeviceWorld: the {noun} buffer was packed for another robot than the SDF-grid buffer (link tables differ)')
+        whole = links2
+    if whole is not None:
+        rows = {r.tobytes() for r in whole}
+        if any(r.tobytes() not in rows for r in links):
+            raise ValueError('DeviceWorld: the geometry was packed for another robot than the other parts (a link row of its table is '
+                             'not in theirs)')
+
+
+class DeviceWorld:
+    """What the in-kernel world predicate reads (csrc/mpb_world.h): a DeviceGeometry and, each optional, a DeviceSDFGrid
+    and a DeviceSelfCollision, all packed for the same robot (check_world_parts).  A configuration is in collision iff one of the
+    three stand-alone predicates says so.  Accepted wherever world_collision_check, rrt_init / rrt_connect_run on an RRT-Connect
+    workspace, path_shortcut and traj_collision_stats accept a DeviceGeometry: they then call the *_world entries.  With neither
+    optional part those entries launch the old kernels."""
+
+    def __init__(self, geom, sdf=None, self_collision=None):
+        if not isinstance(geom, DeviceGeometry):
+            raise TypeError('DeviceWorld(geom, ...): geom must be a DeviceGeometry')
+        if sdf is not None and not isinstance(sdf, DeviceSDFGrid):
+            raise TypeError('DeviceWorld(..., sdf=): a DeviceSDFGrid or None')
+        if self_collision is not None and not isinstance(self_collision, DeviceSelfCollision):
+            raise TypeError('DeviceWorld(..., self_collision=): a DeviceSelfCollision or None')
+        check_world_parts(geom.host, None if sdf is None else sdf.host, None if self_collision is None else self_collision.host)
+        for part in (sdf, self_collision):
+            if part is not None and part.buf.device != geom.buf.device:
+                raise ValueError(f'DeviceWorld: its parts live on different devices ({geom.buf.device} and {part.buf.device})')
+        self.geom, self.sdf, self.self_collision = geom, sdf, self_collision
+        # (a DeviceWorld stands in for its geometry: the wrappers read these three of either)
+        self.buf, self.flags, self.n_dof = geom.buf, geom.flags, geom.n_dof
+
+    def extra(self):
+        """(sdfb, selfb) as the *_world entries take them: null where a part is absent."""
+        return _ptr(None if self.sdf is None else self.sdf.buf), _ptr(None if self.self_collision is None else self.self_collision.buf)
+
+
+def _need_geometry(geom, what):
+    if isinstance(geom, DeviceWorld):
+        raise NotImplementedError(f'{what} reads the obstacle geometry alone and does not take a DeviceWorld; the world is served by '
+                                  f'world_collision_check, rrt_connect_run, path_shortcut and traj_collision_stats')
+
+
+@_on_tensor_device
+def world_collision_check(q, world, with_parts=False):
+    """(N, D) configurations -> bool (N,): in collision with the world -- obstacles, SDF grid or the robot itself -- in ONE launch
+    (mpb_world_collision_check); with_parts also returns (N, 3) fp32 = (c_obs, c_sdf, c_self), the gaps of collision_check,
+    sdf_grid_check and self_collision_check bit for bit, 0 where a part is absent."""
+    if not isinstance(world, DeviceWorld):
+        raise TypeError('world_collision_check takes an ops.DeviceWorld')
+    N, D = q.shape
+    _chk(q, (N, D), 'q')
+    if D != world.n_dof:
+        raise ValueError(f'q has {D} columns, the world {world.n_dof} degrees of freedom')
+    flag = torch.empty(N, device=q.device, dtype=torch.bool)
+    parts = torch.empty(N, 3, device=q.device, dtype=torch.float32) if with_parts else None
+    sdfb, selfb = world.extra()
+    _lib.check(_lib.lib().mpb_world_collision_check(_ptr(q), _ptr(world.buf), int(world.flags), sdfb, selfb, _ptr(flag), _ptr(parts), N, D,
+                                                    _stream()), 'mpb_world_collision_check')
+    return (flag, parts) if with_parts else flag
+
+
 # ---- end effector: pose, Jacobian, batched inverse kinematics (csrc/mpb_ik.hip) ----------------------------------------------------
 IK_MAX_ITERS, IK_MIN_DAMPING = 1024, 1e-2          # include/mpb.h MPB_IK_MAX_ITERS, MPB_IK_MIN_DAMPING
 
@@ -1612,6 +1702,12 @@ def traj_collision_stats(trajs, geom, n_interp=5, with_flags=False):
     first = torch.empty(N, device=trajs.device, dtype=torch.int32)
     gap = torch.empty(N, device=trajs.device, dtype=torch.float32)
     flags = torch.empty(N, max(P, 0), device=trajs.device, dtype=torch.bool) if with_flags else None
+    if isinstance(geom, DeviceWorld):
+        # (the world predicate on the dense points; max_gap: the largest sum of the three parts)
+        _lib.check(_lib.lib().mpb_traj_collision_stats_world(_ptr(trajs), W, _ptr(geom.buf), int(geom.flags), *geom.extra(), n, _ptr(count),
+                                                             _ptr(first), _ptr(gap), _ptr(flags), N, H, D, _stream()),
+                   'mpb_traj_collision_stats_world')
+        return (count, first, gap, flags) if with_flags else (count, first, gap)
     _lib.check(_lib.lib().mpb_traj_collision_stats(_ptr(trajs), W, _ptr(geom.buf), int(geom.flags), n, _ptr(count), _ptr(first),
                                                    _ptr(gap), _ptr(flags), N, H, D, _stream()), 'mpb_traj_collision_stats')
     return (count, first, gap, flags) if with_flags else (count, first, gap)
@@ -1646,6 +1742,13 @@ def rrt_init(ws_buf, ws, start, goal, geom):
     _chk(goal, (ws.B, ws.D), 'goal')
     if ws.D != geom.n_dof:
         raise ValueError(f'the problems have {ws.D} columns, the geometry {geom.n_dof} degrees of freedom')
+    if isinstance(geom, DeviceWorld):
+        if ws.kind != 'connect':
+            _need_geometry(geom, f'mpb_rrt_{ws.kind}_init')
+        _lib.check(_lib.lib().mpb_rrt_connect_init_world(_ptr(ws_buf), ws.nbytes, _ptr(start), _ptr(goal), _ptr(geom.buf), int(geom.flags),
+                                                         *geom.extra(), ws.B, ws.max_nodes, ws.n_pre, ws.D, _stream()),
+                   'mpb_rrt_connect_init_world')
+        return
     sym = f'mpb_rrt_{ws.kind}_init'
     _lib.check(getattr(_lib.lib(), sym)(_ptr(ws_buf), ws.nbytes, _ptr(start), _ptr(goal), _ptr(geom.buf), int(geom.flags), ws.B,
                                         ws.max_nodes, ws.n_pre, ws.D, _stream()), sym)
@@ -1677,6 +1780,12 @@ def rrt_connect_run(ws_buf, ws, geom, pre_samples, sample_idx, paths, lengths, s
     B, D = ws.B, ws.D
     stride, Lmax = _rrt_run_shapes(ws, pre_samples, paths, lengths, status)
     _chk(sample_idx, (B, total_iters), 'sample_idx', allow_none=True, dtype=torch.int32)
+    if isinstance(geom, DeviceWorld):
+        _lib.check(_lib.lib().mpb_rrt_connect_run_world(
+            _ptr(ws_buf), ws.nbytes, _ptr(geom.buf), int(geom.flags), *geom.extra(), _ptr(pre_samples), stride, _ptr(sample_idx),
+            _ptr(paths), _ptr(lengths), _ptr(status), B, ws.max_nodes, ws.n_pre, D, Lmax, int(iter0), int(n_iters), int(total_iters),
+            float(step_size), float(n_radius), _seed64(seed), int(problem_offset) & 0xFFFFFFFF, _stream()), 'mpb_rrt_connect_run_world')
+        return
     _lib.check(_lib.lib().mpb_rrt_connect_run(
         _ptr(ws_buf), ws.nbytes, _ptr(geom.buf), int(geom.flags), _ptr(pre_samples), stride, _ptr(sample_idx), _ptr(paths),
         _ptr(lengths), _ptr(status), B, ws.max_nodes, ws.n_pre, D, Lmax, int(iter0), int(n_iters), int(total_iters),
@@ -1691,6 +1800,7 @@ def rrt_star_run(ws_buf, ws, geom, pre_samples, sample_idx, goal_draw, paths, le
     pre_samples (n_pre, D) shared or (B, n_pre, D); sample_idx and goal_draw both None (device Philox) or both
     (B, total_iters) int32.  paths / lengths / costs hold the current best path of every problem with a goal node after
     every call."""
+    _need_geometry(geom, 'mpb_rrt_star_run')
     B, D = ws.B, ws.D
     stride, Lmax = _rrt_run_shapes(ws, pre_samples, paths, lengths, status)
     if (sample_idx is None) != (goal_draw is None):
@@ -1990,6 +2100,12 @@ def path_shortcut(paths, lengths, geom, n_iters, check_step, draws=None, seed=0,
         _chk(lengths_out, (N,), 'out[1]', dtype=torch.int32)
     stats = torch.empty(N, 4, device=paths.device, dtype=torch.float32)
     log = torch.empty(N, max(n_iters, 0), device=paths.device, dtype=torch.int32) if with_log else None
+    if isinstance(geom, DeviceWorld):
+        _lib.check(_lib.lib().mpb_path_shortcut_world(_ptr(paths), _ptr(lengths), _ptr(paths_out), _ptr(lengths_out), _ptr(stats), _ptr(log),
+                                                      _ptr(geom.buf), int(geom.flags), *geom.extra(), _ptr(draws), N, Lmax, D, n_iters,
+                                                      float(check_step), _seed64(seed), int(problem_offset) & 0xFFFFFFFF, _stream()),
+                   'mpb_path_shortcut_world')
+        return (paths_out, lengths_out, stats, log) if with_log else (paths_out, lengths_out, stats)
     _lib.check(_lib.lib().mpb_path_shortcut(_ptr(paths), _ptr(lengths), _ptr(paths_out), _ptr(lengths_out), _ptr(stats), _ptr(log),
                                             _ptr(geom.buf), int(geom.flags), _ptr(draws), N, Lmax, D, n_iters, float(check_step),
                                             _seed64(seed), int(problem_offset) & 0xFFFFFFFF, _stream()), 'mpb_path_shortcut')

@@ -1,7 +1,8 @@
 """What the batched sample-based planners share (the reference keeps its own in mp_baselines/planners/rrt_base.py): the pool of
 pre-samples, the problems' starts and goals, and the driver that runs B problems to completion in launches of `chunk_iters` iterations.
-RRTConnect (rrt_connect.py) and RRTStar (rrt_star.py) add their refusals, their constructor arguments, their workspace kind, the
-recorded draws they accept and the launch of one chunk.
+RRTConnect (rrt_connect.py) and RRTStar (rrt_star.py) add their constructor arguments, their workspace kind, the recorded draws they
+accept, the launch of one chunk, and what they are launched on (`_scene`): the family refuses a task with a self_field or an sdf_field
+by name -- its kernels' predicate knows obstacles only --, RRTConnect alone serves one built with world_predicate=True.
 
 Differences from the reference they share, all documented in DESIGN.md section 10:
   - `max_time` is honoured between launches of `chunk_iters` iterations (default 1024), not per iteration;
@@ -36,10 +37,7 @@ class RRTBase(MPPlanner):
         super().__init__(name=self.NAME, tensor_args=tensor_args)
         self.device = require_cuda(tensor_args)
         self.task = task
-        if getattr(task, 'self_field', None) is not None:       # (the kernels' in-kernel predicate knows obstacles only)
-            task.require_no_self_field(f'{self.NAME} (the batched RRT kernels)')
-        if getattr(task, 'sdf_field', None) is not None:
-            task.require_no_sdf_field(f'{self.NAME} (the batched RRT kernels)')
+        self.scene = self._scene(task)
         self.n_iters = int(n_iters)
         self.step_size, self.n_radius, self.max_time = float(step_size), float(n_radius), float(max_time)
         self.start_state_pos, self.goal_state_pos = start_state_pos, goal_state_pos
@@ -58,6 +56,15 @@ class RRTBase(MPPlanner):
         self.max_path_nodes = int(max_path_nodes)
         self.workspace = self.status = None
         self.reset()
+
+    def _scene(self, task):
+        """What the planner's kernels are launched on.  Their in-kernel predicate knows obstacles only: a task with a self_field or
+        an sdf_field is refused by name (RRTConnect overrides this: it serves a task built with world_predicate=True)."""
+        if getattr(task, 'self_field', None) is not None:
+            task.require_no_self_field(f'{self.NAME} (the batched RRT kernels)')
+        if getattr(task, 'sdf_field', None) is not None:
+            task.require_no_sdf_field(f'{self.NAME} (the batched RRT kernels)')
+        return task.geom
 
     def reset(self):
         """Top the pool up to n_pre_samples collision-free configurations (rrt_base.py:47-54)."""
@@ -83,7 +90,7 @@ class RRTBase(MPPlanner):
         goals = self.goals.repeat(n_copies, 1) if n_copies > 1 else self.goals
         B, D = starts.shape
         ws = self.Workspace(B, self.max_nodes, self.n_pre_samples, D, self.device)
-        ops.rrt_init(ws.buf, ws, starts, goals, self.task.geom)
+        ops.rrt_init(ws.buf, ws, starts, goals, self.scene)
         out = self._outputs(B, D)
         status = out['status']
         if any(d is None for d in draws) != all(d is None for d in draws):

@@ -17,6 +17,12 @@ from .rrt_base import RRTBase, paths_to_list  # noqa: F401  (paths_to_list: call
 class RRTConnect(RRTBase):
     NAME, Workspace = 'RRTConnect', ops.RRTWorkspace
 
+    def _scene(self, task):
+        """task.world on a task built with world_predicate=True (the tree is then grown against obstacles, SDF grid and the robot
+        itself: mpb_rrt_connect_*_world), else task.geom after the family's refusals."""
+        world = getattr(task, 'world', None)
+        return world if world is not None else super()._scene(task)
+
     def optimize_batched(self, sample_idx=None, n_copies=1, problem_offset=0, **observation):
         """All problems (every start / goal row, n_copies times, copy-major) in one launch sequence.
         sample_idx: None (device Philox; problem b draws from stream problem_offset + b) or (B, n_iters + 1) int32 recorded
@@ -26,5 +32,5 @@ class RRTConnect(RRTBase):
         return out['paths'], out['lengths'], out['status']
 
     def _launch(self, ws, draws, out, it, n, problem_offset):
-        ops.rrt_connect_run(ws.buf, ws, self.task.geom, self.pre_samples, draws[0], out['paths'], out['lengths'], out['status'], it, n,
+        ops.rrt_connect_run(ws.buf, ws, self.scene, self.pre_samples, draws[0], out['paths'], out['lengths'], out['status'], it, n,
                             self.total_iters, self.step_size, self.n_radius, seed=self.seed, problem_offset=problem_offset)

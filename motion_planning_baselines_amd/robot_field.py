@@ -171,12 +171,18 @@ class PlanningTask:
     (mpb_collision_check; the same evaluators as every cost kernel).  `field` may be a list of up to four fields.
 
     self_field: a geometry.SelfCollisionField (the reference's use_self_collision_storm=True).  compute_collision and
-    random_coll_free_q then OR the self predicate in (a second launch, mpb_self_collision_check with or_into); the trajectory
-    validation below and the RRT planners built on the task read `geom` alone and raise NotImplementedError rather than ignore
-    it.
+    random_coll_free_q then OR the self predicate in (a second launch, mpb_self_collision_check with or_into); without
+    world_predicate the trajectory validation below and the RRT planners built on the task read `geom` alone and raise
+    NotImplementedError rather than ignore it.
 
     sdf_field: a geometry.GridSDFField (a precomputed grid of signed distances: geometry the obstacle list cannot hold).  Its predicate
     (mpb_sdf_grid_collision_check with or_into) is ORed in the same way, and the same callers refuse such a task by name.
+
+    world_predicate=True (opt-in): the task builds `world`, an ops.DeviceWorld of geom, sdf_geom and self_geom, and the
+    in-kernel world predicate -- obstacles OR grid OR self, one launch -- serves _in_collision, RRTConnect (and through it
+    MultiSampleBasedPlanner and HybridPlanner), shortcut_paths / RRTConnect.shortcut and the four validation calls.  RRTStar,
+    InfRRTStar, PRM, STRRTConnect, shortcut_trajs_moving, certify_* and compute_clearance keep refusing a task with a self_field or an
+    sdf_field by name.
 
     A geometry.MovingObstacleField is none of these: it is refused by name as field, self_field or sdf_field (the predicates and the
     sample-based planners have no time axis).  check_trajs_moving(trajs, moving_field) validates trajectories against the task's static
@@ -188,7 +194,7 @@ class PlanningTask:
     first row one of the predicates above refuses (mpb_cartesian_path; unlike validation and shortcutting it serves a task with a
     self_field or an sdf_field)."""
 
-    def __init__(self, robot, field, self_field=None, tensor_args=None, seed=0, sdf_field=None):
+    def __init__(self, robot, field, self_field=None, tensor_args=None, seed=0, sdf_field=None, world_predicate=False):
         from .planners.base import require_cuda
         self.tensor_args = tensor_args
         self.device = require_cuda(tensor_args)
@@ -205,6 +211,8 @@ class PlanningTask:
         self.self_geom = None if self_field is None else ops.DeviceSelfCollision(robot, self_field, self.device)
         self.sdf_field = sdf_field
         self.sdf_geom = None if sdf_field is None else ops.DeviceSDFGrid(robot, sdf_field, self.device)
+        self.world_predicate = bool(world_predicate)
+        self.world = ops.DeviceWorld(self.geom, sdf=self.sdf_geom, self_collision=self.self_geom) if self.world_predicate else None
         self.q_dim = robot.q_dim
         self.q_min = robot.q_min.to(self.device)
         self.q_max = robot.q_max.to(self.device)
@@ -218,7 +226,9 @@ class PlanningTask:
 
     def _in_collision(self, q2):
         """(N, D) contiguous fp32 on the device -> bool (N,): collides with the world, (self_field) with itself or (sdf_field) with
-        what the grid holds."""
+        what the grid holds (world_predicate: the one fused launch)."""
+        if self.world is not None:
+            return ops.world_collision_check(q2, self.world)
         flag = ops.collision_check(q2, self.geom)
         for own in (self.self_geom, self.sdf_geom):
             if own is not None:
@@ -337,15 +347,28 @@ class PlanningTask:
         mo = self._moving_geom(moving_field, n_rows)
         return ops.st_shortcut(t.contiguous(), self.geom, mo, w, n_iters, valid=valid, **kw)
 
+    # what serves a task with an sdf_field / a self_field instead of the caller that refuses it
+    _SERVED = ('PlanningTask(..., world_predicate=True) serves RRTConnect, MultiSampleBasedPlanner, HybridPlanner, shortcut_paths and the '
+               'trajectory validation on such a task')
+
     def require_no_sdf_field(self, what):
         if self.sdf_field is not None:
             raise NotImplementedError(f'{what} reads the obstacle geometry alone: it does not serve a task with an sdf_field '
-                                      f'(GridSDFField) yet')
+                                      f'(GridSDFField) yet; {self._SERVED}')
 
     def require_no_self_field(self, what):
         if self.self_field is not None:
             raise NotImplementedError(f'{what} reads the obstacle geometry alone: it does not serve a task with a self_field '
-                                      f'(SelfCollisionField) yet')
+                                      f'(SelfCollisionField) yet; {self._SERVED}')
+
+    def world_or_geom(self, what):
+        """What a kernel with the world predicate is launched on: `world` where the task was built with world_predicate=True, else
+        `geom` -- after refusing, by name, a task whose self_field or sdf_field that kernel would then ignore."""
+        if self.world is not None:
+            return self.world
+        self.require_no_self_field(what)
+        self.require_no_sdf_field(what)
+        return self.geom
 
     def random_q(self, n_samples=1):
         """n_samples configurations uniform within the joint limits, (n_samples, D)."""
@@ -462,13 +485,12 @@ class PlanningTask:
     def _trajs_stats(self, trajs, num_interpolation, with_flags=False):
         """trajs (..., H, W), W >= q_dim, leading dimensions flattened -> (trajs (N, H, W), the outputs of
         ops.traj_collision_stats).  A contiguous fp32 GPU tensor is read in place, velocity columns and all."""
-        self.require_no_self_field('trajectory validation (mpb_traj_collision_stats)')
-        self.require_no_sdf_field('trajectory validation (mpb_traj_collision_stats)')
+        geom = self.world_or_geom('trajectory validation (mpb_traj_collision_stats)')
         t = torch.as_tensor(trajs, dtype=torch.float32, device=self.device)
         if t.dim() < 2 or t.shape[-1] < self.q_dim:
             raise ValueError(f'trajs has shape {tuple(t.shape)}, expected (..., H, W) with W >= {self.q_dim}')
         t = t.reshape(-1, t.shape[-2], t.shape[-1]).contiguous()
-        return t, ops.traj_collision_stats(t, self.geom, n_interp=int(num_interpolation), with_flags=with_flags)
+        return t, ops.traj_collision_stats(t, geom, n_interp=int(num_interpolation), with_flags=with_flags)
 
     def get_trajs_collision_and_free(self, trajs, return_indices=False, num_interpolation=5, **kwargs):
         """(trajs_coll, trajs_free): the trajectories with a dense point in collision and those without, each (n, H, W) in
@@ -551,11 +573,10 @@ class PlanningTask:
     def shortcut_paths(self, paths, lengths, n_iters=64, check_step=0.05, **kwargs):
         """(paths (N, Lmax, D), lengths (N,) int32) device tensors -> (paths, lengths, stats (N, 4)): n_iters shortcut attempts
         per path against this task's obstacle geometry, checked at spacing check_step (ops.path_shortcut, which also takes the
-        keyword arguments draws, seed, problem_offset, with_log, out).  The in-kernel predicate knows obstacles only: a task with
-        a self_field or an sdf_field is refused by name."""
-        self.require_no_self_field('path shortcutting (mpb_path_shortcut)')
-        self.require_no_sdf_field('path shortcutting (mpb_path_shortcut)')
-        return ops.path_shortcut(paths, lengths, self.geom, n_iters, check_step, **kwargs)
+        keyword arguments draws, seed, problem_offset, with_log, out).  Without world_predicate the in-kernel predicate knows
+        obstacles only and a task with a self_field or an sdf_field is refused by name; with it the candidates are checked against the
+        world (mpb_path_shortcut_world)."""
+        return ops.path_shortcut(paths, lengths, self.world_or_geom('path shortcutting (mpb_path_shortcut)'), n_iters, check_step, **kwargs)
 
     # ---- time parameterisation of a trajectory batch (build-defined: DESIGN.md 10) -------------------------------------------------
     def retime_trajs(self, trajs, dt=None, v_max=None, a_max=None, scale=1.0, **kwargs):
