@@ -52,6 +52,9 @@
 /* path certification by clearance bisection in numbers (generated from certify_layout.py): statuses MPB_CERT_*, the interval word, limits,
  * the reach buffer's header, the default slack */
 #include "mpb_certify_layout.h"
+/* space-time certification among moving obstacles in numbers (generated from st_certify_layout.py): MPB_STC_NOT_VALID, the words of a
+ * trajectory's outputs, MPB_STC_NO_OBSTACLE, the default slack */
+#include "mpb_st_certify_layout.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -95,7 +98,8 @@ extern "C" {
  *                        moving obstacles (mpb_path_time_plan), and space-time shortcutting (mpb_st_shortcut): additive.  So were
  *                        the clearance op and the path certifier (mpb_clearance, mpb_path_certify), and the world predicate and the
  *                        *_world entries (mpb_world_collision_check, mpb_rrt_connect_init_world / _run_world, mpb_path_shortcut_world,
- *                        mpb_traj_collision_stats_world). */
+ *                        mpb_traj_collision_stats_world).  So were the clearance of a timed trajectory's rows against a moving field
+ *                        and the space-time certifier (mpb_moving_clearance, mpb_traj_certify_moving): additive. */
 #define MPB_ABI_VERSION 7
 #define MPB_VERSION_TUNING_BUILD 0x40000000
 int mpb_version(void);
@@ -1505,6 +1509,60 @@ int mpb_path_shortcut_world(const float *paths_in, const int *lengths_in, float 
 int mpb_traj_collision_stats_world(const float *trajs, size_t row_stride, const float *geom, int geom_flags, const float *sdfb,
                                    const float *selfb, int n_interp, int *n_in_collision, int *first_in_collision, float *max_gap,
                                    unsigned char *point_in_collision, int N, int H, int D, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Clearance of a timed trajectory against a moving-obstacle field, and the certificate that it is free over the whole CONTINUUM of its
+ * clock, between the rows too (build-defined; definition, proof and what is not built: DESIGN.md 10).  Every other entry that sees a
+ * moving-obstacle buffer decides collisions at the rows only.
+ * The continuum.  A trajectory of R rows and the packed moving-obstacle buffer of the same R rows (mpb_moving_check's format): for
+ * segment h = 0 .. R - 2 and s in [0, 1] the robot stands at q(h, s) = q_h + s (q_{h+1} - q_h) and moving obstacle o (spheres first,
+ * then boxes) has its centre on the CHORD c_o(h, s) = c_{o,h} + s (c_{o,h+1} - c_{o,h}) of the buffer's own per-row centres; boxes
+ * translate and do not rotate.  The static scene is the geometry chain `geom`, as in mpb_path_certify.
+ *   eta_l(h, s) = min( eta_static_l(q),  min_o sd_o(x_l(q); c_o(h, s)) - (margin_moving + r_l) ),     eta = min_l eta_l
+ * eta_static_l is mpb_clearance's eta_l, bit for bit; margin_moving is the buffer's header word.  At a node (s = 0) the sign of the
+ * moving part is mpb_moving_collision_check's answer for that row up to ties within the slack (thr = margin + r_l rounded once as there).
+ * Motion bound.  sphere_sd and box_sd are 1-Lipschitz in the query point AND in the centre.  Over a parameter half-width w about a
+ * midpoint the pair (robot sphere l, moving obstacle o) changes its distance by at most w (Lambda_l + V_{o,h}): Lambda_l the reach sum
+ * of mpb_path_certify (the same reach buffer, the same MPB_CERT_LAMBDA_INFLATE), V_{o,h} = |c_{o,h+1} - c_{o,h}| formed per lane in
+ * fp32 from the two rows' centres and inflated the same way; a static pair by w Lambda_l.
+ *
+ * mpb_moving_clearance: trajs of N x R rows read in place (row h of trajectory n starts at trajs + (n*R + h)*row_stride, its first D
+ *   floats are read); eta (N, R), link (N, R) the arg-min robot sphere (lowest index on a tie) and obstacle (N, R) the arg-min
+ *   obstacle of every row AT ITS OWN TIME: o >= 0 a moving obstacle, -1 - f the static field f of the chain (a tie between the two:
+ *   the static scene).  link and obstacle may be NULL.  One lane per (trajectory, row).  A geometry or moving header that differs
+ *   from what the launcher read: eta = NaN, link = -1, obstacle = MPB_STC_NO_OBSTACLE.
+ *   Refusals, in this order: D > MPB_MAX_DOF, R outside 1 .. MPB_MOVING_MAX_ROWS: MPB_E_UNSUPPORTED; N < 0, D < 1, row_stride < D:
+ *   MPB_E_INVALID; (N == 0: MPB_OK;) a null trajs / geom / moving / eta, geom or moving not 16-byte aligned: MPB_E_INVALID; the
+ *   moving header's refusals (read once per address: mpb_moving_invalidate), its n_dof != D, its n_rows != R: MPB_E_INVALID.
+ *
+ * mpb_traj_certify_moving: the bisection of mpb_path_certify on that continuum.  Level -1: every node against its own row's centres;
+ *   eta - c_req < -S: MPB_CERT_COLLISION, witness (row, s = 0).  Level d = 0, 1, ...: interval j of segment h has the midpoint
+ *   parameter s = (2j + 1) 2^-(d+1), the half-width w = 2^-(d+1), the robot at fmaf(q_{h+1} - q_h, s, q_h) and obstacle o at
+ *   fmaf(c_{o,h+1} - c_{o,h}, s, c_{o,h}) per coordinate, and is
+ *     FREE       when min over pairs of (eta_pair - w bound_pair) - c_req > S  (then eta - c_req > S on the closed interval),
+ *     COLLISION  when eta - c_req < -S at the midpoint,
+ *     else split; the queue order, max_depth, max_intervals and the statuses are mpb_path_certify's, unchanged in meaning
+ *   (MPB_CERT_BAD_INPUT: a non-finite coordinate; MPB_CERT_BUFFER_CHANGED: a geometry, moving or reach header that differs from what
+ *   the launcher read -- nothing else of the buffers is read).
+ *   out_i (N, MPB_STC_OUT_INTS): status, witness row h, witness link, witness obstacle (o >= 0 moving, -1 - f static field f),
+ *   n_evals, depth_max; out_f (N, MPB_STC_OUT_FLOATS): witness s, witness eta, margin_cert (-inf unless MPB_CERT_FREE).  Without a
+ *   witness: row = link = -1, obstacle = MPB_STC_NO_OBSTACLE, s = eta = 0.  The witness TIME t_start + (h + s) dt_row is the
+ *   caller's to form (in fp64: the buffer carries no clock).  MPB_STC_NOT_VALID is never written by the kernel: it is what a caller
+ *   gives a trajectory it did not submit.
+ *   The certificate is about the CHORD motion of the buffer's centres.  Where the field's own motion has a keyframe strictly inside
+ *   a row interval the caller raises c_req by the largest deviation of the two (st_certify_layout.chord_deviation, host, fp64).
+ *   One single-wave workgroup per trajectory, the level's queue in LDS, no atomics, every loop bounded: the same bits on every run.
+ *   Refusals, in this order, all before the launch: D > MPB_MAX_DOF, R outside 1 .. MPB_MOVING_MAX_ROWS, max_depth outside
+ *   0 .. MPB_CERT_MAX_DEPTH, max_intervals outside 1 .. MPB_CERT_MAX_INTERVALS, n_links outside 1 .. MPB_MOVING_MAX_LINKS:
+ *   MPB_E_UNSUPPORTED, each by name; N < 0, D < 1, row_stride < D, S not finite or negative, c_req not finite: MPB_E_INVALID;
+ *   (N == 0: MPB_OK;) a null required pointer, geom / moving / reach not 16-byte aligned: MPB_E_INVALID; the moving header's
+ *   refusals, its n_dof != D, its n_rows != R, its n_links != n_links: MPB_E_INVALID.
+ * ------------------------------------------------------------------------------------------- */
+int mpb_moving_clearance(const float *trajs, size_t row_stride, const float *geom, const float *moving, float *eta, int *link,
+                         int *obstacle, int N, int R, int D, void *stream);
+int mpb_traj_certify_moving(const float *trajs, size_t row_stride, const float *geom, const float *moving, const float *reach,
+                            int n_links, float S, float c_req, int max_depth, int max_intervals, int *out_i, float *out_f, int N,
+                            int R, int D, void *stream);
 
 #ifdef __cplusplus
 }

@@ -111,6 +111,8 @@ SIGNATURES = {
     'mpb_traj_retime_sample': [_p, ctypes.c_size_t] + [_p] * 7 + [_i] * 3 + [_f, _i, _p],
     'mpb_clearance': [_p, _p, _p, _p, _i, _i, _p],
     'mpb_path_certify': [_p, ctypes.c_size_t, _p, _p, _p, _i, _f, _f, _i, _i, _p, _p, _i, _i, _i, _p],
+    'mpb_moving_clearance': [_p, ctypes.c_size_t, _p, _p, _p, _p, _p, _i, _i, _i, _p],
+    'mpb_traj_certify_moving': [_p, ctypes.c_size_t, _p, _p, _p, _i, _f, _f, _i, _i, _p, _p, _i, _i, _i, _p],
     'mpb_world_collision_check': [_p, _p, _i, _p, _p, _p, _p, _i, _i, _p],
     'mpb_rrt_connect_init_world': [_p, ctypes.c_size_t, _p, _p, _p, _i, _p, _p, _i, _i, _i, _i, _p],
     'mpb_rrt_connect_run_world': [_p, ctypes.c_size_t, _p, _i, _p, _p, _p, ctypes.c_size_t, _p, _p, _p, _p] + [_i] * 8 + [_f, _f, _u64, _u32, _p],

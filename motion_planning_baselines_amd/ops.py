@@ -12,7 +12,7 @@ import warnings
 import numpy as np
 import torch
 
-from . import _lib, certify_layout, path_timing_layout, rrt_layout, st_shortcut_layout, strrt_layout
+from . import _lib, certify_layout, path_timing_layout, rrt_layout, st_certify_layout, st_shortcut_layout, strrt_layout
 from .geometry import KIND_CHAIN, MAX_FIELDS, CollisionField, TriangleMesh, count_fields, mesh_pose, occupancy_bytes, pack_geometry, pack_mesh, pack_moving_obstacles, pack_sdf_grid, pack_self_collision
 from .geometry import header as geometry_header
 
@@ -2393,3 +2393,105 @@ def path_certify(paths, geom, reach, lengths=None, slack=None, c_req=0.0, max_de
                                            float(c_req), int(max_depth), int(max_intervals), _ptr(out_i), _ptr(out_f), N, H, D, _stream()),
                'mpb_path_certify')
     return PathCertificate(out_i, out_f, slack, c_req)
+
+
+# ---- clearance and certification of timed trajectories among moving obstacles (csrc/mpb_certify_moving.hip; st_certify_layout.py) ------
+STC_STATUS_NAMES = st_certify_layout.STATUS
+STC_NOT_VALID = len(CERT_STATUS_NAMES)                 # (the values before it are CERT_FREE .. CERT_BUFFER_CHANGED)
+STC_NO_OBSTACLE = st_certify_layout.STC_NO_OBSTACLE
+STC_DEFAULT_SLACK = st_certify_layout.STC_DEFAULT_SLACK
+
+
+def _moving_certify_args(what, trajs, geom, mo):
+    """The shape checks moving_clearance and traj_certify_moving share: (N, R, W, D)."""
+    if not isinstance(geom, DeviceGeometry):
+        raise TypeError(f'{what} takes the DeviceGeometry of the static scene')
+    if not isinstance(mo, DeviceMovingObstacles):
+        raise TypeError(f'{what} takes a DeviceMovingObstacles')
+    if not (isinstance(trajs, torch.Tensor) and trajs.is_cuda):
+        raise _lib.MPBError(f'{what}: trajs must be a GPU tensor; there is no CPU fallback')
+    if trajs.dim() != 3:
+        raise ValueError(f'trajs has shape {tuple(trajs.shape)}, expected (N, R, W)')
+    N, R, W = trajs.shape
+    _chk(trajs, (N, R, W), 'trajs')
+    D = geom.n_dof
+    if W < D:
+        raise ValueError(f'trajs has {W} columns, the geometry {D} degrees of freedom')
+    if (mo.n_dof, mo.n_links) != (geom.n_dof, geom.n_links):
+        raise ValueError(f'{what}: the moving-obstacle buffer is of a robot with {mo.n_dof} joints and {mo.n_links} collision spheres, the '
+                         f'geometry of one with {geom.n_dof} and {geom.n_links}')
+    if R != mo.n_rows:
+        raise ValueError(f'{what}: trajs has n_rows = {R}, the moving-obstacle buffer was packed for n_rows = {mo.n_rows}')
+    _need_whole_link_table(geom, what)
+    if geom.buf.device != trajs.device or mo.buf.device != trajs.device:
+        raise ValueError(f'{what}: trajs, the geometry and the moving-obstacle buffer must live on one device')
+    return N, R, W, D
+
+
+@_on_tensor_device
+def moving_clearance(trajs, geom, mo, with_args=False):
+    """trajs (N, R, W), R == mo.n_rows, read in place (the first D columns of a row) -> eta fp32 (N, R): the clearance of every row AT ITS
+    OWN TIME against the static geometry and the obstacles of a DeviceMovingObstacles as they stand at that row (mpb_moving_clearance;
+    include/mpb.h has the definition): the quantitative counterpart of moving_collision_check OR collision_check.  with_args also returns
+    the arg-min robot sphere int32 (N, R) and the arg-min obstacle int32 (N, R): o >= 0 a moving obstacle (spheres first, then boxes),
+    -1 - f the static field f."""
+    N, R, W, D = _moving_certify_args('moving_clearance', trajs, geom, mo)
+    eta = torch.empty(N, R, device=trajs.device, dtype=torch.float32)
+    link = torch.empty(N, R, device=trajs.device, dtype=torch.int32) if with_args else None
+    obst = torch.empty(N, R, device=trajs.device, dtype=torch.int32) if with_args else None
+    _lib.check(_lib.lib().mpb_moving_clearance(_ptr(trajs), W, _ptr(geom.buf), _ptr(mo.buf), _ptr(eta), _ptr(link), _ptr(obst), N, R, D, _stream()),
+               'mpb_moving_clearance')
+    return (eta, link, obst) if with_args else eta
+
+
+class TrajCertificate:
+    """What traj_certify_moving returns, per trajectory (N,): status int32 (CERT_FREE / CERT_COLLISION / CERT_UNDECIDED_DEPTH /
+    CERT_UNDECIDED_QUEUE / CERT_BAD_INPUT / CERT_BUFFER_CHANGED, and STC_NOT_VALID for a trajectory a caller did not submit), free /
+    collision / undecided bool; the witness of a COLLISION -- witness_row int32 (the segment h; a node: its row and s = 0), witness_s
+    fp32, witness_time fp64 = t_start + (h + s) dt_row formed on the host, witness_link int32, witness_obstacle int32 (o >= 0 a moving
+    obstacle, -1 - f the static field f), witness_eta fp32; -1, 0, NaN, -1, STC_NO_OBSTACLE, 0 without one --; n_evals int32, depth_max
+    int32 (-1: nodes only), margin_cert fp32 a certified lower bound of the continuum's clearance minus c_req, up to the slack (-inf
+    unless FREE); slack and c_req as the launch took them (c_req: the EFFECTIVE one), and the scalar chord_deviation the caller
+    reports (0.0 from ops.traj_certify_moving, which certifies the chord motion)."""
+
+    def __init__(self, out_i, out_f, slack, c_req, t_start, dt_row, chord_deviation=0.0):
+        self.status, self.witness_row, self.witness_link, self.witness_obstacle, self.n_evals, self.depth_max = (out_i[:, k] for k in range(6))
+        self.witness_s, self.witness_eta, self.margin_cert = (out_f[:, k] for k in range(3))
+        self.free, self.collision = self.status == CERT_FREE, self.status == CERT_COLLISION
+        self.undecided = (self.status == CERT_UNDECIDED_DEPTH) | (self.status == CERT_UNDECIDED_QUEUE)
+        time = float(t_start) + (self.witness_row.double() + self.witness_s.double()) * float(dt_row)
+        self.witness_time = torch.where(self.collision, time, torch.full_like(time, float('nan')))
+        self.slack, self.c_req, self.chord_deviation = float(slack), float(c_req), float(chord_deviation)
+
+
+@_on_tensor_device
+def traj_certify_moving(trajs, geom, mo, reach, slack=None, c_req=0.0, max_depth=certify_layout.CERT_DEFAULT_MAX_DEPTH,
+                        max_intervals=certify_layout.CERT_DEFAULT_MAX_INTERVALS):
+    """trajs (N, R, W), R == mo.n_rows, read in place -> a TrajCertificate: is the timed trajectory free of the static geometry AND of
+    the moving obstacles over the whole continuum of its clock -- the robot on the joint-space polyline through the rows, every obstacle
+    on the chord between its centres of consecutive rows -- with clearance above c_req?  Bisection with a motion bound in which the
+    obstacles move too (mpb_traj_certify_moving; include/mpb.h has the definition).  This call certifies the CHORD motion and takes
+    c_req as given; PlanningTask.certify_trajs_moving raises it by the field's chord deviation.  slack: the S of the definition,
+    STC_DEFAULT_SLACK (measured: st_certify_layout.py) when None.  The witness time is formed from mo.field's clock."""
+    what = 'traj_certify_moving'
+    N, R, W, D = _moving_certify_args(what, trajs, geom, mo)
+    if (reach.n_dof, reach.n_links, reach.kind) != (geom.n_dof, geom.n_links, geom.kind):
+        raise ValueError(f'{what}: the reach buffer is of a robot with {reach.n_dof} joints and {reach.n_links} collision spheres '
+                         f'(kind {reach.kind}), the geometry of one with {geom.n_dof} and {geom.n_links} (kind {geom.kind})')
+    if reach.buf.device != trajs.device:
+        raise ValueError(f'{what}: trajs and the reach buffer must live on one device')
+    if not 0 <= int(max_depth) <= certify_layout.CERT_MAX_DEPTH:
+        raise ValueError(f'{what}: max_depth = {max_depth} outside 0 .. CERT_MAX_DEPTH = {certify_layout.CERT_MAX_DEPTH} (the j field of the interval word)')
+    if not 1 <= int(max_intervals) <= certify_layout.CERT_MAX_INTERVALS:
+        raise ValueError(f'{what}: max_intervals = {max_intervals} outside 1 .. CERT_MAX_INTERVALS = {certify_layout.CERT_MAX_INTERVALS} (the queue lives in LDS)')
+    slack = STC_DEFAULT_SLACK if slack is None else float(slack)
+    if not (math.isfinite(slack) and slack >= 0.0 and math.isfinite(float(c_req))):
+        raise ValueError(f'{what}: slack = {slack} must be finite and >= 0, c_req = {c_req} finite')
+    out_i = torch.empty(N, st_certify_layout.STC_OUT_INTS, device=trajs.device, dtype=torch.int32)
+    out_f = torch.empty(N, st_certify_layout.STC_OUT_FLOATS, device=trajs.device, dtype=torch.float32)
+    _lib.check(_lib.lib().mpb_traj_certify_moving(_ptr(trajs), W, _ptr(geom.buf), _ptr(mo.buf), _ptr(reach.buf), int(reach.n_links), slack,
+                                                  float(c_req), int(max_depth), int(max_intervals), _ptr(out_i), _ptr(out_f), N, R, D, _stream()),
+               'mpb_traj_certify_moving')
+    f = mo.field
+    dt_row = (float(f.t_end) - float(f.t_start)) / (R - 1) if R > 1 else 0.0
+    return TrajCertificate(out_i, out_f, slack, c_req, f.t_start, dt_row)

@@ -157,6 +157,24 @@ class STRRTConnect(MPPlanner):
         kw.setdefault('seed', self.seed)
         return ops.st_shortcut(result.trajs, self.task.geom, self.moving, self.w, n_iters, valid=result.found, **kw)
 
+    def certify(self, result, c_req=0.0, **kw):
+        """Certify the found trajectories of an optimize_batched record over the whole continuum of their clock
+        (PlanningTask.certify_trajs_moving on this planner's field: the static obstacles and the moving ones between the rows too, the
+        required clearance raised by the field's chord deviation; **kw: max_depth, max_intervals, slack).  Only the `found` plans are
+        submitted; the others come out with status ops.STC_NOT_VALID and the outputs of a trajectory without a witness (-1, 0, NaN,
+        -1, ops.STC_NO_OBSTACLE, 0; n_evals 0, depth_max -1, margin_cert -inf).  Returns an ops.TrajCertificate over all B problems."""
+        found = result.found
+        B = found.shape[0]
+        idx = torch.nonzero(found).flatten()
+        part = self.task.certify_trajs_moving(result.trajs[idx].contiguous(), self.moving_field, c_req=c_req, **kw)
+        dev = result.trajs.device
+        out_i = torch.tensor([ops.STC_NOT_VALID, -1, -1, ops.STC_NO_OBSTACLE, 0, -1], device=dev, dtype=torch.int32).repeat(B, 1)
+        out_f = torch.tensor([0.0, 0.0, float('-inf')], device=dev, dtype=torch.float32).repeat(B, 1)
+        if idx.numel():
+            out_i[idx] = torch.stack([part.status, part.witness_row, part.witness_link, part.witness_obstacle, part.n_evals, part.depth_max], 1)
+            out_f[idx] = torch.stack([part.witness_s, part.witness_eta, part.margin_cert], 1)
+        return ops.TrajCertificate(out_i, out_f, part.slack, part.c_req, self.moving_field.t_start, self.dt_row, part.chord_deviation)
+
     def optimize(self, opt_iters=None, **observation):
         """One problem: the (R, D) trajectory or None; several: a list of those."""
         r = self.optimize_batched(**observation)

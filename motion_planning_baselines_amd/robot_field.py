@@ -181,7 +181,7 @@ class PlanningTask:
     world_predicate=True (opt-in): the task builds `world`, an ops.DeviceWorld of geom, sdf_geom and self_geom, and the
     in-kernel world predicate -- obstacles OR grid OR self, one launch -- serves _in_collision, RRTConnect (and through it
     MultiSampleBasedPlanner and HybridPlanner), shortcut_paths / RRTConnect.shortcut and the four validation calls.  RRTStar,
-    InfRRTStar, PRM, STRRTConnect, shortcut_trajs_moving, certify_* and compute_clearance keep refusing a task with a self_field or an
+    InfRRTStar, PRM, STRRTConnect, shortcut_trajs_moving, certify_* and compute_clearance(_moving) keep refusing a task with a self_field or an
     sdf_field by name.
 
     A geometry.MovingObstacleField is none of these: it is refused by name as field, self_field or sdf_field (the predicates and the
@@ -204,7 +204,8 @@ class PlanningTask:
                 raise TypeError(f'PlanningTask({name}=...): a MovingObstacleField is no static field -- the task\'s predicates, samplers and '
                                 f'the RRT / PRM / shortcut kernels have no time axis.  Plan among it with planners.STRRTConnect(task, moving_field, n_rows, ...), '
                                 f'freeze it with field.at(t), give it to the optimisers '
-                                f'as CostCollision(field=...), and validate trajectories with check_trajs_moving(trajs, moving_field)')
+                                f'as CostCollision(field=...), validate trajectories with check_trajs_moving(trajs, moving_field) and certify them between the '
+                                f'rows with certify_trajs_moving(trajs, moving_field) (certify_paths / certify_trajs have no clock)')
         self.robot, self.field = robot, field
         self.geom = ops.DeviceGeometry(robot, field, self.device)
         self.self_field = self_field
@@ -568,6 +569,47 @@ class PlanningTask:
         if t.dim() < 2 or t.shape[-1] < self.q_dim:
             raise ValueError(f'trajs has shape {tuple(t.shape)}, expected (..., H, W) with W >= {self.q_dim}')
         return ops.path_certify(t.reshape(-1, t.shape[-2], t.shape[-1]).contiguous(), geom, reach, **kwargs)
+
+    # ---- clearance and the certificate of a timed trajectory among moving obstacles (build-defined: DESIGN.md 10) -----------------------
+    def _moving_certify_args(self, what, trajs, moving_field):
+        """(flat trajs (N, R, W), leading shape, geometry with the whole link table, reach buffer, the packed buffer of (field, R))."""
+        from .geometry import MovingObstacleField
+        geom, reach = self._certify_buffers(what)
+        if not isinstance(moving_field, MovingObstacleField):
+            raise TypeError(f'{what.split(" ")[0]} takes a geometry.MovingObstacleField')
+        t = torch.as_tensor(trajs, dtype=torch.float32, device=self.device)
+        if t.dim() < 2 or t.shape[-1] < self.q_dim:
+            raise ValueError(f'trajs has shape {tuple(t.shape)}, expected (..., R, W) with W >= {self.q_dim}')
+        lead = tuple(t.shape[:-2])
+        t = t.reshape(-1, t.shape[-2], t.shape[-1]).contiguous()
+        return t, lead, geom, reach, self._moving_geom(moving_field, t.shape[1])
+
+    def compute_clearance_moving(self, trajs, moving_field, return_args=False):
+        """trajs (..., R, W), W >= q_dim -> eta (..., R): the signed clearance of every row at ITS OWN TIME of the field's clock over R
+        rows, from the task's static obstacles and the moving ones, margins taken off (ops.moving_clearance): eta < 0 is
+        check_trajs_moving's answer for the row, eta is how far it is from flipping.  return_args adds the arg-min collision sphere and
+        the arg-min obstacle (o >= 0 a moving obstacle, -1 - f the static field f), int32 (..., R)."""
+        t, lead, geom, _, mo = self._moving_certify_args('compute_clearance_moving (mpb_moving_clearance)', trajs, moving_field)
+        eta, link, obst = ops.moving_clearance(t, geom, mo, with_args=True)
+        R = t.shape[1]
+        return (eta.reshape(*lead, R), link.reshape(*lead, R), obst.reshape(*lead, R)) if return_args else eta.reshape(*lead, R)
+
+    def certify_trajs_moving(self, trajs, moving_field, c_req=0.0, max_depth=None, max_intervals=None, slack=None):
+        """trajs (..., R, W), W >= q_dim, leading dimensions flattened -> an ops.TrajCertificate over the N flattened trajectories: which
+        timed plans are free of the task's static obstacles AND of a geometry.MovingObstacleField over the whole continuum of the clock
+        of R rows, with clearance above c_req -- where check_trajs_moving looks at the rows only (ops.traj_certify_moving, which has the
+        definition).  The kernel certifies the chord motion between the rows' centres; the field's own motion is piecewise linear
+        between keyframes, and a keyframe strictly inside a row interval makes the two differ by at most chord_deviation
+        (st_certify_layout.chord_deviation, fp64): the required clearance is raised by it, c_req_eff = c_req + chord_deviation, so that
+        FREE is a statement about the field's own motion.  The result reports chord_deviation and, as c_req, the effective value."""
+        from . import certify_layout, st_certify_layout
+        t, lead, geom, reach, mo = self._moving_certify_args('certify_trajs_moving (mpb_traj_certify_moving)', trajs, moving_field)
+        dev = st_certify_layout.chord_deviation(moving_field, t.shape[1])
+        cert = ops.traj_certify_moving(t, geom, mo, reach, slack=slack, c_req=float(c_req) + dev,
+                                       max_depth=certify_layout.CERT_DEFAULT_MAX_DEPTH if max_depth is None else max_depth,
+                                       max_intervals=certify_layout.CERT_DEFAULT_MAX_INTERVALS if max_intervals is None else max_intervals)
+        cert.chord_deviation = dev
+        return cert
 
     # ---- shortcutting of a path batch (build-defined: DESIGN.md 10) ------------------------------------------------------------
     def shortcut_paths(self, paths, lengths, n_iters=64, check_step=0.05, **kwargs):
