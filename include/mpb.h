@@ -55,6 +55,8 @@
 /* space-time certification among moving obstacles in numbers (generated from st_certify_layout.py): MPB_STC_NOT_VALID, the words of a
  * trajectory's outputs, MPB_STC_NO_OBSTACLE, the default slack */
 #include "mpb_st_certify_layout.h"
+/* linear segments with parabolic blends in numbers (generated from blend_layout.py): statuses MPB_BLEND_*, the default sweep limit */
+#include "mpb_blend_layout.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -99,7 +101,8 @@ extern "C" {
  *                        the clearance op and the path certifier (mpb_clearance, mpb_path_certify), and the world predicate and the
  *                        *_world entries (mpb_world_collision_check, mpb_rrt_connect_init_world / _run_world, mpb_path_shortcut_world,
  *                        mpb_traj_collision_stats_world).  So were the clearance of a timed trajectory's rows against a moving field
- *                        and the space-time certifier (mpb_moving_clearance, mpb_traj_certify_moving): additive. */
+ *                        and the space-time certifier (mpb_moving_clearance, mpb_traj_certify_moving): additive.  So were linear
+ *                        segments with parabolic blends (mpb_path_blend, mpb_path_blend_sample): additive. */
 #define MPB_ABI_VERSION 7
 #define MPB_VERSION_TUNING_BUILD 0x40000000
 int mpb_version(void);
@@ -1416,6 +1419,61 @@ int mpb_traj_retime(const float *trajs, size_t row_stride, const float *v_max, c
 int mpb_traj_retime_sample(const float *trajs, size_t row_stride, const float *x, const float *u, const float *t,
                            const int *retime_status, float *out, int *n_rows, int *status, int N, int H, int D, float dt,
                            int T_rows, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Linear segments with parabolic blends: a joint-space polyline turned into a trajectory a controller can run (Kunz & Stilman 2012,
+ * the idea behind MoveIt's TOTG; the reference has none: build-defined, DESIGN.md 10 has the proofs).  Constant velocity along
+ * every segment, a constant-acceleration blend around every waypoint, a cap on how far a blend may leave its corner.  The limits
+ * hold for EVERY t (not at samples), the trajectory is C1 and rest to rest, and every point of it lies within a known per-joint
+ * distance of a point of the polyline.  It is NOT time-optimal.  Two launches: the timing, then the trajectory sampled at a fixed
+ * control period.  No atomics: the same bits on every run.  Every operation below is rounded to fp32 on its own (no fma).
+ *
+ * mpb_path_blend: paths: N paths of H rows read in place as mpb_traj_retime reads them (row h of path n starts at
+ *   paths + (n*H + h)*row_stride, its first D floats are the joint positions q_h); lengths (N) int32 or NULL (every path has H rows):
+ *   path n is the polyline through its rows 0 .. L-1, 2 <= L <= H, the rows past them are never read.  v_max, a_max (D) device fp32,
+ *   finite and > 0; max_deviation = delta > 0, a joint-space infinity-norm in rad, +inf: no cap; max_sweeps >= 1
+ *   (MPB_BLEND_DEFAULT_MAX_SWEEPS).
+ *   Segments i = 0 .. L-2, waypoints i = 0 .. L-1, dq_i = q_{i+1} - q_i, T_i = max_k (|dq_ik| / v_k) to start with.  Then, repeated:
+ *     v_i = dq_i / T_i, v_{-1} = v_{L-1} = 0;  dv_i = v_i - v_{i-1};  tb_i = max_k (|dv_ik| / a_k);  mdv_i = max_k |dv_ik|;
+ *     cap_i = (8 delta) / mdv_i, none where mdv_i == 0 or delta = +inf;  m_i = min(T_{i-1}, T_i, cap_i) over those that exist.
+ *     Waypoint i is in violation iff tb_i > m_i.  No waypoint in violation: done.  Otherwise, when max_sweeps rescalings have been
+ *     made: MPB_BLEND_NOT_CONVERGED; else f_i = sqrt(m_i / tb_i) at the waypoints in violation and 1 elsewhere, and
+ *     T_i <- T_i / min(f_i, f_{i+1}) for every segment: one more rescaling (slowing both segments of a waypoint by f scales its tb by
+ *     f and its T and cap by 1 / f).
+ *   Then tw_0 = tb_0 * 0.5, tw_{i+1} = tw_i + T_i summed in this order, duration = tw_{L-1} + tb_{L-1} * 0.5,
+ *   dev_i = (mdv_i * tb_i) * 0.125 = max_k |dv_ik| tb_i / 8: inside the blend of waypoint i joint k is never farther than
+ *   |dv_ik| tb_i / 8 <= delta from the polyline; tb_i <= min(T_{i-1}, T_i): neighbouring blends do not overlap.
+ *   Outputs: T (N,H-1), tb, tw, dev (N,H), duration (N), sweeps (N) int32 the rescalings made, status (N) int32, first_bad (N) int32.
+ *   MPB_BLEND_DEGENERATE_SEGMENT: a segment with max_k |dq_ik| == 0 (the caller purges duplicates), first_bad its index (the lowest);
+ *   MPB_BLEND_BAD_INPUT: a length outside 2 .. H, a non-finite coordinate in the path's rows, a limit that is not finite and > 0;
+ *   first_bad is -1 except for a DEGENERATE_SEGMENT.  A path that is not MPB_BLEND_OK has zeros in T, tb, tw, dev and duration 0;
+ *   an OK path has zeros at and past its length.
+ *   Refusals, in this order, all before the first HIP call: D > MPB_MAX_DOF; H > MPB_MAX_H: MPB_E_UNSUPPORTED; H < 2, N < 0, D < 1
+ *   or row_stride < D; max_deviation not > 0 or NaN; max_sweeps < 1; a null pointer (lengths may be NULL): MPB_E_INVALID.
+ *   N == 0: MPB_OK, nothing launched.
+ *
+ * mpb_path_blend_sample: paths, lengths as above, T, tb, tw, duration, blend_status as mpb_path_blend wrote them -> out (N,T_rows,3D):
+ *   row k of path n is the state (positions, velocities, accelerations) at tau = fl32(k * dt); n_rows (N) int32, status (N) int32.
+ *   With a_i = dv_i / tb_i, 0 where tb_i == 0 (v, dv formed from the rows and T as above):
+ *   tau >= duration: the last waypoint at rest.  Else j the last waypoint with tw_j <= tau (none: the window of waypoint 0; j = L-1:
+ *     its window); tau is in the window of j when tau - tw_j <= tb_j * 0.5, else in that of j + 1 when tw_{j+1} - tau <= tb_{j+1} * 0.5,
+ *     else on segment j.  In the window of waypoint i, d = tau - tw_i, s = d + tb_i * 0.5:
+ *       q = (q_i + v_{i-1} d) + ((a_i s) s) * 0.5,  qd = v_{i-1} + a_i s,  qdd = a_i;
+ *     on segment j, d = tau - tw_j:  q = q_j + v_j d,  qd = v_j,  qdd = 0.
+ *   Row 0 is q_0 at rest exactly (s = 0, v_{-1} = 0).
+ *   n_rows = ceil(duration / dt) + 1, the quotient of the two fp32 values taken in fp64 (beyond an int: INT_MAX); n_rows > T_rows:
+ *   MPB_BLEND_TOO_LONG, the T_rows rows that fit are still written.  blend_status != MPB_BLEND_OK: that status, n_rows = 0, every row
+ *   holds the first waypoint at rest (so does a length outside 2 .. H or a duration that is not finite: MPB_BLEND_BAD_INPUT).
+ *   Refusals, in this order, all before the first HIP call: D > MPB_MAX_DOF; H > MPB_MAX_H: MPB_E_UNSUPPORTED; H < 2, N < 0, D < 1
+ *   or row_stride < D; dt not finite or <= 0; T_rows < 1; N * ceil(T_rows / 256) beyond an int; a null pointer (lengths may be
+ *   NULL): MPB_E_INVALID.  N == 0: MPB_OK, nothing launched.
+ * ------------------------------------------------------------------------------------------- */
+int mpb_path_blend(const float *paths, size_t row_stride, const int *lengths, const float *v_max, const float *a_max,
+                   float max_deviation, int max_sweeps, float *T, float *tb, float *tw, float *dev, float *duration, int *sweeps,
+                   int *status, int *first_bad, int N, int H, int D, void *stream);
+int mpb_path_blend_sample(const float *paths, size_t row_stride, const int *lengths, const float *T, const float *tb,
+                          const float *tw, const float *duration, const int *blend_status, float *out, int *n_rows, int *status,
+                          int N, int H, int D, float dt, int T_rows, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Clearance, and the certificate that a joint-space polyline is free BETWEEN its samples (build-defined; definition, proof and

@@ -109,6 +109,8 @@ SIGNATURES = {
     'mpb_prm_query': [_p] * 14 + [_i] * 6 + [_p],
     'mpb_traj_retime': [_p, ctypes.c_size_t] + [_p] * 7 + [_i] * 3 + [_f, _f, _p],
     'mpb_traj_retime_sample': [_p, ctypes.c_size_t] + [_p] * 7 + [_i] * 3 + [_f, _i, _p],
+    'mpb_path_blend': [_p, ctypes.c_size_t, _p, _p, _p, _f, _i] + [_p] * 8 + [_i] * 3 + [_p],
+    'mpb_path_blend_sample': [_p, ctypes.c_size_t] + [_p] * 9 + [_i] * 3 + [_f, _i, _p],
     'mpb_clearance': [_p, _p, _p, _p, _i, _i, _p],
     'mpb_path_certify': [_p, ctypes.c_size_t, _p, _p, _p, _i, _f, _f, _i, _i, _p, _p, _i, _i, _i, _p],
     'mpb_moving_clearance': [_p, ctypes.c_size_t, _p, _p, _p, _p, _p, _i, _i, _i, _p],

@@ -10,7 +10,7 @@ import tempfile
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 # (mpb_lib.hip and mpb_stomp_api.hip are host code only: the library-wide part of the C-ABI and the STOMP entry points)
-SOURCES = ['mpb_lib.hip', 'mpb_stomp_api.hip', 'mpb_kernels.hip', 'mpb_stomp_fused.hip', 'mpb_stomp_fused_hx.hip', 'mpb_chomp.hip', 'mpb_gpmp2.hip', 'mpb_gpmp2_lr.hip', 'mpb_mppi.hip', 'mpb_prior.hip', 'mpb_stoch_gpmp.hip', 'mpb_costs.hip', 'mpb_points.hip', 'mpb_mt19937.hip', 'mpb_rrt_connect.hip', 'mpb_rrt_star.hip', 'mpb_path_shortcut.hip', 'mpb_prm.hip', 'mpb_traj_validate.hip', 'mpb_retime.hip', 'mpb_self_collision.hip', 'mpb_sdf_grid.hip', 'mpb_sdf_mesh.hip', 'mpb_moving_obstacles.hip', 'mpb_strrt.hip', 'mpb_path_timing.hip', 'mpb_st_shortcut.hip', 'mpb_ik.hip', 'mpb_ee_cost.hip', 'mpb_cartesian.hip', 'mpb_certify.hip', 'mpb_certify_moving.hip']
+SOURCES = ['mpb_lib.hip', 'mpb_stomp_api.hip', 'mpb_kernels.hip', 'mpb_stomp_fused.hip', 'mpb_stomp_fused_hx.hip', 'mpb_chomp.hip', 'mpb_gpmp2.hip', 'mpb_gpmp2_lr.hip', 'mpb_mppi.hip', 'mpb_prior.hip', 'mpb_stoch_gpmp.hip', 'mpb_costs.hip', 'mpb_points.hip', 'mpb_mt19937.hip', 'mpb_rrt_connect.hip', 'mpb_rrt_star.hip', 'mpb_path_shortcut.hip', 'mpb_prm.hip', 'mpb_traj_validate.hip', 'mpb_retime.hip', 'mpb_self_collision.hip', 'mpb_sdf_grid.hip', 'mpb_sdf_mesh.hip', 'mpb_moving_obstacles.hip', 'mpb_strrt.hip', 'mpb_path_timing.hip', 'mpb_st_shortcut.hip', 'mpb_ik.hip', 'mpb_ee_cost.hip', 'mpb_cartesian.hip', 'mpb_certify.hip', 'mpb_certify_moving.hip', 'mpb_path_blend.hip']
 # the test aids (include/mpb_debug.h) are a library of their own: the product library exports the product ABI only
 DEBUG_SOURCES = ['mpb_debug.hip']
 # per-file extra flags: the latency-bound single-wave-per-problem kernels (CHOMP, GPMP2 solve, MPPI) gain 3-10 % from
@@ -84,7 +84,7 @@ def _stale():
         return True
     t = min(os.path.getmtime(OUT), os.path.getmtime(DEBUG_OUT))
     deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(('.hip', '.h'))]
-    deps += [os.path.join(os.path.dirname(HERE), 'include', h) for h in ('mpb.h', 'mpb_geom_layout.h', 'mpb_rrt_layout.h', 'mpb_self_layout.h', 'mpb_sdf_layout.h', 'mpb_mesh_layout.h', 'mpb_moving_layout.h', 'mpb_strrt_layout.h', 'mpb_path_timing_layout.h', 'mpb_st_shortcut_layout.h', 'mpb_certify_layout.h', 'mpb_st_certify_layout.h', 'mpb_debug.h')]
+    deps += [os.path.join(os.path.dirname(HERE), 'include', h) for h in ('mpb.h', 'mpb_geom_layout.h', 'mpb_rrt_layout.h', 'mpb_self_layout.h', 'mpb_sdf_layout.h', 'mpb_mesh_layout.h', 'mpb_moving_layout.h', 'mpb_strrt_layout.h', 'mpb_path_timing_layout.h', 'mpb_st_shortcut_layout.h', 'mpb_certify_layout.h', 'mpb_st_certify_layout.h', 'mpb_blend_layout.h', 'mpb_debug.h')]
     return any(os.path.getmtime(d) > t for d in deps)
 
 

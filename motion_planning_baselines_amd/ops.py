@@ -12,7 +12,7 @@ import warnings
 import numpy as np
 import torch
 
-from . import _lib, certify_layout, path_timing_layout, rrt_layout, st_certify_layout, st_shortcut_layout, strrt_layout
+from . import _lib, blend_layout, certify_layout, path_timing_layout, rrt_layout, st_certify_layout, st_shortcut_layout, strrt_layout
 from .geometry import KIND_CHAIN, MAX_FIELDS, CollisionField, TriangleMesh, count_fields, mesh_pose, occupancy_bytes, pack_geometry, pack_mesh, pack_moving_obstacles, pack_sdf_grid, pack_self_collision
 from .geometry import header as geometry_header
 
@@ -2282,6 +2282,102 @@ def traj_retime_sample(trajs, timing, dt, n_rows=None):
         _lib.check(_lib.lib().mpb_traj_retime_sample(_ptr(trajs), W, _ptr(timing.x), _ptr(timing.u), _ptr(timing.t), _ptr(timing.status),
                                                      _ptr(out), _ptr(rows), _ptr(status), N, H, D, dt, n_rows, _stream()),
                    'mpb_traj_retime_sample')
+    return out, rows, status
+
+
+# ---- linear segments with parabolic blends (csrc/mpb_path_blend.hip; the definition: include/mpb.h; blend_layout.py) ------
+BLEND_STATUS = blend_layout.STATUS
+BLEND_OK, BLEND_NOT_CONVERGED, BLEND_DEGENERATE_SEGMENT, BLEND_BAD_INPUT, BLEND_TOO_LONG = range(len(BLEND_STATUS))
+
+BlendTiming = collections.namedtuple('BlendTiming', 'T tb tw dev duration sweeps status first_bad lengths max_deviation n_dof')
+BlendTiming.__doc__ = """What path_blend returns: T (N, H-1) the segment durations, tb (N, H) the blend durations, tw (N, H) the times of
+the waypoints, dev (N, H) = max_k |dv_ik| tb_i / 8 how far the blend of waypoint i leaves the polyline (joint-space infinity-norm),
+duration (N,), sweeps (N,) int32 rescalings made, status (N,) int32 BLEND_OK / BLEND_NOT_CONVERGED / BLEND_DEGENERATE_SEGMENT /
+BLEND_BAD_INPUT, first_bad (N,) int32 the segment of a DEGENERATE_SEGMENT (-1 otherwise); lengths (N,) int32 or None, max_deviation
+and n_dof = D as the launch took them.  A path that is not OK has zeros everywhere, an OK one at and past its length."""
+
+
+def _blend_paths(paths, lengths, what):
+    if not (isinstance(paths, torch.Tensor) and paths.is_cuda):
+        raise _lib.MPBError(f'{what}: paths must be a GPU tensor; there is no CPU fallback')
+    if paths.dim() != 3:
+        raise ValueError(f'paths has shape {tuple(paths.shape)}, expected (N, H, W)')
+    _chk(paths, tuple(paths.shape), 'paths')
+    _chk(lengths, (paths.shape[0],), 'lengths', allow_none=True, dtype=torch.int32)
+    return paths.shape
+
+
+@_on_tensor_device
+def path_blend(paths, v_max, a_max, lengths=None, max_deviation=None, max_sweeps=blend_layout.BLEND_DEFAULT_MAX_SWEEPS):
+    """N joint-space polylines -> linear segments with parabolic blends under per-joint velocity / acceleration limits, in one launch
+    (mpb_path_blend; include/mpb.h has the definition, DESIGN.md 10 the proofs).  paths (N, H, W) is read in place, the first
+    D = len(v_max) columns of a row are the joint positions; lengths (N,) int32 or None: path n is the polyline through its first
+    lengths[n] rows (what the RRT planners, shortcut_paths and path_certify take).  v_max, a_max: (D,) finite and > 0.  max_deviation:
+    how far a blend may leave its corner, a joint-space infinity-norm in rad; None or inf: no cap.
+
+    GUARANTEES: the limits hold for EVERY t, not at samples; the trajectory is C1, rest to rest, starts and ends on the end waypoints;
+    inside the blend of waypoint i joint k is within |dv_ik| tb_i / 8 <= max_deviation of the polyline, on the segments it is ON the
+    polyline.  The result is NOT time-optimal (traj_retime's is, at the waypoints).  Duplicate waypoints are DEGENERATE_SEGMENT: purge
+    them.  Returns a BlendTiming."""
+    N, H, W = _blend_paths(paths, lengths, 'path_blend')
+    lim = []
+    for t, name in ((v_max, 'v_max'), (a_max, 'a_max')):
+        t = torch.as_tensor(t, dtype=torch.float32)
+        if t.dim() != 1 or not bool(torch.isfinite(t).all()) or not bool((t > 0).all()):
+            raise ValueError(f'{name} must be a vector of finite limits > 0 (got {t.tolist() if t.dim() == 1 else tuple(t.shape)})')
+        lim.append(t.to(paths.device).contiguous())
+    D = lim[0].numel()
+    if lim[1].numel() != D or not 1 <= D <= W:
+        raise ValueError(f'v_max has {D} entries, a_max {lim[1].numel()}, the rows of paths {W} columns')
+    delta = math.inf if max_deviation is None else float(max_deviation)
+    if not delta > 0:
+        raise ValueError(f'max_deviation = {max_deviation}: a distance > 0 in rad, or None / inf for no cap')
+    if int(max_sweeps) < 1:
+        raise ValueError(f'max_sweeps = {max_sweeps}: at least one sweep')
+    dev = paths.device
+    T = torch.empty(N, max(H - 1, 0), device=dev)
+    tb, tw, dv = (torch.empty(N, H, device=dev) for _ in range(3))
+    duration = torch.empty(N, device=dev)
+    sweeps, status, first_bad = (torch.empty(N, device=dev, dtype=torch.int32) for _ in range(3))
+    if N > 0:                                                    # (an empty tensor has no address to hand over)
+        _lib.check(_lib.lib().mpb_path_blend(_ptr(paths), W, _ptr(lengths), _ptr(lim[0]), _ptr(lim[1]), delta, int(max_sweeps), _ptr(T), _ptr(tb),
+                                             _ptr(tw), _ptr(dv), _ptr(duration), _ptr(sweeps), _ptr(status), _ptr(first_bad), N, H, D, _stream()),
+                   'mpb_path_blend')
+    return BlendTiming(T, tb, tw, dv, duration, sweeps, status, first_bad, lengths, delta, D)
+
+
+@_on_tensor_device
+def path_blend_sample(paths, timing, dt, n_rows=None):
+    """paths (N, H, W) and their BlendTiming -> the blended trajectories at the fixed control period dt, in one launch
+    (mpb_path_blend_sample): (out (N, n_rows, 3D) positions, velocities and accelerations, rows (N,) int32, status (N,) int32).  Row k
+    is the state at k dt; rows at and past a path's own rows[n] = ceil(duration / dt) + 1 hold its last waypoint at rest.  n_rows=None
+    reads the longest duration back (one synchronisation) and sizes the output to it.  A path with more rows than n_rows is
+    BLEND_TOO_LONG (the rows that fit are written); one whose timing is not BLEND_OK keeps that status, has rows 0 and holds its first
+    waypoint."""
+    N, H, W = _blend_paths(paths, timing.lengths, 'path_blend_sample')
+    _chk(timing.T, (N, max(H - 1, 0)), 'timing.T')
+    for name in ('tb', 'tw', 'dev'):
+        _chk(getattr(timing, name), (N, H), 'timing.' + name)
+    _chk(timing.duration, (N,), 'timing.duration')
+    _chk(timing.status, (N,), 'timing.status', dtype=torch.int32)
+    D = int(timing.n_dof)
+    if not 1 <= D <= W:
+        raise ValueError(f'the timing is of {D} joints, the rows of paths have {W} columns')
+    dt = float(dt)
+    if n_rows is None:
+        if not (dt > 0 and math.isfinite(dt)):
+            raise ValueError(f'dt = {dt}: a finite period > 0')
+        ok = (timing.status == BLEND_OK) & torch.isfinite(timing.duration)
+        Tmax = float(torch.where(ok, timing.duration, torch.zeros_like(timing.duration)).max()) if N else 0.0
+        n_rows = int(math.ceil(Tmax / float(np.float32(dt)))) + 1
+    n_rows = int(n_rows)
+    out = torch.empty(N, max(n_rows, 0), 3 * D, device=paths.device)
+    rows = torch.empty(N, device=paths.device, dtype=torch.int32)
+    status = torch.empty(N, device=paths.device, dtype=torch.int32)
+    if N > 0:
+        _lib.check(_lib.lib().mpb_path_blend_sample(_ptr(paths), W, _ptr(timing.lengths), _ptr(timing.T), _ptr(timing.tb), _ptr(timing.tw),
+                                                    _ptr(timing.duration), _ptr(timing.status), _ptr(out), _ptr(rows), _ptr(status), N, H, D, dt,
+                                                    n_rows, _stream()), 'mpb_path_blend_sample')
     return out, rows, status
 
 

@@ -650,6 +650,84 @@ class PlanningTask:
             trajs_dt, n_rows, sample_status = out.reshape(*lead, *out.shape[1:]), rows.reshape(lead), st.reshape(lead)
         return TrajsRetimed(timing.duration.reshape(lead), timing.status.reshape(lead), timing, trajs_dt, n_rows, sample_status)
 
+    # ---- polylines into executable trajectories: linear segments with parabolic blends (build-defined: DESIGN.md 10) ---------------------
+    def blend_paths(self, paths, lengths=None, dt=None, v_max=None, a_max=None, scale=1.0, max_deviation=None, certificate=None, **kwargs):
+        """paths (..., H, W), W >= q_dim, leading dimensions kept, lengths (...) int32 or None -- what the RRT planners, PRM and
+        shortcut_paths emit -> a PathsBlended: every polyline run at constant velocity along its segments with a constant-acceleration
+        blend around every waypoint (ops.path_blend, which has the guarantees and also takes max_sweeps) and, with a control period dt,
+        sampled at it (ops.path_blend_sample).  v_max, a_max default to the robot's dq_max, ddq_max; both are multiplied by `scale`.
+        Unlike retime_trajs the limits hold for EVERY t and the trajectory stays within a known distance of the polyline; it is not
+        time-optimal.
+
+        certificate: the ops.PathCertificate of certify_paths ON THE SAME paths and lengths.  The result then carries
+        deviation_workspace (...): no collision sphere of the blended trajectory is farther than that from where it is on the polyline
+        (the reach table of the certifier applied to the per-joint deviations), and certified (...) bool: status OK, certificate FREE and
+        deviation_workspace < margin_cert -- the blended trajectory is then free of the obstacles over its whole continuum, with
+        nothing checked again.  max_deviation (rad, joint-space infinity-norm; None: no cap) is the knob that buys `certified` at the
+        price of duration: a smaller cap keeps the blends closer to the corners and makes them slower."""
+        lim = {}
+        for name, given, own in (('v_max', v_max, 'dq_max'), ('a_max', a_max, 'ddq_max')):
+            v = getattr(self.robot, own, None) if given is None else given
+            if v is None:
+                raise ValueError(f'blend_paths: no {name} given and the robot carries no {own}')
+            lim[name] = torch.as_tensor(v, dtype=torch.float32).reshape(-1)
+            if lim[name].numel() != self.q_dim:
+                raise ValueError(f'blend_paths: {name} has {lim[name].numel()} entries, the robot {self.q_dim} joints')
+        scale = float(scale)
+        if not (scale > 0 and scale < float('inf')):
+            raise ValueError(f'blend_paths: scale = {scale}, a finite factor > 0')
+        p = torch.as_tensor(paths, dtype=torch.float32, device=self.device)
+        if p.dim() < 2 or p.shape[-1] < self.q_dim:
+            raise ValueError(f'paths has shape {tuple(p.shape)}, expected (..., H, W) with W >= {self.q_dim}')
+        lead = tuple(p.shape[:-2])
+        p = p.reshape(-1, p.shape[-2], p.shape[-1]).contiguous()
+        if lengths is not None:
+            lengths = torch.as_tensor(lengths, device=self.device).to(torch.int32).reshape(-1).contiguous()
+        timing = ops.path_blend(p, lim['v_max'] * scale, lim['a_max'] * scale, lengths=lengths, max_deviation=max_deviation, **kwargs)
+        res = PathsBlended(timing.duration.reshape(lead), timing.status.reshape(lead), timing)
+        if dt is not None:
+            out, rows, st = ops.path_blend_sample(p, timing, dt)
+            res.trajs_dt, res.n_rows, res.sample_status = out.reshape(*lead, *out.shape[1:]), rows.reshape(lead), st.reshape(lead)
+        if certificate is not None:
+            _, reach = self._certify_buffers('blend_paths with a certificate (mpb_path_certify)')
+            if certificate.status.numel() != p.shape[0]:
+                raise ValueError(f'blend_paths: the certificate is of {certificate.status.numel()} paths, paths holds {p.shape[0]}')
+            dev_w = self._blend_workspace_deviation(p, timing, reach)
+            res.deviation_workspace = dev_w.reshape(lead)
+            res.certified = ((timing.status == ops.BLEND_OK) & (certificate.status == ops.CERT_FREE)
+                             & (dev_w < certificate.margin_cert.to(torch.float64))).reshape(lead)
+        return res
+
+    def _blend_workspace_deviation(self, p, timing, reach):
+        """(N,) fp64 on the device: max over waypoints i and collision spheres l of sum_k rho_kl dev_ik, dev_ik = |dv_ik| tb_i / 8 formed
+        from the timing's T and tb (blend_layout.joint_deviation / workspace_deviation are the same on the host)."""
+        from . import certify_layout
+        N, H, _ = p.shape
+        D = self.q_dim
+        q, T, tb = p[:, :, :D].to(torch.float64), timing.T.to(torch.float64), timing.tb.to(torch.float64)
+        L = torch.full((N,), H, device=p.device, dtype=torch.int64) if timing.lengths is None else timing.lengths.to(torch.int64)
+        seg = (torch.arange(H - 1, device=p.device)[None, :] < (L - 1)[:, None]) & (T > 0)
+        v = torch.where(seg[:, :, None], (q[:, 1:] - q[:, :-1]) / torch.where(seg, T, torch.ones_like(T))[:, :, None], torch.zeros((), dtype=torch.float64, device=p.device))
+        v = torch.nan_to_num(v, nan=0.0, posinf=0.0, neginf=0.0)
+        zero = torch.zeros(N, 1, D, dtype=torch.float64, device=p.device)
+        dv = torch.cat([v, zero], 1) - torch.cat([zero, v], 1)
+        way = torch.arange(H, device=p.device)[None, :] < L[:, None]
+        dev = torch.where(way[:, :, None], dv.abs() * tb[:, :, None] / 8.0, torch.zeros((), dtype=torch.float64, device=p.device))
+        rho = torch.from_numpy(reach.host[certify_layout.REACH_HEADER_WORDS:].reshape(D, reach.n_links).astype('float64')).to(p.device)
+        return (dev @ rho).amax(dim=(1, 2)) if N else torch.zeros(0, dtype=torch.float64, device=p.device)
+
+
+class PathsBlended:
+    """What PlanningTask.blend_paths returns, the leading dimensions of its input kept: durations (...) seconds, status (...) int32
+    (ops.BLEND_OK / BLEND_NOT_CONVERGED / BLEND_DEGENERATE_SEGMENT / BLEND_BAD_INPUT), timing (the flat ops.BlendTiming: T, tb, tw, dev, ...);
+    with a control period also trajs_dt (..., n_rows, 3D) positions, velocities and accelerations at k dt, n_rows (...) int32 the rows
+    each path needs, sample_status (...) int32; with a certificate also deviation_workspace (...) fp64 metres and certified (...) bool;
+    else None."""
+
+    def __init__(self, durations, status, timing):
+        self.durations, self.status, self.timing = durations, status, timing
+        self.trajs_dt = self.n_rows = self.sample_status = self.deviation_workspace = self.certified = None
+
 
 class TrajsRetimed:
     """What PlanningTask.retime_trajs returns, the leading dimensions of its input kept: durations (...) seconds, status (...) int32
